@@ -188,17 +188,42 @@ def class_table(classes, step_ms):
     return out
 
 
+DUMP_BUDGET_BYTES = 63 * 10 ** 6                 # payload; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes every named array (all share the leading image axis) as out_dir/<name>.npy in float32.  When the set is larger than
+    `budget` bytes, all arrays keep the same fixed, seeded sample of image rows, so two builds run with the same arguments write
+    files that compare row for row.  Returns the row indices written."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().float().numpy() for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrays.items()}
+    n = n.pop()
+    per_row = sum(a[:1].nbytes for a in arrays.values())
+    k = min(n, budget // max(per_row, 1))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (batches), >= 1")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="engine option (agd_set_option), for A/B runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's images and heat maps as DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch                                             # device_count() does not initialise the GPU on this image
     cmd = self_launch_command(args.gpus, sys.argv[1:], torch.cuda.device_count())
@@ -273,6 +298,11 @@ def main():
         dt = float(tt.item())
     n_img = world * B * args.steps
     value = n_img / dt
+    if rank == 0 and args.dump_outputs:
+        # what the timed path handed its caller in the last timed step (every rank's rows after the gather), outside the timed region
+        rows = dump_outputs(args.dump_outputs, {"images": imgs, "heatmaps": hms})
+        print(f"dumped images {tuple(imgs.shape)} and heatmaps {tuple(hms.shape)}, rows {rows.tolist()}, to {args.dump_outputs}",
+              file=sys.stderr)
 
     roof = None
     table = None

@@ -133,3 +133,28 @@ def test_bench_launcher_plans_n_ranks_before_touching_the_gpu(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     with pytest.raises(SystemExit, match="WORLD_SIZE 2 != --gpus 4"):
         bench.self_launch_command(4, ["--gpus", "4"], n_devices=8)
+
+
+def test_bench_dump_outputs_float32_within_budget_and_seeded(tmp_path):
+    """`bench.py --dump-outputs`: float32 .npy files of the gathered images + heat maps; whole when they fit the budget, else the
+    same seeded rows of every array on every call (two builds compare output for output)."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    imgs = torch.randint(0, 256, (10, 8, 8, 3), dtype=torch.uint8, generator=g)
+    hms = torch.rand(10, 2, 4, 4, generator=g)
+    rows = bench.dump_outputs(str(tmp_path / "all"), {"images": imgs, "heatmaps": hms})
+    assert rows.tolist() == list(range(10))
+    a = np.load(tmp_path / "all" / "images.npy"); h = np.load(tmp_path / "all" / "heatmaps.npy")
+    assert a.dtype == np.float32 and h.dtype == np.float32
+    np.testing.assert_array_equal(a, imgs.numpy().astype(np.float32)); np.testing.assert_array_equal(h, hms.numpy())
+    per_row = (8 * 8 * 3 + 2 * 4 * 4) * 4
+    r1 = bench.dump_outputs(str(tmp_path / "s1"), {"images": imgs, "heatmaps": hms}, budget=3 * per_row + 1)
+    r2 = bench.dump_outputs(str(tmp_path / "s2"), {"images": imgs, "heatmaps": hms}, budget=3 * per_row + 1)
+    assert len(r1) == 3 and r1.tolist() == r2.tolist() and list(r1) == sorted(set(r1.tolist()))
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in ("images.npy", "heatmaps.npy"))
+    assert total <= 3 * per_row + 2 * 256                                   # payload within budget (+ .npy headers)
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "images.npy"), imgs.numpy()[r1].astype(np.float32))
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "heatmaps.npy"), hms.numpy()[r1])
