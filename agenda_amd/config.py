@@ -52,6 +52,13 @@ class SchedulerConfig:
     set_alpha_to_one: bool = False
     prediction_type: str = "epsilon"  # "v_prediction" for SD-2.1 768
     skip_prk_steps: bool = True       # PNDM only: SD checkpoints set it (pure PLMS); False (Runge-Kutta warm-up) is refused, not ignored
+    # DPMSolverMultistepScheduler only (any other value of the solver keys is refused, not ignored)
+    use_karras_sigmas: bool = False
+    timestep_spacing: str = "linspace"   # DDIM / PNDM always run "leading"
+    algorithm_type: str = "dpmsolver++"
+    solver_order: int = 2
+    solver_type: str = "midpoint"
+    lower_order_final: bool = True
 
 
 @dataclass

@@ -214,6 +214,8 @@ int launch_cfg_ddim(const float* eps_nhwc, int ldc, float* lat_nchw, int B, int 
                     float a_t, float a_p, int vpred, hipStream_t st);
 int launch_cfg_plms(const float* eps_nhwc, int ldc, float* lat, const float* src, const float* h1, const float* h2, const float* h3,
                     float* store, int B, int C, int HW, float guidance, const float* w4, float a, float b, hipStream_t st);
+int launch_cfg_dpm(const float* eps_nhwc, int ldc, float* lat, const float* prev, float* store, int B, int C, int HW, float guidance,
+                   const float* coef5 /* cx, ce, a, b0, b1 */, hipStream_t st);
 int launch_ln_fold_weight(const bf16_t* W, const float* gamma, const float* beta, const float* bias, int N, int K, int geglu_bn, bf16_t* Wf,
                           float* colsum, float* bias_f, hipStream_t st);
 int launch_image_u8(const float* x_nhwc, int ldc, unsigned char* out, long long npix, int C, hipStream_t st);

@@ -226,6 +226,42 @@ int launch_cfg_plms(const float* eps, int ldc, float* lat, const float* src, con
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }
 
+// CFG combine + one DPM-Solver++ (2M) update on fp32 NCHW latents, in place:
+//   m = eps_u + g (eps_c - eps_u);  x0 = cx x + ce m;  lat = a x + b0 x0 + b1 prev;  store (if given) = x0
+// The latent has 4 channels.  One thread per pixel of one image: its eps row (ldc floats, ldc % 4 == 0) is read as one float4 per
+// CFG half, the four channel planes are read / written with lane-contiguous 4-B accesses.  prev (x0 of the previous evaluation;
+// nullptr on the first) and store are the two ping-pong history slots of agd_denoise_dpm, never the same buffer.
+__global__ void cfg_dpm_kernel(const float* __restrict__ eps, int ldc, float* __restrict__ lat, const float* __restrict__ prev,
+                               float* __restrict__ store, int B, int HW, float guidance, float cx, float ce, float a, float b0, float b1) {
+  const long long total = (long long)B * HW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW);
+    const int p = (int)(i - (long long)b * HW);
+    const float4 eu = *reinterpret_cast<const float4*>(eps + i * ldc);
+    const float4 ec = *reinterpret_cast<const float4*>(eps + ((long long)B * HW + i) * ldc);
+    const float m[4] = {eu.x + guidance * (ec.x - eu.x), eu.y + guidance * (ec.y - eu.y),
+                        eu.z + guidance * (ec.z - eu.z), eu.w + guidance * (ec.w - eu.w)};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long long o = ((long long)b * 4 + c) * HW + p;
+      const float x = lat[o];
+      const float x0 = cx * x + ce * m[c];
+      float y = a * x + b0 * x0;
+      if (prev) y += b1 * prev[o];
+      if (store) store[o] = x0;
+      lat[o] = y;
+    }
+  }
+}
+int launch_cfg_dpm(const float* eps, int ldc, float* lat, const float* prev, float* store, int B, int C, int HW, float guidance,
+                   const float* coef5, hipStream_t st) {
+  if (C != 4 || ldc < 4 || (ldc & 3) || ((uintptr_t)eps & 15)) { agd_set_error("cfg_dpm: needs 4 latent channels and 16-B aligned eps rows (C=%d ldc=%d)", C, ldc); return -1; }
+  if (prev && prev == store) { agd_set_error("cfg_dpm: history read and write slots alias"); return -1; }
+  hipLaunchKernelGGL(cfg_dpm_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, st, eps, ldc, lat, prev, store, B, HW, guidance,
+                     coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]);
+  HIP_CHECK_RET(hipGetLastError()); return 0;
+}
+
 // diffusers post-process: (x/2+0.5).clamp(0,1) -> round-half-even(255 x) -> uint8, NHWC
 __global__ void image_u8_kernel(const float* __restrict__ x, int ldc, unsigned char* __restrict__ out, long long npix, int C) {
   const long long total = npix * C;

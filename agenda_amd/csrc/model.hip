@@ -110,7 +110,7 @@ struct agd_ctx {
   DBuf bwd_wsb;                                                 // attention-backward workspace
   float* hook_sum = nullptr; float* hook_scratch = nullptr; int hook_count = 0, hook_Bp = 0, hook_T = 0;
   // denoise scratch
-  DBuf latb, epsb, vae_imgb, plmsb;
+  DBuf latb, epsb, vae_imgb, plmsb, dpmb;
   bf16_t* lat_bf16 = nullptr; float* eps_nhwc = nullptr;
   SplitKWs splitk;                                    // split-K partial slabs of this ctx (stream-ordered reuse)
   int opt_cfg_share = 1;                              // agd_set_option("cfg_shared_prefix")
@@ -1049,7 +1049,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release();
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1506,6 +1506,36 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
       API_CK(c, launch_cfg_plms(c->eps_nhwc, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w,
                                 sample_coeff[i], eps_coeff[i], st)); }
     if (store) { ++head; if (n_hist < 3) ++n_hist; }
+  }
+  return 0;
+}
+
+// The denoise loop under DPM-Solver++ (2M) [upstream-knowledge: diffusers 0.21.2 DPMSolverMultistepScheduler, algorithm_type
+// "dpmsolver++", midpoint]: one model evaluation per step.  The host scheduler (agenda_amd/scheduler.py dpm_program) passes, per
+// evaluation i, the UNet timestep (fractional with Karras sigmas) and coeffs[5 i ..]: cx, ce, a, b0, b1 with
+//   x0 = cx x + ce m  (m: CFG-combined model output; eps or v is folded into cx / ce),  x = a x + b0 x0 + b1 x0_prev
+// so first / second order, the lower-order final step and the prediction type are all host decisions.  x0 ping-pongs between the
+// two halves of the context-owned dpmb buffer: evaluation i reads slot (i - 1) & 1 and writes slot i & 1.
+AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* coeffs,
+                            float guidance, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (n_evals < 1 || !timesteps || !coeffs) { agd_set_error("denoise_dpm: needs >= 1 model evaluation and host timesteps / coeffs (got %d)", n_evals); return fail_ctx(c); }
+  const int B2 = 2 * batch, Cl = c->cfg.in_channels, HW = L * L;
+  API_CK(c, ensure_lat(c, B2, L));
+  if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
+  const size_t n1 = (size_t)batch * Cl * HW;
+  API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
+  float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
+  const float* tp_all = nullptr;
+  API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
+  for (int i = 0; i < n_evals; ++i) {
+    { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true));
+    const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
+    float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
+    { ProfScope ps(c, st, PC_ELEM, 0);
+      API_CK(c, launch_cfg_dpm(c->eps_nhwc, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st)); }
   }
   return 0;
 }

@@ -244,12 +244,17 @@ def parse_args(argv=None):
     p.add_argument("--synthetic-config", type=str, default="sd15", help="architecture for synthetic weights when no checkpoint is given")
     p.add_argument("--stack", type=str, default=None, nargs=3, metavar=("OBJ", "FG", "BG"),
                    help="also write daam_stack_heatmaps/ + daam_inv_heatmaps/ for these three words (postprocess_heatmap.py)")
-    p.add_argument("--scheduler", type=str, default=None, choices=["DDIMScheduler", "PNDMScheduler"],
+    p.add_argument("--scheduler", type=str, default=None, choices=["DDIMScheduler", "PNDMScheduler", "DPMSolverMultistepScheduler"],
                    help="default: the checkpoint's scheduler/scheduler_config.json (PNDM for SD-1.4, as the reference runs it); "
-                        "DDIMScheduler for synthetic weights")
+                        "DDIMScheduler for synthetic weights.  DPMSolverMultistepScheduler: DPM-Solver++ 2M, one UNet evaluation per step")
+    p.add_argument("--use-karras-sigmas", action="store_true",
+                   help="DPMSolverMultistepScheduler only: Karras (rho = 7) noise levels instead of the checkpoint's timestep spacing")
     p.add_argument("--no-gather", action="store_true",
                    help="multi-GPU: every rank writes its own files instead of the final all_gather to rank 0")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.use_karras_sigmas and args.scheduler != "DPMSolverMultistepScheduler":
+        p.error("--use-karras-sigmas needs --scheduler DPMSolverMultistepScheduler")
+    return args
 
 
 def main(argv=None):
@@ -269,6 +274,10 @@ def main(argv=None):
     pipe = (StableDiffusionPipeline.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler)
             if args.pretrained_model_path else
             StableDiffusionPipeline.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler"))
+    if args.use_karras_sigmas:
+        from .scheduler import DPMSolverMultistepScheduler
+        pipe.cfg.sched.use_karras_sigmas = True
+        pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.cfg.sched)
     embeds = torch.load(args.learnable_tokens_embedding_path) if args.learnable_tokens_embedding_path else {}
     if embeds:
         new_tokens, words, prompt = select_learned_tokens(args.prompt, args.initialize_token, list(embeds.keys()),

@@ -25,7 +25,8 @@ import torch
 
 from . import _lib
 from .config import SDConfig, CONFIGS, UNetConfig, VAEConfig, SchedulerConfig, cross_attn_layer_names
-from .scheduler import DDIMScheduler, PNDMScheduler, SCHEDULERS
+from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, SCHEDULERS, scheduler_config_from_json,
+                        scheduler_config_to_json)
 from .text import SimpleTokenizer, SyntheticTextEncoder
 
 
@@ -205,6 +206,20 @@ class Engine:
         b, _, L, _ = latents.shape
         self._ck(self.lib.agd_denoise_plms(self.ctx, _lib.ptr(latents), b, L, n, ts, ca, cb, float(guidance), self._stream()),
                  "agd_denoise_plms")
+        return latents
+
+    def denoise_dpm(self, latents: torch.Tensor, timesteps, cx, ce, a, b0, b1, guidance: float):
+        """The fused loop under DPM-Solver++ 2M (`agd_denoise_dpm`): one model evaluation per timestep; the per-evaluation
+        coefficients are `DPMSolverMultistepScheduler.dpm_program()`'s."""
+        assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
+        n = len(timesteps)
+        if not all(len(x) == n for x in (cx, ce, a, b0, b1)):
+            raise ValueError("denoise_dpm: one (cx, ce, a, b0, b1) per timestep")
+        ts = (C.c_float * n)(*[float(t) for t in timesteps])
+        co = (C.c_float * (5 * n))(*[float(v) for row in zip(cx, ce, a, b0, b1) for v in row])
+        b, _, L, _ = latents.shape
+        self._ck(self.lib.agd_denoise_dpm(self.ctx, _lib.ptr(latents), b, L, n, ts, co, float(guidance), self._stream()),
+                 "agd_denoise_dpm")
         return latents
 
     def vae_decode(self, latents: torch.Tensor, want_f32: bool = False):
@@ -514,12 +529,7 @@ class StableDiffusionPipeline:
                 if sched_name not in SCHEDULERS:
                     raise _lib.AgendaHipError(f"{sp}: scheduler '{sched_name}' is not implemented (have: {sorted(SCHEDULERS)}); "
                                               "pass from_pretrained(..., scheduler='DDIMScheduler') to override")
-            sc = SchedulerConfig(sj.get("num_train_timesteps", 1000), sj.get("beta_start", 0.00085), sj.get("beta_end", 0.012),
-                                 sj.get("steps_offset", 1), sj.get("set_alpha_to_one", False), sj.get("prediction_type", "epsilon"),
-                                 # diffusers' PNDMScheduler defaults skip_prk_steps to False; SD checkpoints store True
-                                 # (that default applies only when the JSON itself is a PNDMScheduler config: an explicit scheduler="PNDMScheduler"
-                                 # override on a DDIM checkpoint has no such key and means the SD form, skip_prk_steps=True)
-                                 bool(sj.get("skip_prk_steps", False)) if sj.get("_class_name") == "PNDMScheduler" else True)
+            sc = scheduler_config_from_json(sj, sched_name)
         cfg = SDConfig(name=os.path.basename(path.rstrip("/")), unet=ucfg, vae=vcfg, sched=sc,
                        default_sample_size=uc.get("sample_size", 64))
         src_path = path
@@ -591,12 +601,7 @@ class StableDiffusionPipeline:
         if sj.get("_class_name") != sched_cls:
             # the pipeline runs a different scheduler than the source directory names (from_pretrained(..., scheduler=...)): a reload
             # must give the scheduler this pipeline ran, so its config is written from the live objects
-            sc = self.cfg.sched
-            sj = {"_class_name": sched_cls, "num_train_timesteps": sc.num_train_timesteps, "beta_start": sc.beta_start, "beta_end": sc.beta_end,
-                  "beta_schedule": "scaled_linear", "steps_offset": sc.steps_offset, "set_alpha_to_one": sc.set_alpha_to_one,
-                  "prediction_type": sc.prediction_type}
-            if sched_cls == "PNDMScheduler":
-                sj["skip_prk_steps"] = bool(sc.skip_prk_steps)
+            sj = scheduler_config_to_json(sched_cls, self.cfg.sched)
             os.makedirs(os.path.join(dst, "scheduler"), exist_ok=True)
             with open(os.path.join(dst, "scheduler", "scheduler_config.json"), "w") as f:
                 json.dump(sj, f, indent=2)
@@ -718,6 +723,8 @@ class StableDiffusionPipeline:
         if isinstance(self.scheduler, PNDMScheduler):
             tsf, ca, cb = self.scheduler.plms_program()
             self.engine.denoise_plms(lat, tsf, ca, cb, guidance_scale)
+        elif isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            self.engine.denoise_dpm(lat, *self.scheduler.dpm_program(), guidance_scale)
         else:
             a_t, a_p = self.scheduler.step_coeffs()
             self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
@@ -747,9 +754,9 @@ class StableDiffusionPipeline:
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil"):
         """image: float [B,3,S,S] in [-1,1] (or uint8 [B,S,S,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
-        # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) gets a DDIM scheduler
-        # built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated PLMS is not
-        # implemented)
+        # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
+        # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
+        # PLMS and DPM-Solver++ img2img are not implemented)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
             image = image.permute(0, 3, 1, 2).float() / 127.5 - 1.0

@@ -93,6 +93,13 @@ int agd_denoise(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_
 int agd_denoise_plms(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_evals, const float* timesteps,
                      const float* sample_coeff, const float* eps_coeff, float guidance, void* stream);
 
+/* ---- the same loop under DPM-Solver++ (2M) (agenda_amd/scheduler.py DPMSolverMultistepScheduler, epsilon or v-prediction, with
+ * or without Karras sigmas): n_evals = steps model evaluations.  Per evaluation i the host passes the UNet timestep (fractional
+ * with Karras sigmas) and coeffs[5 i + 0..4] = cx, ce, a, b0, b1: x0 = cx * sample + ce * model_output, then
+ * sample = a * sample + b0 * x0 + b1 * x0 of evaluation i - 1.  The previous x0 lives in a context-owned buffer. */
+int agd_denoise_dpm(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_evals, const float* timesteps,
+                    const float* coeffs, float guidance, void* stream);
+
 /* ---- `vae.decode(latents / scaling_factor)` + image post-process.
  * out_u8: [B, 8L, 8L, 3] uint8 (may be NULL); out_f32: [B, 8L, 8L, 3] fp32 in [-1,1] (may be NULL) */
 int agd_vae_decode(agd_ctx* ctx, const float* latents, int batch, int latent_side, unsigned char* out_u8,
