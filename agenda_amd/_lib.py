@@ -37,6 +37,17 @@ class AgdConfig(C.Structure):
     ]
 
 
+class AgdVisionConfig(C.Structure):
+    """`agd_vision_config`: the safety checker's CLIP vision tower (agd_safety_configure)."""
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("hidden", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("intermediate", C.c_int),
+        ("image_size", C.c_int), ("patch_size", C.c_int), ("projection_dim", C.c_int),
+        ("n_special", C.c_int), ("n_concepts", C.c_int), ("act", C.c_int),
+        ("eps", C.c_float), ("mean", C.c_float * 3), ("std", C.c_float * 3),
+    ]
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -51,6 +62,8 @@ _SIGS = {
     "agd_set_context": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "agd_text_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "agd_text_set_embedding_row": (C.c_int, [_P, C.c_int, _P]),
+    "agd_safety_configure": (C.c_int, [_P, C.POINTER(AgdVisionConfig)]),
+    "agd_safety_scores": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "agd_unet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_unet_forward_ts": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
     "agd_cfg_ddim_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P]),

@@ -75,6 +75,86 @@ class TextConfig:
 
 
 @dataclass
+class SafetyConfig:
+    """The safety checker (`pipeline.safety_checker`, diffusers StableDiffusionSafetyChecker): its CLIP vision tower under the
+    transformers CLIPVisionConfig field names, the CLIPConfig `projection_dim`, the concept counts, and the CLIPImageProcessor
+    settings of `feature_extractor/preprocessor_config.json`.  Defaults = the SD-1.x checker (ViT-L/14 at 224 px, 3 special-care
+    and 17 concept embeddings)."""
+    hidden_size: int = 1024
+    intermediate_size: int = 4096
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    num_channels: int = 3
+    image_size: int = 224
+    patch_size: int = 14
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+    projection_dim: int = 768
+    n_special: int = 3
+    n_concepts: int = 17
+    # CLIPImageProcessor (resize shortest edge -> center crop -> rescale -> normalize, PIL BICUBIC)
+    size: int = 224
+    crop_size: int = 224
+    resample: int = 3
+    rescale_factor: float = 1 / 255
+    image_mean: Tuple[float, float, float] = (0.48145466, 0.4578275, 0.40821073)
+    image_std: Tuple[float, float, float] = (0.26862954, 0.26130258, 0.27577711)
+
+
+# transformers CLIPVisionConfig / CLIPConfig defaults: what a key missing from safety_checker/config.json means
+_CLIP_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3,
+                             image_size=224, patch_size=32, hidden_act="quick_gelu", layer_norm_eps=1e-5)
+_CLIP_PROJECTION_DIM_DEFAULT = 512
+
+
+def _edge(v, what: str) -> int:
+    """`size` / `crop_size` of a preprocessor config: an int, {"shortest_edge": n} or {"height": n, "width": n}."""
+    if isinstance(v, bool):
+        raise ValueError(f"preprocessor {what}: {v!r} is not a size")
+    if isinstance(v, (int, float)):
+        return int(v)
+    if isinstance(v, dict):
+        if "shortest_edge" in v and len(v) == 1:
+            return int(v["shortest_edge"])
+        if set(v) == {"height", "width"} and v["height"] == v["width"]:
+            return int(v["height"])
+    raise ValueError(f"preprocessor {what} {v!r} is not supported (an int, {{'shortest_edge': n}} or a square {{'height', 'width'}})")
+
+
+def safety_config_from_json(clip_cfg: dict, preprocessor: dict, n_special: int = 3, n_concepts: int = 17) -> SafetyConfig:
+    """SafetyConfig from `safety_checker/config.json` (a CLIPConfig: `vision_config`, else the older `vision_config_dict`, and the
+    top-level `projection_dim`) and `feature_extractor/preprocessor_config.json`.  Preprocessor settings other than resize ->
+    center crop -> rescale by 1/255 -> normalize with BICUBIC (resample 3) are refused, not ignored: the device front end runs
+    exactly that chain."""
+    vis = clip_cfg.get("vision_config") or clip_cfg.get("vision_config_dict") or {}
+    v = {k: vis.get(k, d) for k, d in _CLIP_VISION_DEFAULTS.items()}
+    pp = dict(preprocessor)
+    for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
+        if not pp.get(flag, True):
+            raise ValueError(f"preprocessor_config: {flag}=False is not supported (the checker runs resize -> center crop -> rescale -> normalize)")
+    if int(pp.get("resample", 3)) != 3:
+        raise ValueError(f"preprocessor_config: resample={pp['resample']} is not supported (only 3, BICUBIC)")
+    rf = float(pp.get("rescale_factor", 1 / 255))
+    if abs(rf - 1 / 255) > 1e-12:
+        raise ValueError(f"preprocessor_config: rescale_factor={rf} is not supported (only 1/255)")
+    for k in ("do_pad", "do_flip_channel_order", "do_reduce_labels"):
+        if pp.get(k):
+            raise ValueError(f"preprocessor_config: {k}=True is not supported")
+    size = _edge(pp.get("size", 224), "size")
+    crop = _edge(pp.get("crop_size", 224), "crop_size")
+    if size != crop:
+        raise ValueError(f"preprocessor_config: size {size} != crop_size {crop} is not supported (square images: the crop must be the identity)")
+    if crop != v["image_size"]:
+        raise ValueError(f"preprocessor_config: crop_size {crop} != vision image_size {v['image_size']}")
+    mean = tuple(float(x) for x in pp.get("image_mean", SafetyConfig.image_mean))
+    std = tuple(float(x) for x in pp.get("image_std", SafetyConfig.image_std))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("preprocessor_config: image_mean / image_std must have 3 entries")
+    return SafetyConfig(projection_dim=int(clip_cfg.get("projection_dim", _CLIP_PROJECTION_DIM_DEFAULT)), n_special=n_special,
+                        n_concepts=n_concepts, size=size, crop_size=crop, resample=3, rescale_factor=rf, image_mean=mean, image_std=std, **v)
+
+
+@dataclass
 class SDConfig:
     name: str = "sd15"
     unet: UNetConfig = field(default_factory=UNetConfig)
@@ -84,6 +164,7 @@ class SDConfig:
     vae_scale_factor: int = 8
     default_sample_size: int = 64
     text: "TextConfig | None" = None     # None: no device text encoder (synthetic / external embeddings)
+    safety: "SafetyConfig | None" = None  # None: no safety checker (nothing is blacked out)
 
     def to_dict(self):
         return asdict(self)
@@ -157,6 +238,36 @@ def text_param_shapes(t: TextConfig) -> Dict[str, tuple]:
         p[L + "mlp.fc2.weight"] = (H, I); p[L + "mlp.fc2.bias"] = (H,)
     p["final_layer_norm.weight"] = (H,)
     p["final_layer_norm.bias"] = (H,)
+    return p
+
+
+def safety_param_shapes(s: SafetyConfig) -> Dict[str, tuple]:
+    """diffusers StableDiffusionSafetyChecker state-dict keys (`vision_model` is a transformers CLIPVisionModel, hence the doubled
+    `vision_model.vision_model.` prefix)."""
+    H, I, P = s.hidden_size, s.intermediate_size, s.projection_dim
+    g = s.image_size // s.patch_size
+    V = "vision_model.vision_model."
+    p: Dict[str, tuple] = {V + "embeddings.class_embedding": (H,),
+                           V + "embeddings.patch_embedding.weight": (H, s.num_channels, s.patch_size, s.patch_size),
+                           V + "embeddings.position_embedding.weight": (g * g + 1, H),
+                           V + "pre_layrnorm.weight": (H,), V + "pre_layrnorm.bias": (H,)}
+    for l in range(s.num_hidden_layers):
+        L = V + f"encoder.layers.{l}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            p[L + f"self_attn.{n}.weight"] = (H, H)
+            p[L + f"self_attn.{n}.bias"] = (H,)
+        for n in ("layer_norm1", "layer_norm2"):
+            p[L + n + ".weight"] = (H,)
+            p[L + n + ".bias"] = (H,)
+        p[L + "mlp.fc1.weight"] = (I, H); p[L + "mlp.fc1.bias"] = (I,)
+        p[L + "mlp.fc2.weight"] = (H, I); p[L + "mlp.fc2.bias"] = (H,)
+    p[V + "post_layernorm.weight"] = (H,)
+    p[V + "post_layernorm.bias"] = (H,)
+    p["visual_projection.weight"] = (P, H)
+    p["concept_embeds"] = (s.n_concepts, P)
+    p["special_care_embeds"] = (s.n_special, P)
+    p["concept_embeds_weights"] = (s.n_concepts,)
+    p["special_care_embeds_weights"] = (s.n_special,)
     return p
 
 

@@ -245,3 +245,11 @@ long long attention_backward_ws_floats(int B, int H, int D, int N, int T);
 int launch_transpose_bf16(const bf16_t* in, int R, int Cc, bf16_t* out, hipStream_t st);
 
 int launch_embed_gather(const int* ids, const bf16_t* tok, const bf16_t* pos, bf16_t* out, int B, int T, int H, int vocab_cap, hipStream_t st);
+
+// safety-checker vision tower ends (vision.hip)
+struct VisNorm { float mean0, mean1, mean2, std0, std1, std2; };
+int launch_vis_patchify(const unsigned char* img, int B, int S, int ps, int Kpad, VisNorm nm, bf16_t* rows, float* pix, hipStream_t st);
+int launch_vis_embed_ln(const float* pe, const float* cls, const float* pos, const float* gamma, const float* beta, int B, int np, int H,
+                        float eps, bf16_t* x, hipStream_t st);
+int launch_vis_pooled_head(const bf16_t* x, int B, int T, int H, const float* gamma, const float* beta, float eps, const float* Wp, int P,
+                           const float* E, int n, float* cos_out, hipStream_t st);

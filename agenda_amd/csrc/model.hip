@@ -136,6 +136,8 @@ struct agd_ctx {
   int opt_pc = 49;                                    // agd_set_option("igemm_pc"): producer / consumer igemm (igemm_pc.h) -- bit 0: 1x1 launches on 64 x 160 tiles, bit 1: 3x3 convs of the 16 x 16 maps;
                                                       // bit 4: the row-halo producer / consumer kernel (igemm_pch.h) for 3x3 convs whose 128 x 160 tiles (x K slices) fit one wave of workgroups;
                                                       // bit 5: the 1x1 launches of one 128 x 160 tile per CU (M = 8192, N = 640) on igemm_pc.h's 128-row form
+  // safety checker (agd_safety_configure): the CLIP vision tower's config, its fp32 concept rows (special-care rows first, L2-normalised at finalize)
+  agd_vision_config vis{}; bool vis_on = false; float* vis_concepts = nullptr;
   int opt_xpre = 1;                                   // agd_set_option("attn2_premul"): attn2 of the C = 1280 blocks as two GEMMs against per-image pre-multiplied context matrices (xattn_pre.hip)
   int opt_touch = 3;                                  // agd_set_option("weight_touch"): n > 0 = stream 1x1 weight matrices of >= n MB through the caches right before their launch
   unsigned* touch_sink = nullptr;
@@ -213,6 +215,7 @@ struct GemmOpt {
   int* can_fuse_sc = nullptr;   // query only: *can_fuse_sc = 1 when this launch could take a shortcut that way (nothing is launched)
   int pad = -1;                 // -1: 1 for 3x3, 0 for 1x1
   int hout = 0, wout = 0;       // >0: override (asymmetric (0,1,0,1) padding of the VAE encoder's stride-2 convs)
+  int prof_cls = -1;            // >= 0: the profiler class of this launch (default: PC_CONV3 / PC_GEMM by kernel size)
 };
 static const int kTextExtraRows = 256;   // room for tokenizer.add_tokens() (learned tokens)
 
@@ -284,7 +287,7 @@ static int run_conv(agd_ctx* c, hipStream_t st, const bf16_t* s0, int C0, const 
     if (c->touch_sink) { ProfScope pt(c, st, PC_TOUCH, 0, w_b);
       hipLaunchKernelGGL(touch_kernel, dim3(1024), dim3(256), 0, st, (const u32x4*)w.w, (long long)(w_b / 16), c->touch_sink); }
   }
-  ProfScope ps(c, st, ksize != 1 ? PC_CONV3 : PC_GEMM, 2.0 * p.M * (double)p.N * p.K, in_b + w_b + out_b + 2.0 * B * Hin * Win * (double)(o.sc_C0 + o.sc_C1));
+  ProfScope ps(c, st, o.prof_cls >= 0 ? o.prof_cls : (ksize != 1 ? PC_CONV3 : PC_GEMM), 2.0 * p.M * (double)p.N * p.K, in_b + w_b + out_b + 2.0 * B * Hin * Win * (double)(o.sc_C0 + o.sc_C1));
   return launch_igemm(p, st);
 }
 
@@ -1074,7 +1077,10 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
   }
   if (hipMemcpy(c->stage, ptr, bytes, hipMemcpyDefault) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
   const std::string k(name);
-  if (ndim == 1) {
+  // the safety checker keeps everything but its encoder-layer matrices in fp32 as loaded (embeddings, the 14 x 14 patch conv, the
+  // projection, the concept rows); agd_finalize checks their sizes and builds the padded patch matrix
+  const bool vis_f32 = k.compare(0, 7, "safety.") == 0 && !(ndim == 2 && k.find(".encoder.layers.") != std::string::npos);
+  if (ndim == 1 || vis_f32) {
     float* d = dmalloc<float>(c, (size_t)n); if (!d) return fail_ctx(c);
     hipMemcpy(d, c->stage, bytes, hipMemcpyDeviceToDevice);
     c->V[k] = d; c->Vn[k] = (int)n;
@@ -1100,6 +1106,73 @@ static int concat_rows(agd_ctx* c, const std::vector<const WMat*>& parts, WMat& 
   out.w = dmalloc<bf16_t>(c, (size_t)out.N * out.taps * out.Cpad); if (!out.w) return -1;
   size_t off = 0;
   for (auto* p : parts) { const size_t nb = (size_t)p->N * p->taps * p->Cpad; hipMemcpy(out.w + off, p->w, nb * 2, hipMemcpyDeviceToDevice); off += nb; }
+  return 0;
+}
+
+// q_proj / k_proj / v_proj of every layer of a CLIP encoder as one [3H][H] matrix + bias ("<prefix><l>.self_attn.qkv.*")
+static int fuse_clip_qkv(agd_ctx* c, const std::string& prefix, int layers) {
+  for (int l = 0; l < layers; ++l) {
+    const std::string a = prefix + std::to_string(l) + ".self_attn.";
+    const WMat* q = getW(c, a + "q_proj.weight"); const WMat* k = getW(c, a + "k_proj.weight"); const WMat* v = getW(c, a + "v_proj.weight");
+    const float* bq = getV(c, a + "q_proj.bias"); const float* bk = getV(c, a + "k_proj.bias"); const float* bv = getV(c, a + "v_proj.bias");
+    if (!q || !k || !v || !bq || !bk || !bv) return -1;
+    WMat qkv; if (concat_rows(c, {q, k, v}, qkv)) return -1; c->W[a + "qkv.weight"] = qkv;
+    float* b = dmalloc<float>(c, (size_t)3 * q->N); if (!b) return -1;
+    hipMemcpy(b, bq, (size_t)q->N * 4, hipMemcpyDeviceToDevice); hipMemcpy(b + q->N, bk, (size_t)q->N * 4, hipMemcpyDeviceToDevice);
+    hipMemcpy(b + 2 * q->N, bv, (size_t)q->N * 4, hipMemcpyDeviceToDevice);
+    c->V[a + "qkv.bias"] = b; c->Vn[a + "qkv.bias"] = 3 * q->N;
+  }
+  return 0;
+}
+
+static const char* kVisPre = "safety.vision_model.vision_model.";
+// an fp32 safety tensor of exactly n elements
+static const float* getV_n(agd_ctx* c, const std::string& k, long long n) {
+  const float* p = getV(c, k); if (!p) return nullptr;
+  if (c->Vn[k] != n) { agd_set_error("'%s' has %d elements, the safety config needs %lld", k.c_str(), c->Vn[k], n); return nullptr; }
+  return p;
+}
+
+static int finalize_safety(agd_ctx* c) {
+  const agd_vision_config& v = c->vis;
+  const std::string E = std::string(kVisPre) + "embeddings.";
+  const int H = v.hidden, ps = v.patch_size, g = v.image_size / ps, K = 3 * ps * ps, P = v.projection_dim, n = v.n_special + v.n_concepts;
+  const float* pw = getV_n(c, E + "patch_embedding.weight", (long long)H * K); if (!pw) return -1;
+  if (!getV_n(c, E + "class_embedding", H) || !getV_n(c, E + "position_embedding.weight", (long long)(g * g + 1) * H)) return -1;
+  for (const char* ln : {"pre_layrnorm.", "post_layernorm."})
+    for (const char* wb : {"weight", "bias"}) if (!getV_n(c, std::string(kVisPre) + ln + wb, H)) return -1;
+  if (!getV_n(c, "safety.visual_projection.weight", (long long)P * H)) return -1;
+  const float* sp = getV_n(c, "safety.special_care_embeds", (long long)v.n_special * P); if (!sp) return -1;
+  const float* cp = getV_n(c, "safety.concept_embeds", (long long)v.n_concepts * P); if (!cp) return -1;
+  for (int l = 0; l < v.layers; ++l) {
+    const std::string L = std::string(kVisPre) + "encoder.layers." + std::to_string(l) + ".";
+    for (const char* m : {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "mlp.fc1", "mlp.fc2"}) {
+      const WMat* w = getW(c, L + m + ".weight"); if (!w) return -1;
+      const bool fc1 = !strcmp(m, "mlp.fc1"), fc2 = !strcmp(m, "mlp.fc2");
+      const int want_n = fc1 ? v.intermediate : H, want_k = fc2 ? v.intermediate : H;
+      if (w->N != want_n || w->Cin != want_k) FAIL("'%s%s.weight' is [%d, %d], the safety config needs [%d, %d]", L.c_str(), m, w->N, w->Cin, want_n, want_k);
+      if (!getV_n(c, L + m + ".bias", want_n)) return -1;
+    }
+    for (const char* ln : {"layer_norm1.", "layer_norm2."})
+      for (const char* wb : {"weight", "bias"}) if (!getV_n(c, L + ln + wb, H)) return -1;
+  }
+  if (fuse_clip_qkv(c, std::string(kVisPre) + "encoder.layers.", v.layers)) return -1;
+  // the 14 x 14 / 14 conv as a [H][Kpad] GEMM matrix, K = 3 ps ps zero-padded to the 64-multiple the implicit GEMM steps in
+  { WMat w; w.N = H; w.Cin = K; w.taps = 1; w.Cpad = (K + 63) / 64 * 64;
+    w.w = dmalloc<bf16_t>(c, (size_t)w.N * w.Cpad); if (!w.w) return -1;
+    if (launch_convert_weight(pw, w.w, w.N, K, 1, w.Cpad, 0, 0)) return -1;
+    c->W["safety.patch_matrix"] = w; }
+  // concept rows, L2-normalised once (cosine_distance normalises both sides; the image side is normalised per call)
+  std::vector<float> rows((size_t)n * P);
+  if (hipMemcpy(rows.data(), sp, (size_t)v.n_special * P * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(rows.data() + (size_t)v.n_special * P, cp, (size_t)v.n_concepts * P * 4, hipMemcpyDeviceToHost) != hipSuccess) FAIL("safety: concept read failed");
+  for (int i = 0; i < n; ++i) {
+    double ss = 0; for (int j = 0; j < P; ++j) ss += (double)rows[(size_t)i * P + j] * rows[(size_t)i * P + j];
+    const double inv = 1.0 / std::max(std::sqrt(ss), 1e-12);
+    for (int j = 0; j < P; ++j) rows[(size_t)i * P + j] = (float)(rows[(size_t)i * P + j] * inv);
+  }
+  c->vis_concepts = dmalloc<float>(c, rows.size()); if (!c->vis_concepts) return -1;
+  if (hipMemcpy(c->vis_concepts, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess) FAIL("safety: concept upload failed");
   return 0;
 }
 
@@ -1316,17 +1389,9 @@ AGD_API int agd_finalize(agd_ctx* c) {
     const int dim = g.block_out_channels[0];
     c->temb_buf = dmalloc<float>(c, (size_t)dim * 9); if (!c->temb_buf) return fail_ctx(c); }
   // ---- CLIP text encoder: fused q/k/v projection per layer
-  for (int l = 0; l < g.text_layers; ++l) {
-    const std::string a = "text.encoder.layers." + std::to_string(l) + ".self_attn.";
-    const WMat* q = getW(c, a + "q_proj.weight"); const WMat* k = getW(c, a + "k_proj.weight"); const WMat* v = getW(c, a + "v_proj.weight");
-    const float* bq = getV(c, a + "q_proj.bias"); const float* bk = getV(c, a + "k_proj.bias"); const float* bv = getV(c, a + "v_proj.bias");
-    if (!q || !k || !v || !bq || !bk || !bv) return fail_ctx(c);
-    WMat qkv; API_CK(c, concat_rows(c, {q, k, v}, qkv)); c->W[a + "qkv.weight"] = qkv;
-    float* b = dmalloc<float>(c, (size_t)3 * q->N); if (!b) return fail_ctx(c);
-    hipMemcpy(b, bq, (size_t)q->N * 4, hipMemcpyDeviceToDevice); hipMemcpy(b + q->N, bk, (size_t)q->N * 4, hipMemcpyDeviceToDevice);
-    hipMemcpy(b + 2 * q->N, bv, (size_t)q->N * 4, hipMemcpyDeviceToDevice);
-    c->V[a + "qkv.bias"] = b; c->Vn[a + "qkv.bias"] = 3 * q->N;
-  }
+  API_CK(c, fuse_clip_qkv(c, "text.encoder.layers.", g.text_layers));
+  // ---- safety checker: the vision tower's fused q/k/v, the zero-padded patch matrix, the normalised concept rows
+  if (c->vis_on) API_CK(c, finalize_safety(c));
   hipDeviceSynchronize();
   c->finalized = true;
   return 0;
@@ -2491,12 +2556,48 @@ AGD_API int agd_text_set_embedding_row(agd_ctx* c, int token_id, const float* ro
   return 0;
 }
 
+// The layer loop of a CLIP encoder (transformers CLIPEncoder: pre-LN, fused q/k/v, attention with head dim H / heads,
+// out_proj + residual, pre-LN, fc1 + quick_gelu / gelu, fc2 + residual) over the residual stream x bf16 [B T][H] in place;
+// shared by the text encoder (causal) and the safety checker's vision tower (causal = 0, T = 257).  h / qkv / att / ff are
+// scratch of [B T] rows x H / 3H / H / inter.  prof_cls >= 0 times every launch under that class (the text path keeps its classes).
+struct ClipEnc { std::string prefix; int layers, H, heads, inter, act; float eps; int causal; int prof_cls; };
+static int clip_encoder_layers(agd_ctx* c, hipStream_t st, const ClipEnc& e, int B, int T, bf16_t* x, bf16_t* h, bf16_t* qkv, bf16_t* att,
+                               bf16_t* ff) {
+  const int H = e.H, D = H / e.heads, M = B * T;
+  auto ln = [&](const float* g, const float* b) {
+    if (e.prof_cls < 0) return launch_layernorm(x, h, g, b, M, H, e.eps, st);
+    ProfScope ps(c, st, e.prof_cls, 0, 4.0 * M * (double)H);
+    return launch_layernorm(x, h, g, b, M, H, e.eps, st);
+  };
+  for (int l = 0; l < e.layers; ++l) {
+    const std::string L = e.prefix + std::to_string(l) + ".";
+    const float* g1 = getV(c, L + "layer_norm1.weight"); const float* b1 = getV(c, L + "layer_norm1.bias");
+    const float* g2 = getV(c, L + "layer_norm2.weight"); const float* b2 = getV(c, L + "layer_norm2.bias");
+    const WMat* wqkv = getW(c, L + "self_attn.qkv.weight"); const float* bqkv = getV(c, L + "self_attn.qkv.bias");
+    const WMat* wo = getW(c, L + "self_attn.out_proj.weight"); const float* bo = getV(c, L + "self_attn.out_proj.bias");
+    const WMat* w1 = getW(c, L + "mlp.fc1.weight"); const float* bf1 = getV(c, L + "mlp.fc1.bias");
+    const WMat* w2 = getW(c, L + "mlp.fc2.weight"); const float* bf2 = getV(c, L + "mlp.fc2.bias");
+    if (!g1 || !b1 || !g2 || !b2 || !wqkv || !bqkv || !wo || !bo || !w1 || !bf1 || !w2 || !bf2) return -1;
+    if (ln(g1, b1)) return -1;
+    { GemmOpt o; o.bias = bqkv; o.prof_cls = e.prof_cls; if (run_conv(c, st, h, H, nullptr, 0, 1, 1, M, *wqkv, 1, qkv, o, c->zero_page)) return -1; }
+    { AttnP a{}; a.q = qkv; a.k = qkv + H; a.v = qkv + 2 * H; a.o = att; a.ldq = a.ldk = a.ldv = 3 * H; a.ldo = H;
+      a.sq = a.sk = a.sv = (long long)T * 3 * H; a.so = (long long)T * H; a.B = B; a.H = e.heads; a.D = D; a.Nq = T; a.Nk = T;
+      a.scale = 1.0f / sqrtf((float)D); a.causal = e.causal;
+      if (run_attention(c, st, PC_OTHER, a)) return -1; }
+    { GemmOpt o; o.bias = bo; o.residual = x; o.prof_cls = e.prof_cls; if (run_conv(c, st, att, H, nullptr, 0, 1, 1, M, *wo, 1, x, o, c->zero_page)) return -1; }
+    if (ln(g2, b2)) return -1;
+    { GemmOpt o; o.bias = bf1; o.act = e.act == 0 ? 2 : 3; o.prof_cls = e.prof_cls; if (run_conv(c, st, h, H, nullptr, 0, 1, 1, M, *w1, 1, ff, o, c->zero_page)) return -1; }
+    { GemmOpt o; o.bias = bf2; o.residual = x; o.prof_cls = e.prof_cls; if (run_conv(c, st, ff, e.inter, nullptr, 0, 1, 1, M, *w2, 1, x, o, c->zero_page)) return -1; }
+  }
+  return 0;
+}
+
 AGD_API int agd_text_encode(agd_ctx* c, const int* input_ids, int B, int T, float* out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   const agd_config& g = c->cfg;
   if (g.text_layers <= 0) { agd_set_error("text encoder not configured"); return fail_ctx(c); }
-  const int H = g.text_hidden, heads = g.text_heads, D = H / heads, M = B * T;
+  const int H = g.text_hidden, M = B * T;
   if (T > g.text_max_pos || T > 96) { agd_set_error("text: %d tokens unsupported (max %d)", T, g.text_max_pos < 96 ? g.text_max_pos : 96); return fail_ctx(c); }
   const std::string tx = "text.";
   const WMat* te = getW(c, tx + "embeddings.token_embedding.weight"); const WMat* pe = getW(c, tx + "embeddings.position_embedding.weight");
@@ -2509,30 +2610,84 @@ AGD_API int agd_text_encode(agd_ctx* c, const int* input_ids, int B, int T, floa
   if (!ids || !x || !h || !qkv || !att || !ff) return fail_ctx(c);
   if (hipMemcpyAsync(ids, input_ids, (size_t)M * 4, hipMemcpyDefault, st) != hipSuccess) { agd_set_error("text: ids copy failed"); return fail_ctx(c); }
   API_CK(c, launch_embed_gather(ids, te->w, pe->w, x, B, T, H, te->N + kTextExtraRows, st));
-  for (int l = 0; l < g.text_layers; ++l) {
-    const std::string L = tx + "encoder.layers." + std::to_string(l) + ".";
-    const float* g1 = getV(c, L + "layer_norm1.weight"); const float* b1 = getV(c, L + "layer_norm1.bias");
-    const float* g2 = getV(c, L + "layer_norm2.weight"); const float* b2 = getV(c, L + "layer_norm2.bias");
-    const WMat* wqkv = getW(c, L + "self_attn.qkv.weight"); const float* bqkv = getV(c, L + "self_attn.qkv.bias");
-    const WMat* wo = getW(c, L + "self_attn.out_proj.weight"); const float* bo = getV(c, L + "self_attn.out_proj.bias");
-    const WMat* w1 = getW(c, L + "mlp.fc1.weight"); const float* bf1 = getV(c, L + "mlp.fc1.bias");
-    const WMat* w2 = getW(c, L + "mlp.fc2.weight"); const float* bf2 = getV(c, L + "mlp.fc2.bias");
-    if (!g1 || !b1 || !g2 || !b2 || !wqkv || !bqkv || !wo || !bo || !w1 || !bf1 || !w2 || !bf2) return fail_ctx(c);
-    API_CK(c, launch_layernorm(x, h, g1, b1, M, H, g.text_eps, st));
-    { GemmOpt o; o.bias = bqkv; API_CK(c, run_conv(c, st, h, H, nullptr, 0, 1, 1, M, *wqkv, 1, qkv, o, c->zero_page)); }
-    { AttnP a{}; a.q = qkv; a.k = qkv + H; a.v = qkv + 2 * H; a.o = att; a.ldq = a.ldk = a.ldv = 3 * H; a.ldo = H;
-      a.sq = a.sk = a.sv = (long long)T * 3 * H; a.so = (long long)T * H; a.B = B; a.H = heads; a.D = D; a.Nq = T; a.Nk = T;
-      a.scale = 1.0f / sqrtf((float)D); a.causal = 1;
-      API_CK(c, run_attention(c, st, PC_OTHER, a)); }
-    { GemmOpt o; o.bias = bo; o.residual = x; API_CK(c, run_conv(c, st, att, H, nullptr, 0, 1, 1, M, *wo, 1, x, o, c->zero_page)); }
-    API_CK(c, launch_layernorm(x, h, g2, b2, M, H, g.text_eps, st));
-    { GemmOpt o; o.bias = bf1; o.act = g.text_act == 0 ? 2 : 3; API_CK(c, run_conv(c, st, h, H, nullptr, 0, 1, 1, M, *w1, 1, ff, o, c->zero_page)); }
-    { GemmOpt o; o.bias = bf2; o.residual = x; API_CK(c, run_conv(c, st, ff, g.text_intermediate, nullptr, 0, 1, 1, M, *w2, 1, x, o, c->zero_page)); }
-  }
+  const ClipEnc enc{tx + "encoder.layers.", g.text_layers, H, g.text_heads, g.text_intermediate, g.text_act, g.text_eps, 1, -1};
+  API_CK(c, clip_encoder_layers(c, st, enc, B, T, x, h, qkv, att, ff));
   { const float* gf = getV(c, tx + "final_layer_norm.weight"); const float* bfn = getV(c, tx + "final_layer_norm.bias");
     if (!gf || !bfn) return fail_ctx(c);
     API_CK(c, launch_layernorm(x, h, gf, bfn, M, H, g.text_eps, st));
     API_CK(c, launch_bf16_to_f32(h, out, (long long)M * H, st)); }
+  return 0;
+}
+
+
+// ---------------------------------------------------------------------------------------
+// Safety checker (`pipeline.safety_checker`, data_generation.py:59-62): StableDiffusionSafetyChecker's CLIP vision tower + cosines
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_safety_configure(agd_ctx* c, const agd_vision_config* v) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (!v || v->struct_size != (int)sizeof(agd_vision_config)) {
+    agd_set_error("agd_safety_configure: bad config (struct_size %d != %zu)", v ? v->struct_size : -1, sizeof(agd_vision_config)); return fail_ctx(c); }
+  if (c->finalized) { agd_set_error("agd_safety_configure: call it before agd_finalize"); return fail_ctx(c); }
+  if (v->hidden < 64 || v->hidden > 2048 || v->hidden % 64 || v->heads < 1 || v->hidden % v->heads || v->hidden / v->heads != 64)
+    { agd_set_error("agd_safety_configure: hidden %d / heads %d unsupported (hidden a multiple of 64 up to 2048, head dim 64)", v->hidden, v->heads); return fail_ctx(c); }
+  if (v->layers < 1 || v->intermediate < 64 || v->intermediate % 64 || v->act < 0 || v->act > 1)
+    { agd_set_error("agd_safety_configure: layers %d / intermediate %d / act %d unsupported", v->layers, v->intermediate, v->act); return fail_ctx(c); }
+  if (v->patch_size < 1 || v->image_size < v->patch_size || v->image_size % v->patch_size || v->image_size > 4096)
+    { agd_set_error("agd_safety_configure: image_size %d / patch_size %d unsupported", v->image_size, v->patch_size); return fail_ctx(c); }
+  if (v->projection_dim < 1 || v->hidden + v->projection_dim + 4 > 16384 || v->n_special < 0 || v->n_concepts < 0 || v->n_special + v->n_concepts < 1)
+    { agd_set_error("agd_safety_configure: projection_dim %d / %d special / %d concepts unsupported", v->projection_dim, v->n_special, v->n_concepts); return fail_ctx(c); }
+  for (int i = 0; i < 3; ++i) if (!(v->std[i] > 0.f)) { agd_set_error("agd_safety_configure: image_std[%d] = %g", i, v->std[i]); return fail_ctx(c); }
+  c->vis = *v; c->vis_on = true;
+  return 0;
+}
+
+AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, int side, float* cos_out, float* pixels_out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->vis_on) { agd_set_error("safety checker not configured (agd_safety_configure before agd_finalize)"); return fail_ctx(c); }
+  const agd_vision_config& v = c->vis;
+  if (B < 1 || side < 1 || !images || !cos_out) { agd_set_error("safety_scores: batch %d side %d / null buffer", B, side); return fail_ctx(c); }
+  const int R = v.image_size, ps = v.patch_size, g = R / ps, np = g * g, T = np + 1, H = v.hidden, M = B * T;
+  const int n = v.n_special + v.n_concepts;
+  const std::string E = std::string(kVisPre) + "embeddings.";
+  const WMat* pw = getW(c, "safety.patch_matrix");
+  const float* cls = getV(c, E + "class_embedding"); const float* pos = getV(c, E + "position_embedding.weight");
+  const float* g0 = getV(c, std::string(kVisPre) + "pre_layrnorm.weight"); const float* b0 = getV(c, std::string(kVisPre) + "pre_layrnorm.bias");
+  const float* gp = getV(c, std::string(kVisPre) + "post_layernorm.weight"); const float* bp = getV(c, std::string(kVisPre) + "post_layernorm.bias");
+  const float* wp = getV(c, "safety.visual_projection.weight");
+  if (!pw || !cls || !pos || !g0 || !b0 || !gp || !bp || !wp) return fail_ctx(c);
+  // scratch from the activation arena only (like agd_text_encode): the recorder accumulators, the cached context and the scheduler's
+  // buffers are context-owned allocations this call never touches
+  c->arena.release(0);
+  unsigned char* tmp = nullptr; unsigned char* img = nullptr;
+  if (side != R) {
+    tmp = (unsigned char*)c->arena.alloc((size_t)B * side * R * 3); img = (unsigned char*)c->arena.alloc((size_t)B * R * R * 3);
+    if (!tmp || !img) return fail_ctx(c);
+  }
+  bf16_t* rows = (bf16_t*)c->arena.alloc((size_t)B * np * pw->Cpad * 2); float* pe = (float*)c->arena.alloc((size_t)B * np * H * 4);
+  bf16_t* x = (bf16_t*)c->arena.alloc((size_t)M * H * 2); bf16_t* h = (bf16_t*)c->arena.alloc((size_t)M * H * 2);
+  bf16_t* qkv = (bf16_t*)c->arena.alloc((size_t)M * 3 * H * 2); bf16_t* att = (bf16_t*)c->arena.alloc((size_t)M * H * 2);
+  bf16_t* ff = (bf16_t*)c->arena.alloc((size_t)M * v.intermediate * 2);
+  if (!rows || !pe || !x || !h || !qkv || !att || !ff) return fail_ctx(c);
+  // CLIPImageProcessor: PIL BICUBIC resize of the (square) image to image_size, horizontal pass then vertical (Pillow's order);
+  // the coefficient tables are built and uploaded once per (side, image_size) and cached; the center crop is the identity here
+  if (side != R) {
+    const PilCoeffs* cf = pil_coeffs(side, R); if (!cf) FAIL("safety: resize coefficient upload failed");
+    { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * side * (side + R) * 3);
+      API_CK(c, launch_pil_resample(images, tmp, cf->bounds, cf->kk, cf->ksize, (long long)B * side, side, R, 3, st)); }
+    { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * R * (side + R) * 3);
+      API_CK(c, launch_pil_resample(tmp, img, cf->bounds, cf->kk, cf->ksize, B, side, R, R * 3, st)); }
+  }
+  const VisNorm nm{v.mean[0], v.mean[1], v.mean[2], v.std[0], v.std[1], v.std[2]};
+  { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * R * R * 3 + 2.0 * B * np * pw->Cpad);
+    API_CK(c, launch_vis_patchify(side != R ? img : images, B, R, ps, pw->Cpad, nm, rows, pixels_out, st)); }
+  { GemmOpt o; o.out_f32 = 1; o.prof_cls = PC_OTHER; API_CK(c, run_conv(c, st, rows, pw->Cpad, nullptr, 0, 1, 1, B * np, *pw, 1, pe, o, c->zero_page)); }
+  { ProfScope ps_(c, st, PC_OTHER, 0, 4.0 * B * np * H + 2.0 * M * H);
+    API_CK(c, launch_vis_embed_ln(pe, cls, pos, g0, b0, B, np, H, v.eps, x, st)); }
+  const ClipEnc enc{std::string(kVisPre) + "encoder.layers.", v.layers, H, v.heads, v.intermediate, v.act, v.eps, 0, PC_OTHER};
+  API_CK(c, clip_encoder_layers(c, st, enc, B, T, x, h, qkv, att, ff));
+  { ProfScope ps_(c, st, PC_OTHER, 2.0 * B * (double)v.projection_dim * (H + n), 4.0 * (double)v.projection_dim * (H + n));
+    API_CK(c, launch_vis_pooled_head(x, B, T, H, gp, bp, v.eps, wp, v.projection_dim, c->vis_concepts, n, cos_out, st)); }
   return 0;
 }
 

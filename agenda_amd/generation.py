@@ -249,6 +249,8 @@ def parse_args(argv=None):
                         "DDIMScheduler for synthetic weights.  DPMSolverMultistepScheduler: DPM-Solver++ 2M, one UNet evaluation per step")
     p.add_argument("--use-karras-sigmas", action="store_true",
                    help="DPMSolverMultistepScheduler only: Karras (rho = 7) noise levels instead of the checkpoint's timestep spacing")
+    p.add_argument("--no-safety-checker", action="store_true",
+                   help="load the checkpoint without its safety checker (by default flagged images come back black and are skipped)")
     p.add_argument("--no-gather", action="store_true",
                    help="multi-GPU: every rank writes its own files instead of the final all_gather to rank 0")
     args = p.parse_args(argv)
@@ -271,7 +273,8 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(os.environ.get("AGD_DIST_BACKEND", "nccl"))          # "nccl" = RCCL on ROCm
         own_group = True
-    pipe = (StableDiffusionPipeline.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler)
+    kw = {"safety_checker": None} if args.no_safety_checker else {}
+    pipe = (StableDiffusionPipeline.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
             StableDiffusionPipeline.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler"))
     if args.use_karras_sigmas:

@@ -10,7 +10,8 @@ Differences that are deliberate:
  * DDIM (eta 0) instead of the checkpoint's default scheduler (BASELINE.json's metric);
  * initial latents come from a CPU `torch.Generator` (or are passed explicitly) so the CPU oracle
    and the GPU run share them; a CUDA generator cannot be reproduced on the host;
- * no safety checker (no weights offline): nothing is ever blacked out.
+ * the safety checker runs when the checkpoint has one (`safety_checker/` + `feature_extractor/`, agenda_amd/safety.py);
+   synthetic pipelines and checkpoints without it black nothing out.
 """
 from __future__ import annotations
 
@@ -28,6 +29,9 @@ from .config import SDConfig, CONFIGS, UNetConfig, VAEConfig, SchedulerConfig, c
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, SCHEDULERS, scheduler_config_from_json,
                         scheduler_config_to_json)
 from .text import SimpleTokenizer, SyntheticTextEncoder
+
+
+_KEEP = object()        # from_pretrained(safety_checker=...) not given: load the checkpoint's own checker
 
 
 @dataclass
@@ -152,6 +156,25 @@ class Engine:
         self._ck(self.lib.agd_text_encode(self.ctx, C.c_void_p(ids.data_ptr()), b, t, _lib.ptr(out), self._stream()), "agd_text_encode")
         torch.cuda.synchronize()          # `ids` may be a host tensor: keep it alive until the copy ran
         return out
+
+    def safety_configure(self, scfg):
+        from .safety import vision_config
+        self._vcfg = vision_config(scfg)
+        self._ck(self.lib.agd_safety_configure(self.ctx, C.byref(self._vcfg)), "agd_safety_configure")
+
+    def safety_scores(self, images_u8: torch.Tensor, want_pixels: bool = False):
+        """`agd_safety_scores`: uint8 [B,S,S,3] -> cosines fp32 [B, n_special + n_concepts] (cuda), and the processor's
+        pixel_values [B,3,R,R] when asked."""
+        s = self.cfg.safety
+        img = images_u8.to(device=f"cuda:{self.device}", dtype=torch.uint8).contiguous()
+        if img.ndim != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2]:
+            raise ValueError(f"safety checker takes square uint8 [B,S,S,3] images, got {tuple(img.shape)}")
+        b, side = img.shape[0], img.shape[1]
+        cos = torch.empty(b, s.n_special + s.n_concepts, device=img.device, dtype=torch.float32)
+        pix = torch.empty(b, 3, s.image_size, s.image_size, device=img.device, dtype=torch.float32) if want_pixels else None
+        self._ck(self.lib.agd_safety_scores(self.ctx, _lib.ptr(img), b, side, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
+                 "agd_safety_scores")
+        return (cos, pix) if want_pixels else cos
 
     def text_set_embedding_row(self, token_id: int, row: torch.Tensor):
         row = row.detach().to(torch.float32).contiguous()
@@ -448,7 +471,8 @@ class VAEHandle:
 class StableDiffusionPipeline:
     def __init__(self, cfg: SDConfig, unet_sd: Dict[str, torch.Tensor], vae_sd: Dict[str, torch.Tensor],
                  tokenizer=None, text_encoder=None, device: Union[int, str] = 0, workspace_bytes: int = 0,
-                 text_sd: Optional[Dict[str, torch.Tensor]] = None, scheduler: str = "DDIMScheduler"):
+                 text_sd: Optional[Dict[str, torch.Tensor]] = None, scheduler: str = "DDIMScheduler",
+                 safety_sd: Optional[Dict[str, torch.Tensor]] = None):
         self.cfg = cfg
         dev = int(str(device).split(":")[-1]) if not isinstance(device, int) and ":" in str(device) else (device if isinstance(device, int) else 0)
         self.engine = Engine(cfg, dev, workspace_bytes)
@@ -459,6 +483,11 @@ class StableDiffusionPipeline:
                 raise ValueError("text_sd given but cfg.text is None")
             self.engine.load_state_dict({k[len("text_model."):] if k.startswith("text_model.") else k: v
                                          for k, v in text_sd.items() if "position_ids" not in k}, "text.")
+        if (safety_sd is None) != (getattr(cfg, "safety", None) is None):
+            raise ValueError("the safety checker needs both cfg.safety and safety_sd")
+        if safety_sd is not None:
+            self.engine.safety_configure(cfg.safety)
+            self.engine.load_state_dict({k: v for k, v in safety_sd.items() if "position_ids" not in k}, "safety.")
         self.engine.finalize()
         self.device = torch.device(f"cuda:{dev}")
         self.tokenizer = tokenizer or SimpleTokenizer(cfg.max_tokens)
@@ -481,6 +510,10 @@ class StableDiffusionPipeline:
         # images uint8 [B,H,W,3] (cuda tensor) -> sequence of B bools; flagged images are returned black, which the generation
         # driver then skips exactly as data_generation.py:61-62 does
         self.safety_checker = None
+        if safety_sd is not None:
+            from .safety import HipSafetyChecker
+            self.safety_checker = HipSafetyChecker(self.engine, cfg.safety, safety_sd["special_care_embeds_weights"],
+                                                   safety_sd["concept_embeds_weights"])
 
     # ---- construction -------------------------------------------------------------------
     @classmethod
@@ -496,9 +529,11 @@ class StableDiffusionPipeline:
         return pipe
 
     @classmethod
-    def from_pretrained(cls, path: str, device=0, workspace_bytes: int = 0, scheduler: Optional[str] = None):
+    def from_pretrained(cls, path: str, device=0, workspace_bytes: int = 0, scheduler: Optional[str] = None, safety_checker=_KEEP):
         """Reads the diffusers on-disk layout (`unet/config.json`, `unet/diffusion_pytorch_model.safetensors`,
-        `vae/...`) that `save_pretrained` writes (reference finetune_sd_token.py:164-187)."""
+        `vae/...`) that `save_pretrained` writes (reference finetune_sd_token.py:164-187).  The safety checker is loaded when
+        `model_index.json` names one (`safety_checker/` + `feature_extractor/` must then exist); `safety_checker=None` turns it off
+        and any other object is installed in the slot as given, as with diffusers."""
         from safetensors.torch import load_file
 
         def jload(p):
@@ -572,7 +607,26 @@ class StableDiffusionPipeline:
         elif tsd is not None:
             raise _lib.AgendaHipError(f"{path}: text_encoder/ weights found but no tokenizer/ directory; "
                                       "no silent fallback to the synthetic tokenizer")
-        pipe = cls(cfg, usd, vsd, tokenizer=tok, device=device, workspace_bytes=workspace_bytes, text_sd=tsd, scheduler=sched_name)
+        # the safety checker, when model_index.json names one (diffusers: a non-null entry is loaded or the load fails)
+        ssd = None
+        mi = os.path.join(path, "model_index.json")
+        entry = jload(mi).get("safety_checker") if os.path.exists(mi) else None
+        named = isinstance(entry, (list, tuple)) and len(entry) == 2 and entry[0] is not None and entry[1] is not None
+        if named and safety_checker is _KEEP:
+            from .config import safety_config_from_json
+            scj = os.path.join(path, "safety_checker", "config.json")
+            fej = os.path.join(path, "feature_extractor", "preprocessor_config.json")
+            missing = [p for p in (scj, fej) if not os.path.exists(p)]
+            if missing:
+                raise _lib.AgendaHipError(f"{mi} names a safety checker but {', '.join(missing)} is missing; "
+                                          "pass from_pretrained(..., safety_checker=None) to load without it")
+            ssd = wload("safety_checker")
+            cfg.safety = safety_config_from_json(jload(scj), jload(fej), n_special=int(ssd["special_care_embeds"].shape[0]),
+                                                 n_concepts=int(ssd["concept_embeds"].shape[0]))
+        pipe = cls(cfg, usd, vsd, tokenizer=tok, device=device, workspace_bytes=workspace_bytes, text_sd=tsd, scheduler=sched_name,
+                   safety_sd=ssd)
+        if safety_checker is not _KEEP and safety_checker is not None:
+            pipe.safety_checker = safety_checker
         pipe._source_path = src_path
         return pipe
 
@@ -589,7 +643,9 @@ class StableDiffusionPipeline:
         src, dst = self._source_path, save_directory
         os.makedirs(dst, exist_ok=True)
         same = os.path.realpath(src) == os.path.realpath(dst)          # saving over the source: nothing to copy, only the rewritten files
-        for sub in ("unet", "vae", "scheduler"):
+        from .safety import HipSafetyChecker
+        keep_checker = isinstance(self.safety_checker, HipSafetyChecker) and os.path.isdir(os.path.join(src, "safety_checker"))
+        for sub in ("unet", "vae", "scheduler") + (("safety_checker", "feature_extractor") if keep_checker else ()):
             if not same and os.path.isdir(os.path.join(src, sub)):
                 shutil.copytree(os.path.join(src, sub), os.path.join(dst, sub), dirs_exist_ok=True)
         sched_cls = type(self.scheduler).__name__
@@ -614,6 +670,8 @@ class StableDiffusionPipeline:
             mj = {"_class_name": "StableDiffusionPipeline", "unet": ["diffusers", "UNet2DConditionModel"], "vae": ["diffusers", "AutoencoderKL"],
                   "text_encoder": ["transformers", "CLIPTextModel"], "tokenizer": ["transformers", "CLIPTokenizer"], "safety_checker": [None, None]}
         mj["scheduler"] = ["diffusers", sched_cls]
+        if not keep_checker and isinstance(mj.get("safety_checker"), (list, tuple)) and None not in mj["safety_checker"]:
+            mj["safety_checker"] = [None, None]          # loaded with safety_checker=None: the copy has no checker either (diffusers)
         with open(os.path.join(dst, "model_index.json"), "w") as f:
             json.dump(mj, f, indent=2)
         te = os.path.join(src, "text_encoder")

@@ -12,7 +12,7 @@ from typing import Dict
 
 import torch
 
-from .config import SDConfig, unet_param_shapes, vae_decoder_param_shapes, vae_encoder_param_shapes, text_param_shapes
+from .config import SDConfig, unet_param_shapes, vae_decoder_param_shapes, vae_encoder_param_shapes, text_param_shapes, safety_param_shapes
 
 
 def _bf16_round(t: torch.Tensor) -> torch.Tensor:
@@ -88,6 +88,32 @@ def make_text_weights(cfg: SDConfig, seed: int = 99, device: str = "cpu") -> Dic
             w = torch.randn(shp, generator=g, device=device) * 0.02
         elif k.endswith(".weight") and len(shp) == 2:
             w = torch.randn(shp, generator=g, device=device) / math.sqrt(shp[1])
+        elif k.endswith(".weight"):
+            w = 1.0 + 0.1 * torch.randn(shp, generator=g, device=device)
+        else:
+            w = 0.05 * torch.randn(shp, generator=g, device=device)
+        sd[k] = _bf16_round(w)
+    return sd
+
+
+def make_safety_weights(cfg: SDConfig, seed: int = 77, device: str = "cpu") -> Dict[str, torch.Tensor]:
+    """Random safety-checker weights (diffusers StableDiffusionSafetyChecker key names) for `cfg.safety`: linears and the patch
+    conv ~ N(0, 1/fan_in), class / position embeddings ~ N(0, 0.02), LayerNorm gamma ~ 1, small biases, concept embeddings
+    ~ N(0, 1) and thresholds ~ U(0.1, 0.3); bf16-representable."""
+    g = torch.Generator(device).manual_seed(seed)
+    sd = {}
+    for k, shp in safety_param_shapes(cfg.safety).items():
+        if k.endswith("_weights"):
+            w = 0.1 + 0.2 * torch.rand(shp, generator=g, device=device)
+        elif k in ("concept_embeds", "special_care_embeds"):
+            w = torch.randn(shp, generator=g, device=device)
+        elif "embedding" in k and "patch" not in k:
+            w = torch.randn(shp, generator=g, device=device) * 0.02
+        elif k.endswith(".weight") and len(shp) >= 2:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            w = torch.randn(shp, generator=g, device=device) / math.sqrt(fan_in)
         elif k.endswith(".weight"):
             w = 1.0 + 0.1 * torch.randn(shp, generator=g, device=device)
         else:

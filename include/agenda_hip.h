@@ -68,6 +68,25 @@ int agd_set_context(agd_ctx* ctx, const float* ctx_emb, int batch2, int tokens, 
 int agd_text_encode(agd_ctx* ctx, const int* input_ids, int batch, int tokens, float* out, void* stream);
 int agd_text_set_embedding_row(agd_ctx* ctx, int token_id, const float* row);
 
+/* ---- the safety checker (`pipeline.safety_checker`, a StableDiffusionSafetyChecker: the CLIP ViT vision tower + visual_projection +
+ * cosine_distance against its concept embeddings; data_generation.py:59-62 skips the images it flags).  Configured by
+ * agd_safety_configure BEFORE agd_finalize; weights through agd_load_tensor as "safety." + diffusers state-dict key
+ * ("safety.vision_model.vision_model.…", "safety.visual_projection.weight", "safety.concept_embeds", "safety.special_care_embeds").
+ * agd_finalize fuses q/k/v per layer, zero-pads the patch matrix and L2-normalises the concept rows. */
+typedef struct agd_vision_config {
+  int struct_size;                 /* sizeof(agd_vision_config), ABI guard */
+  int hidden, layers, heads, intermediate, image_size, patch_size, projection_dim;
+  int n_special, n_concepts;       /* rows of special_care_embeds / concept_embeds */
+  int act;                         /* 0 quick_gelu, 1 gelu */
+  float eps;
+  float mean[3], std[3];           /* CLIPImageProcessor image_mean / image_std (rescale 1/255 before them) */
+} agd_vision_config;
+int agd_safety_configure(agd_ctx* ctx, const agd_vision_config* vcfg);
+/* images: uint8 [B,S,S,3] DEVICE (the decoded images) -> PIL-bicubic resize to image_size, rescale, normalize, the tower:
+ * cos_out fp32 [B, n_special + n_concepts] (device; special-care cosines first); pixels_out (may be NULL) fp32 [B,3,image_size,image_size]
+ * = the processor's pixel_values.  Stream-ordered; leaves the recorder accumulators, the context and the scheduler state untouched. */
+int agd_safety_scores(agd_ctx* ctx, const unsigned char* images, int batch, int side, float* cos_out, float* pixels_out, void* stream);
+
 /* ---- `unet(sample, t, encoder_hidden_states).sample`: sample/out fp32 NCHW [B2,4,L,L] */
 int agd_unet_forward(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float* out,
                      void* stream);
