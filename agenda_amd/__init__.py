@@ -7,6 +7,8 @@ from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine  # noqa: F
 from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indices  # noqa: F401
 from .hook import UNetCrossAttentionHooker  # noqa: F401
 from .scheduler import DDIMScheduler  # noqa: F401
+from .controlnet import ControlNetModel, StableDiffusionControlNetPipeline  # noqa: F401
 
 __all__ = ["StableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
-           "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic"]
+           "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic",
+           "ControlNetModel", "StableDiffusionControlNetPipeline"]

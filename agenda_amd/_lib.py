@@ -48,6 +48,18 @@ class AgdVisionConfig(C.Structure):
     ]
 
 
+AGD_CN_MAX_EMB = 8
+
+
+class AgdControlNetConfig(C.Structure):
+    """`agd_controlnet_config`: the ControlNet's conditioning embedding (agd_controlnet_configure)."""
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("n_emb", C.c_int), ("emb_channels", C.c_int * AGD_CN_MAX_EMB),
+        ("bgr", C.c_int),
+    ]
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -64,6 +76,10 @@ _SIGS = {
     "agd_text_set_embedding_row": (C.c_int, [_P, C.c_int, _P]),
     "agd_safety_configure": (C.c_int, [_P, C.POINTER(AgdVisionConfig)]),
     "agd_safety_scores": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "agd_controlnet_configure": (C.c_int, [_P, C.POINTER(AgdControlNetConfig)]),
+    "agd_controlnet_set_cond": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "agd_controlnet_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "agd_controlnet_residuals": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, C.POINTER(C.c_longlong), _P]),
     "agd_unet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_unet_forward_ts": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
     "agd_cfg_ddim_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P]),

@@ -444,3 +444,117 @@ def cross_attn_layer_names(cfg: UNetConfig, include_mid: bool = True) -> List[st
     if include_mid:
         names.append("mid_block.attentions.0.transformer_blocks.0.attn2")
     return names
+
+
+# ==========================================================================================
+# ControlNet (diffusers ControlNetModel) [upstream-knowledge: diffusers 0.21.2]
+# ==========================================================================================
+@dataclass
+class ControlNetConfig:
+    """The parts of a diffusers ControlNet `config.json` the device path implements: the conditioning embedding's channel steps and
+    the channel order of the control image.  Everything else must equal the UNet's (`controlnet_config_from_json` checks it)."""
+    conditioning_embedding_out_channels: Tuple[int, ...] = (16, 32, 96, 256)
+    conditioning_channel_order: str = "rgb"
+
+    def to_json(self, unet: UNetConfig) -> dict:
+        """A diffusers-shaped `config.json` for this ControlNet next to `unet`."""
+        boc = unet.block_out_channels
+        return {"_class_name": "ControlNetModel", "in_channels": unet.in_channels, "conditioning_channels": 3,
+                "block_out_channels": list(boc),
+                "down_block_types": ["CrossAttnDownBlock2D" if x else "DownBlock2D" for x in unet.down_cross],
+                "layers_per_block": unet.layers_per_block, "attention_head_dim": list(unet.num_heads),
+                "cross_attention_dim": unet.cross_attention_dim, "use_linear_projection": unet.use_linear_projection,
+                "norm_num_groups": unet.norm_num_groups, "only_cross_attention": False, "upcast_attention": False,
+                "class_embed_type": None, "addition_embed_type": None, "global_pool_conditions": False,
+                "controlnet_conditioning_channel_order": self.conditioning_channel_order,
+                "conditioning_embedding_out_channels": list(self.conditioning_embedding_out_channels)}
+
+
+def controlnet_config_from_json(cj: dict, unet: UNetConfig) -> ControlNetConfig:
+    """`ControlNetModel.from_pretrained(dir).config` -> ControlNetConfig.  Raises ValueError for what the device path does not implement:
+    global pooling, class / addition embeddings, conditioning_channels != 3, and a block, head or cross-attention layout unlike the UNet's."""
+    if cj.get("global_pool_conditions", False):
+        raise ValueError("ControlNet global_pool_conditions=True (the shuffle ControlNets) is not implemented")
+    for k in ("class_embed_type", "addition_embed_type", "encoder_hid_dim", "encoder_hid_dim_type", "projection_class_embeddings_input_dim"):
+        if cj.get(k) is not None:
+            raise ValueError(f"ControlNet {k}={cj.get(k)!r} is not implemented")
+    if cj.get("num_class_embeds") is not None:
+        raise ValueError(f"ControlNet num_class_embeds={cj.get('num_class_embeds')!r} is not implemented")
+    tlpb = cj.get("transformer_layers_per_block", 1)
+    if any(int(v) != 1 for v in (tlpb if isinstance(tlpb, (list, tuple)) else [tlpb])):
+        raise ValueError(f"ControlNet transformer_layers_per_block={tlpb!r} is not implemented (one transformer block per attention)")
+    if int(cj.get("conditioning_channels", 3)) != 3:
+        raise ValueError(f"ControlNet conditioning_channels={cj.get('conditioning_channels')} is not implemented (3: an RGB control image)")
+    order = cj.get("controlnet_conditioning_channel_order", "rgb")
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"ControlNet controlnet_conditioning_channel_order={order!r}")
+    for k in ("only_cross_attention", "upcast_attention", "resnet_time_scale_shift", "act_fn", "flip_sin_to_cos", "freq_shift",
+              "norm_eps", "downsample_padding", "mid_block_scale_factor"):
+        want = {"only_cross_attention": False, "upcast_attention": False, "resnet_time_scale_shift": "default", "act_fn": "silu",
+                "flip_sin_to_cos": True, "freq_shift": 0, "norm_eps": 1e-5, "downsample_padding": 1, "mid_block_scale_factor": 1}[k]
+        v = cj.get(k, want)
+        if isinstance(v, (list, tuple)):
+            v = list(v)
+            if any(x != want for x in v):
+                raise ValueError(f"ControlNet {k}={cj.get(k)!r} is not implemented")
+        elif v != want:
+            raise ValueError(f"ControlNet {k}={v!r} is not implemented")
+    ahd = cj.get("num_attention_heads") or cj.get("attention_head_dim", 8)
+    heads = tuple(ahd) if isinstance(ahd, (list, tuple)) else (ahd,) * len(cj.get("block_out_channels", ()))
+    got = {"in_channels": cj.get("in_channels", 4), "block_out_channels": tuple(cj.get("block_out_channels", ())),
+           "down_cross": tuple("CrossAttn" in t for t in cj.get("down_block_types", ())),
+           "layers_per_block": cj.get("layers_per_block", 2), "num_heads": heads,
+           "cross_attention_dim": cj.get("cross_attention_dim", 1280), "use_linear_projection": cj.get("use_linear_projection", False),
+           "norm_num_groups": cj.get("norm_num_groups", 32)}
+    for k, v in got.items():
+        if v != getattr(unet, k):
+            raise ValueError(f"ControlNet {k}={v!r} differs from the UNet's {getattr(unet, k)!r}; only ControlNets shaped like their UNet are implemented")
+    emb = tuple(cj.get("conditioning_embedding_out_channels", (16, 32, 96, 256)))
+    if not 2 <= len(emb) <= 8 or any(int(c) < 1 for c in emb):
+        raise ValueError(f"ControlNet conditioning_embedding_out_channels={emb!r} is not implemented (2 .. 8 positive entries)")
+    return ControlNetConfig(conditioning_embedding_out_channels=tuple(int(c) for c in emb), conditioning_channel_order=order)
+
+
+def controlnet_res_channels(unet: UNetConfig) -> List[int]:
+    """Channel counts of the ControlNet's down-block res samples, in order (SD-1.x: 12): conv_in, each resnet / transformer output,
+    each downsampler."""
+    boc = unet.block_out_channels
+    ch = [boc[0]]
+    for i, co in enumerate(boc):
+        ch += [co] * unet.layers_per_block
+        if i != len(boc) - 1:
+            ch.append(co)
+    return ch
+
+
+def controlnet_param_shapes(unet: UNetConfig, cn: ControlNetConfig) -> Dict[str, tuple]:
+    """diffusers ControlNetModel state-dict keys and shapes: the UNet's conv_in, time embedding, down blocks and mid block, the
+    conditioning embedding (conv_in, blocks.0 .. blocks.{2 (n - 1) - 1}, conv_out: 2 n 3x3 convs) and the 1x1 zero convs."""
+    full = unet_param_shapes(unet)
+    p = {k: v for k, v in full.items() if k.startswith(("conv_in.", "time_embedding.", "down_blocks.", "mid_block."))}
+    emb = cn.conditioning_embedding_out_channels
+    e = "controlnet_cond_embedding."
+    p[e + "conv_in.weight"] = (emb[0], 3, 3, 3)
+    p[e + "conv_in.bias"] = (emb[0],)
+    for i in range(len(emb) - 1):
+        p[e + f"blocks.{2 * i}.weight"] = (emb[i], emb[i], 3, 3)
+        p[e + f"blocks.{2 * i}.bias"] = (emb[i],)
+        p[e + f"blocks.{2 * i + 1}.weight"] = (emb[i + 1], emb[i], 3, 3)
+        p[e + f"blocks.{2 * i + 1}.bias"] = (emb[i + 1],)
+    p[e + "conv_out.weight"] = (unet.block_out_channels[0], emb[-1], 3, 3)
+    p[e + "conv_out.bias"] = (unet.block_out_channels[0],)
+    for k, c in enumerate(controlnet_res_channels(unet)):
+        p[f"controlnet_down_blocks.{k}.weight"] = (c, c, 1, 1)
+        p[f"controlnet_down_blocks.{k}.bias"] = (c,)
+    mid = unet.block_out_channels[-1]
+    p["controlnet_mid_block.weight"] = (mid, mid, 1, 1)
+    p["controlnet_mid_block.bias"] = (mid,)
+    return p
+
+
+def controlnet_keep_schedule(n: int, start: float = 0.0, end: float = 1.0) -> List[float]:
+    """StableDiffusionControlNetPipeline's `controlnet_keep` [upstream-knowledge]: evaluation i of n keeps the ControlNet unless
+    i / n < control_guidance_start or (i + 1) / n > control_guidance_end."""
+    if not 0.0 <= start < end <= 1.0:
+        raise ValueError(f"control guidance window [{start}, {end}] must satisfy 0 <= start < end <= 1")
+    return [1.0 - float(i / n < start or (i + 1) / n > end) for i in range(n)]

@@ -227,6 +227,9 @@ struct HeatLayer { const float* acc; int side; int heads; long long img_stride; 
 int launch_daam_global(const HeatLayer* layers, int n_layers, int total_maps, int T, int S, int img, float* out, hipStream_t st);
 int launch_hook_accum(const float* map, int B, int T, int side, int S, float* sum, hipStream_t st);
 int launch_scale(float* x, long long n, float s, hipStream_t st);
+// ControlNet (controlnet.hip): fp32 NCHW [B][3][HW] -> bf16 NHWC [B][HW][Cpad] (optionally BGR-flipped); out = s * in over n floats
+int launch_controlnet_cond_prep(const float* cond, bf16_t* out, int B, int HW, int Cpad, int bgr, hipStream_t st);
+int launch_controlnet_scale_bias(const float* in, float* out, int n, float s, hipStream_t st);
 
 // export path (bit-exact with numpy min-max/astype and PIL Image.resize BICUBIC on uint8)
 int launch_heatmap_u8(const float* hm, int n, int npix, unsigned char* out, hipStream_t st);

@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -71,6 +72,7 @@ struct DBuf {
 
 struct XLayer {
   std::string name; int C = 0, heads = 0, level = 0; bool mid = false;
+  bool cn = false;                                    // a ControlNet layer: K/V and the pre-multiplied form like the UNet's, never recorded
   WMat wkv; DBuf kvb; bf16_t* kv = nullptr; DBuf accb; float* acc = nullptr; int acc_side = 0;
   int acc_heads = 0;                                  // slices in acc per image: `heads`, or fewer = head-group sums (layers at latent resolution)
   DBuf wqTb, wkvTb, woTb; WMat wqT, wkvT, woT;        // transposed weights for the input-gradient GEMMs (built on first backward)
@@ -141,6 +143,13 @@ struct agd_ctx {
   int opt_xpre = 1;                                   // agd_set_option("attn2_premul"): attn2 of the C = 1280 blocks as two GEMMs against per-image pre-multiplied context matrices (xattn_pre.hip)
   int opt_touch = 3;                                  // agd_set_option("weight_touch"): n > 0 = stream 1x1 weight matrices of >= n MB through the caches right before their launch
   unsigned* touch_sink = nullptr;
+  // ControlNet (agd_controlnet_configure): weights "controlnet.*", its transformer layers in xl with cn = true, its own stacked time_emb_proj
+  // (offsets in tproj_off under its "controlnet." prefixes), the zero convs' biases back to back (cn_zb: as loaded, cn_zbs: times cn_zscale)
+  agd_controlnet_config cnc{}; bool cn_on = false;
+  WMat cn_tproj_all; float* cn_tproj_bias = nullptr; float* cn_tproj_out = nullptr; int cn_tproj_total = 0;
+  int cn_nres = 0; float* cn_zb = nullptr; float* cn_zbs = nullptr; int cn_zb_total = 0; std::vector<int> cn_zb_off; float cn_zscale = NAN;
+  DBuf cn_embb; int cn_emb_B2 = 0, cn_emb_L = 0, cn_emb_rep = 0;      // the conditioning embedding [B2][L][L][C0] bf16 (agd_controlnet_set_cond)
+  std::vector<float> cn_sched;                                         // agd_controlnet_set_schedule: one scale per model evaluation
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
@@ -433,6 +442,7 @@ static int run_attention(agd_ctx* c, hipStream_t st, int cls, AttnP& a) {
 static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t* q, int B2, int N, bf16_t* out, bool record,
                            const float* mask = nullptr) {
   const int C = xl.C, D = C / xl.heads, T = c->ctx_T;
+  if (xl.cn) record = false;                           // DAAM and hook.py see the UNet's layers only
   AttnP a{}; a.q = q; a.k = xl.kv; a.v = xl.kv + C; a.o = out;
   a.ldq = C; a.ldk = 2 * C; a.ldv = 2 * C; a.ldo = C;
   a.sq = (long long)N * C; a.sk = (long long)T * 2 * C; a.sv = a.sk; a.so = a.sq;
@@ -775,37 +785,33 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
 
 // time embeddings of n <= 25 timesteps (inference: one timestep serves every batch row); scratch = n * 9 * dim floats,
 // out = [n][tproj_total]: every resnet's time_emb_proj(silu(temb)) from one stacked matrix
-static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float* scratch, float* out) {
+// cn: the ControlNet's own time_embedding and stacked time_emb_proj (out = [n][cn_tproj_total])
+static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float* scratch, float* out, bool cn = false) {
   const int dim = c->cfg.block_out_channels[0], td = dim * 4;
+  const std::string pre = cn ? "controlnet." : "unet.";
   ProfScope ps(c, st, PC_ELEM, 0);
   float* e0 = scratch; float* e1 = e0 + (size_t)n * dim; float* e2 = e1 + (size_t)n * td;
   for (int i = 0; i < n; ++i) CK(launch_timestep_embed(ts[i], e0 + (size_t)i * dim, dim, st));
-  GETW(w1, "unet.time_embedding.linear_1.weight"); GETV(b1, "unet.time_embedding.linear_1.bias");
-  GETW(w2, "unet.time_embedding.linear_2.weight"); GETV(b2, "unet.time_embedding.linear_2.bias");
+  GETW(w1, pre + "time_embedding.linear_1.weight"); GETV(b1, pre + "time_embedding.linear_1.bias");
+  GETW(w2, pre + "time_embedding.linear_2.weight"); GETV(b2, pre + "time_embedding.linear_2.bias");
   CK(launch_small_linear(e0, w1->w, b1, e1, n, td, w1->Cpad, 0, 1, st));     // linear_1 + SiLU
   CK(launch_small_linear(e1, w2->w, b2, e2, n, td, w2->Cpad, 0, 0, st));     // linear_2 -> temb
-  CK(launch_small_linear(e2, c->tproj_all.w, c->tproj_bias, out, n, c->tproj_total, td, 1, 0, st));
+  if (cn) CK(launch_small_linear(e2, c->cn_tproj_all.w, c->cn_tproj_bias, out, n, c->cn_tproj_total, td, 1, 0, st));
+  else CK(launch_small_linear(e2, c->tproj_all.w, c->tproj_bias, out, n, c->tproj_total, td, 1, 0, st));
   return 0;
 }
 
-// x: [B2][L*L][64] bf16 (latent channels zero-padded) -> eps [B2][L*L][out_channels] fp32 NHWC
-// tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
-// cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
-// tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
-static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float* eps_out,
-                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0) {
+// conv_in, the down blocks and the mid block of a UNet-shaped model under the weight prefix u ("unet." or "controlnet."); on_sample(a) sees
+// every res sample in order (conv_in, each resnet / transformer output, each downsampler: the UNet's skips); h = the mid block's output.
+// conv_in_res: added in conv_in's epilogue (the ControlNet's conditioning embedding).  shared: rows [0,B2/2) and [B2/2,B2) of xin (and of
+// conv_in_res) are identical -- everything ahead of the first attn2 runs on B2/2 rows.
+static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int L, bool shared,
+                         const bf16_t* conv_in_res, const std::function<int(const Act&)>& on_sample, Act& h) {
   const agd_config& g = c->cfg;
   const int nl = g.n_levels, G = g.norm_num_groups;
-  const std::string u = "unet.";
-  c->arena.release(0);
-  c->tproj_cur_ld = tproj_row ? tproj_ld : 0;
-  if (tproj_row) c->tproj_cur = tproj_row;
-  else { CK(time_embed(c, st, &t, 1, c->temb_buf, c->tproj_out)); c->tproj_cur = c->tproj_out; }
-  std::vector<Act> skips;
-  const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share;
   const int Bh = shared ? B2 / 2 : B2;
-  Act h = alloc_act(c, B2, L, L, g.block_out_channels[0], true); if (!h.p) return -1;
-  { GETW(w, u + "conv_in.weight"); GETV(b, u + "conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h;
+  h = alloc_act(c, B2, L, L, g.block_out_channels[0], true); if (!h.p) return -1;
+  { GETW(w, u + "conv_in.weight"); GETV(b, u + "conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h; o.residual = conv_in_res;
     CK(run_conv(c, st, xin, 64, nullptr, 0, Bh, L, L, *w, 3, h.p, o, c->zero_page)); }
   if (shared) {                                                             // the skip connection needs all B2 rows (and their partial sums)
     CK(dup_half(c, st, h.p, (long long)Bh * L * L * h.C));
@@ -814,7 +820,7 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
       if (hipMemcpyAsync((char*)h.cpart + nb, h.cpart, nb, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup partials copy failed");
     }
   }
-  skips.push_back(h);
+  CK(on_sample(h));
   for (int i = 0; i < nl; ++i) {
     const int co = g.block_out_channels[i];
     for (int j = 0; j < g.layers_per_block; ++j) {
@@ -832,7 +838,7 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
         Act a; CK(transformer(c, st, u + "down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", h, g.num_heads[i], G, a, first ? 1 : 0));
         h = a;
       }
-      skips.push_back(h);
+      CK(on_sample(h));
     }
     if (i != nl - 1) {
       const std::string k = u + "down_blocks." + std::to_string(i) + ".downsamplers.0.conv.";
@@ -840,7 +846,7 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
       Act d = alloc_act(c, B2, h.H / 2, h.W / 2, co, true); if (!d.p) return -1;
       GemmOpt o; o.bias = b; o.stride = 2; o.out_act = &d;
       CK(run_conv(c, st, h.p, co, nullptr, 0, B2, h.H, h.W, *w, 3, d.p, o, c->zero_page));
-      h = d; skips.push_back(h);
+      h = d; CK(on_sample(h));
     }
   }
   { const int cm = g.block_out_channels[nl - 1];
@@ -849,6 +855,101 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
     Act r; CK(resnet(c, st, u + "mid_block.resnets.0.", h, nullptr, cm, 1e-5f, true, G, r, &ngm)); h = r;
     Act a; CK(transformer(c, st, u + "mid_block.attentions.0.", h, g.num_heads[nl - 1], G, a)); h = a;
     Act r2; CK(resnet(c, st, u + "mid_block.resnets.1.", h, nullptr, cm, 1e-5f, true, G, r2)); h = r2; }
+  return 0;
+}
+
+// The ControlNet forward (diffusers ControlNetModel.forward, SD-1.x) at timestep t: its own time embedding, conv_in(x) + the cached
+// conditioning embedding (conv_in's residual operand), the UNet's down / mid code under the "controlnet." weights, and a 1x1 zero conv
+// per res sample and on the mid output, every result times `scale` (igemm alpha on the accumulator + the bias pre-scaled by cn_zbs).
+// skips / h given (inside unet_walk, after the UNet's mid block): each zero conv runs as soon as its res sample exists, with the UNet's
+//   skip k as its residual operand, into a FRESH activation allocated ahead of the ControlNet's own arena mark, and skip k is repointed to
+//   it -- the launch leaves the GroupNorm partial sums of the injected tensor, while the old Act's partial sums and normed copy describe
+//   the un-injected one.  The mid residual goes into *h the same way.  The ControlNet keeps no skip list of its own.
+// skips == nullptr: the scaled residuals go to res_out as fp32 instead, back to back, NHWC or NCHW (agd_controlnet_residuals).
+static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float scale, bool cfg_shared,
+                           std::vector<Act>* skips, Act* h_unet, float* res_out, int nhwc) {
+  const agd_config& g = c->cfg;
+  if (!c->cn_on) FAIL("controlnet: none loaded (agd_controlnet_configure before agd_finalize)");
+  if (c->cn_emb_B2 != B2 || c->cn_emb_L != L)
+    FAIL("controlnet: the conditioning image is set for %d rows at latent side %d, this forward has %d rows at side %d (agd_controlnet_set_cond)",
+         c->cn_emb_B2, c->cn_emb_L, B2, L);
+  if (skips && ((int)skips->size() != c->cn_nres || !h_unet)) FAIL("controlnet: %zu UNet skips for %d ControlNet res samples", skips->size(), c->cn_nres);
+  std::vector<Act> inj;
+  if (skips) {
+    for (const Act& s : *skips) { inj.push_back(alloc_act(c, s.B, s.H, s.W, s.C, true)); if (!inj.back().p) return -1; }
+    inj.push_back(alloc_act(c, h_unet->B, h_unet->H, h_unet->W, h_unet->C, true)); if (!inj.back().p) return -1;
+  }
+  if (!(scale == c->cn_zscale)) {                       // (the biases are rewritten only when the scale changes; stream-ordered)
+    ProfScope ps(c, st, PC_ELEM, 0);
+    CK(launch_controlnet_scale_bias(c->cn_zb, c->cn_zbs, c->cn_zb_total, scale, st));
+    c->cn_zscale = scale;
+  }
+  const size_t mk = c->arena.mark();
+  const float* tp_save = c->tproj_cur; const int ld_save = c->tproj_cur_ld;
+  CK(time_embed(c, st, &t, 1, c->temb_buf, c->cn_tproj_out, true));
+  c->tproj_cur = c->cn_tproj_out; c->tproj_cur_ld = 0;
+  const std::string u = "controlnet.";
+  int k = 0; long long res_off = 0;
+  auto zero_conv = [&](const Act& s) -> int {
+    const std::string key = u + (k < c->cn_nres ? "controlnet_down_blocks." + std::to_string(k) + "." : std::string("controlnet_mid_block."));
+    GETW(w, key + "weight");
+    if (w->N != s.C || w->Cpad != s.C) FAIL("controlnet: '%sweight' is [%d, %d], res sample %d has %d channels", key.c_str(), w->N, w->Cin, k, s.C);
+    GemmOpt o; o.bias = c->cn_zbs + c->cn_zb_off[k]; o.alpha = scale;
+    if (skips) {
+      Act& base = k < c->cn_nres ? (*skips)[k] : *h_unet;
+      if (base.B != s.B || base.H != s.H || base.W != s.W || base.C != s.C) FAIL("controlnet: res sample %d does not match the UNet's", k);
+      Act& dst = inj[k];
+      o.residual = base.p; o.out_act = &dst;
+      CK(run_conv(c, st, s.p, s.C, nullptr, 0, s.B, s.H, s.W, *w, 1, dst.p, o, c->zero_page));
+      base = dst;                                       // (fresh partial sums, no normed copy)
+    } else {
+      float* dst = res_out + res_off;
+      o.out_f32 = 1;
+      if (nhwc) CK(run_conv(c, st, s.p, s.C, nullptr, 0, s.B, s.H, s.W, *w, 1, dst, o, c->zero_page));
+      else {
+        float* tmp = (float*)c->arena.alloc((size_t)s.n() * 4); if (!tmp) return -1;
+        CK(run_conv(c, st, s.p, s.C, nullptr, 0, s.B, s.H, s.W, *w, 1, tmp, o, c->zero_page));
+        ProfScope ps(c, st, PC_ELEM, 0);
+        CK(launch_nchw_from_nhwc_f32(tmp, s.C, dst, s.B, s.C, s.H * s.W, st));
+      }
+      res_off += s.n();
+    }
+    ++k;
+    return 0;
+  };
+  // the CFG halves see the same latents and the same conditioning rows up to the first attn2 (as in the UNet) when the embedding was set
+  // with an even repeat
+  const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share && c->cn_emb_rep % 2 == 0;
+  Act h;
+  CK(down_mid_walk(c, st, u, xin, B2, L, shared, c->cn_embb.as<bf16_t>(), zero_conv, h));
+  CK(zero_conv(h));
+  c->tproj_cur = tp_save; c->tproj_cur_ld = ld_save;
+  c->arena.release(mk);
+  return 0;
+}
+
+// x: [B2][L*L][64] bf16 (latent channels zero-padded) -> eps [B2][L*L][out_channels] fp32 NHWC
+// tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
+// cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
+// tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
+// cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
+static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float* eps_out,
+                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f) {
+  const agd_config& g = c->cfg;
+  const int nl = g.n_levels, G = g.norm_num_groups;
+  const std::string u = "unet.";
+  c->arena.release(0);
+  c->tproj_cur_ld = tproj_row ? tproj_ld : 0;
+  if (tproj_row) c->tproj_cur = tproj_row;
+  else { CK(time_embed(c, st, &t, 1, c->temb_buf, c->tproj_out)); c->tproj_cur = c->tproj_out; }
+  std::vector<Act> skips;
+  const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share;
+  Act h;
+  CK(down_mid_walk(c, st, u, xin, B2, L, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h));
+  if (cn_scale != 0.f) {
+    if (c->tproj_cur_ld != 0) FAIL("controlnet: per-image timesteps are not supported");
+    CK(controlnet_walk(c, st, xin, B2, L, t, cn_scale, cfg_shared, &skips, &h, nullptr, 0));
+  }
   for (int i = 0; i < nl; ++i) {
     const int lvl = nl - 1 - i, co = g.block_out_channels[lvl];
     for (int j = 0; j < g.layers_per_block + 1; ++j) {
@@ -1052,7 +1153,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release();
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1077,6 +1178,7 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
   }
   if (hipMemcpy(c->stage, ptr, bytes, hipMemcpyDefault) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
   const std::string k(name);
+  if (k.compare(0, 11, "controlnet.") == 0 && !c->cn_on) { agd_set_error("'%s': call agd_controlnet_configure before loading ControlNet weights", name); return fail_ctx(c); }
   // the safety checker keeps everything but its encoder-layer matrices in fp32 as loaded (embeddings, the 14 x 14 patch conv, the
   // projection, the concept rows); agd_finalize checks their sizes and builds the padded patch matrix
   const bool vis_f32 = k.compare(0, 7, "safety.") == 0 && !(ndim == 2 && k.find(".encoder.layers.") != std::string::npos);
@@ -1176,6 +1278,53 @@ static int finalize_safety(agd_ctx* c) {
   return 0;
 }
 
+// ControlNet res samples (SD-1.x: 12): conv_in, layers_per_block per level, a downsampler per level but the last; their channel counts
+static std::vector<int> controlnet_res_channels(const agd_config& g) {
+  std::vector<int> ch{g.block_out_channels[0]};
+  for (int i = 0; i < g.n_levels; ++i) {
+    for (int j = 0; j < g.layers_per_block; ++j) ch.push_back(g.block_out_channels[i]);
+    if (i != g.n_levels - 1) ch.push_back(g.block_out_channels[i]);
+  }
+  return ch;
+}
+
+static int finalize_controlnet(agd_ctx* c) {
+  const agd_config& g = c->cfg;
+  const agd_controlnet_config& e = c->cnc;
+  const std::string u = "controlnet.", E = u + "controlnet_cond_embedding.";
+  // ControlNetConditioningEmbedding: conv_in 3 -> e0, per step (c -> c, c -> c' stride 2) as blocks.0 .. blocks.{2 (n - 1) - 1}, conv_out e_last -> C0
+  auto want = [&](const std::string& k, int n, int cin) -> int {
+    const WMat* w = getW(c, k + ".weight"); if (!w) return -1;
+    if (w->N != n || w->Cin != cin || w->taps != 9) FAIL("'%s.weight' is [%d, %d, %d taps], the ControlNet config needs [%d, %d, 3x3]", k.c_str(), w->N, w->Cin, w->taps, n, cin);
+    auto b = c->Vn.find(k + ".bias"); if (b == c->Vn.end() || b->second != n) FAIL("'%s.bias' missing or not %d long", k.c_str(), n);
+    return 0;
+  };
+  CK(want(E + "conv_in", e.emb_channels[0], 3));
+  for (int i = 0; i + 1 < e.n_emb; ++i) {
+    CK(want(E + "blocks." + std::to_string(2 * i), e.emb_channels[i], e.emb_channels[i]));
+    CK(want(E + "blocks." + std::to_string(2 * i + 1), e.emb_channels[i + 1], e.emb_channels[i]));
+  }
+  CK(want(E + "conv_out", g.block_out_channels[0], e.emb_channels[e.n_emb - 1]));
+  const std::vector<int> ch = controlnet_res_channels(g);
+  c->cn_nres = (int)ch.size();
+  std::vector<std::string> keys;
+  for (int k = 0; k < c->cn_nres; ++k) keys.push_back(u + "controlnet_down_blocks." + std::to_string(k));
+  keys.push_back(u + "controlnet_mid_block");
+  std::vector<int> n_of(ch); n_of.push_back(g.block_out_channels[g.n_levels - 1]);
+  c->cn_zb_off.clear(); int total = 0;
+  for (size_t k = 0; k < keys.size(); ++k) {
+    const WMat* w = getW(c, keys[k] + ".weight"); if (!w) return -1;
+    if (w->N != n_of[k] || w->Cin != n_of[k] || w->taps != 1) FAIL("'%s.weight' is [%d, %d, %d taps], the UNet needs a 1x1 [%d, %d]", keys[k].c_str(), w->N, w->Cin, w->taps, n_of[k], n_of[k]);
+    auto b = c->Vn.find(keys[k] + ".bias"); if (b == c->Vn.end() || b->second != n_of[k]) FAIL("'%s.bias' missing or not %d long", keys[k].c_str(), n_of[k]);
+    c->cn_zb_off.push_back(total); total += n_of[k];
+  }
+  c->cn_zb = dmalloc<float>(c, total); c->cn_zbs = dmalloc<float>(c, total); if (!c->cn_zb || !c->cn_zbs) return -1;
+  for (size_t k = 0; k < keys.size(); ++k)
+    if (hipMemcpy(c->cn_zb + c->cn_zb_off[k], c->V[keys[k] + ".bias"], (size_t)n_of[k] * 4, hipMemcpyDeviceToDevice) != hipSuccess) FAIL("controlnet: bias copy failed");
+  c->cn_zb_total = total; c->cn_zscale = NAN;
+  return 0;
+}
+
 AGD_API int agd_finalize(agd_ctx* c) {
   if (!c) return -1;
   hipSetDevice(c->device);
@@ -1188,6 +1337,11 @@ AGD_API int agd_finalize(agd_ctx* c) {
   for (int i = 0; i < nl; ++i)
     if (g.down_cross[i]) for (int j = 0; j < g.layers_per_block; ++j) tf.push_back({"unet.down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", i});
   tf.push_back({"unet.mid_block.attentions.0.", nl - 1});
+  if (c->cn_on) {                                   // the ControlNet's blocks: after every recorder layer (xl order is daam's for the UNet's)
+    for (int i = 0; i < nl; ++i)
+      if (g.down_cross[i]) for (int j = 0; j < g.layers_per_block; ++j) tf.push_back({"controlnet.down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", i});
+    tf.push_back({"controlnet.mid_block.attentions.0.", nl - 1});
+  }
   for (auto& pr : tf) {
     const std::string t = pr.first + "transformer_blocks.0.";
     const WMat* q = getW(c, t + "attn1.to_q.weight"); const WMat* k = getW(c, t + "attn1.to_k.weight"); const WMat* v = getW(c, t + "attn1.to_v.weight");
@@ -1197,6 +1351,7 @@ AGD_API int agd_finalize(agd_ctx* c) {
     if (!ck || !cv) return fail_ctx(c);
     XLayer xl; xl.name = t + "attn2"; xl.C = q->N; xl.level = pr.second; xl.heads = g.num_heads[pr.second];
     xl.mid = pr.first.find("mid_block") != std::string::npos;
+    xl.cn = pr.first.compare(0, 11, "controlnet.") == 0;
     API_CK(c, concat_rows(c, {ck, cv}, xl.wkv));
     if (xl.C % xl.heads) { agd_set_error("%s: C %d not divisible by heads %d", xl.name.c_str(), xl.C, xl.heads); return fail_ctx(c); }
     // pre-multiplied attn2 (xattn_pre.hip) where it saves work: H x 80 padded token columns <= C / 2, i.e. head dim >= 160 (SD-1.x: the C = 1280 blocks)
@@ -1355,7 +1510,7 @@ AGD_API int agd_finalize(agd_ctx* c) {
   // ---- UNet resnets with a conv_shortcut: conv2's matrix once more with the shortcut's columns appended to every row, and the two biases summed
   { std::vector<std::string> pres;
     const std::string tail = "conv_shortcut.weight";
-    for (auto& kv : c->W) if (kv.first.compare(0, 5, "unet.") == 0 && kv.first.size() > tail.size() && kv.first.compare(kv.first.size() - tail.size(), tail.size(), tail) == 0)
+    for (auto& kv : c->W) if ((kv.first.compare(0, 5, "unet.") == 0 || kv.first.compare(0, 11, "controlnet.") == 0) && kv.first.size() > tail.size() && kv.first.compare(kv.first.size() - tail.size(), tail.size(), tail) == 0)
       pres.push_back(kv.first.substr(0, kv.first.size() - tail.size()));
     for (const std::string& pre : pres) {
       const WMat* w2 = getW(c, pre + "conv2.weight"); const WMat* ws = getW(c, pre + "conv_shortcut.weight");
@@ -1374,24 +1529,32 @@ AGD_API int agd_finalize(agd_ctx* c) {
       if (hipMemcpy(fb, ha.data(), f.N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { agd_set_error("finalize: bias write failed"); return fail_ctx(c); }
       c->W[pre + "conv2.sc"] = f; c->V[pre + "conv2.sc.bias"] = fb; c->Vn[pre + "conv2.sc.bias"] = f.N;
     } }
-  // ---- all time_emb_proj stacked into one [sum Cout][4*dim] matrix
-  { std::vector<const WMat*> parts; std::vector<std::string> pres; int total = 0;
-    for (auto& kv : c->W) if (ends_with(kv.first, "time_emb_proj.weight")) pres.push_back(kv.first.substr(0, kv.first.size() - strlen("time_emb_proj.weight")));
+  // ---- all time_emb_proj stacked into one [sum Cout][4*dim] matrix; the ControlNet's (its own time embedding feeds them) into a second one
+  for (const bool cn : {false, true}) {
+    if (cn && !c->cn_on) break;
+    WMat& all = cn ? c->cn_tproj_all : c->tproj_all; float*& bias = cn ? c->cn_tproj_bias : c->tproj_bias;
+    float*& out = cn ? c->cn_tproj_out : c->tproj_out; int& total_out = cn ? c->cn_tproj_total : c->tproj_total;
+    std::vector<const WMat*> parts; std::vector<std::string> pres; int total = 0;
+    for (auto& kv : c->W)
+      if (ends_with(kv.first, "time_emb_proj.weight") && (kv.first.compare(0, 11, "controlnet.") == 0) == cn) pres.push_back(kv.first.substr(0, kv.first.size() - strlen("time_emb_proj.weight")));
     std::sort(pres.begin(), pres.end());
     for (auto& p : pres) { const WMat* w = getW(c, p + "time_emb_proj.weight"); parts.push_back(w); c->tproj_off[p] = total; total += w->N; }
     if (!parts.empty()) {
-      API_CK(c, concat_rows(c, parts, c->tproj_all)); c->tproj_total = total;
-      c->tproj_bias = dmalloc<float>(c, total); c->tproj_out = dmalloc<float>(c, total);
-      if (!c->tproj_bias || !c->tproj_out) return fail_ctx(c);
+      API_CK(c, concat_rows(c, parts, all)); total_out = total;
+      bias = dmalloc<float>(c, total); out = dmalloc<float>(c, total);
+      if (!bias || !out) return fail_ctx(c);
       for (auto& p : pres) { const float* b = getV(c, p + "time_emb_proj.bias"); if (!b) return fail_ctx(c);
-        hipMemcpy(c->tproj_bias + c->tproj_off[p], b, (size_t)c->Vn[p + "time_emb_proj.bias"] * 4, hipMemcpyDeviceToDevice); }
-    }
-    const int dim = g.block_out_channels[0];
+        hipMemcpy(bias + c->tproj_off[p], b, (size_t)c->Vn[p + "time_emb_proj.bias"] * 4, hipMemcpyDeviceToDevice); }
+    } else if (cn) { agd_set_error("finalize: the ControlNet has no time_emb_proj weights"); return fail_ctx(c); }
+  }
+  { const int dim = g.block_out_channels[0];
     c->temb_buf = dmalloc<float>(c, (size_t)dim * 9); if (!c->temb_buf) return fail_ctx(c); }
   // ---- CLIP text encoder: fused q/k/v projection per layer
   API_CK(c, fuse_clip_qkv(c, "text.encoder.layers.", g.text_layers));
   // ---- safety checker: the vision tower's fused q/k/v, the zero-padded patch matrix, the normalised concept rows
   if (c->vis_on) API_CK(c, finalize_safety(c));
+  // ---- ControlNet: the conditioning embedding's shapes, the zero convs' biases back to back
+  if (c->cn_on) API_CK(c, finalize_controlnet(c));
   hipDeviceSynchronize();
   c->finalized = true;
   return 0;
@@ -1443,13 +1606,27 @@ static int ensure_lat(agd_ctx* c, int B2, int L) {
 }
 
 static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timesteps, int n, const float** out);
+// the ControlNet schedule of a call of n model evaluations on B2 rows at latent side L: nullptr = none set (the UNet alone); else its length
+// must be n, and a conditioning embedding for exactly these rows must exist when any scale is non-zero (checked before anything runs)
+static int cn_schedule_for(agd_ctx* c, int n, int B2, int L, const float** out) {
+  *out = nullptr;
+  if (c->cn_sched.empty()) return 0;
+  if ((int)c->cn_sched.size() != n) FAIL("controlnet: the schedule has %zu scales, this call runs %d model evaluations (agd_controlnet_set_schedule)", c->cn_sched.size(), n);
+  bool any = false; for (float v : c->cn_sched) any = any || v != 0.f;
+  if (any && (c->cn_emb_B2 != B2 || c->cn_emb_L != L))
+    FAIL("controlnet: no conditioning image set for %d rows at latent side %d (agd_controlnet_set_cond has %d rows at side %d)", B2, L, c->cn_emb_B2, c->cn_emb_L);
+  *out = c->cn_sched.data();
+  return 0;
+}
 AGD_API int agd_unet_forward(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float* out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, L));
   const int Cl = c->cfg.in_channels;
+  const float* cs = nullptr;
+  API_CK(c, cn_schedule_for(c, 1, batch2, L, &cs));                          // a one-element ControlNet schedule: one injected forward
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, L * L, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, L, timestep, c->eps_nhwc));
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, L, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, L * L, st)); }
   return 0;
 }
@@ -1459,6 +1636,7 @@ AGD_API int agd_unet_forward(agd_ctx* c, const float* sample, int batch2, int L,
 AGD_API int agd_unet_forward_ts(agd_ctx* c, const float* sample, int batch2, int L, const float* timesteps, float* out, void* stream) {
   API_CK(c, need_final(c));
   if (!timesteps || batch2 < 1) { agd_set_error("unet_forward_ts: bad arguments"); return fail_ctx(c); }
+  if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, L));
   const int Cl = c->cfg.in_channels;
@@ -1516,11 +1694,13 @@ AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_step
   const int B2 = 2 * batch, Cl = c->cfg.in_channels, HW = L * L;
   API_CK(c, ensure_lat(c, B2, L));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
+  const float* cs = nullptr;                                       // the ControlNet's per-step scales (none: the UNet alone)
+  API_CK(c, cn_schedule_for(c, n_steps, B2, L, &cs));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
   for (int s = 0; s < n_steps; ++s) {
     { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f));
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
   }
@@ -1548,12 +1728,14 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
   API_CK(c, c->plmsb.ensure(n1 * 5 * sizeof(float)));            // 4 history slots + the kept sample
   float* hist[4]; for (int k = 0; k < 4; ++k) hist[k] = c->plmsb.as<float>() + n1 * k;
   float* kept = c->plmsb.as<float>() + n1 * 4;
+  const float* cs = nullptr;
+  API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
   for (int i = 0; i < n_evals; ++i) {
     { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
     const float* src = latents; float* store = nullptr;
@@ -1592,11 +1774,13 @@ AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
+  const float* cs = nullptr;
+  API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   for (int i = 0; i < n_evals; ++i) {
     { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     { ProfScope ps(c, st, PC_ELEM, 0);
@@ -1689,7 +1873,7 @@ AGD_API int agd_record_reset(agd_ctx* c, int batch, int L, void* stream) {
   c->rec_T = T;
   if (c->rec_mode == 1) {
     for (auto& xl : c->xl) {
-      if (xl.mid) continue;
+      if (xl.mid || xl.cn) continue;
       const int side = L >> xl.level;
       if (side < 1 || (L / side) == 8) { xl.acc = nullptr; xl.acc_side = 0; continue; }
       // capacity-tracked: a larger batch / token count / side than the block was allocated for reallocates it
@@ -2710,5 +2894,110 @@ AGD_API int agd_vae_encode(agd_ctx* c, const float* image, int batch, int side, 
     hipMemcpyAsync(logvar_out + (size_t)b * lc * L * L, mom_nchw + ((size_t)b * 2 + 1) * lc * L * L, (size_t)lc * L * L * 4, hipMemcpyDeviceToDevice, st);
   }
   hipStreamSynchronize(st);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// ControlNet (diffusers ControlNetModel + StableDiffusionControlNetPipeline, SD-1.x): the walk is controlnet_walk inside unet_walk
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_controlnet_configure(agd_ctx* c, const agd_controlnet_config* e) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (!e || e->struct_size != (int)sizeof(agd_controlnet_config)) {
+    agd_set_error("agd_controlnet_configure: bad config (struct_size %d != %zu)", e ? e->struct_size : -1, sizeof(agd_controlnet_config)); return fail_ctx(c); }
+  if (c->finalized) { agd_set_error("agd_controlnet_configure: call it before agd_finalize"); return fail_ctx(c); }
+  if (e->n_emb < 2 || e->n_emb > AGD_CN_MAX_EMB) { agd_set_error("agd_controlnet_configure: %d embedding channel counts (2 .. %d)", e->n_emb, AGD_CN_MAX_EMB); return fail_ctx(c); }
+  for (int i = 0; i < e->n_emb; ++i)
+    if (e->emb_channels[i] < 1 || e->emb_channels[i] > 4096) { agd_set_error("agd_controlnet_configure: embedding channels[%d] = %d", i, e->emb_channels[i]); return fail_ctx(c); }
+  c->cnc = *e; c->cn_on = true;
+  return 0;
+}
+
+// the conditioning embedding, once per call: conv_in (+ SiLU), per step a 3x3 (+ SiLU) and a stride-2 3x3 (+ SiLU), conv_out -- 2 n_emb igemm
+// launches (SD-1.x: eight).  The 3-channel image is zero-padded to 64 channels like the VAE encoder's input; maps whose width is not a
+// multiple of 64 (16 / 32 / 96 by default) are written with a 64-multiple row stride into zeroed buffers, so every conv reads whole
+// 64-channel chunks.  It runs on the `batch` distinct images only; the other repeat - 1 row blocks are copies.
+AGD_API int agd_controlnet_set_cond(agd_ctx* c, const float* cond, int batch, int side, int repeat, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->cn_on) { agd_set_error("controlnet_set_cond: no ControlNet loaded"); return fail_ctx(c); }
+  const agd_controlnet_config& e = c->cnc;
+  const int sh = e.n_emb - 1, L = side >> sh, C0 = c->cfg.block_out_channels[0];
+  if (!cond || batch < 1 || repeat < 1 || L < 1 || (L << sh) != side)
+    { agd_set_error("controlnet_set_cond: batch %d / repeat %d / side %d (a multiple of %d)", batch, repeat, side, 1 << sh); return fail_ctx(c); }
+  const int B2 = batch * repeat;
+  c->cn_emb_B2 = 0; c->cn_emb_L = 0;                               // (unset until the embedding below is complete)
+  c->arena.release(0);
+  // ping-pong scratch: the largest map of the chain -- the padded input (S x S x 64) or any intermediate output (Ho x Ho x its padded width)
+  size_t big = (size_t)batch * side * side * 64;
+  { long long h = side;
+    auto out_elems = [&](int ch) -> size_t { const size_t ld = (size_t)(ch + 63) / 64 * 64; return (size_t)batch * (size_t)h * (size_t)h * ld; };
+    big = std::max(big, out_elems(e.emb_channels[0]));
+    for (int i = 0; i + 1 < e.n_emb; ++i) { big = std::max(big, out_elems(e.emb_channels[i])); h /= 2; big = std::max(big, out_elems(e.emb_channels[i + 1])); } }
+  big *= 2;
+  bf16_t* buf[2] = {(bf16_t*)c->arena.alloc(big), (bf16_t*)c->arena.alloc(big)};
+  if (!buf[0] || !buf[1]) return fail_ctx(c);
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_controlnet_cond_prep(cond, buf[0], batch, side * side, 64, e.bgr, st)); }
+  API_CK(c, c->cn_embb.ensure((size_t)B2 * L * L * C0 * 2));
+  const std::string E = "controlnet.controlnet_cond_embedding.";
+  int cur = 0, H = side, Cin = 64;
+  auto conv = [&](const std::string& k, int stride, bool last) -> int {
+    GETW(w, E + k + ".weight"); GETV(b, E + k + ".bias");
+    if (w->Cpad != Cin) FAIL("controlnet_set_cond: '%s' reads %d channels, the map has %d", k.c_str(), w->Cpad, Cin);
+    const int Ho = H / stride, ld = last ? w->N : (w->N + 63) / 64 * 64;
+    if (last ? w->N != C0 : (size_t)batch * Ho * Ho * ld * 2 > big) FAIL("controlnet_set_cond: '%s' output [%d x %d x %d] does not fit its buffer", k.c_str(), Ho, Ho, ld);
+    bf16_t* out = last ? c->cn_embb.as<bf16_t>() : buf[cur ^ 1];
+    if (!last && ld != w->N && hipMemsetAsync(out, 0, (size_t)batch * Ho * Ho * ld * 2, st) != hipSuccess) FAIL("controlnet_set_cond: memset");
+    GemmOpt o; o.bias = b; o.act = last ? 0 : 1; o.stride = stride; o.ldo = ld;
+    CK(run_conv(c, st, buf[cur], Cin, nullptr, 0, batch, H, H, *w, 3, out, o, c->zero_page));
+    cur ^= 1; H = Ho; Cin = ld;
+    return 0;
+  };
+  API_CK(c, conv("conv_in", 1, false));
+  for (int i = 0; i + 1 < e.n_emb; ++i) {
+    API_CK(c, conv("blocks." + std::to_string(2 * i), 1, false));
+    API_CK(c, conv("blocks." + std::to_string(2 * i + 1), 2, false));
+  }
+  API_CK(c, conv("conv_out", 1, true));
+  { const size_t blk = (size_t)batch * L * L * C0;                 // rows r and r + batch are the same image
+    ProfScope ps(c, st, PC_ELEM, 0);
+    for (int r = 1; r < repeat; ++r)
+      if (hipMemcpyAsync(c->cn_embb.as<bf16_t>() + r * blk, c->cn_embb.as<bf16_t>(), blk * 2, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        { agd_set_error("controlnet_set_cond: row copy failed"); return fail_ctx(c); } }
+  c->cn_emb_B2 = B2; c->cn_emb_L = L; c->cn_emb_rep = repeat;
+  return 0;
+}
+
+AGD_API int agd_controlnet_set_schedule(agd_ctx* c, const float* scales, int n) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (n < 0 || (n > 0 && !scales)) { agd_set_error("controlnet_set_schedule: %d scales", n); return fail_ctx(c); }
+  if (n > 0 && !c->cn_on) { agd_set_error("controlnet_set_schedule: no ControlNet loaded"); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i) if (!std::isfinite(scales[i])) { agd_set_error("controlnet_set_schedule: scale %d is %g", i, scales[i]); return fail_ctx(c); }
+  c->cn_sched.assign(scales, scales + n);
+  return 0;
+}
+
+
+AGD_API int agd_controlnet_residuals(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float scale, int nhwc,
+                                     float* out, long long* n_out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->cn_on) { agd_set_error("controlnet_residuals: no ControlNet loaded"); return fail_ctx(c); }
+  if (batch2 < 1 || L < 1 || (L >> (c->cfg.n_levels - 1)) < 1) { agd_set_error("controlnet_residuals: batch2 %d latent side %d", batch2, L); return fail_ctx(c); }
+  long long n = 0;
+  { int side = L, k = 0;
+    const std::vector<int> ch = controlnet_res_channels(c->cfg);
+    n += (long long)batch2 * ch[k++] * side * side;
+    for (int i = 0; i < c->cfg.n_levels; ++i) {
+      for (int j = 0; j < c->cfg.layers_per_block; ++j) n += (long long)batch2 * ch[k++] * side * side;
+      if (i != c->cfg.n_levels - 1) { side /= 2; n += (long long)batch2 * ch[k++] * side * side; }
+    }
+    n += (long long)batch2 * c->cfg.block_out_channels[c->cfg.n_levels - 1] * side * side; }
+  if (n_out) *n_out = n;
+  if (!out) return 0;
+  if (!sample) { agd_set_error("controlnet_residuals: null sample"); return fail_ctx(c); }
+  API_CK(c, ensure_lat(c, batch2, L));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, c->cfg.in_channels, L * L, 64, 1, 1.0f, st)); }
+  c->arena.release(0);
+  API_CK(c, controlnet_walk(c, st, c->lat_bf16, batch2, L, timestep, scale, false, nullptr, nullptr, out, nhwc));
   return 0;
 }

@@ -61,8 +61,9 @@ def stack_heatmaps(obj: np.ndarray, fg: np.ndarray, bg: np.ndarray):
 def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Optional[str] = None,
                    prompt_embeds: Optional[torch.Tensor] = None, num_inference_steps: int = 50,
                    guidance_scale: float = 7.5, height: Optional[int] = None, rec_tokens: Optional[int] = None,
-                   word_rows: Optional[Sequence[Sequence[int]]] = None):
-    """One hot-path pass: len(seeds) images + per-word DAAM maps.
+                   word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None):
+    """One hot-path pass: len(seeds) images + per-word DAAM maps.  control: extra keyword arguments of a ControlNet pipeline's call
+    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`).
     Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, S, S] on GPU)."""
     from .trace import trace
     from . import synthetic
@@ -73,10 +74,10 @@ def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Opt
     with trace(pipe, rec_tokens=rec_tokens) as trc:
         if prompt_embeds is None:
             out = pipe([prompt] * B, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                       latents=lat, height=side, width=side, output_type="pt")
+                       latents=lat, height=side, width=side, output_type="pt", **(control or {}))
         else:
             out = pipe(prompt_embeds=prompt_embeds, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                       latents=lat, height=side, width=side, output_type="pt")
+                       latents=lat, height=side, width=side, output_type="pt", **(control or {}))
         hms = []
         for i in range(B):
             g = trc.compute_global_heat_map(prompt=prompt, image_index=i)
@@ -253,10 +254,37 @@ def parse_args(argv=None):
                    help="load the checkpoint without its safety checker (by default flagged images come back black and are skipped)")
     p.add_argument("--no-gather", action="store_true",
                    help="multi-GPU: every rank writes its own files instead of the final all_gather to rank 0")
+    p.add_argument("--controlnet-model-path", type=str, default=None, help="a diffusers ControlNetModel directory: ControlNet-conditioned txt2img")
+    p.add_argument("--control-image", type=str, default=None,
+                   help="control image file (every seed), or a directory: seed s uses its sorted file s mod n")
+    p.add_argument("--controlnet-conditioning-scale", type=float, default=1.0)
+    p.add_argument("--control-guidance-start", type=float, default=0.0)
+    p.add_argument("--control-guidance-end", type=float, default=1.0)
     args = p.parse_args(argv)
+    if (args.controlnet_model_path is None) != (args.control_image is None):
+        p.error("--controlnet-model-path and --control-image go together")
+    if not 0.0 <= args.control_guidance_start < args.control_guidance_end <= 1.0:
+        p.error("--control-guidance-start / --control-guidance-end: 0 <= start < end <= 1")
     if args.use_karras_sigmas and args.scheduler != "DPMSolverMultistepScheduler":
         p.error("--use-karras-sigmas needs --scheduler DPMSolverMultistepScheduler")
     return args
+
+
+def control_image_files(path: str) -> List[str]:
+    """The control image of every seed: one file, or a directory's image files in sorted order (seed s takes file s mod n)."""
+    if os.path.isdir(path):
+        files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp", ".webp")))
+        if not files:
+            raise FileNotFoundError(f"no control images in {path}")
+        return files
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    return [path]
+
+
+def control_images_for(files: Sequence[str], seeds: Sequence[int]):
+    from PIL import Image
+    return [Image.open(files[s % len(files)]).convert("RGB") for s in seeds]
 
 
 def main(argv=None):
@@ -274,9 +302,16 @@ def main(argv=None):
         dist.init_process_group(os.environ.get("AGD_DIST_BACKEND", "nccl"))          # "nccl" = RCCL on ROCm
         own_group = True
     kw = {"safety_checker": None} if args.no_safety_checker else {}
-    pipe = (StableDiffusionPipeline.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
+    cls, cn_files = StableDiffusionPipeline, None
+    if args.controlnet_model_path:
+        from .controlnet import ControlNetModel, StableDiffusionControlNetPipeline
+        cls = StableDiffusionControlNetPipeline
+        kw["controlnet"] = ControlNetModel.from_pretrained(args.controlnet_model_path)
+        cn_files = control_image_files(args.control_image)
+    pipe = (cls.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
-            StableDiffusionPipeline.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler"))
+            cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
+                               **({"controlnet": kw["controlnet"]} if cn_files else {})))
     if args.use_karras_sigmas:
         from .scheduler import DPMSolverMultistepScheduler
         pipe.cfg.sched.use_karras_sigmas = True
@@ -298,7 +333,11 @@ def main(argv=None):
     for r in range(rounds):
         chunk = seeds[r * args.batch_size:(r + 1) * args.batch_size]
         if chunk:
-            imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps)
+            control = None
+            if cn_files:
+                control = {"image": control_images_for(cn_files, chunk), "controlnet_conditioning_scale": args.controlnet_conditioning_scale,
+                           "control_guidance_start": args.control_guidance_start, "control_guidance_end": args.control_guidance_end}
+            imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)
             continue

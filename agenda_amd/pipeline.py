@@ -176,6 +176,44 @@ class Engine:
                  "agd_safety_scores")
         return (cos, pix) if want_pixels else cos
 
+    def controlnet_configure(self, cncfg):
+        self._cncfg = _lib.AgdControlNetConfig()
+        self._cncfg.struct_size = C.sizeof(_lib.AgdControlNetConfig)
+        emb = cncfg.conditioning_embedding_out_channels
+        self._cncfg.n_emb = len(emb)
+        for i, c in enumerate(emb):
+            self._cncfg.emb_channels[i] = int(c)
+        self._cncfg.bgr = int(cncfg.conditioning_channel_order == "bgr")
+        self._ck(self.lib.agd_controlnet_configure(self.ctx, C.byref(self._cncfg)), "agd_controlnet_configure")
+
+    def controlnet_set_cond(self, cond: torch.Tensor, repeat: int = 2):
+        """`agd_controlnet_set_cond`: the control image fp32 [B,3,S,S] in [0,1] -> the conditioning embedding of B * repeat UNet rows
+        ([cond; cond] for the CFG batch), computed once."""
+        cond = self._h2d(cond)
+        b, c, h, w = cond.shape
+        if c != 3 or h != w:
+            raise ValueError(f"control image must be [B,3,S,S], got {tuple(cond.shape)}")
+        self._ck(self.lib.agd_controlnet_set_cond(self.ctx, _lib.ptr(cond), b, h, int(repeat), self._stream()), "agd_controlnet_set_cond")
+        self._cond_keepalive = cond
+
+    def controlnet_set_schedule(self, scales):
+        """Per-model-evaluation conditioning scales of the next fused loop (or one-element: the next unet_forward); empty clears."""
+        n = len(scales)
+        arr = (C.c_float * max(n, 1))(*[float(x) for x in scales])
+        self._ck(self.lib.agd_controlnet_set_schedule(self.ctx, arr, n), "agd_controlnet_set_schedule")
+
+    def controlnet_residuals(self, sample: torch.Tensor, timestep: float, scale: float = 1.0, nhwc: bool = False) -> torch.Tensor:
+        """`agd_controlnet_residuals`: the scaled ControlNet residuals of one forward, back to back in one fp32 vector (down residuals in
+        res-sample order, then the mid residual; each [B2,C,h,w], or [B2,h,w,C] with nhwc)."""
+        sample = sample.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        b2, _, L, _ = sample.shape
+        n = C.c_longlong(0)
+        self._ck(self.lib.agd_controlnet_residuals(self.ctx, None, b2, L, 0.0, 0.0, int(nhwc), None, C.byref(n), None), "agd_controlnet_residuals")
+        out = torch.empty(n.value, device=sample.device, dtype=torch.float32)
+        self._ck(self.lib.agd_controlnet_residuals(self.ctx, _lib.ptr(sample), b2, L, float(timestep), float(scale), int(nhwc), _lib.ptr(out),
+                                                   C.byref(n), self._stream()), "agd_controlnet_residuals")
+        return out
+
     def text_set_embedding_row(self, token_id: int, row: torch.Tensor):
         row = row.detach().to(torch.float32).contiguous()
         self._ck(self.lib.agd_text_set_embedding_row(self.ctx, int(token_id), C.c_void_p(row.data_ptr())), "agd_text_set_embedding_row")
@@ -488,6 +526,7 @@ class StableDiffusionPipeline:
         if safety_sd is not None:
             self.engine.safety_configure(cfg.safety)
             self.engine.load_state_dict({k: v for k, v in safety_sd.items() if "position_ids" not in k}, "safety.")
+        self._load_extra()
         self.engine.finalize()
         self.device = torch.device(f"cuda:{dev}")
         self.tokenizer = tokenizer or SimpleTokenizer(cfg.max_tokens)
@@ -515,6 +554,9 @@ class StableDiffusionPipeline:
             self.safety_checker = HipSafetyChecker(self.engine, cfg.safety, safety_sd["special_care_embeds_weights"],
                                                    safety_sd["concept_embeds_weights"])
 
+    def _load_extra(self):
+        """Models a subclass adds to the engine before it is finalized (StableDiffusionControlNetPipeline: the ControlNet)."""
+
     # ---- construction -------------------------------------------------------------------
     @classmethod
     def from_synthetic(cls, cfg: Union[str, SDConfig] = "sd15", seed: int = 1234, device=0, workspace_bytes: int = 0,
@@ -529,7 +571,7 @@ class StableDiffusionPipeline:
         return pipe
 
     @classmethod
-    def from_pretrained(cls, path: str, device=0, workspace_bytes: int = 0, scheduler: Optional[str] = None, safety_checker=_KEEP):
+    def from_pretrained(cls, path: str, device=0, workspace_bytes: int = 0, scheduler: Optional[str] = None, safety_checker=_KEEP, **init_kw):
         """Reads the diffusers on-disk layout (`unet/config.json`, `unet/diffusion_pytorch_model.safetensors`,
         `vae/...`) that `save_pretrained` writes (reference finetune_sd_token.py:164-187).  The safety checker is loaded when
         `model_index.json` names one (`safety_checker/` + `feature_extractor/` must then exist); `safety_checker=None` turns it off
@@ -624,7 +666,7 @@ class StableDiffusionPipeline:
             cfg.safety = safety_config_from_json(jload(scj), jload(fej), n_special=int(ssd["special_care_embeds"].shape[0]),
                                                  n_concepts=int(ssd["concept_embeds"].shape[0]))
         pipe = cls(cfg, usd, vsd, tokenizer=tok, device=device, workspace_bytes=workspace_bytes, text_sd=tsd, scheduler=sched_name,
-                   safety_sd=ssd)
+                   safety_sd=ssd, **init_kw)
         if safety_checker is not _KEEP and safety_checker is not None:
             pipe.safety_checker = safety_checker
         pipe._source_path = src_path

@@ -120,3 +120,12 @@ def make_safety_weights(cfg: SDConfig, seed: int = 77, device: str = "cpu") -> D
             w = 0.05 * torch.randn(shp, generator=g, device=device)
         sd[k] = _bf16_round(w)
     return sd
+
+
+def make_controlnet_weights(cfg: SDConfig, cncfg=None, seed: int = 555, gain: float = 1.0, bias_std: float = 0.0,
+                            perturb_norm: float = 0.0, device: str = "cpu") -> Dict[str, torch.Tensor]:
+    """Random ControlNet weights (diffusers ControlNetModel key names) for `cfg.unet`, drawn like the UNet's.  The zero convs are NOT
+    zero: N(0, 1/fan_in) like every other matrix (a trained ControlNet's are far from zero, and zeros would hide a broken injection)."""
+    from .config import ControlNetConfig, controlnet_param_shapes
+    g = torch.Generator(device).manual_seed(seed)
+    return _fill(controlnet_param_shapes(cfg.unet, cncfg or ControlNetConfig()), g, gain, bias_std, perturb_norm)

@@ -87,6 +87,31 @@ int agd_safety_configure(agd_ctx* ctx, const agd_vision_config* vcfg);
  * = the processor's pixel_values.  Stream-ordered; leaves the recorder accumulators, the context and the scheduler state untouched. */
 int agd_safety_scores(agd_ctx* ctx, const unsigned char* images, int batch, int side, float* cos_out, float* pixels_out, void* stream);
 
+/* ---- ControlNet (diffusers ControlNetModel, SD-1.x: the UNet's down blocks + mid block, a conditioning embedding and 1x1 zero convs).
+ * Configured by agd_controlnet_configure BEFORE agd_finalize; weights through agd_load_tensor as "controlnet." + diffusers state-dict key.
+ * Its block layout, heads and cross-attention width are the UNet's (the host refuses anything else).  Its transformer layers are never
+ * recorded (DAAM and the hook.py recorder see the UNet's layers only). */
+#define AGD_CN_MAX_EMB 8
+typedef struct agd_controlnet_config {
+  int struct_size;                 /* sizeof(agd_controlnet_config), ABI guard */
+  int n_emb;                       /* len(conditioning_embedding_out_channels), 2 .. AGD_CN_MAX_EMB */
+  int emb_channels[AGD_CN_MAX_EMB];
+  int bgr;                         /* controlnet_conditioning_channel_order == "bgr": the image's channels are flipped first */
+} agd_controlnet_config;
+int agd_controlnet_configure(agd_ctx* ctx, const agd_controlnet_config* cncfg);
+/* the conditioning image cond fp32 [batch,3,S,S] (device) in [0,1] -> the embedding, computed once and kept for batch * repeat UNet rows
+ * (repeat 2: [cond; cond], the CFG doubling); S = latent side << (n_emb - 1). */
+int agd_controlnet_set_cond(agd_ctx* ctx, const float* cond, int batch, int side, int repeat, void* stream);
+/* per-model-evaluation conditioning scales (controlnet_conditioning_scale x the guidance window), host array of n floats, consumed by the
+ * next agd_denoise / agd_denoise_plms / agd_denoise_dpm (n must equal its evaluation count) or agd_unet_forward (n = 1).  A scale of
+ * exactly 0 skips the ControlNet for that evaluation.  n = 0 clears the schedule: the UNet runs alone. */
+int agd_controlnet_set_schedule(agd_ctx* ctx, const float* scales, int n);
+/* one ControlNet forward: the 13 (SD-1.x) scaled residuals, down residuals in res-sample order then the mid residual, written back to back
+ * into out fp32 (device) per residual as [batch2][C][h][w] (nhwc = 0) or [batch2][h][w][C] (nhwc = 1); returns the float count in *n_out.
+ * out = NULL: only the count.  The conditioning embedding must be set for batch2 rows. */
+int agd_controlnet_residuals(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float scale, int nhwc,
+                             float* out, long long* n_out, void* stream);
+
 /* ---- `unet(sample, t, encoder_hidden_states).sample`: sample/out fp32 NCHW [B2,4,L,L] */
 int agd_unet_forward(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float* out,
                      void* stream);
