@@ -8,7 +8,8 @@ from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indice
 from .hook import UNetCrossAttentionHooker  # noqa: F401
 from .scheduler import DDIMScheduler  # noqa: F401
 from .controlnet import ControlNetModel, StableDiffusionControlNetPipeline  # noqa: F401
+from .inpaint import StableDiffusionInpaintPipeline  # noqa: F401
 
 __all__ = ["StableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
            "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic",
-           "ControlNetModel", "StableDiffusionControlNetPipeline"]
+           "ControlNetModel", "StableDiffusionControlNetPipeline", "StableDiffusionInpaintPipeline"]

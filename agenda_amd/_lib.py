@@ -80,6 +80,10 @@ _SIGS = {
     "agd_controlnet_set_cond": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "agd_controlnet_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "agd_controlnet_residuals": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, C.POINTER(C.c_longlong), _P]),
+    "agd_inpaint_prepare": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "agd_inpaint_set": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "agd_inpaint_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "agd_inpaint_clear": (C.c_int, [_P]),
     "agd_unet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_unet_forward_ts": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
     "agd_cfg_ddim_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P]),

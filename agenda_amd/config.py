@@ -221,6 +221,28 @@ def tiny21() -> SDConfig:
 CONFIGS = {"sd15": sd15, "sd21": sd21, "tiny": tiny, "tiny40": tiny40, "tiny21": tiny21}
 
 
+def inpaint_variant(cfg: SDConfig) -> SDConfig:
+    """`cfg` with an inpainting UNet: in_channels = latents + mask + masked-image latents (9 for SD); everything else unchanged."""
+    import copy
+    out = copy.deepcopy(cfg)
+    out.unet.in_channels = out.unet.out_channels + 1 + out.vae.latent_channels
+    out.name = cfg.name + "-inpaint"
+    return out
+
+
+def inpaint_flavour(cfg: SDConfig) -> str:
+    """How a UNet inpaints [upstream-knowledge: diffusers 0.21.2 StableDiffusionInpaintPipeline]: "concat" when it takes latents + mask +
+    masked-image latents (in_channels = out_channels + 1 + the VAE's latent channels: 9 for SD), "blend" when it takes the latents only
+    (the latents are blended with the noised image latents after every step).  Any other width raises."""
+    u = cfg.unet
+    if u.in_channels == u.out_channels:
+        return "blend"
+    if u.in_channels == u.out_channels + 1 + cfg.vae.latent_channels:
+        return "concat"
+    raise ValueError(f"inpainting needs a UNet of {u.out_channels} or {u.out_channels + 1 + cfg.vae.latent_channels} input channels "
+                     f"(latents, or latents + mask + masked-image latents), this one takes {u.in_channels}")
+
+
 def text_param_shapes(t: TextConfig) -> Dict[str, tuple]:
     """transformers CLIPTextModel state-dict keys (without the `text_model.` prefix of transformers 4.x)."""
     H, I = t.hidden_size, t.intermediate_size

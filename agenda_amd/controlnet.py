@@ -5,7 +5,8 @@ The ControlNet runs inside every fused denoise loop (`agd_denoise`, `agd_denoise
 its down and mid blocks run on the same latents, timestep and prompt embeddings, and its scaled residuals are added to the UNet's skip
 connections and mid output.  Its conditioning embedding depends on the control image alone and is computed once per call.  DAAM and the
 hook.py hooker see the UNet's cross-attention only.  Rules restated from the published pipeline are marked [upstream-knowledge].
-Not implemented, and refused: guess mode, several ControlNets (MultiControlNet), ControlNet img2img / inpainting.
+Not implemented, and refused: guess mode, several ControlNets (MultiControlNet), ControlNet img2img / inpainting (StableDiffusionInpaintPipeline
+runs inpainting without a ControlNet).
 """
 from __future__ import annotations
 

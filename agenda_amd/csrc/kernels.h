@@ -230,6 +230,14 @@ int launch_scale(float* x, long long n, float s, hipStream_t st);
 // ControlNet (controlnet.hip): fp32 NCHW [B][3][HW] -> bf16 NHWC [B][HW][Cpad] (optionally BGR-flipped); out = s * in over n floats
 int launch_controlnet_cond_prep(const float* cond, bf16_t* out, int B, int HW, int Cpad, int bgr, hipStream_t st);
 int launch_controlnet_scale_bias(const float* in, float* out, int n, float s, hipStream_t st);
+// Inpainting (inpaint.hip): the mask front end (image [-1,1], masked image, latent-resolution binary mask), the 9-channel UNet input
+// (latents | mask | masked-image latents | zero pad, bf16 NHWC), the 4-channel blend x = (1 - m)(sa x0img + sb n) + m x
+int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int S, int f, float* image_out,
+                         float* masked_out, float* mask_lat, hipStream_t st);
+int launch_prep_inpaint(const float* lat, const float* mask, const float* cond, bf16_t* out, int B, int Cl, int Cm, int Cc, int HW, int Cpad,
+                        int dup, hipStream_t st);
+int launch_inpaint_blend(float* lat, const float* x0img, const float* noise, const float* mask, int B, int C, int HW, float sa, float sb,
+                         hipStream_t st);
 
 // export path (bit-exact with numpy min-max/astype and PIL Image.resize BICUBIC on uint8)
 int launch_heatmap_u8(const float* hm, int n, int npix, unsigned char* out, hipStream_t st);

@@ -150,6 +150,11 @@ struct agd_ctx {
   int cn_nres = 0; float* cn_zb = nullptr; float* cn_zbs = nullptr; int cn_zb_total = 0; std::vector<int> cn_zb_off; float cn_zscale = NAN;
   DBuf cn_embb; int cn_emb_B2 = 0, cn_emb_L = 0, cn_emb_rep = 0;      // the conditioning embedding [B2][L][L][C0] bf16 (agd_controlnet_set_cond)
   std::vector<float> cn_sched;                                         // agd_controlnet_set_schedule: one scale per model evaluation
+  // inpainting (agd_inpaint_set): ip_mode 0 = none, 1 = the 9-channel UNet input (mask + masked-image latents in ip_condb), 2 = the 4-channel
+  // blend (image latents in ip_condb, the noise in ip_noiseb, (sa, sb) per model evaluation in ip_sched); all fp32 NCHW for ip_B images
+  int ip_mode = 0, ip_B = 0, ip_L = 0, ip_Cm = 0, ip_Cc = 0;
+  DBuf ip_maskb, ip_condb, ip_noiseb;
+  std::vector<float> ip_sched;
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
@@ -1618,6 +1623,36 @@ static int cn_schedule_for(agd_ctx* c, int n, int B2, int L, const float** out) 
   *out = c->cn_sched.data();
   return 0;
 }
+// the inpaint state of a fused loop of n model evaluations on `batch` images at latent side L: *blend = the (sa, sb) schedule of the
+// 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
+static int inpaint_for(agd_ctx* c, int n, int batch, int L, const float** blend) {
+  *blend = nullptr;
+  if (c->ip_mode == 0) {
+    if (c->cfg.in_channels != c->cfg.out_channels)
+      FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first", c->cfg.in_channels, c->cfg.out_channels);
+    return 0;
+  }
+  if (c->ip_B != batch || c->ip_L != L) FAIL("inpaint: the state holds %d images at latent side %d, this call runs %d at side %d", c->ip_B, c->ip_L, batch, L);
+  if (!c->cn_sched.empty()) FAIL("inpaint: a ControlNet schedule is set; ControlNet inpainting is not implemented");
+  if (c->ip_mode == 2) {
+    if ((int)c->ip_sched.size() != 2 * n) FAIL("inpaint: the blend schedule has %zu entries, this call runs %d model evaluations (agd_inpaint_set_schedule)", c->ip_sched.size() / 2, n);
+    *blend = c->ip_sched.data();
+  }
+  return 0;
+}
+// the UNet input of one CFG evaluation: the latents (txt2img) or latents | mask | masked-image latents (9-channel inpainting), both CFG halves
+static int prep_unet_input(agd_ctx* c, hipStream_t st, const float* latents, int batch, int HW) {
+  ProfScope ps(c, st, PC_ELEM, 0);
+  if (c->ip_mode == 1)
+    return launch_prep_inpaint(latents, c->ip_maskb.as<float>(), c->ip_condb.as<float>(), c->lat_bf16, batch, c->cfg.out_channels, c->ip_Cm, c->ip_Cc, HW, 64, 2, st);
+  return launch_prep_latents(latents, c->lat_bf16, batch, c->cfg.out_channels, HW, 64, 2, 1.0f, st);
+}
+// the 4-channel blend after the step of evaluation i (sab = (sa, sb) of that evaluation)
+static int inpaint_blend(agd_ctx* c, hipStream_t st, float* latents, int batch, int HW, const float* sab) {
+  ProfScope ps(c, st, PC_ELEM, 0);
+  return launch_inpaint_blend(latents, c->ip_condb.as<float>(), c->ip_noiseb.as<float>(), c->ip_maskb.as<float>(), batch, c->cfg.out_channels, HW,
+                              sab[0], sab[1], st);
+}
 AGD_API int agd_unet_forward(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float* out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
@@ -1691,18 +1726,21 @@ AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_step
                            const float* alpha_prev, float guidance, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
-  const int B2 = 2 * batch, Cl = c->cfg.in_channels, HW = L * L;
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;            // Cl: the latent channels (a 9-channel UNet's input has more)
   API_CK(c, ensure_lat(c, B2, L));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const float* cs = nullptr;                                       // the ControlNet's per-step scales (none: the UNet alone)
   API_CK(c, cn_schedule_for(c, n_steps, B2, L, &cs));
+  const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per step (none: no blend)
+  API_CK(c, inpaint_for(c, n_steps, batch, L, &ib));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
   for (int s = 0; s < n_steps; ++s) {
-    { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
+    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
     API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f));
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
+    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * s));
   }
   return 0;
 }
@@ -1721,7 +1759,7 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
   hipStream_t st = S(stream);
   if (c->cfg.prediction_type != 0) { agd_set_error("denoise_plms: epsilon prediction only"); return fail_ctx(c); }
   if (n_evals < 2) { agd_set_error("denoise_plms: needs >= 2 model evaluations (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.in_channels, HW = L * L;
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;
   API_CK(c, ensure_lat(c, B2, L));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const size_t n1 = (size_t)batch * Cl * HW;
@@ -1730,11 +1768,13 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
   float* kept = c->plmsb.as<float>() + n1 * 4;
   const float* cs = nullptr;
   API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
+  const float* ib = nullptr;                                       // the blend rewrites `latents` only: the kept sample stays unblended
+  API_CK(c, inpaint_for(c, n_evals, batch, L, &ib));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
   for (int i = 0; i < n_evals; ++i) {
-    { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
+    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
     API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
@@ -1752,6 +1792,7 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_plms(c->eps_nhwc, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w,
                                 sample_coeff[i], eps_coeff[i], st)); }
+    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
     if (store) { ++head; if (n_hist < 3) ++n_hist; }
   }
   return 0;
@@ -1768,7 +1809,7 @@ AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   if (n_evals < 1 || !timesteps || !coeffs) { agd_set_error("denoise_dpm: needs >= 1 model evaluation and host timesteps / coeffs (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.in_channels, HW = L * L;
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;
   API_CK(c, ensure_lat(c, B2, L));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const size_t n1 = (size_t)batch * Cl * HW;
@@ -1776,15 +1817,18 @@ AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
   const float* cs = nullptr;
   API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
+  const float* ib = nullptr;
+  API_CK(c, inpaint_for(c, n_evals, batch, L, &ib));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   for (int i = 0; i < n_evals; ++i) {
-    { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, Cl, HW, 64, 2, 1.0f, st)); }
+    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
     API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_dpm(c->eps_nhwc, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st)); }
+    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
   }
   return 0;
 }
@@ -2999,5 +3043,64 @@ AGD_API int agd_controlnet_residuals(agd_ctx* c, const float* sample, int batch2
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, c->cfg.in_channels, L * L, 64, 1, 1.0f, st)); }
   c->arena.release(0);
   API_CK(c, controlnet_walk(c, st, c->lat_bf16, batch2, L, timestep, scale, false, nullptr, nullptr, out, nhwc));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Inpainting (diffusers StableDiffusionInpaintPipeline): the mask front end once per call, then a state the three fused loops read
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_inpaint_prepare(agd_ctx* c, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int side,
+                                float* image_out, float* masked_out, float* mask_lat_out, void* stream) {
+  API_CK(c, need_final(c));
+  if (!image || !mask) { agd_set_error("inpaint_prepare: null image or mask"); return fail_ctx(c); }
+  const int f = 1 << (c->cfg.vae_n_levels - 1);
+  ProfScope ps(c, S(stream), PC_ELEM, 0);
+  API_CK(c, launch_inpaint_front(image, image_f32 != 0, mask, mask_f32 != 0, batch, side, f, image_out, masked_out, mask_lat_out, S(stream)));
+  return 0;
+}
+
+AGD_API int agd_inpaint_set(agd_ctx* c, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
+                            int batch, int L, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  const int Cl = c->cfg.out_channels, Cin = c->cfg.in_channels;
+  if (!mask || !cond || batch < 1 || L < 1) { agd_set_error("inpaint_set: null mask / cond, or batch %d latent side %d", batch, L); return fail_ctx(c); }
+  int mode = 0;
+  if (Cin == Cl) {
+    if (mask_channels != 1 || cond_channels != Cl || !noise)
+      { agd_set_error("inpaint_set: the %d-channel UNet blends: needs a 1-channel mask, %d-channel image latents and the noise (got %d, %d%s)",
+                      Cin, Cl, mask_channels, cond_channels, noise ? "" : ", no noise"); return fail_ctx(c); }
+    mode = 2;
+  } else {
+    if (mask_channels < 1 || cond_channels < 1 || Cl + mask_channels + cond_channels != Cin || Cin > 64 || noise)
+      { agd_set_error("inpaint_set: %d latent + %d mask + %d masked-latent channels do not make the UNet's %d input channels%s", Cl, mask_channels,
+                      cond_channels, Cin, noise ? " (and a concatenating UNet takes no noise)" : ""); return fail_ctx(c); }
+    mode = 1;
+  }
+  c->ip_mode = 0; c->ip_sched.clear();
+  const size_t hw = (size_t)L * L, nm = (size_t)batch * mask_channels * hw, nc = (size_t)batch * cond_channels * hw;
+  API_CK(c, c->ip_maskb.ensure(nm * 4)); API_CK(c, c->ip_condb.ensure(nc * 4));
+  if (hipMemcpyAsync(c->ip_maskb.p, mask, nm * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(c->ip_condb.p, cond, nc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("inpaint_set: copy failed"); return fail_ctx(c); }
+  if (noise) {
+    API_CK(c, c->ip_noiseb.ensure(nc * 4));
+    if (hipMemcpyAsync(c->ip_noiseb.p, noise, nc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("inpaint_set: copy failed"); return fail_ctx(c); }
+  }
+  c->ip_mode = mode; c->ip_B = batch; c->ip_L = L; c->ip_Cm = mask_channels; c->ip_Cc = cond_channels;
+  return 0;
+}
+
+AGD_API int agd_inpaint_set_schedule(agd_ctx* c, const float* sa_sb, int n) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (c->ip_mode != 2) { agd_set_error("inpaint_set_schedule: no blend state (agd_inpaint_set on a UNet that takes the latent channels only)"); return fail_ctx(c); }
+  if (n < 1 || !sa_sb) { agd_set_error("inpaint_set_schedule: %d entries", n); return fail_ctx(c); }
+  for (int i = 0; i < 2 * n; ++i) if (!std::isfinite(sa_sb[i])) { agd_set_error("inpaint_set_schedule: entry %d is %g", i / 2, sa_sb[i]); return fail_ctx(c); }
+  c->ip_sched.assign(sa_sb, sa_sb + 2 * n);
+  return 0;
+}
+
+AGD_API int agd_inpaint_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  c->ip_mode = 0; c->ip_B = c->ip_L = c->ip_Cm = c->ip_Cc = 0; c->ip_sched.clear();
   return 0;
 }

@@ -63,7 +63,8 @@ def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Opt
                    guidance_scale: float = 7.5, height: Optional[int] = None, rec_tokens: Optional[int] = None,
                    word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None):
     """One hot-path pass: len(seeds) images + per-word DAAM maps.  control: extra keyword arguments of a ControlNet pipeline's call
-    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`).
+    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`) or of an inpainting one
+    (`inpaint_inputs_for`).
     Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, S, S] on GPU)."""
     from .trace import trace
     from . import synthetic
@@ -260,7 +261,18 @@ def parse_args(argv=None):
     p.add_argument("--controlnet-conditioning-scale", type=float, default=1.0)
     p.add_argument("--control-guidance-start", type=float, default=0.0)
     p.add_argument("--control-guidance-end", type=float, default=1.0)
+    p.add_argument("--init-image", type=str, default=None,
+                   help="inpainting: the image to paint into (a file for every seed, or a directory: seed s uses its sorted file s mod n)")
+    p.add_argument("--mask-image", type=str, default=None,
+                   help="inpainting: the mask, white = repaint (file or directory, paired with --init-image by sorted name)")
+    p.add_argument("--strength", type=float, default=1.0, help="inpainting: 1 starts from noise; < 1 (DDIM only) from the noised image")
     args = p.parse_args(argv)
+    if (args.init_image is None) != (args.mask_image is None):
+        p.error("--init-image and --mask-image go together")
+    if args.init_image is not None and args.controlnet_model_path:
+        p.error("ControlNet inpainting is not implemented (--init-image with --controlnet-model-path)")
+    if args.init_image is None and args.strength != 1.0:
+        p.error("--strength needs --init-image / --mask-image")
     if (args.controlnet_model_path is None) != (args.control_image is None):
         p.error("--controlnet-model-path and --control-image go together")
     if not 0.0 <= args.control_guidance_start < args.control_guidance_end <= 1.0:
@@ -287,6 +299,16 @@ def control_images_for(files: Sequence[str], seeds: Sequence[int]):
     return [Image.open(files[s % len(files)]).convert("RGB") for s in seeds]
 
 
+def inpaint_inputs_for(pairs: Sequence, seeds: Sequence[int], strength: float) -> dict:
+    """The inpainting call's image / mask_image of every seed (seed s takes pair s mod n) and strength.  The start noise is the seeds'
+    latents (generate_batch passes them); the VAE posterior draws come from a CPU generator seeded with the batch's first seed, so a
+    batch paints the same images in every run."""
+    from PIL import Image
+    picked = [pairs[s % len(pairs)] for s in seeds]
+    return {"image": [Image.open(i).convert("RGB") for i, _ in picked], "mask_image": [Image.open(m).convert("L") for _, m in picked],
+            "strength": strength, "generator": torch.Generator().manual_seed(int(seeds[0]))}
+
+
 def main(argv=None):
     import torch.distributed as dist
     from . import StableDiffusionPipeline
@@ -308,6 +330,13 @@ def main(argv=None):
         cls = StableDiffusionControlNetPipeline
         kw["controlnet"] = ControlNetModel.from_pretrained(args.controlnet_model_path)
         cn_files = control_image_files(args.control_image)
+    ip_files = None
+    if args.init_image:
+        from .inpaint import StableDiffusionInpaintPipeline
+        cls = StableDiffusionInpaintPipeline
+        ip_files = list(zip(control_image_files(args.init_image), control_image_files(args.mask_image)))
+        if len(ip_files) != len(control_image_files(args.init_image)) or len(ip_files) != len(control_image_files(args.mask_image)):
+            raise ValueError(f"{args.init_image} and {args.mask_image} hold different numbers of images")
     pipe = (cls.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
             cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
@@ -337,6 +366,8 @@ def main(argv=None):
             if cn_files:
                 control = {"image": control_images_for(cn_files, chunk), "controlnet_conditioning_scale": args.controlnet_conditioning_scale,
                            "control_guidance_start": args.control_guidance_start, "control_guidance_end": args.control_guidance_end}
+            if ip_files:
+                control = inpaint_inputs_for(ip_files, chunk, args.strength)
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)

@@ -214,6 +214,50 @@ class Engine:
                                                    C.byref(n), self._stream()), "agd_controlnet_residuals")
         return out
 
+    def inpaint_prepare(self, image: torch.Tensor, mask: torch.Tensor, want_image: bool, want_masked: bool):
+        """`agd_inpaint_prepare`: image uint8 [B,S,S,3] or float [B,3,S,S] in [-1,1], mask uint8 or float [B,S,S] -> (x, mask_lat): x fp32
+        [n B,3,S,S] holds the [-1,1] image rows (want_image), then the masked-image rows (want_masked), ready for one vae_encode; mask_lat
+        fp32 [B,1,L,L] binary."""
+        dev = f"cuda:{self.device}"
+        img_f32 = image.dtype != torch.uint8
+        image = image.to(device=dev, dtype=torch.float32 if img_f32 else torch.uint8).contiguous()
+        mask_f32 = mask.dtype != torch.uint8
+        mask = mask.to(device=dev, dtype=torch.float32 if mask_f32 else torch.uint8).contiguous()
+        b = image.shape[0]
+        S = image.shape[2] if img_f32 else image.shape[1]
+        L = S // self.cfg.vae_scale_factor
+        x = torch.empty((int(want_image) + int(want_masked)) * b, 3, S, S, device=dev, dtype=torch.float32)
+        m = torch.empty(b, 1, L, L, device=dev, dtype=torch.float32)
+        xi = _lib.ptr(x) if want_image else None
+        xm = C.c_void_p(x.data_ptr() + (b * 3 * S * S * 4 if want_image else 0)) if want_masked else None
+        self._ck(self.lib.agd_inpaint_prepare(self.ctx, C.c_void_p(image.data_ptr()), int(img_f32), C.c_void_p(mask.data_ptr()), int(mask_f32), b, S,
+                                              xi, xm, _lib.ptr(m), self._stream()), "agd_inpaint_prepare")
+        self._inpaint_keep = (image, mask)
+        return x, m
+
+    def inpaint_set(self, mask: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor] = None):
+        """`agd_inpaint_set`: mask [B,Cm,L,L] and cond [B,Cc,L,L] (masked-image latents, or image latents with the noise for the blend)."""
+        dev = f"cuda:{self.device}"
+        f = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+        mask, cond, noise = f(mask), f(cond), f(noise)
+        b, cm, L, _ = mask.shape
+        if cond.shape[0] != b or tuple(cond.shape[2:]) != (L, L) or (noise is not None and noise.shape != cond.shape):
+            raise ValueError(f"inpaint state shapes disagree: mask {tuple(mask.shape)}, cond {tuple(cond.shape)}, "
+                             f"noise {None if noise is None else tuple(noise.shape)}")
+        self._ck(self.lib.agd_inpaint_set(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, L, self._stream()),
+                 "agd_inpaint_set")
+        self._inpaint_state = (mask, cond, noise)
+
+    def inpaint_set_schedule(self, sa_sb):
+        """The blend's (sa, sb) per model evaluation of the next fused loop."""
+        n = len(sa_sb)
+        arr = (C.c_float * max(2 * n, 1))(*[float(v) for pair in sa_sb for v in pair])
+        self._ck(self.lib.agd_inpaint_set_schedule(self.ctx, arr, n), "agd_inpaint_set_schedule")
+
+    def inpaint_clear(self):
+        self._ck(self.lib.agd_inpaint_clear(self.ctx), "agd_inpaint_clear")
+        self._inpaint_state = None
+
     def text_set_embedding_row(self, token_id: int, row: torch.Tensor):
         row = row.detach().to(torch.float32).contiguous()
         self._ck(self.lib.agd_text_set_embedding_row(self.ctx, int(token_id), C.c_void_p(row.data_ptr())), "agd_text_set_embedding_row")
@@ -776,6 +820,7 @@ class StableDiffusionPipeline:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1):
+        self._refuse_inpainting_unet()
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
         if height != width or height % 64:
@@ -790,7 +835,7 @@ class StableDiffusionPipeline:
         if latents is None:
             # data_generation.py:58 seeds `torch.Generator(device="cuda")`: accepted (torch's device Philox stream; whether it is
             # bit-identical to an NVIDIA run of the reference is not verifiable here).  CPU generators give host-reproducible latents.
-            Cl = self.cfg.unet.in_channels
+            Cl = self.cfg.unet.out_channels
             if isinstance(generator, (list, tuple)):           # diffusers randn_tensor: one (1, C, L, L) draw per generator
                 if len(generator) != B:
                     raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {B}.")
@@ -800,7 +845,7 @@ class StableDiffusionPipeline:
                 latents = torch.cat(parts, 0)
             else:                                              # ONE (B, C, L, L) draw, kept on the generator's device (no host round trip)
                 latents = torch.randn(B, Cl, L, L, generator=generator, device=generator.device if generator is not None else "cpu")
-        expect = (B, self.cfg.unet.in_channels, L, L)
+        expect = (B, self.cfg.unet.out_channels, L, L)
         if tuple(latents.shape) != expect:                 # diffusers prepare_latents raises the same way
             raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
         lat = self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
@@ -816,6 +861,11 @@ class StableDiffusionPipeline:
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
         return self._finish(lat, B, output_type)
+
+    def _refuse_inpainting_unet(self):
+        if self.cfg.unet.in_channels != self.cfg.unet.out_channels:
+            raise ValueError(f"this UNet takes {self.cfg.unet.in_channels} input channels (an inpainting checkpoint): txt2img and img2img need "
+                             f"{self.cfg.unet.out_channels}; use StableDiffusionInpaintPipeline")
 
     def _denoise(self, lat, num_inference_steps, guidance_scale):
         """`for t in scheduler.timesteps: unet -> CFG -> scheduler.step`, fused on the device, under the pipeline's scheduler."""
@@ -857,6 +907,7 @@ class StableDiffusionPipeline:
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
         # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
         # PLMS and DPM-Solver++ img2img are not implemented)
+        self._refuse_inpainting_unet()
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
             image = image.permute(0, 3, 1, 2).float() / 127.5 - 1.0
@@ -865,7 +916,7 @@ class StableDiffusionPipeline:
             prompts = [prompt] * B if isinstance(prompt, str) else list(prompt)
             prompt_embeds = self.encode_prompt(prompts)
         L = S // self.vae_scale_factor
-        shape = (B, self.cfg.unet.in_channels, L, L)
+        shape = (B, self.cfg.unet.out_channels, L, L)
         if generator is not None and generator.device.type != "cpu":
             raise ValueError("use a CPU torch.Generator")
         noise_enc = noise_enc if noise_enc is not None else torch.randn(shape, generator=generator)

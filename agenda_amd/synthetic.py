@@ -74,7 +74,7 @@ def make_latents(cfg: SDConfig, seeds, latent_side: int) -> torch.Tensor:
     out = []
     for s in seeds:
         g = torch.Generator("cpu").manual_seed(int(s))
-        out.append(torch.randn(1, cfg.unet.in_channels, latent_side, latent_side, generator=g))
+        out.append(torch.randn(1, cfg.unet.out_channels, latent_side, latent_side, generator=g))
     return torch.cat(out, 0)
 
 

@@ -112,6 +112,26 @@ int agd_controlnet_set_schedule(agd_ctx* ctx, const float* scales, int n);
 int agd_controlnet_residuals(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float scale, int nhwc,
                              float* out, long long* n_out, void* stream);
 
+/* ---- inpainting (diffusers StableDiffusionInpaintPipeline).  A 9-channel UNet (in_channels = latent + 1 + latent) reads
+ * latents | mask | masked-image latents every evaluation; a UNet that takes the latent channels only is blended after every scheduler
+ * step instead.  The state is set once per call and cleared explicitly; without it every loop runs plain txt2img. */
+/* the front end, once per call, device pointers: image uint8 NHWC [batch,S,S,3] (image_f32 = 0: x / 255, then 2 x - 1) or fp32 NCHW
+ * [batch,3,S,S] already in [-1,1] (image_f32 = 1); mask uint8 [batch,S,S] (mask_f32 = 0: / 255) or fp32 [batch,S,S] in [0,1], binarized
+ * (m < 0.5 -> 0, else 1).  Writes, each may be NULL: image_out fp32 NCHW [batch,3,S,S], masked_out = image * (m < 0.5), mask_lat_out fp32
+ * [batch,1,L,L] with L = S / the VAE's downscale f and latent pixel (i, j) = mask pixel (f i, f j). */
+int agd_inpaint_prepare(agd_ctx* ctx, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int side,
+                        float* image_out, float* masked_out, float* mask_lat_out, void* stream);
+/* the state, copied from device fp32 NCHW tensors of `batch` images (both CFG halves read them): mask [batch,mask_channels,L,L] and cond
+ * [batch,cond_channels,L,L].  A 9-channel UNet: cond = the masked-image latents, latent + mask_channels + cond_channels must equal
+ * in_channels, noise = NULL.  A UNet of latent input channels: cond = the image latents, mask_channels = 1, noise [batch,latent,L,L] (the
+ * draw that started the loop), and a blend schedule must follow.  The next loop must run on `batch` images at latent side L. */
+int agd_inpaint_set(agd_ctx* ctx, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
+                    int batch, int latent_side, void* stream);
+/* the blend's (sa, sb) per model evaluation, host array of 2 n floats; n must equal the next loop's evaluation count.  After the step of
+ * evaluation i: x = (1 - m) (sa_i image_latents + sb_i noise) + m x. */
+int agd_inpaint_set_schedule(agd_ctx* ctx, const float* sa_sb, int n);
+int agd_inpaint_clear(agd_ctx* ctx);
+
 /* ---- `unet(sample, t, encoder_hidden_states).sample`: sample/out fp32 NCHW [B2,4,L,L] */
 int agd_unet_forward(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float* out,
                      void* stream);
