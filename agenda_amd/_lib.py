@@ -84,6 +84,11 @@ _SIGS = {
     "agd_inpaint_set": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "agd_inpaint_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "agd_inpaint_clear": (C.c_int, [_P]),
+    "agd_lora_add": (C.c_int, [_P, C.c_char_p, _P, _P, C.c_int, C.c_float]),
+    "agd_lora_set_scale": (C.c_int, [_P, C.c_float, _P]),
+    "agd_lora_clear": (C.c_int, [_P]),
+    "agd_lora_count": (C.c_int, [_P]),
+    "agd_lora_scale": (C.c_float, [_P]),
     "agd_unet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_unet_forward_ts": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
     "agd_cfg_ddim_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P]),

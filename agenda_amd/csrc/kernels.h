@@ -264,3 +264,17 @@ int launch_vis_embed_ln(const float* pe, const float* cls, const float* pos, con
                         float eps, bf16_t* x, hipStream_t st);
 int launch_vis_pooled_head(const bf16_t* x, int B, int T, int H, const float* gamma, const float* beta, float eps, const float* Wp, int P,
                            const float* E, int n, float* cos_out, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
+// LoRA merge (lora.hip): one descriptor per target matrix, its 64 x 64 output tiles numbered from tile0 (ascending across descriptors)
+// ---------------------------------------------------------------------------------------
+struct LoraMergeD {
+  bf16_t* dst; const bf16_t* base;    // the engine's packed raw matrix [N][Cpad] and its bf16 base copy (same layout)
+  const float* down; const float* up; // fp32 factors: down [r][Cin], up [N][r] (rows in checkpoint order; the GEGLU interleave is applied on read)
+  int N, Cin, Cpad, r, geglu;         // geglu: 16 for ff.net.0.proj (convert_weight_kernel's [8 values | 8 gates] rows), else 0
+  float coef;                         // alpha / r
+  int tile0;
+};
+int lora_merge_tiles(int N, int Cpad);
+// dst = bf16(float(base) + s * coef * up @ down) for every descriptor (d in device memory); copy_only: dst = base
+int launch_lora_merge(const LoraMergeD* d, int n_desc, int total_tiles, float s, int copy_only, hipStream_t st);

@@ -155,6 +155,12 @@ struct agd_ctx {
   int ip_mode = 0, ip_B = 0, ip_L = 0, ip_Cm = 0, ip_Cc = 0;
   DBuf ip_maskb, ip_condb, ip_noiseb;
   std::vector<float> ip_sched;
+  // LoRA (agd_lora_add / agd_lora_set_scale / agd_lora_clear): per target its fp32 factors and a bf16 copy of its base matrix (merge descriptors
+  // on the host and in lora_descb), merged into the raw matrices and re-derived in place; lora_scratch: 8 C C bf16 for derive_tblock
+  std::vector<std::string> lora_keys; std::vector<LoraMergeD> lora_d; int lora_tiles = 0;
+  DBuf lora_descb; bf16_t* lora_scratch = nullptr; size_t lora_scratch_n = 0;
+  float lora_scale = 0.f; bool lora_dirty = false;
+  bool ctx_stale = false;                             // the raw matrices changed after agd_set_context: the projected context must be rebuilt
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
@@ -875,6 +881,7 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
                            std::vector<Act>* skips, Act* h_unet, float* res_out, int nhwc) {
   const agd_config& g = c->cfg;
   if (!c->cn_on) FAIL("controlnet: none loaded (agd_controlnet_configure before agd_finalize)");
+  if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   if (c->cn_emb_B2 != B2 || c->cn_emb_L != L)
     FAIL("controlnet: the conditioning image is set for %d rows at latent side %d, this forward has %d rows at side %d (agd_controlnet_set_cond)",
          c->cn_emb_B2, c->cn_emb_L, B2, L);
@@ -941,6 +948,7 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float* eps_out,
                      const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f) {
   const agd_config& g = c->cfg;
+  if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   const int nl = g.n_levels, G = g.norm_num_groups;
   const std::string u = "unet.";
   c->arena.release(0);
@@ -1158,7 +1166,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1207,22 +1215,34 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
   return 0;
 }
 
-static int concat_rows(agd_ctx* c, const std::vector<const WMat*>& parts, WMat& out) {
-  out = WMat(); out.Cin = parts[0]->Cin; out.Cpad = parts[0]->Cpad; out.taps = parts[0]->taps;
-  for (auto* p : parts) { if (p->Cpad != out.Cpad || p->taps != out.taps) FAIL("concat_rows: mismatched K"); out.N += p->N; }
-  out.w = dmalloc<bf16_t>(c, (size_t)out.N * out.taps * out.Cpad); if (!out.w) return -1;
+// alloc = false: `out` is an earlier concatenation of the same parts, rewritten in place
+static int concat_rows(agd_ctx* c, const std::vector<const WMat*>& parts, WMat& out, bool alloc = true) {
+  if (alloc) {
+    out = WMat(); out.Cin = parts[0]->Cin; out.Cpad = parts[0]->Cpad; out.taps = parts[0]->taps;
+    for (auto* p : parts) { if (p->Cpad != out.Cpad || p->taps != out.taps) FAIL("concat_rows: mismatched K"); out.N += p->N; }
+    out.w = dmalloc<bf16_t>(c, (size_t)out.N * out.taps * out.Cpad); if (!out.w) return -1;
+  } else {
+    int n = 0; for (auto* p : parts) { if (p->Cpad != out.Cpad || p->taps != out.taps) FAIL("concat_rows: mismatched K"); n += p->N; }
+    if (n != out.N || !out.w) FAIL("concat_rows: %d rows do not match the earlier %d", n, out.N);
+  }
   size_t off = 0;
   for (auto* p : parts) { const size_t nb = (size_t)p->N * p->taps * p->Cpad; hipMemcpy(out.w + off, p->w, nb * 2, hipMemcpyDeviceToDevice); off += nb; }
   return 0;
 }
 
-// q_proj / k_proj / v_proj of every layer of a CLIP encoder as one [3H][H] matrix + bias ("<prefix><l>.self_attn.qkv.*")
-static int fuse_clip_qkv(agd_ctx* c, const std::string& prefix, int layers) {
+// q_proj / k_proj / v_proj of every layer of a CLIP encoder as one [3H][H] matrix + bias ("<prefix><l>.self_attn.qkv.*");
+// alloc = false (agd_lora_set_scale, the text encoder): the fused matrices are rewritten in place from the current q / k / v (biases unchanged)
+static int fuse_clip_qkv(agd_ctx* c, const std::string& prefix, int layers, bool alloc = true) {
   for (int l = 0; l < layers; ++l) {
     const std::string a = prefix + std::to_string(l) + ".self_attn.";
     const WMat* q = getW(c, a + "q_proj.weight"); const WMat* k = getW(c, a + "k_proj.weight"); const WMat* v = getW(c, a + "v_proj.weight");
     const float* bq = getV(c, a + "q_proj.bias"); const float* bk = getV(c, a + "k_proj.bias"); const float* bv = getV(c, a + "v_proj.bias");
     if (!q || !k || !v || !bq || !bk || !bv) return -1;
+    if (!alloc) {
+      auto it = c->W.find(a + "qkv.weight"); if (it == c->W.end()) FAIL("derived form '%sqkv.weight' missing", a.c_str());
+      if (concat_rows(c, {q, k, v}, it->second, false)) return -1;
+      continue;
+    }
     WMat qkv; if (concat_rows(c, {q, k, v}, qkv)) return -1; c->W[a + "qkv.weight"] = qkv;
     float* b = dmalloc<float>(c, (size_t)3 * q->N); if (!b) return -1;
     hipMemcpy(b, bq, (size_t)q->N * 4, hipMemcpyDeviceToDevice); hipMemcpy(b + q->N, bk, (size_t)q->N * 4, hipMemcpyDeviceToDevice);
@@ -1330,12 +1350,11 @@ static int finalize_controlnet(agd_ctx* c) {
   return 0;
 }
 
-AGD_API int agd_finalize(agd_ctx* c) {
-  if (!c) return -1;
-  hipSetDevice(c->device);
+// The transformer blocks, in the order agd_finalize registers their cross-attention layers (daam's: up, down, mid), the ControlNet's after
+// them: (prefix "...attentions.<j>.", level)
+static std::vector<std::pair<std::string, int>> transformer_prefixes(agd_ctx* c) {
   const agd_config& g = c->cfg;
-  // ---- enumerate transformer blocks: fused QKV + cross K/V weights, recorder layers (daam order: up, down, mid)
-  std::vector<std::pair<std::string, int>> tf;   // (prefix, level)
+  std::vector<std::pair<std::string, int>> tf;
   const int nl = g.n_levels;
   for (int i = 0; i < nl; ++i) { const int lvl = nl - 1 - i;
     if (g.down_cross[lvl]) for (int j = 0; j < g.layers_per_block + 1; ++j) tf.push_back({"unet.up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", lvl}); }
@@ -1347,18 +1366,51 @@ AGD_API int agd_finalize(agd_ctx* c) {
       if (g.down_cross[i]) for (int j = 0; j < g.layers_per_block; ++j) tf.push_back({"controlnet.down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", i});
     tf.push_back({"controlnet.mid_block.attentions.0.", nl - 1});
   }
-  for (auto& pr : tf) {
-    const std::string t = pr.first + "transformer_blocks.0.";
+  return tf;
+}
+
+// Every form one transformer block derives from its raw matrices: the fused QKV, the cross K/V (and its XLayer), the pre-multiplied attn2
+// parts, the three LayerNorm folds, [Wp W2 | Wp] with Wp b2 + bp, and the fragment orders.  alloc = true (agd_finalize) allocates them;
+// alloc = false (agd_lora_set_scale) rewrites the same blocks in place from the current raw matrices through the same launches, so the two
+// cannot drift.  scratch: nullptr = load-time blocks, allocated and freed here; else 8 C C bf16 of room the caller owns.
+static int derive_tblock(agd_ctx* c, const std::string& pre, int level, bool alloc, bf16_t* scratch) {
+  const agd_config& g = c->cfg;
+  // the destination of a derived matrix / vector: a fresh block at finalize, the existing one when rewritten
+  auto wbuf = [&](const std::string& key, size_t n) -> bf16_t* {
+    if (alloc) return dmalloc<bf16_t>(c, n);
+    auto it = c->W.find(key);
+    if (it == c->W.end() || !it->second.w) { agd_set_error("derived form '%s' missing", key.c_str()); return nullptr; }
+    return it->second.w;
+  };
+  auto vbuf = [&](const std::string& key, size_t n) -> float* {
+    if (alloc) return dmalloc<float>(c, n);
+    auto it = c->V.find(key);
+    if (it == c->V.end() || !it->second) { agd_set_error("derived form '%s' missing", key.c_str()); return nullptr; }
+    return it->second;
+  };
+  {
+    const std::string t = pre + "transformer_blocks.0.";
     const WMat* q = getW(c, t + "attn1.to_q.weight"); const WMat* k = getW(c, t + "attn1.to_k.weight"); const WMat* v = getW(c, t + "attn1.to_v.weight");
     if (!q || !k || !v) return fail_ctx(c);
-    WMat qkv; API_CK(c, concat_rows(c, {q, k, v}, qkv)); c->W[t + "attn1.qkv"] = qkv;
+    if (alloc) { WMat qkv; API_CK(c, concat_rows(c, {q, k, v}, qkv)); c->W[t + "attn1.qkv"] = qkv; }
+    else { auto it = c->W.find(t + "attn1.qkv"); if (it == c->W.end()) FAIL("derived form '%sattn1.qkv' missing", t.c_str());
+      API_CK(c, concat_rows(c, {q, k, v}, it->second, false)); }
     const WMat* ck = getW(c, t + "attn2.to_k.weight"); const WMat* cv = getW(c, t + "attn2.to_v.weight");
     if (!ck || !cv) return fail_ctx(c);
-    XLayer xl; xl.name = t + "attn2"; xl.C = q->N; xl.level = pr.second; xl.heads = g.num_heads[pr.second];
-    xl.mid = pr.first.find("mid_block") != std::string::npos;
-    xl.cn = pr.first.compare(0, 11, "controlnet.") == 0;
-    API_CK(c, concat_rows(c, {ck, cv}, xl.wkv));
-    if (xl.C % xl.heads) { agd_set_error("%s: C %d not divisible by heads %d", xl.name.c_str(), xl.C, xl.heads); return fail_ctx(c); }
+    XLayer xl_new; XLayer* xp = &xl_new;
+    if (alloc) {
+      XLayer& xl = xl_new; xl.name = t + "attn2"; xl.C = q->N; xl.level = level; xl.heads = g.num_heads[level];
+      xl.mid = pre.find("mid_block") != std::string::npos;
+      xl.cn = pre.compare(0, 11, "controlnet.") == 0;
+      API_CK(c, concat_rows(c, {ck, cv}, xl.wkv));
+      if (xl.C % xl.heads) { agd_set_error("%s: C %d not divisible by heads %d", xl.name.c_str(), xl.C, xl.heads); return fail_ctx(c); }
+    } else {
+      auto it = c->xl_idx.find(t + "attn2"); if (it == c->xl_idx.end()) FAIL("cross-attn layer %sattn2 not registered", t.c_str());
+      xp = &c->xl[it->second];
+      API_CK(c, concat_rows(c, {ck, cv}, xp->wkv, false));
+      xp->wqT.w = nullptr; xp->wkvT.w = nullptr; xp->woT.w = nullptr;     // the backward's transposes: rebuilt (same buffers) on next use
+    }
+    XLayer& xl = *xp;
     // pre-multiplied attn2 (xattn_pre.hip) where it saves work: H x 80 padded token columns <= C / 2, i.e. head dim >= 160 (SD-1.x: the C = 1280 blocks)
     { const WMat* wq2 = getW(c, t + "attn2.to_q.weight"); const WMat* wo2 = getW(c, t + "attn2.to_out.0.weight");
       auto be2 = c->V.find(t + "norm2.bias");
@@ -1367,12 +1419,12 @@ AGD_API int agd_finalize(agd_ctx* c) {
       //  half-chip chain kernel)
       if (wq2 && wo2 && be2 != c->V.end() && D2 % 8 == 0 && C2 % 160 == 0 && C2 % 64 == 0 && (xl.heads * XATTN_TP) % 64 == 0 && xl.heads * XATTN_TP <= C2 &&
           wq2->taps == 1 && wq2->N == C2 && wq2->Cpad == C2 && wo2->taps == 1 && wo2->N == C2 && wo2->Cpad == C2) {
-        xl.pm_wqT = dmalloc<bf16_t>(c, (size_t)C2 * C2); xl.pm_wqb = dmalloc<float>(c, C2);
+        if (alloc) { xl.pm_wqT = dmalloc<bf16_t>(c, (size_t)C2 * C2); xl.pm_wqb = dmalloc<float>(c, C2); }
         if (!xl.pm_wqT || !xl.pm_wqb) return fail_ctx(c);
         API_CK(c, launch_transpose_bf16(wq2->w, C2, C2, xl.pm_wqT, 0));
         API_CK(c, launch_matvec_bf16(wq2->w, be2->second, xl.pm_wqb, C2, C2, 0));       // (Wq beta)[(h,d)]
       } }
-    c->xl_idx[xl.name] = (int)c->xl.size(); c->xl.push_back(xl);
+    if (alloc) { c->xl_idx[xl.name] = (int)c->xl.size(); c->xl.push_back(xl); }
     // LayerNorm folded into the three GEMMs it feeds: W' = W diag(gamma), colsum(W'), bias' = bias + W beta
     struct Fold { const char* w; const char* bias; const char* ln; int geglu; };
     const Fold folds[3] = {{"attn1.qkv", nullptr, "norm1", 0}, {"attn2.to_q.weight", nullptr, "norm2", 0}, {"ff.net.0.proj.weight", "ff.net.0.proj.bias", "norm3", 16}};
@@ -1382,29 +1434,30 @@ AGD_API int agd_finalize(agd_ctx* c) {
       const float* b0 = f.bias ? getV(c, t + f.bias) : nullptr;
       if (f.bias && !b0) return fail_ctx(c);
       if (w->taps != 1 || w->Cpad != w->Cin) { agd_set_error("%s: cannot fold LayerNorm (padded K)", (t + f.w).c_str()); return fail_ctx(c); }
-      WMat wf = *w; wf.w = dmalloc<bf16_t>(c, (size_t)w->N * w->Cpad);
-      float* cs = dmalloc<float>(c, w->N); float* bf = dmalloc<float>(c, w->N);
+      const std::string k = t + f.w + ".lnfold";
+      WMat wf = *w; wf.w = wbuf(k, (size_t)w->N * w->Cpad);
+      float* cs = vbuf(k + ".cs", w->N); float* bf = vbuf(k + ".bias", w->N);
       if (!wf.w || !cs || !bf) return fail_ctx(c);
       API_CK(c, launch_ln_fold_weight(w->w, ga, be, b0, w->N, w->Cpad, f.geglu, wf.w, cs, bf, 0));
-      const std::string k = t + f.w + ".lnfold";
-      c->W[k] = wf; c->V[k + ".cs"] = cs; c->V[k + ".bias"] = bf; c->Vn[k + ".cs"] = w->N; c->Vn[k + ".bias"] = w->N;
+      if (alloc) { c->W[k] = wf; c->V[k + ".cs"] = cs; c->V[k + ".bias"] = bf; c->Vn[k + ".cs"] = w->N; c->Vn[k + ".bias"] = w->N; }
     }
     if (q->N == 1280) {                                 // the C = 1280 GEGLU matrix once more in igemm_wreg.h's fragment order (option wreg_mask bit 0)
       auto it = c->W.find(t + "ff.net.0.proj.weight.lnfold");
       if (it != c->W.end() && it->second.taps == 1 && it->second.N % 256 == 0) {
         WMat& wm_ = it->second;
-        wm_.wfrag = dmalloc<bf16_t>(c, (size_t)wm_.N * wm_.Cpad); if (!wm_.wfrag) return fail_ctx(c);
+        if (alloc) wm_.wfrag = dmalloc<bf16_t>(c, (size_t)wm_.N * wm_.Cpad);
+        if (!wm_.wfrag) return fail_ctx(c);
         API_CK(c, launch_frag_order_w(wm_.w, wm_.wfrag, wm_.N, wm_.Cpad, 4, wm_.Cpad, 0)); wm_.wfrag_ni = 4;
       }
     }
     // ff.net.2 and proj_out pre-multiplied: [Wp W2 | Wp] (rows of 5 C) and Wp b2 + bp, for the blocks whose feed-forward runs as separate launches
-    { const WMat* w2 = getW(c, t + "ff.net.2.weight"); const WMat* wp = getW(c, pr.first + "proj_out.weight");
-      auto b2 = c->V.find(t + "ff.net.2.bias"); auto bp = c->V.find(pr.first + "proj_out.bias");
+    { const WMat* w2 = getW(c, t + "ff.net.2.weight"); const WMat* wp = getW(c, pre + "proj_out.weight");
+      auto b2 = c->V.find(t + "ff.net.2.bias"); auto bp = c->V.find(pre + "proj_out.bias");
       if (w2 && wp && b2 != c->V.end() && bp != c->V.end() && w2->taps == 1 && wp->taps == 1 && wp->N == q->N && wp->Cpad == q->N && w2->N == q->N && w2->Cpad == 4 * q->N) {
         const int C = q->N;
-        bf16_t* w2t = dmalloc<bf16_t>(c, (size_t)4 * C * C);
+        bf16_t* w2t = alloc ? dmalloc<bf16_t>(c, (size_t)4 * C * C) : scratch;
         WMat wc = *wp; wc.N = C; wc.taps = 1; wc.Cpad = 5 * C; wc.Cin = 5 * C; wc.wfrag = nullptr; wc.wfrag_ni = 0; wc.sc_cols = 0;
-        wc.w = dmalloc<bf16_t>(c, (size_t)C * 5 * C); float* bc = dmalloc<float>(c, C);
+        wc.w = wbuf(pre + "ffproj.weight", (size_t)C * 5 * C); float* bc = vbuf(pre + "ffproj.bias", C);
         if (!w2t || !wc.w || !bc) return fail_ctx(c);
         API_CK(c, launch_transpose_bf16(w2->w, C, 4 * C, w2t, 0));                       // W2 [C][4C] -> [4C][C]
         { WMat wt; wt.w = w2t; wt.N = 4 * C; wt.Cin = C; wt.Cpad = C; wt.taps = 1;        // (Wp W2)[n][k] = sum_j Wp[n][j] W2T[k][j]: Wp's rows as the activation rows
@@ -1420,17 +1473,17 @@ AGD_API int agd_finalize(agd_ctx* c) {
           hbp[n] = (float)a;
         }
         if (hipMemcpy(bc, hbp.data(), C * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { agd_set_error("finalize: ff/proj bias write failed"); return fail_ctx(c); }
-        c->W[pr.first + "ffproj.weight"] = wc; c->V[pr.first + "ffproj.bias"] = bc; c->Vn[pr.first + "ffproj.bias"] = C;
+        if (alloc) { c->W[pre + "ffproj.weight"] = wc; c->V[pre + "ffproj.bias"] = bc; c->Vn[pre + "ffproj.bias"] = C; }
         if (C == 320) {                                   // the fused feed-forward kernel's form of it: Wp W2 alone, in ff.net.2's fragment order
-          bf16_t* tmpc = dmalloc<bf16_t>(c, (size_t)C * 4 * C); WMat f2p = *w2; f2p.wfrag = nullptr; f2p.wfrag_ni = 0;
-          f2p.w = dmalloc<bf16_t>(c, (size_t)C * 4 * C);
+          bf16_t* tmpc = alloc ? dmalloc<bf16_t>(c, (size_t)C * 4 * C) : scratch + (size_t)4 * C * C; WMat f2p = *w2; f2p.wfrag = nullptr; f2p.wfrag_ni = 0;
+          f2p.w = wbuf(t + "ff.w2p.frag", (size_t)C * 4 * C);
           if (!tmpc || !f2p.w) return fail_ctx(c);
           if (hipMemcpy2D(tmpc, (size_t)4 * C * 2, wc.w, (size_t)5 * C * 2, (size_t)4 * C * 2, C, hipMemcpyDeviceToDevice) != hipSuccess) { agd_set_error("finalize: Wp W2 copy failed"); return fail_ctx(c); }
           API_CK(c, launch_frag_order_w(tmpc, f2p.w, C, 4 * C, C / 64, 128, 0));
-          c->W[t + "ff.w2p.frag"] = f2p;
-          hipDeviceSynchronize(); dfree(c, tmpc);          // load-time scratch
+          if (alloc) c->W[t + "ff.w2p.frag"] = f2p;
+          hipDeviceSynchronize(); if (alloc) dfree(c, tmpc);          // load-time scratch
         }
-        hipDeviceSynchronize(); dfree(c, w2t);
+        hipDeviceSynchronize(); if (alloc) dfree(c, w2t);
       } }
     // fused row-panel kernels (tblock.hip, C = 320 blocks): the matrices once more in MFMA fragment order
     if (q->N == 320 || q->N == 640) {                 // (C = 640: the attn2 chain only -- a wave's GEMM tile is 80 columns whatever C: NI = 5)
@@ -1439,62 +1492,72 @@ AGD_API int agd_finalize(agd_ctx* c) {
       if (!w1 || !w2) return fail_ctx(c);
       if (C == 320 && w1->N == 8 * C && w1->Cpad == C && w2->N == C && w2->Cpad == 4 * C && w2->taps == 1) {
         WMat f1 = *w1, f2 = *w2;
-        f1.w = dmalloc<bf16_t>(c, (size_t)w1->N * C); f2.w = dmalloc<bf16_t>(c, (size_t)C * 4 * C);
+        f1.w = wbuf(t + "ff.w1.frag", (size_t)w1->N * C); f2.w = wbuf(t + "ff.w2.frag", (size_t)C * 4 * C);
         if (!f1.w || !f2.w) return fail_ctx(c);
         API_CK(c, launch_frag_order_w1(w1->w, f1.w, C, 4 * C, 0));
         API_CK(c, launch_frag_order_w(w2->w, f2.w, C, 4 * C, C / 64, 128, 0));
-        c->W[t + "ff.w1.frag"] = f1; c->W[t + "ff.w2.frag"] = f2;
-        const WMat* wp = getW(c, pr.first + "proj_out.weight");
+        if (alloc) { c->W[t + "ff.w1.frag"] = f1; c->W[t + "ff.w2.frag"] = f2; }
+        const WMat* wp = getW(c, pre + "proj_out.weight");
         if (!wp) return fail_ctx(c);
         if (wp->N == C && wp->Cpad == C && wp->taps == 1) {
-          WMat fp_ = *wp; fp_.w = dmalloc<bf16_t>(c, (size_t)C * C); if (!fp_.w) return fail_ctx(c);
+          WMat fp_ = *wp; fp_.w = wbuf(pre + "proj_out.frag", (size_t)C * C); if (!fp_.w) return fail_ctx(c);
           API_CK(c, launch_frag_order_w(wp->w, fp_.w, C, C, C / 64, C, 0));
-          c->W[pr.first + "proj_out.frag"] = fp_;
+          if (alloc) c->W[pre + "proj_out.frag"] = fp_;
         }
 
       }
       if (C == 640) {                                   // proj_in / proj_out once more in igemm_wreg.h's fragment order (option wreg_mask bit 1)
         for (const char* nm : {"proj_in.weight", "proj_out.weight"}) {
-          auto it = c->W.find(pr.first + nm); if (it == c->W.end()) { agd_set_error("finalize: missing weight '%s%s'", pr.first.c_str(), nm); return fail_ctx(c); }
+          auto it = c->W.find(pre + nm); if (it == c->W.end()) { agd_set_error("finalize: missing weight '%s%s'", pre.c_str(), nm); return fail_ctx(c); }
           WMat& wm_ = it->second;
           if (wm_.taps == 1 && wm_.N % 128 == 0 && wm_.Cpad % 64 == 0) {
-            wm_.wfrag = dmalloc<bf16_t>(c, (size_t)wm_.N * wm_.Cpad); if (!wm_.wfrag) return fail_ctx(c);
+            if (alloc) wm_.wfrag = dmalloc<bf16_t>(c, (size_t)wm_.N * wm_.Cpad);
+            if (!wm_.wfrag) return fail_ctx(c);
             API_CK(c, launch_frag_order_w(wm_.w, wm_.wfrag, wm_.N, wm_.Cpad, 2, wm_.Cpad, 0)); wm_.wfrag_ni = 2;
           }
         }
       }
-      { const WMat* wi = getW(c, pr.first + "proj_in.weight");
+      { const WMat* wi = getW(c, pre + "proj_in.weight");
         if (!wi) return fail_ctx(c);
         if (wi->N == C && wi->Cpad == C && wi->taps == 1) {
-          WMat fi = *wi; fi.w = dmalloc<bf16_t>(c, (size_t)C * C); if (!fi.w) return fail_ctx(c);
+          WMat fi = *wi; fi.w = wbuf(pre + "proj_in.frag", (size_t)C * C); if (!fi.w) return fail_ctx(c);
           API_CK(c, launch_frag_order_w(wi->w, fi.w, C, C, 5, C, 0));
-          c->W[pr.first + "proj_in.frag"] = fi;
+          if (alloc) c->W[pre + "proj_in.frag"] = fi;
         } }
       const WMat* wq = getW(c, t + "attn2.to_q.weight"); const WMat* wo = getW(c, t + "attn2.to_out.0.weight");
       if (!wq || !wo) return fail_ctx(c);
       if (wq->N == C && wq->Cpad == C && wq->taps == 1 && wo->N == C && wo->Cpad == C && wo->taps == 1 && xl.heads == 8) {
         WMat fq = *wq, fo = *wo;
-        fq.w = dmalloc<bf16_t>(c, (size_t)C * C); fo.w = dmalloc<bf16_t>(c, (size_t)C * C);
+        fq.w = wbuf(t + "attn2.to_q.frag", (size_t)C * C); fo.w = wbuf(t + "attn2.to_out.frag", (size_t)C * C);
         if (!fq.w || !fo.w) return fail_ctx(c);
         API_CK(c, launch_frag_order_w(wq->w, fq.w, C, C, 5, C, 0));
         API_CK(c, launch_frag_order_w(wo->w, fo.w, C, C, 5, C, 0));
-        c->W[t + "attn2.to_q.frag"] = fq; c->W[t + "attn2.to_out.frag"] = fo;
+        if (alloc) { c->W[t + "attn2.to_q.frag"] = fq; c->W[t + "attn2.to_out.frag"] = fo; }
         { const WMat* wqkv = getW(c, t + "attn1.qkv"); if (!wqkv) return fail_ctx(c);
           if (wqkv->N == 3 * C && wqkv->Cpad == C && wqkv->taps == 1) {
-            WMat fqkv = *wqkv; fqkv.w = dmalloc<bf16_t>(c, (size_t)3 * C * C); if (!fqkv.w) return fail_ctx(c);
+            WMat fqkv = *wqkv; fqkv.w = wbuf(t + "attn1.qkv.frag", (size_t)3 * C * C); if (!fqkv.w) return fail_ctx(c);
             API_CK(c, launch_frag_order_w(wqkv->w, fqkv.w, 3 * C, C, 5, C, 0));
-            c->W[t + "attn1.qkv.frag"] = fqkv;
+            if (alloc) c->W[t + "attn1.qkv.frag"] = fqkv;
           } }
         const WMat* wo1 = getW(c, t + "attn1.to_out.0.weight");
         if (!wo1) return fail_ctx(c);
         if (wo1->N == C && wo1->Cpad == C && wo1->taps == 1) {
-          WMat f1o = *wo1; f1o.w = dmalloc<bf16_t>(c, (size_t)C * C); if (!f1o.w) return fail_ctx(c);
+          WMat f1o = *wo1; f1o.w = wbuf(t + "attn1.to_out.frag", (size_t)C * C); if (!f1o.w) return fail_ctx(c);
           API_CK(c, launch_frag_order_w(wo1->w, f1o.w, C, C, 5, C, 0));
-          c->W[t + "attn1.to_out.frag"] = f1o;
+          if (alloc) c->W[t + "attn1.to_out.frag"] = f1o;
         }
       }
     }
   }
+  return 0;
+}
+
+AGD_API int agd_finalize(agd_ctx* c) {
+  if (!c) return -1;
+  hipSetDevice(c->device);
+  const agd_config& g = c->cfg;
+  // ---- transformer blocks: fused QKV + cross K/V weights, recorder layers (daam order: up, down, mid), every derived form
+  for (auto& pr : transformer_prefixes(c)) API_CK(c, derive_tblock(c, pr.first, pr.second, true, nullptr));
   // ---- the UNet's upsampling convs once more as the merged phase matrices [4 Cout][4 taps][Cin] (+ the bias four times)
   { std::vector<std::string> keys;
     const std::string tail = "upsamplers.0.conv.weight";
@@ -1599,6 +1662,7 @@ AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int to
       xl.pm_ready = true;
     }
   }
+  c->ctx_stale = false;
   return 0;
 }
 
@@ -3104,3 +3168,123 @@ AGD_API int agd_inpaint_clear(agd_ctx* c) {
   c->ip_mode = 0; c->ip_B = c->ip_L = c->ip_Cm = c->ip_Cc = 0; c->ip_sched.clear();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// LoRA (diffusers load_lora_weights / cross_attention_kwargs={"scale": s}): low-rank updates of the UNet transformer blocks' linears and
+// the text encoder's, merged into the raw matrices on the device (lora.hip) and every form derived from them rewritten in place
+// (derive_tblock, fuse_clip_qkv) -- the denoise loop then runs the same kernels on the same buffers
+// ---------------------------------------------------------------------------------------
+static const char* kLoraUnetTargets[] = {"transformer_blocks.0.attn1.to_q.weight", "transformer_blocks.0.attn1.to_k.weight", "transformer_blocks.0.attn1.to_v.weight",
+                                         "transformer_blocks.0.attn1.to_out.0.weight", "transformer_blocks.0.attn2.to_q.weight", "transformer_blocks.0.attn2.to_k.weight",
+                                         "transformer_blocks.0.attn2.to_v.weight", "transformer_blocks.0.attn2.to_out.0.weight", "transformer_blocks.0.ff.net.0.proj.weight",
+                                         "transformer_blocks.0.ff.net.2.weight", "proj_in.weight", "proj_out.weight"};
+static const char* kLoraTextTargets[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.out_proj.weight",
+                                         "mlp.fc1.weight", "mlp.fc2.weight"};
+static const char* kTextLayers = "text.encoder.layers.";
+
+// the UNet transformer block (prefix) a target key belongs to; "" for a text-encoder target or no target at all
+static std::string lora_block_of(agd_ctx* c, const std::string& key) {
+  for (auto& pr : transformer_prefixes(c)) {
+    if (pr.first.compare(0, 5, "unet.") != 0 || key.compare(0, pr.first.size(), pr.first) != 0) continue;
+    for (const char* s : kLoraUnetTargets) if (key.compare(pr.first.size(), std::string::npos, s) == 0) return pr.first;
+  }
+  return "";
+}
+static bool lora_text_target(agd_ctx* c, const std::string& key) {
+  for (int l = 0; l < c->cfg.text_layers; ++l) {
+    const std::string L = std::string(kTextLayers) + std::to_string(l) + ".";
+    if (key.compare(0, L.size(), L) != 0) continue;
+    for (const char* s : kLoraTextTargets) if (key.compare(L.size(), std::string::npos, s) == 0) return true;
+  }
+  return false;
+}
+
+// rewrites, in place, every derived form of the blocks the LoRA touches (and the text encoder's fused q/k/v)
+static int lora_rederive(agd_ctx* c) {
+  bool text = false;
+  for (const std::string& k : c->lora_keys) if (k.compare(0, 5, "text.") == 0) text = true;
+  for (auto& pr : transformer_prefixes(c)) {
+    if (pr.first.compare(0, 5, "unet.") != 0) continue;              // the ControlNet's blocks: never a LoRA target
+    bool hit = false;
+    for (const std::string& k : c->lora_keys) if (k.compare(0, pr.first.size(), pr.first) == 0) { hit = true; break; }
+    if (hit) CK(derive_tblock(c, pr.first, pr.second, false, c->lora_scratch));
+  }
+  if (text) CK(fuse_clip_qkv(c, kTextLayers, c->cfg.text_layers, false));
+  return 0;
+}
+
+AGD_API int agd_lora_add(agd_ctx* c, const char* target_key, const float* down, const float* up, int rank, float alpha) {
+  API_CK(c, need_final(c));
+  if (!target_key || !down || !up) { agd_set_error("agd_lora_add: null argument"); return fail_ctx(c); }
+  const std::string k(target_key);
+  for (const char* refused : {"controlnet.", "safety.", "vae."})
+    if (k.compare(0, strlen(refused), refused) == 0) { agd_set_error("agd_lora_add: '%s': LoRA on the %.*s is not supported", target_key, (int)strlen(refused) - 1, refused); return fail_ctx(c); }
+  const std::string block = lora_block_of(c, k);
+  if (block.empty() && !lora_text_target(c, k)) { agd_set_error("agd_lora_add: '%s' is not a LoRA target (transformer-block linears, proj_in / proj_out, text-encoder q/k/v/out_proj/fc1/fc2)", target_key); return fail_ctx(c); }
+  auto it = c->W.find(k);
+  if (it == c->W.end()) { agd_set_error("agd_lora_add: no weight '%s' loaded", target_key); return fail_ctx(c); }
+  const WMat& w = it->second;
+  if (w.taps != 1) { agd_set_error("agd_lora_add: '%s' is not a linear / 1x1 matrix", target_key); return fail_ctx(c); }
+  if (rank < 1 || rank > 4096 || !(alpha > 0.f) || !std::isfinite(alpha)) { agd_set_error("agd_lora_add: '%s': rank %d / alpha %g", target_key, rank, (double)alpha); return fail_ctx(c); }
+  for (const std::string& o : c->lora_keys) if (o == k) { agd_set_error("agd_lora_add: '%s' already has a LoRA (one adapter at a time: agd_lora_clear first)", target_key); return fail_ctx(c); }
+  // room the in-place re-derivation of this block needs ([4C][C] transposed W2 + [C][4C] Wp W2), held from here on: set_scale allocates nothing
+  if (!block.empty()) {
+    const WMat* q = getW(c, block + "transformer_blocks.0.attn1.to_q.weight"); if (!q) return fail_ctx(c);
+    const size_t need = (size_t)8 * q->N * q->N;
+    if (need > c->lora_scratch_n) {
+      hipDeviceSynchronize(); dfree(c, c->lora_scratch); c->lora_scratch = nullptr; c->lora_scratch_n = 0;
+      c->lora_scratch = dmalloc<bf16_t>(c, need); if (!c->lora_scratch) return fail_ctx(c);
+      c->lora_scratch_n = need;
+    }
+  }
+  LoraMergeD d{};
+  d.N = w.N; d.Cin = w.Cin; d.Cpad = w.Cpad; d.r = rank; d.geglu = ends_with(k, "ff.net.0.proj.weight") ? 16 : 0; d.coef = alpha / (float)rank;
+  d.dst = w.w;
+  float* dn = dmalloc<float>(c, (size_t)rank * w.Cin); float* upd = dmalloc<float>(c, (size_t)w.N * rank); bf16_t* base = dmalloc<bf16_t>(c, (size_t)w.N * w.Cpad);
+  if (!dn || !upd || !base) { dfree(c, dn); dfree(c, upd); dfree(c, base); return fail_ctx(c); }
+  // the target's first touch: its base matrix is still what was loaded (a target takes one LoRA at a time)
+  if (hipMemcpy(dn, down, (size_t)rank * w.Cin * 4, hipMemcpyDefault) != hipSuccess || hipMemcpy(upd, up, (size_t)w.N * rank * 4, hipMemcpyDefault) != hipSuccess ||
+      hipMemcpy(base, w.w, (size_t)w.N * w.Cpad * 2, hipMemcpyDeviceToDevice) != hipSuccess) {
+    dfree(c, dn); dfree(c, upd); dfree(c, base); agd_set_error("agd_lora_add: '%s': factor upload failed", target_key); return fail_ctx(c); }
+  d.down = dn; d.up = upd; d.base = base; d.tile0 = c->lora_tiles;
+  c->lora_keys.push_back(k); c->lora_d.push_back(d); c->lora_tiles += lora_merge_tiles(d.N, d.Cpad);
+  API_CK(c, c->lora_descb.ensure(c->lora_d.size() * sizeof(LoraMergeD)));
+  if (hipMemcpy(c->lora_descb.p, c->lora_d.data(), c->lora_d.size() * sizeof(LoraMergeD), hipMemcpyHostToDevice) != hipSuccess) { agd_set_error("agd_lora_add: descriptor upload failed"); return fail_ctx(c); }
+  c->lora_dirty = true;                                // the new target is still at its base: the next set_scale merges everything
+  return 0;
+}
+
+// s = 0 copies the base matrices back; a repeated s does nothing.  Synchronous: the merge and re-derivation run on the null stream after
+// `stream` has drained.  Allocates nothing.
+static int lora_apply(agd_ctx* c, float s, hipStream_t st) {
+  if (hipStreamSynchronize(st) != hipSuccess) FAIL("lora: stream sync failed");
+  c->lora_dirty = true;                                // until the whole rewrite has succeeded
+  CK(launch_lora_merge(c->lora_descb.as<LoraMergeD>(), (int)c->lora_d.size(), c->lora_tiles, s, s == 0.f ? 1 : 0, 0));
+  CK(lora_rederive(c));
+  if (hipDeviceSynchronize() != hipSuccess) FAIL("lora: merge failed");
+  c->lora_scale = s; c->lora_dirty = false; c->ctx_stale = true;
+  return 0;
+}
+
+AGD_API int agd_lora_set_scale(agd_ctx* c, float s, void* stream) {
+  API_CK(c, need_final(c));
+  if (!std::isfinite(s)) { agd_set_error("agd_lora_set_scale: scale %g", (double)s); return fail_ctx(c); }
+  if (c->lora_d.empty()) { agd_set_error("agd_lora_set_scale: no LoRA loaded (agd_lora_add)"); return fail_ctx(c); }
+  if (!c->lora_dirty && s == c->lora_scale) return 0;
+  API_CK(c, lora_apply(c, s, S(stream)));
+  return 0;
+}
+
+AGD_API int agd_lora_clear(agd_ctx* c) {
+  API_CK(c, need_final(c));
+  if (c->lora_d.empty()) return 0;
+  API_CK(c, lora_apply(c, 0.f, 0));                    // the base matrices back, every derived form from them
+  for (auto& d : c->lora_d) { dfree(c, (void*)d.down); dfree(c, (void*)d.up); dfree(c, (void*)d.base); }
+  dfree(c, c->lora_scratch); c->lora_scratch = nullptr; c->lora_scratch_n = 0;
+  c->lora_descb.release();
+  c->lora_keys.clear(); c->lora_d.clear(); c->lora_tiles = 0; c->lora_scale = 0.f; c->lora_dirty = false;
+  return 0;
+}
+
+AGD_API int agd_lora_count(agd_ctx* c) { return c ? (int)c->lora_d.size() : 0; }
+AGD_API float agd_lora_scale(agd_ctx* c) { return c ? c->lora_scale : 0.f; }

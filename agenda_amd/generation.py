@@ -266,7 +266,13 @@ def parse_args(argv=None):
     p.add_argument("--mask-image", type=str, default=None,
                    help="inpainting: the mask, white = repaint (file or directory, paired with --init-image by sorted name)")
     p.add_argument("--strength", type=float, default=1.0, help="inpainting: 1 starts from noise; < 1 (DDIM only) from the noised image")
+    p.add_argument("--lora-path", type=str, default=None,
+                   help="a LoRA file or directory (kohya or diffusers format) merged into the UNet / text encoder on every rank")
+    p.add_argument("--lora-weight-name", type=str, default=None, help="the LoRA file inside --lora-path (default pytorch_lora_weights.safetensors, then .bin)")
+    p.add_argument("--lora-scale", type=float, default=1.0, help="the LoRA's strength (cross_attention_kwargs scale)")
     args = p.parse_args(argv)
+    if args.lora_path is None and (args.lora_weight_name is not None or args.lora_scale != 1.0):
+        p.error("--lora-weight-name / --lora-scale need --lora-path")
     if (args.init_image is None) != (args.mask_image is None):
         p.error("--init-image and --mask-image go together")
     if args.init_image is not None and args.controlnet_model_path:
@@ -341,6 +347,9 @@ def main(argv=None):
             if args.pretrained_model_path else
             cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
                                **({"controlnet": kw["controlnet"]} if cn_files else {})))
+    if args.lora_path:
+        pipe.load_lora_weights(args.lora_path, weight_name=args.lora_weight_name)
+        pipe.fuse_lora(lora_scale=args.lora_scale)
     if args.use_karras_sigmas:
         from .scheduler import DPMSolverMultistepScheduler
         pipe.cfg.sched.use_karras_sigmas = True

@@ -191,7 +191,7 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
                  negative_prompt=None, num_images_per_prompt: int = 1, generator: Optional[torch.Generator] = None,
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  noise_enc_image: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                 noise_enc_masked: Optional[torch.Tensor] = None):
+                 noise_enc_masked: Optional[torch.Tensor] = None, cross_attention_kwargs: Optional[dict] = None):
         """image / mask_image as `prepare_mask_and_image` takes them.  Noise draws come from a CPU generator in diffusers' order, or are
         passed explicitly (noise_enc_image [N,4,L,L], noise (or latents) [B,4,L,L], noise_enc_masked [N,4,L,L]; N distinct images)."""
         if image is None or mask_image is None:
@@ -201,6 +201,7 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
         if height != width or height % 64:
             raise ValueError("height == width, multiple of 64 required")
         flavour = check_request(self.cfg, self.scheduler, strength, num_inference_steps)
+        self._apply_lora_scale(cross_attention_kwargs)
         L = height // self.vae_scale_factor
         img, mask = prepare_mask_and_image(image, mask_image, height, width)
         if prompt_embeds is None:

@@ -258,6 +258,19 @@ class Engine:
         self._ck(self.lib.agd_inpaint_clear(self.ctx), "agd_inpaint_clear")
         self._inpaint_state = None
 
+    def lora_add(self, key: str, down: torch.Tensor, up: torch.Tensor, alpha: float):
+        """Stages one target's fp32 factors (down [r, in], up [out, r]) and a copy of its base matrix; the weights stay at the base."""
+        d, u = down.detach().to("cpu", torch.float32).contiguous(), up.detach().to("cpu", torch.float32).contiguous()
+        self._ck(self.lib.agd_lora_add(self.ctx, key.encode(), C.c_void_p(d.data_ptr()), C.c_void_p(u.data_ptr()), int(d.shape[0]), float(alpha)),
+                 f"agd_lora_add({key})")
+
+    def lora_set_scale(self, s: float):
+        """Merges the staged LoRA at scale s and rewrites every derived form (no work when s is the current scale)."""
+        self._ck(self.lib.agd_lora_set_scale(self.ctx, float(s), self._stream()), "agd_lora_set_scale")
+
+    def lora_clear(self):
+        self._ck(self.lib.agd_lora_clear(self.ctx), "agd_lora_clear")
+
     def text_set_embedding_row(self, token_id: int, row: torch.Tensor):
         row = row.detach().to(torch.float32).contiguous()
         self._ck(self.lib.agd_text_set_embedding_row(self.ctx, int(token_id), C.c_void_p(row.data_ptr())), "agd_text_set_embedding_row")
@@ -588,6 +601,7 @@ class StableDiffusionPipeline:
         self._hooker = None
         self._last_prompt = None
         self._progress = {}
+        self._lora = None                 # load_lora_weights: {"targets": n, "fused": scale or None}
         self._source_path = None          # from_pretrained: the checkpoint directory (save_pretrained re-exports from it)
         # diffusers' `pipeline.safety_checker` slot: None (no checker weights ship with this repo) or a callable
         # images uint8 [B,H,W,3] (cuda tensor) -> sequence of B bools; flagged images are returned black, which the generation
@@ -716,6 +730,47 @@ class StableDiffusionPipeline:
         pipe._source_path = src_path
         return pipe
 
+    # ---- LoRA (diffusers 0.21 LoraLoaderMixin surface; merged on the device, lora.py / agd_lora_*) -----------------------------
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name: Optional[str] = None, **kwargs):
+        """One LoRA adapter for the UNet transformer blocks and the text encoder: a state dict, a file, or a directory holding
+        `weight_name` (default pytorch_lora_weights.safetensors, then .bin).  A second load replaces the first.  Its strength is
+        `cross_attention_kwargs={"scale": s}` per call (default 1.0), or fixed by fuse_lora()."""
+        from . import lora
+        entries = lora.lora_to_engine(lora.load_lora_state_dict(pretrained_model_name_or_path_or_dict, weight_name), self.cfg)
+        self.unload_lora_weights()
+        try:
+            for e in entries:
+                self.engine.lora_add(e.key, e.down, e.up, e.alpha)
+        except Exception:
+            self.engine.lora_clear()
+            raise
+        self._lora = {"targets": len(entries), "fused": None}
+
+    def unload_lora_weights(self):
+        """The base weights back (bit for bit) and the LoRA state freed."""
+        if getattr(self, "_lora", None) is not None:
+            self.engine.lora_clear()
+        self._lora = None
+
+    def fuse_lora(self, lora_scale: float = 1.0):
+        """Keeps the LoRA merged at `lora_scale`: per-call scales are ignored until unfuse_lora()."""
+        if getattr(self, "_lora", None) is None:
+            raise ValueError("fuse_lora: no LoRA loaded (load_lora_weights first)")
+        self.engine.lora_set_scale(float(lora_scale))
+        self._lora["fused"] = float(lora_scale)
+
+    def unfuse_lora(self):
+        if getattr(self, "_lora", None) is not None:
+            self._lora["fused"] = None
+
+    def _apply_lora_scale(self, cross_attention_kwargs: Optional[dict]):
+        """Before the prompt is encoded and the context projected: the call's LoRA scale (a fused scale wins)."""
+        st = getattr(self, "_lora", None)
+        if st is None:
+            return
+        s = st["fused"] if st["fused"] is not None else float((cross_attention_kwargs or {}).get("scale", 1.0))
+        self.engine.lora_set_scale(s)
+
     def save_pretrained(self, save_directory: str):
         """`pipeline.save_pretrained(dir)` (finetune_sd_token.py:164-187 writes its result this way): the diffusers layout
         `from_pretrained` reads.  This pipeline is an inference engine -- UNet / VAE / scheduler are exactly what was loaded, so
@@ -724,6 +779,8 @@ class StableDiffusionPipeline:
         tokenizer is saved with its added tokens and the text encoder with its current (resized) embedding table."""
         import shutil
         from safetensors.torch import load_file, save_file
+        if getattr(self, "_lora", None) is not None:
+            raise ValueError("save_pretrained: a LoRA is loaded; call unload_lora_weights() to save the base weights")
         if self._source_path is None:
             raise ValueError("save_pretrained: this pipeline was built from in-memory weights (no checkpoint directory to re-export)")
         src, dst = self._source_path, save_directory
@@ -819,8 +876,10 @@ class StableDiffusionPipeline:
     def __call__(self, prompt: Union[str, List[str], None] = None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
-                 prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1):
+                 prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
+                 cross_attention_kwargs: Optional[dict] = None):
         self._refuse_inpainting_unet()
+        self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
         if height != width or height % 64:
@@ -901,13 +960,15 @@ class StableDiffusionPipeline:
     @torch.no_grad()
     def img2img(self, prompt=None, image: torch.Tensor = None, strength: float = 0.8, num_inference_steps: int = 50,
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
-                noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil"):
+                noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
+                cross_attention_kwargs: Optional[dict] = None):
         """image: float [B,3,S,S] in [-1,1] (or uint8 [B,S,S,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
         # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
         # PLMS and DPM-Solver++ img2img are not implemented)
         self._refuse_inpainting_unet()
+        self._apply_lora_scale(cross_attention_kwargs)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
             image = image.permute(0, 3, 1, 2).float() / 127.5 - 1.0

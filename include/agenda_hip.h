@@ -322,6 +322,23 @@ int agd_op_resize_u8_pil(const unsigned char* in, int n, int H, int W, int C, in
 int agd_op_stack_heatmaps(const unsigned char* obj, const unsigned char* fg, const unsigned char* bg, long long npix,
                           unsigned char* rgb, unsigned char* inv, void* stream);
 
+/* ---- LoRA (diffusers load_lora_weights + cross_attention_kwargs={"scale": s}): one adapter of low-rank updates on the UNet transformer
+ * blocks' linears (attn1 / attn2 to_q, to_k, to_v, to_out.0; ff.net.0.proj; ff.net.2; proj_in; proj_out) and the text encoder's (q/k/v/out_proj,
+ * fc1, fc2), merged on the device: W = bf16(float(W_base) + s * (alpha / rank) * up @ down), then every form finalize derived from W is
+ * rewritten in place.  Call after agd_finalize.
+ * agd_lora_add: target_key = the engine key agd_load_tensor saw ("unet.<diffusers key>", "text.encoder.layers.<l>.self_attn.q_proj.weight", ...;
+ *   "controlnet.", "safety." and "vae." keys are refused); down fp32 [rank][in], up fp32 [out][rank] (host or device; 1x1-conv factors
+ *   flattened).  Stages the factors and a bf16 copy of the target's base matrix (first touch); the weights stay at the base until
+ *   agd_lora_set_scale.  A target takes one LoRA at a time.
+ * agd_lora_set_scale: merges at scale s and re-derives (synchronous; allocates nothing).  s equal to the current scale: no work; s = 0: the
+ *   base matrices.  Afterwards the projected context is stale: agd_unet_forward / the fused loops fail until agd_set_context runs again.
+ * agd_lora_clear: the base matrices back (re-derived), the LoRA state freed. */
+int agd_lora_add(agd_ctx* ctx, const char* target_key, const float* down, const float* up, int rank, float alpha);
+int agd_lora_set_scale(agd_ctx* ctx, float s, void* stream);
+int agd_lora_clear(agd_ctx* ctx);
+int agd_lora_count(agd_ctx* ctx);                    /* targets staged */
+float agd_lora_scale(agd_ctx* ctx);                  /* the scale the weights hold now */
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
