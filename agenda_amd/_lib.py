@@ -99,6 +99,22 @@ _SIGS = {
     "agd_denoise_dpm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _P]),
     "agd_vae_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "agd_vae_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "agd_safety_scores_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "agd_controlnet_set_cond_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "agd_controlnet_residuals_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, C.POINTER(C.c_longlong), _P]),
+    "agd_inpaint_prepare_hw": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "agd_inpaint_set_hw": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "agd_unet_forward_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "agd_unet_forward_ts_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
+    "agd_cfg_ddim_step_hw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P]),
+    "agd_denoise_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_float), C.c_float, _P]),
+    "agd_denoise_plms_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.c_float, _P]),
+    "agd_denoise_dpm_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _P]),
+    "agd_vae_decode_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "agd_vae_encode_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "agd_record_reset_hw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "agd_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "agd_record_config": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "agd_record_reset": (C.c_int, [_P, C.c_int, C.c_int, _P]),

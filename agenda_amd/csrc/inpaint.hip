@@ -6,16 +6,16 @@ static inline int grid_for(long long n) { long long g = (n + 255) / 256; return 
 
 // One thread per image pixel.  image: uint8 NHWC [B][S][S][3] (x / 255, then 2 x - 1, in fp32) or, image_f32, fp32 NCHW [B][3][S][S]
 // already in [-1,1]; mask: uint8 [B][S][S] (/ 255) or, mask_f32, fp32 [B][S][S] in [0,1], binarized m < 0.5 -> 0, else 1.
-// image_out / masked_out fp32 NCHW [B][3][S][S] (masked = image * (m < 0.5)); mask_lat fp32 [B][1][S/f][S/f] takes pixel (f i, f j)
+// image_out / masked_out fp32 NCHW [B][3][H][W] (masked = image * (m < 0.5)); mask_lat fp32 [B][1][H/f][W/f] takes pixel (f i, f j)
 // (nearest).  Any output may be null.
-__global__ void inpaint_front_kernel(const void* __restrict__ image, int image_f32, const void* __restrict__ mask, int mask_f32, int B, int S,
-                                     int f, float* __restrict__ image_out, float* __restrict__ masked_out, float* __restrict__ mask_lat) {
-  const long long HW = (long long)S * S, total = (long long)B * HW;
-  const int L = S / f;
+__global__ void inpaint_front_kernel(const void* __restrict__ image, int image_f32, const void* __restrict__ mask, int mask_f32, int B, int H,
+                                     int W, int f, float* __restrict__ image_out, float* __restrict__ masked_out, float* __restrict__ mask_lat) {
+  const long long HW = (long long)H * W, total = (long long)B * HW;
+  const int Lh = H / f, Lw = W / f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int b = (int)(i / HW);
     const long long p = i - (long long)b * HW;
-    const int y = (int)(p / S), x = (int)(p - (long long)y * S);
+    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
     const float m = mask_f32 ? ((const float*)mask)[i] : (float)((const unsigned char*)mask)[i] / 255.0f;
     const float mb = m < 0.5f ? 0.f : 1.f;
     const float keep = mb < 0.5f ? 1.f : 0.f;
@@ -28,13 +28,13 @@ __global__ void inpaint_front_kernel(const void* __restrict__ image, int image_f
       if (image_out) image_out[o] = v;
       if (masked_out) masked_out[o] = v * keep;
     }
-    if (mask_lat && y % f == 0 && x % f == 0) mask_lat[((long long)b * L + y / f) * L + x / f] = mb;
+    if (mask_lat && y % f == 0 && x % f == 0) mask_lat[((long long)b * Lh + y / f) * Lw + x / f] = mb;
   }
 }
-int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int S, int f, float* image_out,
+int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int H, int W, int f, float* image_out,
                          float* masked_out, float* mask_lat, hipStream_t st) {
-  if (B < 1 || f < 1 || S < f || S % f) { agd_set_error("inpaint front end: batch %d side %d (a multiple of %d)", B, S, f); return -1; }
-  hipLaunchKernelGGL(inpaint_front_kernel, dim3(grid_for((long long)B * S * S)), dim3(256), 0, st, image, image_f32, mask, mask_f32, B, S, f,
+  if (B < 1 || f < 1 || H < f || H % f || W < f || W % f) { agd_set_error("inpaint front end: batch %d size %d x %d (each side a multiple of %d)", B, H, W, f); return -1; }
+  hipLaunchKernelGGL(inpaint_front_kernel, dim3(grid_for((long long)B * H * W)), dim3(256), 0, st, image, image_f32, mask, mask_f32, B, H, W, f,
                      image_out, masked_out, mask_lat);
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }

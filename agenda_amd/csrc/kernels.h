@@ -223,8 +223,8 @@ int launch_nchw_from_nhwc_f32(const float* x, int ldc, float* out, int B, int C,
 int launch_softmax_rows(const float* s, bf16_t* p, int rows, int cols, hipStream_t st);
 
 // Heat maps
-struct HeatLayer { const float* acc; int side; int heads; long long img_stride; long long head_stride; };
-int launch_daam_global(const HeatLayer* layers, int n_layers, int total_maps, int T, int S, int img, float* out, hipStream_t st);
+struct HeatLayer { const float* acc; int h, w; int heads; long long img_stride; long long head_stride; };   // accumulators [T][h][w]
+int launch_daam_global(const HeatLayer* layers, int n_layers, int total_maps, int T, int Sh, int Sw, int img, float* out, hipStream_t st);
 int launch_hook_accum(const float* map, int B, int T, int side, int S, float* sum, hipStream_t st);
 int launch_scale(float* x, long long n, float s, hipStream_t st);
 // ControlNet (controlnet.hip): fp32 NCHW [B][3][HW] -> bf16 NHWC [B][HW][Cpad] (optionally BGR-flipped); out = s * in over n floats
@@ -232,7 +232,7 @@ int launch_controlnet_cond_prep(const float* cond, bf16_t* out, int B, int HW, i
 int launch_controlnet_scale_bias(const float* in, float* out, int n, float s, hipStream_t st);
 // Inpainting (inpaint.hip): the mask front end (image [-1,1], masked image, latent-resolution binary mask), the 9-channel UNet input
 // (latents | mask | masked-image latents | zero pad, bf16 NHWC), the 4-channel blend x = (1 - m)(sa x0img + sb n) + m x
-int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int S, int f, float* image_out,
+int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int H, int W, int f, float* image_out,
                          float* masked_out, float* mask_lat, hipStream_t st);
 int launch_prep_inpaint(const float* lat, const float* mask, const float* cond, bf16_t* out, int B, int Cl, int Cm, int Cc, int HW, int Cpad,
                         int dup, hipStream_t st);

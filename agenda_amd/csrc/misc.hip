@@ -322,10 +322,11 @@ AGD_DEV float cc1(float x) { const float A = -0.75f; return ((A + 2.f) * x - (A 
 AGD_DEV float cc2(float x) { const float A = -0.75f; return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
 AGD_DEV void cubic_coeffs(float t, float* c) { c[0] = cc2(t + 1.f); c[1] = cc1(t); c[2] = cc1(1.f - t); c[3] = cc2(2.f - t); }
 
-AGD_DEV float bicubic_at(const float* __restrict__ m, int side, int S, int oy, int ox) {
-  if (side == S) return m[oy * side + ox];
-  const float scale = (float)side / (float)S;
-  const float ry = scale * (oy + 0.5f) - 0.5f, rx = scale * (ox + 0.5f) - 0.5f;
+// m: [ih][iw] -> the value at output pixel (oy, ox) of an oh x ow resize; each axis has its own scale (torch computes in / out per axis)
+AGD_DEV float bicubic_at(const float* __restrict__ m, int ih, int iw, int oh, int ow, int oy, int ox) {
+  if (ih == oh && iw == ow) return m[oy * iw + ox];
+  const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
+  const float ry = sy * (oy + 0.5f) - 0.5f, rx = sx * (ox + 0.5f) - 0.5f;
   const float fy = floorf(ry), fx = floorf(rx);
   const int iy = (int)fy, ix = (int)fx;
   float cy[4], cx[4];
@@ -334,12 +335,12 @@ AGD_DEV float bicubic_at(const float* __restrict__ m, int side, int S, int oy, i
   float acc = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int yy = min(max(iy - 1 + i, 0), side - 1);
+    const int yy = min(max(iy - 1 + i, 0), ih - 1);
     float r = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int xx = min(max(ix - 1 + j, 0), side - 1);
-      r += m[yy * side + xx] * cx[j];
+      const int xx = min(max(ix - 1 + j, 0), iw - 1);
+      r += m[yy * iw + xx] * cx[j];
     }
     acc += r * cy[i];
   }
@@ -348,26 +349,26 @@ AGD_DEV float bicubic_at(const float* __restrict__ m, int side, int S, int oy, i
 
 struct HeatLayers { HeatLayer l[24]; int n; };
 
-// daam compute_global_heat_map: mean over every (layer, head) accumulator of clamp(bicubic(acc), 0)
-__global__ void daam_global_kernel(HeatLayers L, int total_maps, int T, int S, int img, float* __restrict__ out) {
+// daam compute_global_heat_map: mean over every (layer, head) accumulator of clamp(bicubic(acc), 0), out [T][Sh][Sw]
+__global__ void daam_global_kernel(HeatLayers L, int total_maps, int T, int Sh, int Sw, int img, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= T * S * S) return;
-  const int ox = i % S, oy = (i / S) % S, t = i / (S * S);
+  if (i >= T * Sh * Sw) return;
+  const int ox = i % Sw, oy = (i / Sw) % Sh, t = i / (Sh * Sw);
   float sum = 0.f;
   for (int li = 0; li < L.n; ++li) {
     const HeatLayer& hl = L.l[li];
     for (int h = 0; h < hl.heads; ++h) {
-      const float* m = hl.acc + img * hl.img_stride + h * hl.head_stride + (long long)t * hl.side * hl.side;
-      sum += fmaxf(bicubic_at(m, hl.side, S, oy, ox), 0.f);
+      const float* m = hl.acc + img * hl.img_stride + h * hl.head_stride + (long long)t * hl.h * hl.w;
+      sum += fmaxf(bicubic_at(m, hl.h, hl.w, Sh, Sw, oy, ox), 0.f);
     }
   }
   out[i] = sum / (float)total_maps;
 }
-int launch_daam_global(const HeatLayer* layers, int n_layers, int total_maps, int T, int S, int img, float* out, hipStream_t st) {
+int launch_daam_global(const HeatLayer* layers, int n_layers, int total_maps, int T, int Sh, int Sw, int img, float* out, hipStream_t st) {
   if (n_layers > 24) { agd_set_error("daam_global: too many layers"); return -1; }
   HeatLayers L; L.n = n_layers;
   for (int i = 0; i < n_layers; ++i) L.l[i] = layers[i];
-  hipLaunchKernelGGL(daam_global_kernel, dim3((T * S * S + 255) / 256), dim3(256), 0, st, L, total_maps, T, S, img, out);
+  hipLaunchKernelGGL(daam_global_kernel, dim3((T * Sh * Sw + 255) / 256), dim3(256), 0, st, L, total_maps, T, Sh, Sw, img, out);
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }
 
@@ -377,7 +378,7 @@ __global__ void hook_accum_kernel(const float* __restrict__ map, int BT, int sid
   if (i >= (long long)BT * S * S) return;
   const int ox = (int)(i % S), oy = (int)((i / S) % S);
   const long long bt = i / ((long long)S * S);
-  sum[i] += fmaxf(bicubic_at(map + bt * side * side, side, S, oy, ox), 0.f);
+  sum[i] += fmaxf(bicubic_at(map + bt * side * side, side, side, S, S, oy, ox), 0.f);
 }
 int launch_hook_accum(const float* map, int B, int T, int side, int S, float* sum, hipStream_t st) {
   const long long n = (long long)B * T * S * S;

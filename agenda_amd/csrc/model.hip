@@ -73,7 +73,7 @@ struct DBuf {
 struct XLayer {
   std::string name; int C = 0, heads = 0, level = 0; bool mid = false;
   bool cn = false;                                    // a ControlNet layer: K/V and the pre-multiplied form like the UNet's, never recorded
-  WMat wkv; DBuf kvb; bf16_t* kv = nullptr; DBuf accb; float* acc = nullptr; int acc_side = 0;
+  WMat wkv; DBuf kvb; bf16_t* kv = nullptr; DBuf accb; float* acc = nullptr; int acc_h = 0, acc_w = 0;
   int acc_heads = 0;                                  // slices in acc per image: `heads`, or fewer = head-group sums (layers at latent resolution)
   DBuf wqTb, wkvTb, woTb; WMat wqT, wkvT, woT;        // transposed weights for the input-gradient GEMMs (built on first backward)
   // attn2 against per-image pre-multiplied context matrices (xattn_pre.hip; the C = 1280 blocks): load-time parts (to_q transposed, Wq . norm2.bias)
@@ -105,7 +105,7 @@ struct agd_ctx {
   std::vector<XLayer> xl; std::unordered_map<std::string, int> xl_idx;
   DBuf ctxb; bf16_t* ctx_bf16 = nullptr; int ctx_B2 = 0, ctx_T = 0;
   // recorder
-  int rec_mode = 0, rec_is_train = 0, rec_T_cfg = 0, rec_T = 0, rec_B = 0, rec_L = 0;   // rec_T: rows the accumulators were sized for (set by record_reset)
+  int rec_mode = 0, rec_is_train = 0, rec_T_cfg = 0, rec_T = 0, rec_B = 0, rec_L = 0, rec_Lh = 0, rec_Lw = 0;   // rec_T: rows the accumulators were sized for (set by record_reset); rec_L: hook.py's square side
   DBuf hook_sumb, hook_scratchb, hook_headsb, hook_storeb;     // hook_heads: per-head probabilities of one call; hook_store: kept per-call maps (train mode)
   struct HookRec { size_t off; int Bp, T, N; };
   std::vector<HookRec> hook_recs; size_t hook_store_used = 0;
@@ -148,11 +148,11 @@ struct agd_ctx {
   agd_controlnet_config cnc{}; bool cn_on = false;
   WMat cn_tproj_all; float* cn_tproj_bias = nullptr; float* cn_tproj_out = nullptr; int cn_tproj_total = 0;
   int cn_nres = 0; float* cn_zb = nullptr; float* cn_zbs = nullptr; int cn_zb_total = 0; std::vector<int> cn_zb_off; float cn_zscale = NAN;
-  DBuf cn_embb; int cn_emb_B2 = 0, cn_emb_L = 0, cn_emb_rep = 0;      // the conditioning embedding [B2][L][L][C0] bf16 (agd_controlnet_set_cond)
+  DBuf cn_embb; int cn_emb_B2 = 0, cn_emb_Lh = 0, cn_emb_Lw = 0, cn_emb_rep = 0;      // the conditioning embedding [B2][Lh][Lw][C0] bf16 (agd_controlnet_set_cond)
   std::vector<float> cn_sched;                                         // agd_controlnet_set_schedule: one scale per model evaluation
   // inpainting (agd_inpaint_set): ip_mode 0 = none, 1 = the 9-channel UNet input (mask + masked-image latents in ip_condb), 2 = the 4-channel
   // blend (image latents in ip_condb, the noise in ip_noiseb, (sa, sb) per model evaluation in ip_sched); all fp32 NCHW for ip_B images
-  int ip_mode = 0, ip_B = 0, ip_L = 0, ip_Cm = 0, ip_Cc = 0;
+  int ip_mode = 0, ip_B = 0, ip_Lh = 0, ip_Lw = 0, ip_Cm = 0, ip_Cc = 0;
   DBuf ip_maskb, ip_condb, ip_noiseb;
   std::vector<float> ip_sched;
   // LoRA (agd_lora_add / agd_lora_set_scale / agd_lora_clear): per target its fp32 factors and a bf16 copy of its base matrix (merge descriptors
@@ -450,7 +450,8 @@ static int run_attention(agd_ctx* c, hipStream_t st, int cls, AttnP& a) {
 }
 
 // cross-attention attn2 body shared by the UNet walk and the agd_cross_attn seam
-static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t* q, int B2, int N, bf16_t* out, bool record,
+// qh x qw: the query map (N = qh * qw); the seam passes the square side of its token count
+static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t* q, int B2, int N, int qh, int qw, bf16_t* out, bool record,
                            const float* mask = nullptr) {
   const int C = xl.C, D = C / xl.heads, T = c->ctx_T;
   if (xl.cn) record = false;                           // DAAM and hook.py see the UNet's layers only
@@ -459,11 +460,11 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   a.sq = (long long)N * C; a.sk = (long long)T * 2 * C; a.sv = a.sk; a.so = a.sq;
   a.B = B2; a.H = xl.heads; a.D = D; a.Nq = N; a.Nk = T; a.scale = 1.0f / sqrtf((float)D);
   a.record_mode = 0; a.mask = mask;
-  const int side = (int)lrintf(sqrtf((float)N));
+  const int side = qh;                                 // (hook.py mode: square maps only)
   bool hook_call = false;
   if (record && c->rec_mode == 1 && !xl.mid && xl.acc) {
-    // daam: factor = latent_side / side; recorded iff factor != 8 (mid block); conditional half only
-    if (c->rec_L / side != 8 && side == xl.acc_side && B2 / 2 == c->rec_B) {
+    // daam: factor = sqrt(latent h * w / N) = Lh / qh; recorded iff factor != 8 (mid block); conditional half only
+    if (c->rec_Lh / qh != 8 && qh == xl.acc_h && qw == xl.acc_w && B2 / 2 == c->rec_B) {
       a.rec_b0 = B2 / 2; a.rec = xl.acc; a.rec_T = c->rec_T;
       a.rec_head_stride = (long long)c->rec_T * N; a.rec_img_stride = a.rec_head_stride * xl.acc_heads;
       if (xl.acc_heads < xl.heads) {                 // latent-resolution layer: head-group sums (attention.hip RECORD 2)
@@ -474,6 +475,7 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   } else if (record && c->rec_mode == 2 && c->hook_scratch) {
     const int b0 = c->rec_is_train ? 0 : B2 / 2;
     if (B2 - b0 == c->hook_Bp) {
+      if (qh != qw) FAIL("the hook.py recorder takes square maps only (h = w = sqrt(N)); this call's map is %d x %d", qh, qw);
       if (T != c->hook_T || side > c->rec_L) FAIL("hook recorder was reset for %d tokens / latent side %d but this call has %d tokens / side %d: call clear() (agd_record_reset) after changing the context", c->hook_T, c->rec_L, T, side);
       // per-head probabilities of this call (plain read-modify-write rows, like the DAAM accumulators), then an ORDERED
       // head mean (hook.py:55): reproducible run to run, unlike float atomics across the head workgroups
@@ -647,7 +649,7 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
   { auto itx = c->xl_idx.find(t + "attn2");              // the ONE predicate of that form: the chain kernel steps aside exactly where it holds
     if (itx != c->xl_idx.end()) {
       const XLayer& xq = c->xl[itx->second];
-      xpre_rec = c->rec_mode == 1 && !xq.mid && xq.acc && c->rec_L / x.H != 8 && x.H == xq.acc_side && x.W == x.H && B / 2 == c->rec_B;
+      xpre_rec = c->rec_mode == 1 && !xq.mid && xq.acc && c->rec_Lh / x.H != 8 && x.H == xq.acc_h && x.W == xq.acc_w && B / 2 == c->rec_B;
       xpre_ready = xq.pm_ready && c->opt_xpre && fold && HW % 64 == 0 && c->rec_mode != 2 && c->ctx_T <= XATTN_TP && !dup && (!xpre_rec || xq.acc_heads == xq.heads);
     } }
   const bool chain_fuse = (c->opt_tb_fuse & 2) && (C == 320 || (C == 640 && (c->opt_tb_fuse & 32))) && heads == 8 && HW % (C == 320 ? 128 : 64) == 0 && c->ctx_T <= 96 &&
@@ -693,7 +695,7 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
       AttnChainP ap{}; ap.h = h.p; ap.out = h.p; ap.gamma = g2; ap.beta = b2_; ap.ln_eps = lneps; ap.wqf = fq->w; ap.wof = fo->w; ap.bo = bo;
       ap.kv = xl.kv; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)D);
       double rec_bytes = 0;
-      if (c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_L / x.H != 8 && x.H == xl.acc_side && x.W == x.H && B / 2 == c->rec_B) {   // daam's rule, as cross_attention()
+      if (c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_Lh / x.H != 8 && x.H == xl.acc_h && x.W == xl.acc_w && B / 2 == c->rec_B) {   // daam's rule, as cross_attention()
         ap.record = 1; ap.rec = xl.acc; ap.rec_b0 = B / 2; ap.rec_T = c->rec_T; ap.rec_hpb = heads / xl.acc_heads;
         ap.rec_head_stride = (long long)c->rec_T * HW; ap.rec_img_stride = ap.rec_head_stride * xl.acc_heads;
         rec_bytes = 8.0 * (B - ap.rec_b0) * xl.acc_heads * (double)c->rec_T * HW;
@@ -745,7 +747,7 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
   { bf16_t* q = qkv;
     CK(consume(t + "norm2", t + "attn2.to_q.weight", nullptr, 0, q));
     auto it = c->xl_idx.find(t + "attn2");
-    CK(cross_attention(c, st, c->xl[it->second], q, B, HW, att, true));
+    CK(cross_attention(c, st, c->xl[it->second], q, B, HW, x.H, x.W, att, true));
     GETW(wo, t + "attn2.to_out.0.weight"); GETV(bo, t + "attn2.to_out.0.bias");
     GemmOpt oo; oo.bias = bo; oo.residual = h.p;
     CK(produce(att, C, *wo, oo, h.p, false, !ff_fused)); }
@@ -816,18 +818,18 @@ static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float*
 // every res sample in order (conv_in, each resnet / transformer output, each downsampler: the UNet's skips); h = the mid block's output.
 // conv_in_res: added in conv_in's epilogue (the ControlNet's conditioning embedding).  shared: rows [0,B2/2) and [B2/2,B2) of xin (and of
 // conv_in_res) are identical -- everything ahead of the first attn2 runs on B2/2 rows.
-static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int L, bool shared,
+static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int Lh, int Lw, bool shared,
                          const bf16_t* conv_in_res, const std::function<int(const Act&)>& on_sample, Act& h) {
   const agd_config& g = c->cfg;
   const int nl = g.n_levels, G = g.norm_num_groups;
   const int Bh = shared ? B2 / 2 : B2;
-  h = alloc_act(c, B2, L, L, g.block_out_channels[0], true); if (!h.p) return -1;
+  h = alloc_act(c, B2, Lh, Lw, g.block_out_channels[0], true); if (!h.p) return -1;
   { GETW(w, u + "conv_in.weight"); GETV(b, u + "conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h; o.residual = conv_in_res;
-    CK(run_conv(c, st, xin, 64, nullptr, 0, Bh, L, L, *w, 3, h.p, o, c->zero_page)); }
+    CK(run_conv(c, st, xin, 64, nullptr, 0, Bh, Lh, Lw, *w, 3, h.p, o, c->zero_page)); }
   if (shared) {                                                             // the skip connection needs all B2 rows (and their partial sums)
-    CK(dup_half(c, st, h.p, (long long)Bh * L * L * h.C));
+    CK(dup_half(c, st, h.p, (long long)Bh * Lh * Lw * h.C));
     if (h.cpart_bm > 0) {
-      const size_t nb = (size_t)((long long)Bh * L * L / h.cpart_bm) * h.C * 2 * sizeof(float);
+      const size_t nb = (size_t)((long long)Bh * Lh * Lw / h.cpart_bm) * h.C * 2 * sizeof(float);
       if (hipMemcpyAsync((char*)h.cpart + nb, h.cpart, nb, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup partials copy failed");
     }
   }
@@ -877,14 +879,14 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
 //   it -- the launch leaves the GroupNorm partial sums of the injected tensor, while the old Act's partial sums and normed copy describe
 //   the un-injected one.  The mid residual goes into *h the same way.  The ControlNet keeps no skip list of its own.
 // skips == nullptr: the scaled residuals go to res_out as fp32 instead, back to back, NHWC or NCHW (agd_controlnet_residuals).
-static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float scale, bool cfg_shared,
+static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float scale, bool cfg_shared,
                            std::vector<Act>* skips, Act* h_unet, float* res_out, int nhwc) {
   const agd_config& g = c->cfg;
   if (!c->cn_on) FAIL("controlnet: none loaded (agd_controlnet_configure before agd_finalize)");
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
-  if (c->cn_emb_B2 != B2 || c->cn_emb_L != L)
-    FAIL("controlnet: the conditioning image is set for %d rows at latent side %d, this forward has %d rows at side %d (agd_controlnet_set_cond)",
-         c->cn_emb_B2, c->cn_emb_L, B2, L);
+  if (c->cn_emb_B2 != B2 || c->cn_emb_Lh != Lh || c->cn_emb_Lw != Lw)
+    FAIL("controlnet: the conditioning image is set for %d rows at latent sides %d x %d, this forward has %d rows at %d x %d (agd_controlnet_set_cond)",
+         c->cn_emb_B2, c->cn_emb_Lh, c->cn_emb_Lw, B2, Lh, Lw);
   if (skips && ((int)skips->size() != c->cn_nres || !h_unet)) FAIL("controlnet: %zu UNet skips for %d ControlNet res samples", skips->size(), c->cn_nres);
   std::vector<Act> inj;
   if (skips) {
@@ -933,19 +935,19 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
   // with an even repeat
   const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share && c->cn_emb_rep % 2 == 0;
   Act h;
-  CK(down_mid_walk(c, st, u, xin, B2, L, shared, c->cn_embb.as<bf16_t>(), zero_conv, h));
+  CK(down_mid_walk(c, st, u, xin, B2, Lh, Lw, shared, c->cn_embb.as<bf16_t>(), zero_conv, h));
   CK(zero_conv(h));
   c->tproj_cur = tp_save; c->tproj_cur_ld = ld_save;
   c->arena.release(mk);
   return 0;
 }
 
-// x: [B2][L*L][64] bf16 (latent channels zero-padded) -> eps [B2][L*L][out_channels] fp32 NHWC
+// x: [B2][Lh*Lw][64] bf16 (latent channels zero-padded) -> eps [B2][Lh*Lw][out_channels] fp32 NHWC
 // tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
 // cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
 // tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
 // cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
-static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int L, float t, float* eps_out,
+static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
                      const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f) {
   const agd_config& g = c->cfg;
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
@@ -958,10 +960,10 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
   std::vector<Act> skips;
   const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share;
   Act h;
-  CK(down_mid_walk(c, st, u, xin, B2, L, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h));
+  CK(down_mid_walk(c, st, u, xin, B2, Lh, Lw, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h));
   if (cn_scale != 0.f) {
     if (c->tproj_cur_ld != 0) FAIL("controlnet: per-image timesteps are not supported");
-    CK(controlnet_walk(c, st, xin, B2, L, t, cn_scale, cfg_shared, &skips, &h, nullptr, 0));
+    CK(controlnet_walk(c, st, xin, B2, Lh, Lw, t, cn_scale, cfg_shared, &skips, &h, nullptr, 0));
   }
   for (int i = 0; i < nl; ++i) {
     const int lvl = nl - 1 - i, co = g.block_out_channels[lvl];
@@ -994,21 +996,21 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
       h = d;
     }
   }
-  { Act n = alloc_act(c, B2, L, L, h.C); if (!n.p) return -1;
+  { Act n = alloc_act(c, B2, Lh, Lw, h.C); if (!n.p) return -1;
     GETV(gg, u + "conv_norm_out.weight"); GETV(gb, u + "conv_norm_out.bias");
-    CK(run_gn(c, st, h.p, h.C, nullptr, 0, B2, L * L, gg, gb, G, 1e-5f, 1, n.p, &h));
+    CK(run_gn(c, st, h.p, h.C, nullptr, 0, B2, Lh * Lw, gg, gb, G, 1e-5f, 1, n.p, &h));
     GETW(w, u + "conv_out.weight"); GETV(b, u + "conv_out.bias");
     GemmOpt o; o.bias = b; o.out_f32 = 1; o.ldo = g.out_channels;
-    CK(run_conv(c, st, n.p, h.C, nullptr, 0, B2, L, L, *w, 3, eps_out, o, c->zero_page)); }
+    CK(run_conv(c, st, n.p, h.C, nullptr, 0, B2, Lh, Lw, *w, 3, eps_out, o, c->zero_page)); }
   return 0;
 }
 
-// AutoencoderKL mid-block attention: single head over N = L*L tokens, C channels, through batched GEMMs
-static int vae_mid_attention(agd_ctx* c, hipStream_t st, const std::string& a, int G, int B, int L, int top, Act& h) {
-    const int N = L * L, C = top, M = B * N;
-    Act out = alloc_act(c, B, L, L, C, true); if (!out.p) return -1;
+// AutoencoderKL mid-block attention: single head over N = Lh*Lw tokens, C channels, through batched GEMMs
+static int vae_mid_attention(agd_ctx* c, hipStream_t st, const std::string& a, int G, int B, int Lh, int Lw, int top, Act& h) {
+    const int N = Lh * Lw, C = top, M = B * N;
+    Act out = alloc_act(c, B, Lh, Lw, C, true); if (!out.p) return -1;
     const size_t mk = c->arena.mark();
-    Act n = alloc_act(c, B, L, L, C); if (!n.p) return -1;
+    Act n = alloc_act(c, B, Lh, Lw, C); if (!n.p) return -1;
     GETV(gg, a + "group_norm.weight"); GETV(gb, a + "group_norm.bias");
     CK(run_gn(c, st, h.p, C, nullptr, 0, B, N, gg, gb, G, 1e-6f, 0, n.p, &h));
     bf16_t* q = (bf16_t*)c->arena.alloc((size_t)M * C * 2); bf16_t* k = (bf16_t*)c->arena.alloc((size_t)M * C * 2);
@@ -1041,23 +1043,23 @@ static int vae_mid_attention(agd_ctx* c, hipStream_t st, const std::string& a, i
   return 0;
 }
 
-// AutoencoderKL.decode: z [B][L*L][64] bf16 (already divided by scaling factor) -> fp32 NHWC [B][8L*8L][ldo=4]
-static int vae_walk(agd_ctx* c, hipStream_t st, const bf16_t* zin, int B, int L, float* img_out) {
+// AutoencoderKL.decode: z [B][Lh*Lw][64] bf16 (already divided by scaling factor) -> fp32 NHWC [B][8Lh*8Lw][ldo=4]
+static int vae_walk(agd_ctx* c, hipStream_t st, const bf16_t* zin, int B, int Lh, int Lw, float* img_out) {
   const agd_config& g = c->cfg;
   const int nl = g.vae_n_levels, G = g.vae_norm_num_groups;
   const std::string v = "vae.";
   c->arena.release(0);
   const int top = g.vae_block_out_channels[nl - 1];
   // post_quant_conv (1x1, 4->4) written into a zeroed 64-channel buffer so conv_in sees padded input
-  bf16_t* pq = (bf16_t*)c->arena.alloc((size_t)B * L * L * 64 * 2); if (!pq) return -1;
-  if (hipMemsetAsync(pq, 0, (size_t)B * L * L * 64 * 2, st) != hipSuccess) FAIL("memset pq");
+  bf16_t* pq = (bf16_t*)c->arena.alloc((size_t)B * Lh * Lw * 64 * 2); if (!pq) return -1;
+  if (hipMemsetAsync(pq, 0, (size_t)B * Lh * Lw * 64 * 2, st) != hipSuccess) FAIL("memset pq");
   { GETW(w, v + "post_quant_conv.weight"); GETV(b, v + "post_quant_conv.bias"); GemmOpt o; o.bias = b; o.ldo = 64;
-    CK(run_conv(c, st, zin, 64, nullptr, 0, B, L, L, *w, 1, pq, o, c->zero_page)); }
-  Act h = alloc_act(c, B, L, L, top, true); if (!h.p) return -1;
+    CK(run_conv(c, st, zin, 64, nullptr, 0, B, Lh, Lw, *w, 1, pq, o, c->zero_page)); }
+  Act h = alloc_act(c, B, Lh, Lw, top, true); if (!h.p) return -1;
   { GETW(w, v + "decoder.conv_in.weight"); GETV(b, v + "decoder.conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h;
-    CK(run_conv(c, st, pq, 64, nullptr, 0, B, L, L, *w, 3, h.p, o, c->zero_page)); }
+    CK(run_conv(c, st, pq, 64, nullptr, 0, B, Lh, Lw, *w, 3, h.p, o, c->zero_page)); }
   { Act r; CK(resnet(c, st, v + "decoder.mid_block.resnets.0.", h, nullptr, top, 1e-6f, false, G, r)); h = r; }
-  CK(vae_mid_attention(c, st, v + "decoder.mid_block.attentions.0.", G, B, L, top, h));
+  CK(vae_mid_attention(c, st, v + "decoder.mid_block.attentions.0.", G, B, Lh, Lw, top, h));
   { Act r; CK(resnet(c, st, v + "decoder.mid_block.resnets.1.", h, nullptr, top, 1e-6f, false, G, r)); h = r; }
   for (int i = 0; i < nl; ++i) {
     const int co = g.vae_block_out_channels[nl - 1 - i];
@@ -1090,15 +1092,15 @@ static int vae_walk(agd_ctx* c, hipStream_t st, const bf16_t* zin, int B, int L,
   return 0;
 }
 
-// AutoencoderKL.encode: x [B][S*S][64] bf16 (3 image channels zero-padded) -> moments fp32 NHWC [B][L*L][2*lc]
-static int vae_encode_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B, int S_, float* moments) {
+// AutoencoderKL.encode: x [B][Sh*Sw][64] bf16 (3 image channels zero-padded) -> moments fp32 NHWC [B][Lh*Lw][2*lc]
+static int vae_encode_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B, int Sh, int Sw, float* moments) {
   const agd_config& g = c->cfg;
   const int nl = g.vae_n_levels, G = g.vae_norm_num_groups, lc = g.vae_latent_channels;
   const std::string v = "vae.";
   c->arena.release(0);
-  Act h = alloc_act(c, B, S_, S_, g.vae_block_out_channels[0], true); if (!h.p) return -1;
+  Act h = alloc_act(c, B, Sh, Sw, g.vae_block_out_channels[0], true); if (!h.p) return -1;
   { GETW(w, v + "encoder.conv_in.weight"); GETV(b, v + "encoder.conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h;
-    CK(run_conv(c, st, xin, 64, nullptr, 0, B, S_, S_, *w, 3, h.p, o, c->zero_page)); }
+    CK(run_conv(c, st, xin, 64, nullptr, 0, B, Sh, Sw, *w, 3, h.p, o, c->zero_page)); }
   for (int i = 0; i < nl; ++i) {
     const int co = g.vae_block_out_channels[i];
     for (int j = 0; j < g.vae_layers_per_block; ++j) {
@@ -1114,20 +1116,20 @@ static int vae_encode_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B,
       h = d;
     }
   }
-  const int top = g.vae_block_out_channels[nl - 1], L = h.H;
+  const int top = g.vae_block_out_channels[nl - 1], Lh = h.H, Lw = h.W;
   { Act r; CK(resnet(c, st, v + "encoder.mid_block.resnets.0.", h, nullptr, top, 1e-6f, false, G, r)); h = r; }
-  CK(vae_mid_attention(c, st, v + "encoder.mid_block.attentions.0.", G, B, L, top, h));
+  CK(vae_mid_attention(c, st, v + "encoder.mid_block.attentions.0.", G, B, Lh, Lw, top, h));
   { Act r; CK(resnet(c, st, v + "encoder.mid_block.resnets.1.", h, nullptr, top, 1e-6f, false, G, r)); h = r; }
-  Act n = alloc_act(c, B, L, L, top); if (!n.p) return -1;
+  Act n = alloc_act(c, B, Lh, Lw, top); if (!n.p) return -1;
   GETV(gg, v + "encoder.conv_norm_out.weight"); GETV(gb, v + "encoder.conv_norm_out.bias");
-  CK(run_gn(c, st, h.p, top, nullptr, 0, B, L * L, gg, gb, G, 1e-6f, 1, n.p, &h));
+  CK(run_gn(c, st, h.p, top, nullptr, 0, B, Lh * Lw, gg, gb, G, 1e-6f, 1, n.p, &h));
   // conv_out (top -> 2*lc) into a zeroed 64-channel buffer, then quant_conv 1x1 (2*lc -> 2*lc) in fp32 out
-  bf16_t* co64 = (bf16_t*)c->arena.alloc((size_t)B * L * L * 64 * 2); if (!co64) return -1;
-  if (hipMemsetAsync(co64, 0, (size_t)B * L * L * 64 * 2, st) != hipSuccess) FAIL("memset enc");
+  bf16_t* co64 = (bf16_t*)c->arena.alloc((size_t)B * Lh * Lw * 64 * 2); if (!co64) return -1;
+  if (hipMemsetAsync(co64, 0, (size_t)B * Lh * Lw * 64 * 2, st) != hipSuccess) FAIL("memset enc");
   { GETW(w, v + "encoder.conv_out.weight"); GETV(b, v + "encoder.conv_out.bias"); GemmOpt o; o.bias = b; o.ldo = 64;
-    CK(run_conv(c, st, n.p, top, nullptr, 0, B, L, L, *w, 3, co64, o, c->zero_page)); }
+    CK(run_conv(c, st, n.p, top, nullptr, 0, B, Lh, Lw, *w, 3, co64, o, c->zero_page)); }
   { GETW(w, v + "quant_conv.weight"); GETV(b, v + "quant_conv.bias"); GemmOpt o; o.bias = b; o.out_f32 = 1; o.ldo = 2 * lc;
-    CK(run_conv(c, st, co64, 64, nullptr, 0, B, L, L, *w, 1, moments, o, c->zero_page)); }
+    CK(run_conv(c, st, co64, 64, nullptr, 0, B, Lh, Lw, *w, 1, moments, o, c->zero_page)); }
   return 0;
 }
 
@@ -1666,37 +1668,39 @@ AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int to
   return 0;
 }
 
-static int ensure_lat(agd_ctx* c, int B2, int L) {
-  const size_t need = (size_t)B2 * L * L * 64;
+static int ensure_lat(agd_ctx* c, int B2, int Lh, int Lw) {
+  const size_t need = (size_t)B2 * Lh * Lw * 64;
   const int oc = c->cfg.out_channels > 4 ? c->cfg.out_channels : 4;
-  CK(c->latb.ensure(need * 2)); CK(c->epsb.ensure((size_t)B2 * L * L * oc * 4));
+  CK(c->latb.ensure(need * 2)); CK(c->epsb.ensure((size_t)B2 * Lh * Lw * oc * 4));
   c->lat_bf16 = c->latb.as<bf16_t>(); c->eps_nhwc = c->epsb.as<float>();
   return 0;
 }
 
 static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timesteps, int n, const float** out);
-// the ControlNet schedule of a call of n model evaluations on B2 rows at latent side L: nullptr = none set (the UNet alone); else its length
-// must be n, and a conditioning embedding for exactly these rows must exist when any scale is non-zero (checked before anything runs)
-static int cn_schedule_for(agd_ctx* c, int n, int B2, int L, const float** out) {
+// the ControlNet schedule of a call of n model evaluations on B2 rows at latent size Lh x Lw: nullptr = none set (the UNet alone); else its
+// length must be n, and a conditioning embedding for exactly these rows must exist when any scale is non-zero (checked before anything runs)
+static int cn_schedule_for(agd_ctx* c, int n, int B2, int Lh, int Lw, const float** out) {
   *out = nullptr;
   if (c->cn_sched.empty()) return 0;
   if ((int)c->cn_sched.size() != n) FAIL("controlnet: the schedule has %zu scales, this call runs %d model evaluations (agd_controlnet_set_schedule)", c->cn_sched.size(), n);
   bool any = false; for (float v : c->cn_sched) any = any || v != 0.f;
-  if (any && (c->cn_emb_B2 != B2 || c->cn_emb_L != L))
-    FAIL("controlnet: no conditioning image set for %d rows at latent side %d (agd_controlnet_set_cond has %d rows at side %d)", B2, L, c->cn_emb_B2, c->cn_emb_L);
+  if (any && (c->cn_emb_B2 != B2 || c->cn_emb_Lh != Lh || c->cn_emb_Lw != Lw))
+    FAIL("controlnet: no conditioning image set for %d rows at latent sides %d x %d (agd_controlnet_set_cond has %d rows at %d x %d)", B2, Lh, Lw, c->cn_emb_B2,
+         c->cn_emb_Lh, c->cn_emb_Lw);
   *out = c->cn_sched.data();
   return 0;
 }
-// the inpaint state of a fused loop of n model evaluations on `batch` images at latent side L: *blend = the (sa, sb) schedule of the
+// the inpaint state of a fused loop of n model evaluations on `batch` images at latent size Lh x Lw: *blend = the (sa, sb) schedule of the
 // 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
-static int inpaint_for(agd_ctx* c, int n, int batch, int L, const float** blend) {
+static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float** blend) {
   *blend = nullptr;
   if (c->ip_mode == 0) {
     if (c->cfg.in_channels != c->cfg.out_channels)
       FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first", c->cfg.in_channels, c->cfg.out_channels);
     return 0;
   }
-  if (c->ip_B != batch || c->ip_L != L) FAIL("inpaint: the state holds %d images at latent side %d, this call runs %d at side %d", c->ip_B, c->ip_L, batch, L);
+  if (c->ip_B != batch || c->ip_Lh != Lh || c->ip_Lw != Lw)
+    FAIL("inpaint: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->ip_B, c->ip_Lh, c->ip_Lw, batch, Lh, Lw);
   if (!c->cn_sched.empty()) FAIL("inpaint: a ControlNet schedule is set; ControlNet inpainting is not implemented");
   if (c->ip_mode == 2) {
     if ((int)c->ip_sched.size() != 2 * n) FAIL("inpaint: the blend schedule has %zu entries, this call runs %d model evaluations (agd_inpaint_set_schedule)", c->ip_sched.size() / 2, n);
@@ -1717,44 +1721,61 @@ static int inpaint_blend(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   return launch_inpaint_blend(latents, c->ip_condb.as<float>(), c->ip_noiseb.as<float>(), c->ip_maskb.as<float>(), batch, c->cfg.out_channels, HW,
                               sab[0], sab[1], st);
 }
-AGD_API int agd_unet_forward(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float* out, void* stream) {
+// a latent size of a _hw entry point: both sides positive; a rectangular one must halve exactly at every UNet level (the 64-pixel rule
+// per axis).  Square sizes keep the acceptance the one-side entry points always had.
+static int check_latent_hw(agd_ctx* c, const char* what, int Lh, int Lw) {
+  const int f = 1 << (c->cfg.n_levels - 1);
+  if (Lh < 1 || Lw < 1 || (Lh != Lw && (Lh % f || Lw % f))) FAIL("%s: latent size %d x %d (each side a positive multiple of %d)", what, Lh, Lw, f);
+  return 0;
+}
+
+AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int Lh, int Lw, float timestep, float* out, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "unet_forward", Lh, Lw));
   hipStream_t st = S(stream);
-  API_CK(c, ensure_lat(c, batch2, L));
+  API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
   const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, 1, batch2, L, &cs));                          // a one-element ControlNet schedule: one injected forward
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, L * L, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, L, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f));
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, L * L, st)); }
+  API_CK(c, cn_schedule_for(c, 1, batch2, Lh, Lw, &cs));                     // a one-element ControlNet schedule: one injected forward
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
+}
+AGD_API int agd_unet_forward(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float* out, void* stream) {
+  return agd_unet_forward_hw(c, sample, batch2, L, L, timestep, out, stream);
 }
 
 // the training call `unet(noisy, timesteps[bsz], encoder_hidden_states)` (finetune_sd_token.py:1027): one timestep PER IMAGE
 // (host array of batch2 floats): every image gets its own time-embedding row in the resnets' row add
-AGD_API int agd_unet_forward_ts(agd_ctx* c, const float* sample, int batch2, int L, const float* timesteps, float* out, void* stream) {
+AGD_API int agd_unet_forward_ts_hw(agd_ctx* c, const float* sample, int batch2, int Lh, int Lw, const float* timesteps, float* out, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "unet_forward_ts", Lh, Lw));
   if (!timesteps || batch2 < 1) { agd_set_error("unet_forward_ts: bad arguments"); return fail_ctx(c); }
   if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   hipStream_t st = S(stream);
-  API_CK(c, ensure_lat(c, batch2, L));
+  API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, batch2, &tp_all));
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, L * L, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, L, timesteps[0], c->eps_nhwc, tp_all, false, c->tproj_total));
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, L * L, st)); }
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timesteps[0], c->eps_nhwc, tp_all, false, c->tproj_total));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
+}
+AGD_API int agd_unet_forward_ts(agd_ctx* c, const float* sample, int batch2, int L, const float* timesteps, float* out, void* stream) {
+  return agd_unet_forward_ts_hw(c, sample, batch2, L, L, timesteps, out, stream);
 }
 
 // eps strides for cfg_ddim: NCHW eps handled by transposing through the NHWC kernel's stride form
-AGD_API int agd_cfg_ddim_step(agd_ctx* c, const float* eps, float* latents, int batch, int L, float guidance, float alpha_t,
+AGD_API int agd_cfg_ddim_step_hw(agd_ctx* c, const float* eps, float* latents, int batch, int Lh, int Lw, float guidance, float alpha_t,
                                  float alpha_prev, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "cfg_ddim_step", Lh, Lw));
   hipStream_t st = S(stream);
-  API_CK(c, ensure_lat(c, 2 * batch, L));
+  API_CK(c, ensure_lat(c, 2 * batch, Lh, Lw));
   // NCHW eps -> NHWC scratch (tiny), then the fused kernel
-  const int C = c->cfg.out_channels, HW = L * L;
+  const int C = c->cfg.out_channels, HW = Lh * Lw;
   // reuse nchw_from_nhwc in the reverse direction: treat eps as "NHWC with ldc=HW" is not valid; do an explicit pass
   float* tmp = c->eps_nhwc;
   // out[b][p][c] = eps[b][c][p]  == nchw_from_nhwc with (C,HW) swapped
@@ -1762,6 +1783,10 @@ AGD_API int agd_cfg_ddim_step(agd_ctx* c, const float* eps, float* latents, int 
   ProfScope ps(c, st, PC_ELEM, 0);
   API_CK(c, launch_cfg_ddim(tmp, C, latents, batch, C, HW, guidance, alpha_t, alpha_prev, c->cfg.prediction_type, st));
   return 0;
+}
+AGD_API int agd_cfg_ddim_step(agd_ctx* c, const float* eps, float* latents, int batch, int L, float guidance, float alpha_t,
+                                 float alpha_prev, void* stream) {
+  return agd_cfg_ddim_step_hw(c, eps, latents, batch, L, L, guidance, alpha_t, alpha_prev, stream);
 }
 
 // time embeddings of every model evaluation of a denoise loop, 8 timesteps per launch (the stacked time_emb_proj matrix is
@@ -1786,27 +1811,32 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
   return 0;
 }
 
-AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_steps, const float* timesteps, const float* alpha_t,
+AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw, int n_steps, const float* timesteps, const float* alpha_t,
                            const float* alpha_prev, float guidance, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "denoise", Lh, Lw));
   hipStream_t st = S(stream);
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;            // Cl: the latent channels (a 9-channel UNet's input has more)
-  API_CK(c, ensure_lat(c, B2, L));
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;          // Cl: the latent channels (a 9-channel UNet's input has more)
+  API_CK(c, ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const float* cs = nullptr;                                       // the ControlNet's per-step scales (none: the UNet alone)
-  API_CK(c, cn_schedule_for(c, n_steps, B2, L, &cs));
+  API_CK(c, cn_schedule_for(c, n_steps, B2, Lh, Lw, &cs));
   const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per step (none: no blend)
-  API_CK(c, inpaint_for(c, n_steps, batch, L, &ib));
+  API_CK(c, inpaint_for(c, n_steps, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
   for (int s = 0; s < n_steps; ++s) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f));
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
     if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * s));
   }
   return 0;
+}
+AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_steps, const float* timesteps, const float* alpha_t,
+                           const float* alpha_prev, float guidance, void* stream) {
+  return agd_denoise_hw(c, latents, batch, L, L, n_steps, timesteps, alpha_t, alpha_prev, guidance, stream);
 }
 
 // The denoise loop under the reference's ACTUAL scheduler: `pipeline(prompt, num_inference_steps=20)` at
@@ -1817,29 +1847,30 @@ AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_step
 //   i = 0: e0                       (the sample is kept: evaluation 1 restarts from it)
 //   i = 1: (e1 + e0) / 2 from the KEPT sample (e1 is not added to the history)
 //   then : (3 e - h1) / 2 ; (23 e - 16 h1 + 5 h2) / 12 ; (55 e - 59 h1 + 37 h2 - 9 h3) / 24
-AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* sample_coeff,
+AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw, int n_evals, const float* timesteps, const float* sample_coeff,
                              const float* eps_coeff, float guidance, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "denoise_plms", Lh, Lw));
   hipStream_t st = S(stream);
   if (c->cfg.prediction_type != 0) { agd_set_error("denoise_plms: epsilon prediction only"); return fail_ctx(c); }
   if (n_evals < 2) { agd_set_error("denoise_plms: needs >= 2 model evaluations (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;
-  API_CK(c, ensure_lat(c, B2, L));
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;
+  API_CK(c, ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->plmsb.ensure(n1 * 5 * sizeof(float)));            // 4 history slots + the kept sample
   float* hist[4]; for (int k = 0; k < 4; ++k) hist[k] = c->plmsb.as<float>() + n1 * k;
   float* kept = c->plmsb.as<float>() + n1 * 4;
   const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
+  API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
   const float* ib = nullptr;                                       // the blend rewrites `latents` only: the kept sample stays unblended
-  API_CK(c, inpaint_for(c, n_evals, batch, L, &ib));
+  API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
   for (int i = 0; i < n_evals; ++i) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
     const float* src = latents; float* store = nullptr;
@@ -1861,6 +1892,10 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
   }
   return 0;
 }
+AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* sample_coeff,
+                             const float* eps_coeff, float guidance, void* stream) {
+  return agd_denoise_plms_hw(c, latents, batch, L, L, n_evals, timesteps, sample_coeff, eps_coeff, guidance, stream);
+}
 
 // The denoise loop under DPM-Solver++ (2M) [upstream-knowledge: diffusers 0.21.2 DPMSolverMultistepScheduler, algorithm_type
 // "dpmsolver++", midpoint]: one model evaluation per step.  The host scheduler (agenda_amd/scheduler.py dpm_program) passes, per
@@ -1868,26 +1903,27 @@ AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n
 //   x0 = cx x + ce m  (m: CFG-combined model output; eps or v is folded into cx / ce),  x = a x + b0 x0 + b1 x0_prev
 // so first / second order, the lower-order final step and the prediction type are all host decisions.  x0 ping-pongs between the
 // two halves of the context-owned dpmb buffer: evaluation i reads slot (i - 1) & 1 and writes slot i & 1.
-AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* coeffs,
+AGD_API int agd_denoise_dpm_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw, int n_evals, const float* timesteps, const float* coeffs,
                             float guidance, void* stream) {
   API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "denoise_dpm", Lh, Lw));
   hipStream_t st = S(stream);
   if (n_evals < 1 || !timesteps || !coeffs) { agd_set_error("denoise_dpm: needs >= 1 model evaluation and host timesteps / coeffs (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = L * L;
-  API_CK(c, ensure_lat(c, B2, L));
+  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;
+  API_CK(c, ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
   const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, n_evals, B2, L, &cs));
+  API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
   const float* ib = nullptr;
-  API_CK(c, inpaint_for(c, n_evals, batch, L, &ib));
+  API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   for (int i = 0; i < n_evals; ++i) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, L, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     { ProfScope ps(c, st, PC_ELEM, 0);
@@ -1896,24 +1932,32 @@ AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_
   }
   return 0;
 }
+AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* coeffs,
+                            float guidance, void* stream) {
+  return agd_denoise_dpm_hw(c, latents, batch, L, L, n_evals, timesteps, coeffs, guidance, stream);
+}
 
-AGD_API int agd_vae_decode(agd_ctx* c, const float* latents, int batch, int L, unsigned char* out_u8, float* out_f32, void* stream) {
+AGD_API int agd_vae_decode_hw(agd_ctx* c, const float* latents, int batch, int Lh, int Lw, unsigned char* out_u8, float* out_f32, void* stream) {
   API_CK(c, need_final(c));
+  if (Lh < 1 || Lw < 1) { agd_set_error("vae_decode: latent size %d x %d", Lh, Lw); return fail_ctx(c); }
   hipStream_t st = S(stream);
-  API_CK(c, ensure_lat(c, batch, L));
-  const int S8 = L << (c->cfg.vae_n_levels - 1);
-  const long long npix = (long long)batch * S8 * S8;
+  API_CK(c, ensure_lat(c, batch, Lh, Lw));
+  const int sh = c->cfg.vae_n_levels - 1;
+  const long long npix = (long long)batch * (Lh << sh) * (Lw << sh);
   { ProfScope ps(c, st, PC_ELEM, 0);
-    API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, c->cfg.vae_latent_channels, L * L, 64, 1, 1.0f / c->cfg.vae_scaling_factor, st)); }
-  API_CK(c, c->vae_imgb.ensure((size_t)npix * 4 * 4));     // grows once per (batch, side); stream-ordered reuse, no sync
+    API_CK(c, launch_prep_latents(latents, c->lat_bf16, batch, c->cfg.vae_latent_channels, Lh * Lw, 64, 1, 1.0f / c->cfg.vae_scaling_factor, st)); }
+  API_CK(c, c->vae_imgb.ensure((size_t)npix * 4 * 4));     // grows once per (batch, size); stream-ordered reuse, no sync
   float* img = c->vae_imgb.as<float>();
-  int rc = vae_walk(c, st, c->lat_bf16, batch, L, img);
+  int rc = vae_walk(c, st, c->lat_bf16, batch, Lh, Lw, img);
   if (rc == 0 && out_u8) { ProfScope ps(c, st, PC_ELEM, 0); rc = launch_image_u8(img, 4, out_u8, npix, c->cfg.vae_out_channels, st); }
   if (rc == 0 && out_f32) {
     // [npix][4] -> [npix][3] : "NCHW from NHWC" with HW=1 does exactly that per pixel
     rc = launch_nchw_from_nhwc_f32(img, 4, out_f32, (int)npix, c->cfg.vae_out_channels, 1, st);
   }
   return rc ? fail_ctx(c) : 0;
+}
+AGD_API int agd_vae_decode(agd_ctx* c, const float* latents, int batch, int L, unsigned char* out_u8, float* out_f32, void* stream) {
+  return agd_vae_decode_hw(c, latents, batch, L, L, out_u8, out_f32, stream);
 }
 
 // ---- options --------------------------------------------------------------------------
@@ -1969,39 +2013,44 @@ AGD_API int agd_hook_reset(agd_ctx* c, int rows, int L, void* stream) {
   if (c->rec_mode != 2) { agd_set_error("hook_reset: recorder is not in hook.py mode (agd_record_config(2, ..))"); return fail_ctx(c); }
   if (rows < 1 || L < 1) { agd_set_error("hook_reset: rows %d latent side %d", rows, L); return fail_ctx(c); }
   API_CK(c, hook_reset_rows(c, rows, L, S(stream)));
-  c->rec_B = c->rec_is_train ? (rows + 1) / 2 : rows; c->rec_L = L;
+  c->rec_B = c->rec_is_train ? (rows + 1) / 2 : rows; c->rec_L = c->rec_Lh = c->rec_Lw = L;
   return 0;
 }
 
-AGD_API int agd_record_reset(agd_ctx* c, int batch, int L, void* stream) {
+AGD_API int agd_record_reset_hw(agd_ctx* c, int batch, int Lh, int Lw, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
-  if (batch < 1 || L < 1) { agd_set_error("record_reset: batch %d latent side %d", batch, L); return fail_ctx(c); }
+  if (batch < 1 || Lh < 1 || Lw < 1) { agd_set_error("record_reset: batch %d latent size %d x %d", batch, Lh, Lw); return fail_ctx(c); }
+  if (c->rec_mode == 2 && Lh != Lw) { agd_set_error("record_reset: the hook.py recorder takes square latents only (got %d x %d)", Lh, Lw); return fail_ctx(c); }
   const int T = c->rec_T_cfg > 0 ? c->rec_T_cfg : c->cfg.max_tokens;
   c->rec_T = T;
   if (c->rec_mode == 1) {
     for (auto& xl : c->xl) {
       if (xl.mid || xl.cn) continue;
-      const int side = L >> xl.level;
-      if (side < 1 || (L / side) == 8) { xl.acc = nullptr; xl.acc_side = 0; continue; }
+      // daam: a layer's maps are (Lh / f) x (Lw / f) with f = sqrt(Lh * Lw / N) = 2^level; f == 8 is not recorded
+      const int h = Lh >> xl.level, w = Lw >> xl.level;
+      if (h < 1 || w < 1 || (Lh / h) == 8) { xl.acc = nullptr; xl.acc_h = xl.acc_w = 0; continue; }
       // capacity-tracked: a larger batch / token count / side than the block was allocated for reallocates it
       // daam averages clamp(bicubic(map), 0) over every (layer, head) map.  At latent resolution the resize is the identity and the
       // clamp cannot fire (sums of probabilities), so heads are summed in the recording kernel: down to 1/8 of the state and traffic
       xl.acc_heads = xl.heads;
-      if (side == L) {       // heads per workgroup: as many as still leave >= 256 workgroups (UNet batch x head groups x 128-query tiles)
+      if (xl.level == 0) {   // heads per workgroup: as many as still leave >= 256 workgroups (UNet batch x head groups x 128-query tiles)
         int hpb = xl.heads;
-        while (hpb > 1 && hpb % 2 == 0 && (long long)2 * batch * (xl.heads / hpb) * ((side * side + 127) / 128) < 256) hpb /= 2;
+        while (hpb > 1 && hpb % 2 == 0 && (long long)2 * batch * (xl.heads / hpb) * ((h * w + 127) / 128) < 256) hpb /= 2;
         xl.acc_heads = xl.heads / hpb;
       }
-      const size_t n = (size_t)batch * xl.acc_heads * T * side * side;
-      API_CK(c, xl.accb.ensure(n * 4)); xl.acc = xl.accb.as<float>(); xl.acc_side = side;
+      const size_t n = (size_t)batch * xl.acc_heads * T * h * w;
+      API_CK(c, xl.accb.ensure(n * 4)); xl.acc = xl.accb.as<float>(); xl.acc_h = h; xl.acc_w = w;
       if (hipMemsetAsync(xl.acc, 0, n * 4, st) != hipSuccess) { agd_set_error("memset acc"); return fail_ctx(c); }
     }
   } else if (c->rec_mode == 2) {
-    API_CK(c, hook_reset_rows(c, c->rec_is_train ? 2 * batch : batch, L, st));   // `batch` = images; UNet batch is 2*batch under CFG
+    API_CK(c, hook_reset_rows(c, c->rec_is_train ? 2 * batch : batch, Lh, st));   // `batch` = images; UNet batch is 2*batch under CFG
   }
-  c->rec_B = batch; c->rec_L = L;
+  c->rec_B = batch; c->rec_L = Lh; c->rec_Lh = Lh; c->rec_Lw = Lw;
   return 0;
+}
+AGD_API int agd_record_reset(agd_ctx* c, int batch, int L, void* stream) {
+  return agd_record_reset_hw(c, batch, L, L, stream);
 }
 
 AGD_API int agd_daam_global(agd_ctx* c, int img, int rows, float* out, void* stream) {
@@ -2010,13 +2059,13 @@ AGD_API int agd_daam_global(agd_ctx* c, int img, int rows, float* out, void* str
   std::vector<HeatLayer> hl; int total = 0;
   for (auto& xl : c->xl) {
     if (!xl.acc || xl.mid) continue;
-    HeatLayer h; h.acc = xl.acc; h.side = xl.acc_side; h.heads = xl.acc_heads;
-    h.head_stride = (long long)c->rec_T * xl.acc_side * xl.acc_side; h.img_stride = h.head_stride * xl.acc_heads;
+    HeatLayer h; h.acc = xl.acc; h.h = xl.acc_h; h.w = xl.acc_w; h.heads = xl.acc_heads;
+    h.head_stride = (long long)c->rec_T * xl.acc_h * xl.acc_w; h.img_stride = h.head_stride * xl.acc_heads;
     hl.push_back(h); total += xl.heads;                            // the mean is over (layer, head) maps either way
   }
   if (hl.empty() || c->rec_mode != 1) { agd_set_error("No heat maps found. Did you forget to call `with trace(...)`?"); c->err = g_err; return -2; }
   if (rows > c->rec_T || img >= c->rec_B) { agd_set_error("daam_global: rows %d > recorded %d or img %d >= %d", rows, c->rec_T, img, c->rec_B); return fail_ctx(c); }
-  { ProfScope ps(c, st, PC_HEAT, 0); API_CK(c, launch_daam_global(hl.data(), (int)hl.size(), total, rows, c->rec_L, img, out, st)); }
+  { ProfScope ps(c, st, PC_HEAT, 0); API_CK(c, launch_daam_global(hl.data(), (int)hl.size(), total, rows, c->rec_Lh, c->rec_Lw, img, out, st)); }
   return 0;
 }
 
@@ -2080,7 +2129,8 @@ AGD_API int agd_attn_processor(agd_ctx* c, const char* layer, const float* hidde
   if (is_attn2) {
     const WMat* wq = getW(c, an + "to_q.weight"); if (!wq) return fail_ctx(c);
     { GemmOpt o; API_CK(c, run_conv(c, st, x, C, nullptr, 0, 1, 1, M, *wq, 1, q, o, c->zero_page)); }
-    API_CK(c, cross_attention(c, st, xl, q, batch2, n_query, att, record != 0, attn_mask));
+    const int qs = (int)lrintf(sqrtf((float)n_query));      // the seam's query maps are square (hook.py's _unravel_attn)
+    API_CK(c, cross_attention(c, st, xl, q, batch2, n_query, qs, qs, att, record != 0, attn_mask));
   } else {
     const WMat* wqkv = getW(c, t + "attn1.qkv"); if (!wqkv) return fail_ctx(c);
     { GemmOpt o; API_CK(c, run_conv(c, st, x, C, nullptr, 0, 1, 1, M, *wqkv, 1, q, o, c->zero_page)); }
@@ -2507,8 +2557,8 @@ AGD_API int agd_op_attention_headsum(const float* q, const float* k, const float
 AGD_API int agd_op_bicubic_clamp_mean(const float* maps, int n_maps, int T, int side, int S_, float* out, void* stream) {
   hipStream_t st = S(stream);
   // n_maps accumulators of [T][side][side]: treat as one layer with n_maps "heads"
-  HeatLayer h; h.acc = maps; h.side = side; h.heads = n_maps; h.head_stride = (long long)T * side * side; h.img_stride = 0;
-  CK(launch_daam_global(&h, 1, n_maps, T, S_, 0, out, st));
+  HeatLayer h; h.acc = maps; h.h = h.w = side; h.heads = n_maps; h.head_stride = (long long)T * side * side; h.img_stride = 0;
+  CK(launch_daam_global(&h, 1, n_maps, T, S_, S_, 0, out, st));
   hipStreamSynchronize(st);
   return 0;
 }
@@ -2933,12 +2983,12 @@ AGD_API int agd_safety_configure(agd_ctx* c, const agd_vision_config* v) {
   return 0;
 }
 
-AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, int side, float* cos_out, float* pixels_out, void* stream) {
+AGD_API int agd_safety_scores_hw(agd_ctx* c, const unsigned char* images, int B, int ih, int iw, float* cos_out, float* pixels_out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   if (!c->vis_on) { agd_set_error("safety checker not configured (agd_safety_configure before agd_finalize)"); return fail_ctx(c); }
   const agd_vision_config& v = c->vis;
-  if (B < 1 || side < 1 || !images || !cos_out) { agd_set_error("safety_scores: batch %d side %d / null buffer", B, side); return fail_ctx(c); }
+  if (B < 1 || ih < 1 || iw < 1 || !images || !cos_out) { agd_set_error("safety_scores: batch %d size %d x %d / null buffer", B, ih, iw); return fail_ctx(c); }
   const int R = v.image_size, ps = v.patch_size, g = R / ps, np = g * g, T = np + 1, H = v.hidden, M = B * T;
   const int n = v.n_special + v.n_concepts;
   const std::string E = std::string(kVisPre) + "embeddings.";
@@ -2951,28 +3001,50 @@ AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, in
   // scratch from the activation arena only (like agd_text_encode): the recorder accumulators, the cached context and the scheduler's
   // buffers are context-owned allocations this call never touches
   c->arena.release(0);
-  unsigned char* tmp = nullptr; unsigned char* img = nullptr;
-  if (side != R) {
-    tmp = (unsigned char*)c->arena.alloc((size_t)B * side * R * 3); img = (unsigned char*)c->arena.alloc((size_t)B * R * R * 3);
+  // CLIPImageProcessor geometry: the shortest edge resized to image_size, the long one to int(image_size * long / short), then the
+  // image_size x image_size center crop at ((rh - R) / 2, (rw - R) / 2)
+  const int rh = ih <= iw ? R : (int)((long long)R * ih / iw), rw = ih <= iw ? (int)((long long)R * iw / ih) : R;
+  const bool resize = rh != ih || rw != iw, crop = rh != R || rw != R;
+  unsigned char* tmp = nullptr; unsigned char* img = nullptr; unsigned char* cropped = nullptr;
+  if (resize) {
+    tmp = (unsigned char*)c->arena.alloc((size_t)B * ih * rw * 3); img = (unsigned char*)c->arena.alloc((size_t)B * rh * rw * 3);
     if (!tmp || !img) return fail_ctx(c);
   }
+  if (crop) { cropped = (unsigned char*)c->arena.alloc((size_t)B * R * R * 3); if (!cropped) return fail_ctx(c); }
   bf16_t* rows = (bf16_t*)c->arena.alloc((size_t)B * np * pw->Cpad * 2); float* pe = (float*)c->arena.alloc((size_t)B * np * H * 4);
   bf16_t* x = (bf16_t*)c->arena.alloc((size_t)M * H * 2); bf16_t* h = (bf16_t*)c->arena.alloc((size_t)M * H * 2);
   bf16_t* qkv = (bf16_t*)c->arena.alloc((size_t)M * 3 * H * 2); bf16_t* att = (bf16_t*)c->arena.alloc((size_t)M * H * 2);
   bf16_t* ff = (bf16_t*)c->arena.alloc((size_t)M * v.intermediate * 2);
   if (!rows || !pe || !x || !h || !qkv || !att || !ff) return fail_ctx(c);
-  // CLIPImageProcessor: PIL BICUBIC resize of the (square) image to image_size, horizontal pass then vertical (Pillow's order);
-  // the coefficient tables are built and uploaded once per (side, image_size) and cached; the center crop is the identity here
-  if (side != R) {
-    const PilCoeffs* cf = pil_coeffs(side, R); if (!cf) FAIL("safety: resize coefficient upload failed");
-    { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * side * (side + R) * 3);
-      API_CK(c, launch_pil_resample(images, tmp, cf->bounds, cf->kk, cf->ksize, (long long)B * side, side, R, 3, st)); }
-    { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * R * (side + R) * 3);
-      API_CK(c, launch_pil_resample(tmp, img, cf->bounds, cf->kk, cf->ksize, B, side, R, R * 3, st)); }
+  // CLIPImageProcessor: PIL BICUBIC resize, horizontal pass then vertical (Pillow's order; a pass whose axis keeps its size is skipped
+  // in both Pillow and here); the coefficient tables are built and uploaded once per (in, out) and cached
+  const unsigned char* src = images;
+  if (resize) {
+    const unsigned char* hsrc = images; unsigned char* hdst = rh != ih ? tmp : img;
+    if (rw != iw) {
+      const PilCoeffs* cf = pil_coeffs(iw, rw); if (!cf) FAIL("safety: resize coefficient upload failed");
+      ProfScope ps_(c, st, PC_OTHER, 0, (double)B * ih * (iw + rw) * 3);
+      API_CK(c, launch_pil_resample(images, hdst, cf->bounds, cf->kk, cf->ksize, (long long)B * ih, iw, rw, 3, st));
+      hsrc = hdst;
+    }
+    if (rh != ih) {
+      const PilCoeffs* cf = pil_coeffs(ih, rh); if (!cf) FAIL("safety: resize coefficient upload failed");
+      ProfScope ps_(c, st, PC_OTHER, 0, (double)B * rw * (ih + rh) * 3);
+      API_CK(c, launch_pil_resample(hsrc, img, cf->bounds, cf->kk, cf->ksize, B, ih, rh, rw * 3, st));
+    }
+    src = img;
+  }
+  if (crop) {
+    const int top = (rh - R) / 2, left = (rw - R) / 2;
+    ProfScope ps_(c, st, PC_OTHER, 0, 2.0 * B * R * R * 3);
+    for (int b = 0; b < B; ++b)
+      if (hipMemcpy2DAsync(cropped + (size_t)b * R * R * 3, (size_t)R * 3, src + (((size_t)b * rh + top) * rw + left) * 3, (size_t)rw * 3,
+                           (size_t)R * 3, R, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("safety: center crop copy failed");
+    src = cropped;
   }
   const VisNorm nm{v.mean[0], v.mean[1], v.mean[2], v.std[0], v.std[1], v.std[2]};
   { ProfScope ps_(c, st, PC_OTHER, 0, (double)B * R * R * 3 + 2.0 * B * np * pw->Cpad);
-    API_CK(c, launch_vis_patchify(side != R ? img : images, B, R, ps, pw->Cpad, nm, rows, pixels_out, st)); }
+    API_CK(c, launch_vis_patchify(src, B, R, ps, pw->Cpad, nm, rows, pixels_out, st)); }
   { GemmOpt o; o.out_f32 = 1; o.prof_cls = PC_OTHER; API_CK(c, run_conv(c, st, rows, pw->Cpad, nullptr, 0, 1, 1, B * np, *pw, 1, pe, o, c->zero_page)); }
   { ProfScope ps_(c, st, PC_OTHER, 0, 4.0 * B * np * H + 2.0 * M * H);
     API_CK(c, launch_vis_embed_ln(pe, cls, pos, g0, b0, B, np, H, v.eps, x, st)); }
@@ -2982,27 +3054,34 @@ AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, in
     API_CK(c, launch_vis_pooled_head(x, B, T, H, gp, bp, v.eps, wp, v.projection_dim, c->vis_concepts, n, cos_out, st)); }
   return 0;
 }
+AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, int side, float* cos_out, float* pixels_out, void* stream) {
+  return agd_safety_scores_hw(c, images, B, side, side, cos_out, pixels_out, stream);
+}
 
 
 // `vae.encode(image).latent_dist` moments: image fp32 NCHW [B,3,S,S] in [-1,1] -> mean, logvar fp32 NCHW [B,lc,L,L]
-AGD_API int agd_vae_encode(agd_ctx* c, const float* image, int batch, int side, float* mean_out, float* logvar_out, void* stream) {
+AGD_API int agd_vae_encode_hw(agd_ctx* c, const float* image, int batch, int h, int w, float* mean_out, float* logvar_out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
-  const int lc = c->cfg.vae_latent_channels, L = side >> (c->cfg.vae_n_levels - 1);
-  if (side % (1 << (c->cfg.vae_n_levels - 1)) || side % 8) { agd_set_error("vae_encode: side %d not divisible", side); return fail_ctx(c); }
+  const int lc = c->cfg.vae_latent_channels, f = 1 << (c->cfg.vae_n_levels - 1), Lh = h / f, Lw = w / f;
+  if (h < 1 || w < 1 || h % f || h % 8 || w % f || w % 8) { agd_set_error("vae_encode: size %d x %d not divisible", h, w); return fail_ctx(c); }
+  const size_t hw = (size_t)Lh * Lw;
   Tmp tmp;
-  bf16_t* x = tmp.get<bf16_t>((size_t)batch * side * side * 64); float* mom = tmp.get<float>((size_t)batch * L * L * 2 * lc);
-  float* mom_nchw = tmp.get<float>((size_t)batch * L * L * 2 * lc);
+  bf16_t* x = tmp.get<bf16_t>((size_t)batch * h * w * 64); float* mom = tmp.get<float>((size_t)batch * hw * 2 * lc);
+  float* mom_nchw = tmp.get<float>((size_t)batch * hw * 2 * lc);
   if (!x || !mom || !mom_nchw) return fail_ctx(c);
-  API_CK(c, launch_prep_latents(image, x, batch, c->cfg.vae_out_channels, side * side, 64, 1, 1.0f, st));
-  API_CK(c, vae_encode_walk(c, st, x, batch, side, mom));
-  API_CK(c, launch_nchw_from_nhwc_f32(mom, 2 * lc, mom_nchw, batch, 2 * lc, L * L, st));
+  API_CK(c, launch_prep_latents(image, x, batch, c->cfg.vae_out_channels, h * w, 64, 1, 1.0f, st));
+  API_CK(c, vae_encode_walk(c, st, x, batch, h, w, mom));
+  API_CK(c, launch_nchw_from_nhwc_f32(mom, 2 * lc, mom_nchw, batch, 2 * lc, (int)hw, st));
   for (int b = 0; b < batch; ++b) {
-    hipMemcpyAsync(mean_out + (size_t)b * lc * L * L, mom_nchw + (size_t)b * 2 * lc * L * L, (size_t)lc * L * L * 4, hipMemcpyDeviceToDevice, st);
-    hipMemcpyAsync(logvar_out + (size_t)b * lc * L * L, mom_nchw + ((size_t)b * 2 + 1) * lc * L * L, (size_t)lc * L * L * 4, hipMemcpyDeviceToDevice, st);
+    hipMemcpyAsync(mean_out + (size_t)b * lc * hw, mom_nchw + (size_t)b * 2 * lc * hw, (size_t)lc * hw * 4, hipMemcpyDeviceToDevice, st);
+    hipMemcpyAsync(logvar_out + (size_t)b * lc * hw, mom_nchw + ((size_t)b * 2 + 1) * lc * hw, (size_t)lc * hw * 4, hipMemcpyDeviceToDevice, st);
   }
   hipStreamSynchronize(st);
   return 0;
+}
+AGD_API int agd_vae_encode(agd_ctx* c, const float* image, int batch, int side, float* mean_out, float* logvar_out, void* stream) {
+  return agd_vae_encode_hw(c, image, batch, side, side, mean_out, logvar_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3024,40 +3103,40 @@ AGD_API int agd_controlnet_configure(agd_ctx* c, const agd_controlnet_config* e)
 // launches (SD-1.x: eight).  The 3-channel image is zero-padded to 64 channels like the VAE encoder's input; maps whose width is not a
 // multiple of 64 (16 / 32 / 96 by default) are written with a 64-multiple row stride into zeroed buffers, so every conv reads whole
 // 64-channel chunks.  It runs on the `batch` distinct images only; the other repeat - 1 row blocks are copies.
-AGD_API int agd_controlnet_set_cond(agd_ctx* c, const float* cond, int batch, int side, int repeat, void* stream) {
+AGD_API int agd_controlnet_set_cond_hw(agd_ctx* c, const float* cond, int batch, int ih, int iw, int repeat, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   if (!c->cn_on) { agd_set_error("controlnet_set_cond: no ControlNet loaded"); return fail_ctx(c); }
   const agd_controlnet_config& e = c->cnc;
-  const int sh = e.n_emb - 1, L = side >> sh, C0 = c->cfg.block_out_channels[0];
-  if (!cond || batch < 1 || repeat < 1 || L < 1 || (L << sh) != side)
-    { agd_set_error("controlnet_set_cond: batch %d / repeat %d / side %d (a multiple of %d)", batch, repeat, side, 1 << sh); return fail_ctx(c); }
+  const int sh = e.n_emb - 1, Lh = ih >> sh, Lw = iw >> sh, C0 = c->cfg.block_out_channels[0];
+  if (!cond || batch < 1 || repeat < 1 || Lh < 1 || Lw < 1 || (Lh << sh) != ih || (Lw << sh) != iw)
+    { agd_set_error("controlnet_set_cond: batch %d / repeat %d / size %d x %d (each side a multiple of %d)", batch, repeat, ih, iw, 1 << sh); return fail_ctx(c); }
   const int B2 = batch * repeat;
-  c->cn_emb_B2 = 0; c->cn_emb_L = 0;                               // (unset until the embedding below is complete)
+  c->cn_emb_B2 = 0; c->cn_emb_Lh = c->cn_emb_Lw = 0;               // (unset until the embedding below is complete)
   c->arena.release(0);
-  // ping-pong scratch: the largest map of the chain -- the padded input (S x S x 64) or any intermediate output (Ho x Ho x its padded width)
-  size_t big = (size_t)batch * side * side * 64;
-  { long long h = side;
-    auto out_elems = [&](int ch) -> size_t { const size_t ld = (size_t)(ch + 63) / 64 * 64; return (size_t)batch * (size_t)h * (size_t)h * ld; };
+  // ping-pong scratch: the largest map of the chain -- the padded input (H x W x 64) or any intermediate output (Ho x Wo x its padded width)
+  size_t big = (size_t)batch * ih * iw * 64;
+  { long long h = ih, w = iw;
+    auto out_elems = [&](int ch) -> size_t { const size_t ld = (size_t)(ch + 63) / 64 * 64; return (size_t)batch * (size_t)h * (size_t)w * ld; };
     big = std::max(big, out_elems(e.emb_channels[0]));
-    for (int i = 0; i + 1 < e.n_emb; ++i) { big = std::max(big, out_elems(e.emb_channels[i])); h /= 2; big = std::max(big, out_elems(e.emb_channels[i + 1])); } }
+    for (int i = 0; i + 1 < e.n_emb; ++i) { big = std::max(big, out_elems(e.emb_channels[i])); h /= 2; w /= 2; big = std::max(big, out_elems(e.emb_channels[i + 1])); } }
   big *= 2;
   bf16_t* buf[2] = {(bf16_t*)c->arena.alloc(big), (bf16_t*)c->arena.alloc(big)};
   if (!buf[0] || !buf[1]) return fail_ctx(c);
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_controlnet_cond_prep(cond, buf[0], batch, side * side, 64, e.bgr, st)); }
-  API_CK(c, c->cn_embb.ensure((size_t)B2 * L * L * C0 * 2));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_controlnet_cond_prep(cond, buf[0], batch, ih * iw, 64, e.bgr, st)); }
+  API_CK(c, c->cn_embb.ensure((size_t)B2 * Lh * Lw * C0 * 2));
   const std::string E = "controlnet.controlnet_cond_embedding.";
-  int cur = 0, H = side, Cin = 64;
+  int cur = 0, H = ih, W = iw, Cin = 64;
   auto conv = [&](const std::string& k, int stride, bool last) -> int {
     GETW(w, E + k + ".weight"); GETV(b, E + k + ".bias");
     if (w->Cpad != Cin) FAIL("controlnet_set_cond: '%s' reads %d channels, the map has %d", k.c_str(), w->Cpad, Cin);
-    const int Ho = H / stride, ld = last ? w->N : (w->N + 63) / 64 * 64;
-    if (last ? w->N != C0 : (size_t)batch * Ho * Ho * ld * 2 > big) FAIL("controlnet_set_cond: '%s' output [%d x %d x %d] does not fit its buffer", k.c_str(), Ho, Ho, ld);
+    const int Ho = H / stride, Wo = W / stride, ld = last ? w->N : (w->N + 63) / 64 * 64;
+    if (last ? w->N != C0 : (size_t)batch * Ho * Wo * ld * 2 > big) FAIL("controlnet_set_cond: '%s' output [%d x %d x %d] does not fit its buffer", k.c_str(), Ho, Wo, ld);
     bf16_t* out = last ? c->cn_embb.as<bf16_t>() : buf[cur ^ 1];
-    if (!last && ld != w->N && hipMemsetAsync(out, 0, (size_t)batch * Ho * Ho * ld * 2, st) != hipSuccess) FAIL("controlnet_set_cond: memset");
+    if (!last && ld != w->N && hipMemsetAsync(out, 0, (size_t)batch * Ho * Wo * ld * 2, st) != hipSuccess) FAIL("controlnet_set_cond: memset");
     GemmOpt o; o.bias = b; o.act = last ? 0 : 1; o.stride = stride; o.ldo = ld;
-    CK(run_conv(c, st, buf[cur], Cin, nullptr, 0, batch, H, H, *w, 3, out, o, c->zero_page));
-    cur ^= 1; H = Ho; Cin = ld;
+    CK(run_conv(c, st, buf[cur], Cin, nullptr, 0, batch, H, W, *w, 3, out, o, c->zero_page));
+    cur ^= 1; H = Ho; W = Wo; Cin = ld;
     return 0;
   };
   API_CK(c, conv("conv_in", 1, false));
@@ -3066,13 +3145,16 @@ AGD_API int agd_controlnet_set_cond(agd_ctx* c, const float* cond, int batch, in
     API_CK(c, conv("blocks." + std::to_string(2 * i + 1), 2, false));
   }
   API_CK(c, conv("conv_out", 1, true));
-  { const size_t blk = (size_t)batch * L * L * C0;                 // rows r and r + batch are the same image
+  { const size_t blk = (size_t)batch * Lh * Lw * C0;               // rows r and r + batch are the same image
     ProfScope ps(c, st, PC_ELEM, 0);
     for (int r = 1; r < repeat; ++r)
       if (hipMemcpyAsync(c->cn_embb.as<bf16_t>() + r * blk, c->cn_embb.as<bf16_t>(), blk * 2, hipMemcpyDeviceToDevice, st) != hipSuccess)
         { agd_set_error("controlnet_set_cond: row copy failed"); return fail_ctx(c); } }
-  c->cn_emb_B2 = B2; c->cn_emb_L = L; c->cn_emb_rep = repeat;
+  c->cn_emb_B2 = B2; c->cn_emb_Lh = Lh; c->cn_emb_Lw = Lw; c->cn_emb_rep = repeat;
   return 0;
+}
+AGD_API int agd_controlnet_set_cond(agd_ctx* c, const float* cond, int batch, int side, int repeat, void* stream) {
+  return agd_controlnet_set_cond_hw(c, cond, batch, side, side, repeat, stream);
 }
 
 AGD_API int agd_controlnet_set_schedule(agd_ctx* c, const float* scales, int n) {
@@ -3085,50 +3167,60 @@ AGD_API int agd_controlnet_set_schedule(agd_ctx* c, const float* scales, int n) 
 }
 
 
-AGD_API int agd_controlnet_residuals(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float scale, int nhwc,
-                                     float* out, long long* n_out, void* stream) {
+AGD_API int agd_controlnet_residuals_hw(agd_ctx* c, const float* sample, int batch2, int Lh, int Lw, float timestep, float scale, int nhwc,
+                                        float* out, long long* n_out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   if (!c->cn_on) { agd_set_error("controlnet_residuals: no ControlNet loaded"); return fail_ctx(c); }
-  if (batch2 < 1 || L < 1 || (L >> (c->cfg.n_levels - 1)) < 1) { agd_set_error("controlnet_residuals: batch2 %d latent side %d", batch2, L); return fail_ctx(c); }
+  const int sh = c->cfg.n_levels - 1;
+  if (batch2 < 1 || Lh < 1 || Lw < 1 || (Lh >> sh) < 1 || (Lw >> sh) < 1) { agd_set_error("controlnet_residuals: batch2 %d latent size %d x %d", batch2, Lh, Lw); return fail_ctx(c); }
+  API_CK(c, check_latent_hw(c, "controlnet_residuals", Lh, Lw));
   long long n = 0;
-  { int side = L, k = 0;
+  { long long h = Lh, w = Lw; int k = 0;
     const std::vector<int> ch = controlnet_res_channels(c->cfg);
-    n += (long long)batch2 * ch[k++] * side * side;
+    n += (long long)batch2 * ch[k++] * h * w;
     for (int i = 0; i < c->cfg.n_levels; ++i) {
-      for (int j = 0; j < c->cfg.layers_per_block; ++j) n += (long long)batch2 * ch[k++] * side * side;
-      if (i != c->cfg.n_levels - 1) { side /= 2; n += (long long)batch2 * ch[k++] * side * side; }
+      for (int j = 0; j < c->cfg.layers_per_block; ++j) n += (long long)batch2 * ch[k++] * h * w;
+      if (i != c->cfg.n_levels - 1) { h /= 2; w /= 2; n += (long long)batch2 * ch[k++] * h * w; }
     }
-    n += (long long)batch2 * c->cfg.block_out_channels[c->cfg.n_levels - 1] * side * side; }
+    n += (long long)batch2 * c->cfg.block_out_channels[c->cfg.n_levels - 1] * h * w; }
   if (n_out) *n_out = n;
   if (!out) return 0;
   if (!sample) { agd_set_error("controlnet_residuals: null sample"); return fail_ctx(c); }
-  API_CK(c, ensure_lat(c, batch2, L));
-  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, c->cfg.in_channels, L * L, 64, 1, 1.0f, st)); }
+  API_CK(c, ensure_lat(c, batch2, Lh, Lw));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, c->cfg.in_channels, Lh * Lw, 64, 1, 1.0f, st)); }
   c->arena.release(0);
-  API_CK(c, controlnet_walk(c, st, c->lat_bf16, batch2, L, timestep, scale, false, nullptr, nullptr, out, nhwc));
+  API_CK(c, controlnet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, scale, false, nullptr, nullptr, out, nhwc));
   return 0;
+}
+AGD_API int agd_controlnet_residuals(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float scale, int nhwc,
+                                     float* out, long long* n_out, void* stream) {
+  return agd_controlnet_residuals_hw(c, sample, batch2, L, L, timestep, scale, nhwc, out, n_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------
 // Inpainting (diffusers StableDiffusionInpaintPipeline): the mask front end once per call, then a state the three fused loops read
 // ---------------------------------------------------------------------------------------
-AGD_API int agd_inpaint_prepare(agd_ctx* c, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int side,
-                                float* image_out, float* masked_out, float* mask_lat_out, void* stream) {
+AGD_API int agd_inpaint_prepare_hw(agd_ctx* c, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int h, int w,
+                                   float* image_out, float* masked_out, float* mask_lat_out, void* stream) {
   API_CK(c, need_final(c));
   if (!image || !mask) { agd_set_error("inpaint_prepare: null image or mask"); return fail_ctx(c); }
   const int f = 1 << (c->cfg.vae_n_levels - 1);
   ProfScope ps(c, S(stream), PC_ELEM, 0);
-  API_CK(c, launch_inpaint_front(image, image_f32 != 0, mask, mask_f32 != 0, batch, side, f, image_out, masked_out, mask_lat_out, S(stream)));
+  API_CK(c, launch_inpaint_front(image, image_f32 != 0, mask, mask_f32 != 0, batch, h, w, f, image_out, masked_out, mask_lat_out, S(stream)));
   return 0;
 }
+AGD_API int agd_inpaint_prepare(agd_ctx* c, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int side,
+                                float* image_out, float* masked_out, float* mask_lat_out, void* stream) {
+  return agd_inpaint_prepare_hw(c, image, image_f32, mask, mask_f32, batch, side, side, image_out, masked_out, mask_lat_out, stream);
+}
 
-AGD_API int agd_inpaint_set(agd_ctx* c, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
-                            int batch, int L, void* stream) {
+AGD_API int agd_inpaint_set_hw(agd_ctx* c, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
+                               int batch, int Lh, int Lw, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   const int Cl = c->cfg.out_channels, Cin = c->cfg.in_channels;
-  if (!mask || !cond || batch < 1 || L < 1) { agd_set_error("inpaint_set: null mask / cond, or batch %d latent side %d", batch, L); return fail_ctx(c); }
+  if (!mask || !cond || batch < 1 || Lh < 1 || Lw < 1) { agd_set_error("inpaint_set: null mask / cond, or batch %d latent size %d x %d", batch, Lh, Lw); return fail_ctx(c); }
   int mode = 0;
   if (Cin == Cl) {
     if (mask_channels != 1 || cond_channels != Cl || !noise)
@@ -3142,7 +3234,7 @@ AGD_API int agd_inpaint_set(agd_ctx* c, const float* mask, int mask_channels, co
     mode = 1;
   }
   c->ip_mode = 0; c->ip_sched.clear();
-  const size_t hw = (size_t)L * L, nm = (size_t)batch * mask_channels * hw, nc = (size_t)batch * cond_channels * hw;
+  const size_t hw = (size_t)Lh * Lw, nm = (size_t)batch * mask_channels * hw, nc = (size_t)batch * cond_channels * hw;
   API_CK(c, c->ip_maskb.ensure(nm * 4)); API_CK(c, c->ip_condb.ensure(nc * 4));
   if (hipMemcpyAsync(c->ip_maskb.p, mask, nm * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
       hipMemcpyAsync(c->ip_condb.p, cond, nc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("inpaint_set: copy failed"); return fail_ctx(c); }
@@ -3150,8 +3242,12 @@ AGD_API int agd_inpaint_set(agd_ctx* c, const float* mask, int mask_channels, co
     API_CK(c, c->ip_noiseb.ensure(nc * 4));
     if (hipMemcpyAsync(c->ip_noiseb.p, noise, nc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("inpaint_set: copy failed"); return fail_ctx(c); }
   }
-  c->ip_mode = mode; c->ip_B = batch; c->ip_L = L; c->ip_Cm = mask_channels; c->ip_Cc = cond_channels;
+  c->ip_mode = mode; c->ip_B = batch; c->ip_Lh = Lh; c->ip_Lw = Lw; c->ip_Cm = mask_channels; c->ip_Cc = cond_channels;
   return 0;
+}
+AGD_API int agd_inpaint_set(agd_ctx* c, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
+                            int batch, int L, void* stream) {
+  return agd_inpaint_set_hw(c, mask, mask_channels, cond, cond_channels, noise, batch, L, L, stream);
 }
 
 AGD_API int agd_inpaint_set_schedule(agd_ctx* c, const float* sa_sb, int n) {
@@ -3165,7 +3261,7 @@ AGD_API int agd_inpaint_set_schedule(agd_ctx* c, const float* sa_sb, int n) {
 
 AGD_API int agd_inpaint_clear(agd_ctx* c) {
   if (!c) { agd_set_error("null ctx"); return -1; }
-  c->ip_mode = 0; c->ip_B = c->ip_L = c->ip_Cm = c->ip_Cc = 0; c->ip_sched.clear();
+  c->ip_mode = 0; c->ip_B = c->ip_Lh = c->ip_Lw = c->ip_Cm = c->ip_Cc = 0; c->ip_sched.clear();
   return 0;
 }
 

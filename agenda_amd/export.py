@@ -50,10 +50,12 @@ def stack_heatmaps(obj: torch.Tensor, fg: torch.Tensor, bg: torch.Tensor):
     return rgb, inv
 
 
-def export_batch(images_u8: torch.Tensor, heatmaps: torch.Tensor, image_size: int):
-    """images uint8 [B,H,W,3], heat maps fp32 [B,nw,S,S] (cuda) -> (uint8 [B,size,size,3], uint8 [B,nw,size,size]):
-    exactly the PNG payloads `data_generation.py:60,76-86` writes."""
-    small = resize_u8(images_u8, (image_size, image_size))
+def export_batch(images_u8: torch.Tensor, heatmaps: torch.Tensor, image_size):
+    """images uint8 [B,H,W,3], heat maps fp32 [B,nw,h,w] (cuda) -> (uint8 [B,sh,sw,3], uint8 [B,nw,sh,sw]):
+    exactly the PNG payloads `data_generation.py:60,76-86` writes.  `image_size`: one side (square output, the reference's
+    `resize((S, S))`) or an (sh, sw) pair."""
+    sh, sw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
+    small = resize_u8(images_u8, (sh, sw))
     B, nw = heatmaps.shape[:2]
-    hm = resize_u8(heatmaps_to_u8(heatmaps).reshape(B * nw, *heatmaps.shape[2:]), (image_size, image_size))
-    return small, hm.reshape(B, nw, image_size, image_size)
+    hm = resize_u8(heatmaps_to_u8(heatmaps).reshape(B * nw, *heatmaps.shape[2:]), (sh, sw))
+    return small, hm.reshape(B, nw, sh, sw)

@@ -61,24 +61,29 @@ def stack_heatmaps(obj: np.ndarray, fg: np.ndarray, bg: np.ndarray):
 def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Optional[str] = None,
                    prompt_embeds: Optional[torch.Tensor] = None, num_inference_steps: int = 50,
                    guidance_scale: float = 7.5, height: Optional[int] = None, rec_tokens: Optional[int] = None,
-                   word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None):
+                   word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None, width: Optional[int] = None):
     """One hot-path pass: len(seeds) images + per-word DAAM maps.  control: extra keyword arguments of a ControlNet pipeline's call
     (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`) or of an inpainting one
     (`inpaint_inputs_for`).
-    Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, S, S] on GPU)."""
+    Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, H/8, W/8] on GPU)."""
     from .trace import trace
     from . import synthetic
     B = len(seeds)
-    side = height or pipe.cfg.default_sample_size * pipe.vae_scale_factor
-    L = side // pipe.vae_scale_factor
-    lat = synthetic.make_latents(pipe.cfg, seeds, L)      # CPU generator per image seed (data_generation.py:58)
+    side = pipe.cfg.default_sample_size * pipe.vae_scale_factor
+    height, width = height or side, width or side
+    f = pipe.vae_scale_factor
+    if height == width:
+        lat = synthetic.make_latents(pipe.cfg, seeds, height // f)      # CPU generator per image seed (data_generation.py:58)
+    else:                                                               # the same per-seed draw at the rectangular shape
+        lat = torch.cat([torch.randn(1, pipe.cfg.unet.out_channels, height // f, width // f, generator=torch.Generator("cpu").manual_seed(int(s)))
+                         for s in seeds], 0)
     with trace(pipe, rec_tokens=rec_tokens) as trc:
         if prompt_embeds is None:
             out = pipe([prompt] * B, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                       latents=lat, height=side, width=side, output_type="pt", **(control or {}))
+                       latents=lat, height=height, width=width, output_type="pt", **(control or {}))
         else:
             out = pipe(prompt_embeds=prompt_embeds, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                       latents=lat, height=side, width=side, output_type="pt", **(control or {}))
+                       latents=lat, height=height, width=width, output_type="pt", **(control or {}))
         hms = []
         for i in range(B):
             g = trc.compute_global_heat_map(prompt=prompt, image_index=i)
@@ -195,13 +200,15 @@ def gather_outputs(images: torch.Tensor, heatmaps: torch.Tensor, seeds: Optional
     return pend if async_op else pend.wait()
 
 
-def save_outputs(save_dir: str, seeds, images_u8, heatmaps, words, image_size: int, stack_words=None, exported: bool = False):
+def save_outputs(save_dir: str, seeds, images_u8, heatmaps, words, image_size, stack_words=None, exported: bool = False):
     """data_generation.py:60-62,66-86: resize, skip all-black, images/ + daam_<word>_heatmaps/ PNGs.
     CUDA tensors take the device export path (agenda_amd/export.py: min-max -> uint8 -> PIL-exact bicubic resize on
     the GPU, one D2H copy of the finished buffers); numpy inputs take the reference's literal host code.  Both
     produce identical bytes (tests/test_export.py).  `stack_words=(obj, fg, bg)` additionally writes
-    daam_stack_heatmaps/ + daam_inv_heatmaps/ as postprocess_heatmap.py:44-50 would."""
+    daam_stack_heatmaps/ + daam_inv_heatmaps/ as postprocess_heatmap.py:44-50 would.  `image_size`: one side (square PNGs, the
+    reference's `resize((S, S))`) or an (h, w) pair."""
     from PIL import Image
+    sh, sw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
     os.makedirs(os.path.join(save_dir, "images"), exist_ok=True)
     if exported:                                # already the final payloads (export_batch ran before the gather)
         small, hm = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (images_u8, heatmaps))
@@ -211,9 +218,9 @@ def save_outputs(save_dir: str, seeds, images_u8, heatmaps, words, image_size: i
         small, hm = small.cpu().numpy(), hm.cpu().numpy()
     else:
         images_u8, heatmaps = np.asarray(images_u8), np.asarray(heatmaps)
-        small = np.stack([np.asarray(Image.fromarray(im).resize((image_size, image_size))) for im in images_u8])
-        hm = np.stack([np.stack([np.asarray(Image.fromarray(export_heatmap_u8(h)).resize((image_size, image_size)))
-                                 for h in hs]) if len(hs) else np.zeros((0, image_size, image_size), np.uint8) for hs in heatmaps])
+        small = np.stack([np.asarray(Image.fromarray(im).resize((sw, sh))) for im in images_u8])
+        hm = np.stack([np.stack([np.asarray(Image.fromarray(export_heatmap_u8(h)).resize((sw, sh)))
+                                 for h in hs]) if len(hs) else np.zeros((0, sh, sw), np.uint8) for hs in heatmaps])
     for i, seed in enumerate(seeds):
         if np.max(small[i]) < 1e-5:             # NSFW content filter (black image), data_generation.py:61-62
             continue
@@ -240,7 +247,10 @@ def parse_args(argv=None):
     p.add_argument("--word_token_heatmaps", type=str, default=None, nargs="+")
     p.add_argument("--store_learnable_token_heatmaps", action="store_true")
     p.add_argument("--num-images", type=int, default=10000)
-    p.add_argument("--image-size", type=int, default=112)
+    p.add_argument("--image-size", type=int, default=[112], nargs="+", metavar="S",
+                   help="saved PNG size: one value S (square, S x S) or two values H W")
+    p.add_argument("--height", type=int, default=None, help="generated image height, a multiple of 64 (default: the checkpoint's size)")
+    p.add_argument("--width", type=int, default=None, help="generated image width, a multiple of 64 (default: the checkpoint's size)")
     p.add_argument("--batch-size", type=int, default=4)
     p.add_argument("--num-inference-steps", type=int, default=20)
     p.add_argument("--synthetic-config", type=str, default="sd15", help="architecture for synthetic weights when no checkpoint is given")
@@ -285,6 +295,13 @@ def parse_args(argv=None):
         p.error("--control-guidance-start / --control-guidance-end: 0 <= start < end <= 1")
     if args.use_karras_sigmas and args.scheduler != "DPMSolverMultistepScheduler":
         p.error("--use-karras-sigmas needs --scheduler DPMSolverMultistepScheduler")
+    if len(args.image_size) not in (1, 2) or min(args.image_size) < 1:
+        p.error("--image-size takes one positive value S (square) or two, H W")
+    args.image_size = args.image_size[0] if len(args.image_size) == 1 else tuple(args.image_size)
+    for name in ("height", "width"):
+        v = getattr(args, name)
+        if v is not None and (v < 1 or v % 64):
+            p.error(f"--{name} {v}: a positive multiple of 64")
     return args
 
 
@@ -377,7 +394,8 @@ def main(argv=None):
                            "control_guidance_start": args.control_guidance_start, "control_guidance_end": args.control_guidance_end}
             if ip_files:
                 control = inpaint_inputs_for(ip_files, chunk, args.strength)
-            imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control)
+            imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
+                                       height=args.height, width=args.width)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)
             continue
@@ -388,8 +406,9 @@ def main(argv=None):
         if chunk:
             small, hm8 = export.export_batch(imgs, hms, S)
         else:
-            small = torch.zeros(0, S, S, 3, dtype=torch.uint8, device=dev)
-            hm8 = torch.zeros(0, len(words), S, S, dtype=torch.uint8, device=dev)
+            sh, sw = (S, S) if isinstance(S, int) else S
+            small = torch.zeros(0, sh, sw, 3, dtype=torch.uint8, device=dev)
+            hm8 = torch.zeros(0, len(words), sh, sw, dtype=torch.uint8, device=dev)
         if dist.get_backend() == "gloo":
             small, hm8 = small.cpu(), hm8.cpu()
         round_seeds = sorted(s_ for rk in range(world) for s_ in shard_seeds(args.num_images, rk, world)[r * args.batch_size:(r + 1) * args.batch_size])

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .config import SDConfig, inpaint_flavour, inpaint_variant
-from .pipeline import PipelineOutput, StableDiffusionPipeline
+from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 
 
@@ -135,19 +135,20 @@ def check_request(cfg: SDConfig, scheduler, strength: float, num_inference_steps
     return flavour
 
 
-def draw_noises(generator, n_images: int, batch: int, c: int, L: int, need_image: bool, need_masked: bool, noise_enc_image=None,
+def draw_noises(generator, n_images: int, batch: int, c: int, L, need_image: bool, need_masked: bool, noise_enc_image=None,
                 noise=None, noise_enc_masked=None):
     """The call's N(0, 1) draws in diffusers' order [upstream-knowledge]: the image's posterior sample (when its latents are needed),
     the start noise, the masked image's posterior sample (9-channel UNets).  Explicit tensors replace draws; a draw is taken only where
-    no tensor is given.  CPU generators only (host-reproducible)."""
+    no tensor is given.  CPU generators only (host-reproducible).  `L`: the latent side, or an (Lh, Lw) pair."""
+    Lh, Lw = (L, L) if isinstance(L, int) else tuple(L)
     if generator is not None and (not isinstance(generator, torch.Generator) or generator.device.type != "cpu"):
         raise ValueError("use one CPU torch.Generator")
     ne = me = None
     if need_image:
-        ne = noise_enc_image if noise_enc_image is not None else torch.randn(n_images, c, L, L, generator=generator)
-    nz = noise if noise is not None else torch.randn(batch, c, L, L, generator=generator)
+        ne = noise_enc_image if noise_enc_image is not None else torch.randn(n_images, c, Lh, Lw, generator=generator)
+    nz = noise if noise is not None else torch.randn(batch, c, Lh, Lw, generator=generator)
     if need_masked:
-        me = noise_enc_masked if noise_enc_masked is not None else torch.randn(n_images, c, L, L, generator=generator)
+        me = noise_enc_masked if noise_enc_masked is not None else torch.randn(n_images, c, Lh, Lw, generator=generator)
     return ne, nz, me
 
 
@@ -198,11 +199,12 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
             raise ValueError("StableDiffusionInpaintPipeline needs image= and mask_image=")
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
-        if height != width or height % 64:
-            raise ValueError("height == width, multiple of 64 required")
+        check_image_size(height, width)
         flavour = check_request(self.cfg, self.scheduler, strength, num_inference_steps)
+        Lh, Lw = height // self.vae_scale_factor, width // self.vae_scale_factor
+        self._refuse_rectangular_hook(Lh, Lw)
         self._apply_lora_scale(cross_attention_kwargs)
-        L = height // self.vae_scale_factor
+        L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
         img, mask = prepare_mask_and_image(image, mask_image, height, width)
         if prompt_embeds is None:
             prompts = [prompt] if isinstance(prompt, str) else list(prompt)
@@ -223,11 +225,11 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
         if noise is None and latents is not None:
             noise = latents                                       # diffusers: `noise = latents`
         ne, nz, me = draw_noises(generator, n, B, Cl, L, need_image, need_masked, noise_enc_image, noise, noise_enc_masked)
-        if tuple(nz.shape) != (B, Cl, L, L):
-            raise ValueError(f"Unexpected noise shape, got {tuple(nz.shape)}, expected {(B, Cl, L, L)}")
+        if tuple(nz.shape) != (B, Cl, Lh, Lw):
+            raise ValueError(f"Unexpected noise shape, got {tuple(nz.shape)}, expected {(B, Cl, Lh, Lw)}")
         for t_, nm in ((ne, "noise_enc_image"), (me, "noise_enc_masked")):
-            if t_ is not None and tuple(t_.shape) != (n, Cl, L, L):
-                raise ValueError(f"Unexpected {nm} shape, got {tuple(t_.shape)}, expected {(n, Cl, L, L)}")
+            if t_ is not None and tuple(t_.shape) != (n, Cl, Lh, Lw):
+                raise ValueError(f"Unexpected {nm} shape, got {tuple(t_.shape)}, expected {(n, Cl, Lh, Lw)}")
         eng = self.engine
         x, mask_lat = eng.inpaint_prepare(img, mask, need_image, need_masked)
         mean, logvar = eng.vae_encode(x)                          # image rows, then masked-image rows: one encoder pass

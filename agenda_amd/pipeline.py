@@ -19,7 +19,7 @@ import ctypes as C
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -45,6 +45,20 @@ class PipelineOutput:
     images: list
     latents: Optional[torch.Tensor] = None
     nsfw_content_detected: Optional[list] = None
+
+
+def _hw(L) -> Tuple[int, int]:
+    """A latent (or pixel) size given as one side (square) or as an (h, w) pair."""
+    if isinstance(L, (tuple, list)):
+        h, w = L
+        return int(h), int(w)
+    return int(L), int(L)
+
+
+def check_image_size(height: int, width: int, multiple: int = 64) -> None:
+    """The pipelines' size rule: each side a positive multiple of 64, applied per axis (height and width may differ)."""
+    if not all(isinstance(v, int) and v > 0 and v % multiple == 0 for v in (height, width)):
+        raise ValueError(f"height and width must each be a positive multiple of {multiple}, got height={height}, width={width}")
 
 
 def _make_cfg(cfg: SDConfig, workspace_bytes: int) -> _lib.AgdConfig:
@@ -163,17 +177,21 @@ class Engine:
         self._ck(self.lib.agd_safety_configure(self.ctx, C.byref(self._vcfg)), "agd_safety_configure")
 
     def safety_scores(self, images_u8: torch.Tensor, want_pixels: bool = False):
-        """`agd_safety_scores`: uint8 [B,S,S,3] -> cosines fp32 [B, n_special + n_concepts] (cuda), and the processor's
+        """`agd_safety_scores`: uint8 [B,H,W,3] -> cosines fp32 [B, n_special + n_concepts] (cuda), and the processor's
         pixel_values [B,3,R,R] when asked."""
         s = self.cfg.safety
         img = images_u8.to(device=f"cuda:{self.device}", dtype=torch.uint8).contiguous()
-        if img.ndim != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2]:
-            raise ValueError(f"safety checker takes square uint8 [B,S,S,3] images, got {tuple(img.shape)}")
-        b, side = img.shape[0], img.shape[1]
+        if img.ndim != 4 or img.shape[3] != 3:
+            raise ValueError(f"safety checker takes uint8 [B,H,W,3] images, got {tuple(img.shape)}")
+        b, h, w = img.shape[0], img.shape[1], img.shape[2]
         cos = torch.empty(b, s.n_special + s.n_concepts, device=img.device, dtype=torch.float32)
         pix = torch.empty(b, 3, s.image_size, s.image_size, device=img.device, dtype=torch.float32) if want_pixels else None
-        self._ck(self.lib.agd_safety_scores(self.ctx, _lib.ptr(img), b, side, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
-                 "agd_safety_scores")
+        if h == w:
+            self._ck(self.lib.agd_safety_scores(self.ctx, _lib.ptr(img), b, h, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
+                     "agd_safety_scores")
+        else:
+            self._ck(self.lib.agd_safety_scores_hw(self.ctx, _lib.ptr(img), b, h, w, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
+                     "agd_safety_scores_hw")
         return (cos, pix) if want_pixels else cos
 
     def controlnet_configure(self, cncfg):
@@ -187,13 +205,16 @@ class Engine:
         self._ck(self.lib.agd_controlnet_configure(self.ctx, C.byref(self._cncfg)), "agd_controlnet_configure")
 
     def controlnet_set_cond(self, cond: torch.Tensor, repeat: int = 2):
-        """`agd_controlnet_set_cond`: the control image fp32 [B,3,S,S] in [0,1] -> the conditioning embedding of B * repeat UNet rows
+        """`agd_controlnet_set_cond`: the control image fp32 [B,3,H,W] in [0,1] -> the conditioning embedding of B * repeat UNet rows
         ([cond; cond] for the CFG batch), computed once."""
         cond = self._h2d(cond)
         b, c, h, w = cond.shape
-        if c != 3 or h != w:
-            raise ValueError(f"control image must be [B,3,S,S], got {tuple(cond.shape)}")
-        self._ck(self.lib.agd_controlnet_set_cond(self.ctx, _lib.ptr(cond), b, h, int(repeat), self._stream()), "agd_controlnet_set_cond")
+        if c != 3:
+            raise ValueError(f"control image must be [B,3,H,W], got {tuple(cond.shape)}")
+        if h == w:
+            self._ck(self.lib.agd_controlnet_set_cond(self.ctx, _lib.ptr(cond), b, h, int(repeat), self._stream()), "agd_controlnet_set_cond")
+        else:
+            self._ck(self.lib.agd_controlnet_set_cond_hw(self.ctx, _lib.ptr(cond), b, h, w, int(repeat), self._stream()), "agd_controlnet_set_cond_hw")
         self._cond_keepalive = cond
 
     def controlnet_set_schedule(self, scales):
@@ -206,46 +227,59 @@ class Engine:
         """`agd_controlnet_residuals`: the scaled ControlNet residuals of one forward, back to back in one fp32 vector (down residuals in
         res-sample order, then the mid residual; each [B2,C,h,w], or [B2,h,w,C] with nhwc)."""
         sample = sample.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-        b2, _, L, _ = sample.shape
+        b2, _, Lh, Lw = sample.shape
         n = C.c_longlong(0)
-        self._ck(self.lib.agd_controlnet_residuals(self.ctx, None, b2, L, 0.0, 0.0, int(nhwc), None, C.byref(n), None), "agd_controlnet_residuals")
+        self._ck(self.lib.agd_controlnet_residuals_hw(self.ctx, None, b2, Lh, Lw, 0.0, 0.0, int(nhwc), None, C.byref(n), None), "agd_controlnet_residuals")
         out = torch.empty(n.value, device=sample.device, dtype=torch.float32)
-        self._ck(self.lib.agd_controlnet_residuals(self.ctx, _lib.ptr(sample), b2, L, float(timestep), float(scale), int(nhwc), _lib.ptr(out),
-                                                   C.byref(n), self._stream()), "agd_controlnet_residuals")
+        if Lh == Lw:
+            self._ck(self.lib.agd_controlnet_residuals(self.ctx, _lib.ptr(sample), b2, Lh, float(timestep), float(scale), int(nhwc), _lib.ptr(out),
+                                                       C.byref(n), self._stream()), "agd_controlnet_residuals")
+        else:
+            self._ck(self.lib.agd_controlnet_residuals_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(timestep), float(scale), int(nhwc),
+                                                          _lib.ptr(out), C.byref(n), self._stream()), "agd_controlnet_residuals_hw")
         return out
 
     def inpaint_prepare(self, image: torch.Tensor, mask: torch.Tensor, want_image: bool, want_masked: bool):
-        """`agd_inpaint_prepare`: image uint8 [B,S,S,3] or float [B,3,S,S] in [-1,1], mask uint8 or float [B,S,S] -> (x, mask_lat): x fp32
-        [n B,3,S,S] holds the [-1,1] image rows (want_image), then the masked-image rows (want_masked), ready for one vae_encode; mask_lat
-        fp32 [B,1,L,L] binary."""
+        """`agd_inpaint_prepare`: image uint8 [B,H,W,3] or float [B,3,H,W] in [-1,1], mask uint8 or float [B,H,W] -> (x, mask_lat): x fp32
+        [n B,3,H,W] holds the [-1,1] image rows (want_image), then the masked-image rows (want_masked), ready for one vae_encode; mask_lat
+        fp32 [B,1,H/8,W/8] binary."""
         dev = f"cuda:{self.device}"
         img_f32 = image.dtype != torch.uint8
         image = image.to(device=dev, dtype=torch.float32 if img_f32 else torch.uint8).contiguous()
         mask_f32 = mask.dtype != torch.uint8
         mask = mask.to(device=dev, dtype=torch.float32 if mask_f32 else torch.uint8).contiguous()
         b = image.shape[0]
-        S = image.shape[2] if img_f32 else image.shape[1]
-        L = S // self.cfg.vae_scale_factor
-        x = torch.empty((int(want_image) + int(want_masked)) * b, 3, S, S, device=dev, dtype=torch.float32)
-        m = torch.empty(b, 1, L, L, device=dev, dtype=torch.float32)
+        H, W = tuple(image.shape[2:4]) if img_f32 else tuple(image.shape[1:3])
+        f = self.cfg.vae_scale_factor
+        x = torch.empty((int(want_image) + int(want_masked)) * b, 3, H, W, device=dev, dtype=torch.float32)
+        m = torch.empty(b, 1, H // f, W // f, device=dev, dtype=torch.float32)
         xi = _lib.ptr(x) if want_image else None
-        xm = C.c_void_p(x.data_ptr() + (b * 3 * S * S * 4 if want_image else 0)) if want_masked else None
-        self._ck(self.lib.agd_inpaint_prepare(self.ctx, C.c_void_p(image.data_ptr()), int(img_f32), C.c_void_p(mask.data_ptr()), int(mask_f32), b, S,
-                                              xi, xm, _lib.ptr(m), self._stream()), "agd_inpaint_prepare")
+        xm = C.c_void_p(x.data_ptr() + (b * 3 * H * W * 4 if want_image else 0)) if want_masked else None
+        img_p, mask_p = C.c_void_p(image.data_ptr()), C.c_void_p(mask.data_ptr())
+        if H == W:
+            self._ck(self.lib.agd_inpaint_prepare(self.ctx, img_p, int(img_f32), mask_p, int(mask_f32), b, H, xi, xm, _lib.ptr(m), self._stream()),
+                     "agd_inpaint_prepare")
+        else:
+            self._ck(self.lib.agd_inpaint_prepare_hw(self.ctx, img_p, int(img_f32), mask_p, int(mask_f32), b, H, W, xi, xm, _lib.ptr(m),
+                                                     self._stream()), "agd_inpaint_prepare_hw")
         self._inpaint_keep = (image, mask)
         return x, m
 
     def inpaint_set(self, mask: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor] = None):
-        """`agd_inpaint_set`: mask [B,Cm,L,L] and cond [B,Cc,L,L] (masked-image latents, or image latents with the noise for the blend)."""
+        """`agd_inpaint_set`: mask [B,Cm,Lh,Lw] and cond [B,Cc,Lh,Lw] (masked-image latents, or image latents with the noise for the blend)."""
         dev = f"cuda:{self.device}"
         f = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
         mask, cond, noise = f(mask), f(cond), f(noise)
-        b, cm, L, _ = mask.shape
-        if cond.shape[0] != b or tuple(cond.shape[2:]) != (L, L) or (noise is not None and noise.shape != cond.shape):
+        b, cm, Lh, Lw = mask.shape
+        if cond.shape[0] != b or tuple(cond.shape[2:]) != (Lh, Lw) or (noise is not None and noise.shape != cond.shape):
             raise ValueError(f"inpaint state shapes disagree: mask {tuple(mask.shape)}, cond {tuple(cond.shape)}, "
                              f"noise {None if noise is None else tuple(noise.shape)}")
-        self._ck(self.lib.agd_inpaint_set(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, L, self._stream()),
-                 "agd_inpaint_set")
+        if Lh == Lw:
+            self._ck(self.lib.agd_inpaint_set(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, Lh, self._stream()),
+                     "agd_inpaint_set")
+        else:
+            self._ck(self.lib.agd_inpaint_set_hw(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, Lh, Lw,
+                                                 self._stream()), "agd_inpaint_set_hw")
         self._inpaint_state = (mask, cond, noise)
 
     def inpaint_set_schedule(self, sa_sb):
@@ -279,16 +313,24 @@ class Engine:
         """`timestep`: a number (one timestep for the batch) or a [B] tensor / sequence (one per image, the training call)."""
         sample = sample.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
         out = torch.empty_like(sample)
-        b2, _, L, _ = sample.shape
+        b2, _, Lh, Lw = sample.shape
         ts = timestep.detach().flatten().tolist() if torch.is_tensor(timestep) else (list(timestep) if isinstance(timestep, (list, tuple)) else [timestep])
         if len(ts) == 1:
-            self._ck(self.lib.agd_unet_forward(self.ctx, _lib.ptr(sample), b2, L, float(ts[0]), _lib.ptr(out), self._stream()),
-                     "agd_unet_forward")
+            if Lh == Lw:
+                self._ck(self.lib.agd_unet_forward(self.ctx, _lib.ptr(sample), b2, Lh, float(ts[0]), _lib.ptr(out), self._stream()),
+                         "agd_unet_forward")
+            else:
+                self._ck(self.lib.agd_unet_forward_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(ts[0]), _lib.ptr(out), self._stream()),
+                         "agd_unet_forward_hw")
         else:
             if len(ts) != b2:
                 raise ValueError(f"timestep has {len(ts)} entries for a batch of {b2}")
             arr = (C.c_float * b2)(*[float(t) for t in ts])
-            self._ck(self.lib.agd_unet_forward_ts(self.ctx, _lib.ptr(sample), b2, L, arr, _lib.ptr(out), self._stream()), "agd_unet_forward_ts")
+            if Lh == Lw:
+                self._ck(self.lib.agd_unet_forward_ts(self.ctx, _lib.ptr(sample), b2, Lh, arr, _lib.ptr(out), self._stream()), "agd_unet_forward_ts")
+            else:
+                self._ck(self.lib.agd_unet_forward_ts_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, arr, _lib.ptr(out), self._stream()),
+                         "agd_unet_forward_ts_hw")
         return out
 
     def denoise(self, latents: torch.Tensor, timesteps, a_t, a_p, guidance: float):
@@ -297,9 +339,11 @@ class Engine:
         ts = (C.c_float * n)(*[float(t) for t in timesteps])
         at = (C.c_float * n)(*[float(x) for x in a_t])
         ap = (C.c_float * n)(*[float(x) for x in a_p])
-        b, _, L, _ = latents.shape
-        self._ck(self.lib.agd_denoise(self.ctx, _lib.ptr(latents), b, L, n, ts, at, ap, float(guidance), self._stream()),
-                 "agd_denoise")
+        b, _, Lh, Lw = latents.shape
+        if Lh == Lw:
+            self._ck(self.lib.agd_denoise(self.ctx, _lib.ptr(latents), b, Lh, n, ts, at, ap, float(guidance), self._stream()), "agd_denoise")
+        else:
+            self._ck(self.lib.agd_denoise_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, at, ap, float(guidance), self._stream()), "agd_denoise_hw")
         return latents
 
     def cfg_ddim_step(self, eps: torch.Tensor, latents: torch.Tensor, guidance: float, alpha_t: float, alpha_prev: float):
@@ -307,11 +351,15 @@ class Engine:
         (eta 0) update of `latents` [B,4,L,L] in place (`agd_cfg_ddim_step`; the fused loop is `denoise`)."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
         eps = eps.to(device=latents.device, dtype=torch.float32).contiguous()
-        b, _, L, _ = latents.shape
+        b, _, Lh, Lw = latents.shape
         if eps.shape[0] != 2 * b:
             raise ValueError(f"eps batch {eps.shape[0]} != 2 x latents batch {b}")
-        self._ck(self.lib.agd_cfg_ddim_step(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, L, float(guidance), float(alpha_t),
-                                            float(alpha_prev), self._stream()), "agd_cfg_ddim_step")
+        if Lh == Lw:
+            self._ck(self.lib.agd_cfg_ddim_step(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, Lh, float(guidance), float(alpha_t),
+                                                float(alpha_prev), self._stream()), "agd_cfg_ddim_step")
+        else:
+            self._ck(self.lib.agd_cfg_ddim_step_hw(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, Lh, Lw, float(guidance), float(alpha_t),
+                                                   float(alpha_prev), self._stream()), "agd_cfg_ddim_step_hw")
         return latents
 
     def denoise_plms(self, latents: torch.Tensor, timesteps, sample_coeff, eps_coeff, guidance: float):
@@ -321,9 +369,13 @@ class Engine:
         ts = (C.c_float * n)(*[float(t) for t in timesteps])
         ca = (C.c_float * n)(*[float(x) for x in sample_coeff])
         cb = (C.c_float * n)(*[float(x) for x in eps_coeff])
-        b, _, L, _ = latents.shape
-        self._ck(self.lib.agd_denoise_plms(self.ctx, _lib.ptr(latents), b, L, n, ts, ca, cb, float(guidance), self._stream()),
-                 "agd_denoise_plms")
+        b, _, Lh, Lw = latents.shape
+        if Lh == Lw:
+            self._ck(self.lib.agd_denoise_plms(self.ctx, _lib.ptr(latents), b, Lh, n, ts, ca, cb, float(guidance), self._stream()),
+                     "agd_denoise_plms")
+        else:
+            self._ck(self.lib.agd_denoise_plms_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, ca, cb, float(guidance), self._stream()),
+                     "agd_denoise_plms_hw")
         return latents
 
     def denoise_dpm(self, latents: torch.Tensor, timesteps, cx, ce, a, b0, b1, guidance: float):
@@ -335,29 +387,39 @@ class Engine:
             raise ValueError("denoise_dpm: one (cx, ce, a, b0, b1) per timestep")
         ts = (C.c_float * n)(*[float(t) for t in timesteps])
         co = (C.c_float * (5 * n))(*[float(v) for row in zip(cx, ce, a, b0, b1) for v in row])
-        b, _, L, _ = latents.shape
-        self._ck(self.lib.agd_denoise_dpm(self.ctx, _lib.ptr(latents), b, L, n, ts, co, float(guidance), self._stream()),
-                 "agd_denoise_dpm")
+        b, _, Lh, Lw = latents.shape
+        if Lh == Lw:
+            self._ck(self.lib.agd_denoise_dpm(self.ctx, _lib.ptr(latents), b, Lh, n, ts, co, float(guidance), self._stream()), "agd_denoise_dpm")
+        else:
+            self._ck(self.lib.agd_denoise_dpm_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, co, float(guidance), self._stream()),
+                     "agd_denoise_dpm_hw")
         return latents
 
     def vae_decode(self, latents: torch.Tensor, want_f32: bool = False):
         latents = latents.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-        b, _, L, _ = latents.shape
-        S = L * (2 ** (len(self.cfg.vae.block_out_channels) - 1))
-        u8 = torch.empty(b, S, S, 3, device=latents.device, dtype=torch.uint8)
-        f32 = torch.empty(b, S, S, 3, device=latents.device, dtype=torch.float32) if want_f32 else None
-        self._ck(self.lib.agd_vae_decode(self.ctx, _lib.ptr(latents), b, L, _lib.ptr(u8), _lib.ptr(f32), self._stream()),
-                 "agd_vae_decode")
+        b, _, Lh, Lw = latents.shape
+        f = 2 ** (len(self.cfg.vae.block_out_channels) - 1)
+        u8 = torch.empty(b, Lh * f, Lw * f, 3, device=latents.device, dtype=torch.uint8)
+        f32 = torch.empty(b, Lh * f, Lw * f, 3, device=latents.device, dtype=torch.float32) if want_f32 else None
+        if Lh == Lw:
+            self._ck(self.lib.agd_vae_decode(self.ctx, _lib.ptr(latents), b, Lh, _lib.ptr(u8), _lib.ptr(f32), self._stream()), "agd_vae_decode")
+        else:
+            self._ck(self.lib.agd_vae_decode_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, _lib.ptr(u8), _lib.ptr(f32), self._stream()),
+                     "agd_vae_decode_hw")
         return (u8, f32) if want_f32 else u8
 
     def vae_encode(self, image: torch.Tensor):
-        """`vae.encode(image).latent_dist` moments: image [B,3,S,S] in [-1,1] -> (mean, logvar) fp32 [B,4,S/8,S/8]."""
+        """`vae.encode(image).latent_dist` moments: image [B,3,H,W] in [-1,1] -> (mean, logvar) fp32 [B,4,H/8,W/8]."""
         image = image.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-        b, _, S, _ = image.shape
-        L = S // (2 ** (len(self.cfg.vae.block_out_channels) - 1))
-        mean = torch.empty(b, self.cfg.vae.latent_channels, L, L, device=image.device, dtype=torch.float32)
+        b, _, H, W = image.shape
+        f = 2 ** (len(self.cfg.vae.block_out_channels) - 1)
+        mean = torch.empty(b, self.cfg.vae.latent_channels, H // f, W // f, device=image.device, dtype=torch.float32)
         logvar = torch.empty_like(mean)
-        self._ck(self.lib.agd_vae_encode(self.ctx, _lib.ptr(image), b, S, _lib.ptr(mean), _lib.ptr(logvar), self._stream()), "agd_vae_encode")
+        if H == W:
+            self._ck(self.lib.agd_vae_encode(self.ctx, _lib.ptr(image), b, H, _lib.ptr(mean), _lib.ptr(logvar), self._stream()), "agd_vae_encode")
+        else:
+            self._ck(self.lib.agd_vae_encode_hw(self.ctx, _lib.ptr(image), b, H, W, _lib.ptr(mean), _lib.ptr(logvar), self._stream()),
+                     "agd_vae_encode_hw")
         return mean, logvar.clamp_(-30.0, 20.0)
 
     def set_option(self, name: str, value: int):
@@ -367,11 +429,18 @@ class Engine:
     def record_config(self, mode: int, is_train: bool = False, rec_tokens: int = 0):
         self._ck(self.lib.agd_record_config(self.ctx, mode, int(is_train), rec_tokens), "agd_record_config")
 
-    def record_reset(self, batch: int, L: int):
-        self._ck(self.lib.agd_record_reset(self.ctx, batch, L, self._stream()), "agd_record_reset")
+    def record_reset(self, batch: int, L):
+        """`L`: the latent side, or an (Lh, Lw) pair."""
+        Lh, Lw = _hw(L)
+        if Lh == Lw:
+            self._ck(self.lib.agd_record_reset(self.ctx, batch, Lh, self._stream()), "agd_record_reset")
+        else:
+            self._ck(self.lib.agd_record_reset_hw(self.ctx, batch, Lh, Lw, self._stream()), "agd_record_reset_hw")
 
-    def daam_global(self, img: int, rows: int, S: int) -> torch.Tensor:
-        out = torch.empty(rows, S, S, device=f"cuda:{self.device}", dtype=torch.float32)
+    def daam_global(self, img: int, rows: int, S) -> torch.Tensor:
+        """[rows, Lh, Lw] at the size the last record_reset stored; `S`: the latent side, or an (Lh, Lw) pair."""
+        Sh, Sw = _hw(S)
+        out = torch.empty(rows, Sh, Sw, device=f"cuda:{self.device}", dtype=torch.float32)
         rc = self.lib.agd_daam_global(self.ctx, img, rows, _lib.ptr(out), self._stream())
         if rc == -2:
             raise RuntimeError(self.lib.agd_last_error(self.ctx).decode())
@@ -882,9 +951,10 @@ class StableDiffusionPipeline:
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
-        if height != width or height % 64:
-            raise ValueError("height == width, multiple of 64 required")
-        L = height // self.vae_scale_factor
+        check_image_size(height, width)
+        Lh, Lw = height // self.vae_scale_factor, width // self.vae_scale_factor
+        self._refuse_rectangular_hook(Lh, Lw)
+        L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
         if prompt_embeds is None:
             prompts = [prompt] if isinstance(prompt, str) else list(prompt)
             prompts = [p for p in prompts for _ in range(num_images_per_prompt)]
@@ -895,16 +965,16 @@ class StableDiffusionPipeline:
             # data_generation.py:58 seeds `torch.Generator(device="cuda")`: accepted (torch's device Philox stream; whether it is
             # bit-identical to an NVIDIA run of the reference is not verifiable here).  CPU generators give host-reproducible latents.
             Cl = self.cfg.unet.out_channels
-            if isinstance(generator, (list, tuple)):           # diffusers randn_tensor: one (1, C, L, L) draw per generator
+            if isinstance(generator, (list, tuple)):           # diffusers randn_tensor: one (1, C, Lh, Lw) draw per generator
                 if len(generator) != B:
                     raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {B}.")
-                parts = [torch.randn(1, Cl, L, L, generator=g, device=g.device if g is not None else "cpu") for g in generator]
+                parts = [torch.randn(1, Cl, Lh, Lw, generator=g, device=g.device if g is not None else "cpu") for g in generator]
                 if len({p_.device for p_ in parts}) > 1:
                     parts = [p_.cpu() for p_ in parts]
                 latents = torch.cat(parts, 0)
-            else:                                              # ONE (B, C, L, L) draw, kept on the generator's device (no host round trip)
-                latents = torch.randn(B, Cl, L, L, generator=generator, device=generator.device if generator is not None else "cpu")
-        expect = (B, self.cfg.unet.out_channels, L, L)
+            else:                                              # ONE (B, C, Lh, Lw) draw, kept on the generator's device (no host round trip)
+                latents = torch.randn(B, Cl, Lh, Lw, generator=generator, device=generator.device if generator is not None else "cpu")
+        expect = (B, self.cfg.unet.out_channels, Lh, Lw)
         if tuple(latents.shape) != expect:                 # diffusers prepare_latents raises the same way
             raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
         lat = self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
@@ -920,6 +990,12 @@ class StableDiffusionPipeline:
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
         return self._finish(lat, B, output_type)
+
+    def _refuse_rectangular_hook(self, Lh: int, Lw: int):
+        """hook.py's `_unravel_attn` unravels every map as h = w = sqrt(N): a rectangular generate has no meaning there."""
+        if self._hooker is not None and Lh != Lw:
+            raise ValueError(f"UNetCrossAttentionHooker records square latents only (h = w = sqrt(N), as hook.py's _unravel_attn); "
+                             f"got a {Lh * self.vae_scale_factor} x {Lw * self.vae_scale_factor} generate")
 
     def _refuse_inpainting_unet(self):
         if self.cfg.unet.in_channels != self.cfg.unet.out_channels:
@@ -962,7 +1038,7 @@ class StableDiffusionPipeline:
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
                 cross_attention_kwargs: Optional[dict] = None):
-        """image: float [B,3,S,S] in [-1,1] (or uint8 [B,S,S,3]).  Noise draws come from a CPU generator (or are passed
+        """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
         # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
@@ -972,12 +1048,16 @@ class StableDiffusionPipeline:
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
             image = image.permute(0, 3, 1, 2).float() / 127.5 - 1.0
-        B, _, S, _ = image.shape
+        B, _, H, W = image.shape
+        if H != W:                                             # (square images keep the acceptance they always had)
+            check_image_size(H, W)
+        Lh, Lw = H // self.vae_scale_factor, W // self.vae_scale_factor
+        self._refuse_rectangular_hook(Lh, Lw)
+        L = Lh if Lh == Lw else (Lh, Lw)
         if prompt_embeds is None:
             prompts = [prompt] * B if isinstance(prompt, str) else list(prompt)
             prompt_embeds = self.encode_prompt(prompts)
-        L = S // self.vae_scale_factor
-        shape = (B, self.cfg.unet.out_channels, L, L)
+        shape = (B, self.cfg.unet.out_channels, Lh, Lw)
         if generator is not None and generator.device.type != "cpu":
             raise ValueError("use a CPU torch.Generator")
         noise_enc = noise_enc if noise_enc is not None else torch.randn(shape, generator=generator)

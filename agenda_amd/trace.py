@@ -1,7 +1,12 @@
 """`daam.trace` surface (reference data_generation/data_generation.py:57,64,74-77) over the fused
 HIP recorder.  Semantics restated from the public `daam` package [upstream-knowledge, SURVEY.md
 §8a rows D1-D4]: per-(layer, head) time-summed conditional-half maps, mid block excluded,
-bicubic -> clamp -> mean, rows truncated to len(tokenize(prompt)) + 2."""
+bicubic -> clamp -> mean, rows truncated to len(tokenize(prompt)) + 2.
+
+Rectangular generates (height != width) give maps of [rows, Lh, Lw].  daam itself is square-only (its `_unravel_attn` takes
+h = w = sqrt(N)); here a layer's maps are (Lh / f) x (Lw / f) with daam's own factor f = sqrt(Lh * Lw / N), resized by bicubic with
+separate y and x scales (torch `F.interpolate(size=(Lh, Lw), mode="bicubic", align_corners=False)`).  That is the direct
+generalisation of daam's formula, not a behaviour daam has: parity-unpinned.  Square generates are exactly daam's."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -56,7 +61,7 @@ class trace:
         # recording fewer rows than 77 is safe: daam only ever reads the first len(tokens)+2 rows
         self.rec_tokens = rec_tokens or pipe.cfg.max_tokens
         self.batch = 0
-        self.latent_side = 0
+        self.latent_side = 0                 # the latent side, or (Lh, Lw) after a rectangular generate
         self.last_prompt = None
         self._ran = False
 
@@ -72,10 +77,11 @@ class trace:
         self.pipe._apply_record_mode()
         return False
 
-    def _on_generate(self, batch: int, latent_side: int, prompt: Optional[str]):
+    def _on_generate(self, batch: int, latent_side, prompt: Optional[str]):
         self.batch, self.latent_side, self.last_prompt, self._ran = batch, latent_side, prompt, True
 
     def compute_global_heat_map(self, prompt: Optional[str] = None, image_index: int = 0, normalize: bool = False) -> GlobalHeatMap:
+        """Heat maps [rows, Lh, Lw] of image `image_index` (word maps from it are [Lh, Lw])."""
         if not self._ran:
             raise RuntimeError("No heat maps found. Did you forget to call `with trace(...)`?")
         prompt = prompt if prompt is not None else self.last_prompt

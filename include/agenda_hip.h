@@ -15,6 +15,8 @@
  * (NULL = default stream); calls are stream-ordered with no hidden syncs except where noted.
  * One ctx per GPU per process; calls on one ctx must be serialised by the caller.
  */
+/* Image sizes: every entry point that takes one latent side (or pixel side) has a `_hw` form taking (height, width); the one-side
+ * form is that call with h == w.  Rectangular latents must halve exactly at every UNet level (a multiple of 64 pixels per axis). */
 #ifndef AGENDA_HIP_H
 #define AGENDA_HIP_H
 #ifdef __cplusplus
@@ -86,6 +88,8 @@ int agd_safety_configure(agd_ctx* ctx, const agd_vision_config* vcfg);
  * cos_out fp32 [B, n_special + n_concepts] (device; special-care cosines first); pixels_out (may be NULL) fp32 [B,3,image_size,image_size]
  * = the processor's pixel_values.  Stream-ordered; leaves the recorder accumulators, the context and the scheduler state untouched. */
 int agd_safety_scores(agd_ctx* ctx, const unsigned char* images, int batch, int side, float* cos_out, float* pixels_out, void* stream);
+/* the same on [batch][h][w][3] images of any size: CLIPImageProcessor's shortest-edge resize to image_size, then the center crop */
+int agd_safety_scores_hw(agd_ctx* ctx, const unsigned char* images, int batch, int h, int w, float* cos_out, float* pixels_out, void* stream);
 
 /* ---- ControlNet (diffusers ControlNetModel, SD-1.x: the UNet's down blocks + mid block, a conditioning embedding and 1x1 zero convs).
  * Configured by agd_controlnet_configure BEFORE agd_finalize; weights through agd_load_tensor as "controlnet." + diffusers state-dict key.
@@ -102,6 +106,7 @@ int agd_controlnet_configure(agd_ctx* ctx, const agd_controlnet_config* cncfg);
 /* the conditioning image cond fp32 [batch,3,S,S] (device) in [0,1] -> the embedding, computed once and kept for batch * repeat UNet rows
  * (repeat 2: [cond; cond], the CFG doubling); S = latent side << (n_emb - 1). */
 int agd_controlnet_set_cond(agd_ctx* ctx, const float* cond, int batch, int side, int repeat, void* stream);
+int agd_controlnet_set_cond_hw(agd_ctx* ctx, const float* cond, int batch, int h, int w, int repeat, void* stream);   /* [batch][3][h][w] */
 /* per-model-evaluation conditioning scales (controlnet_conditioning_scale x the guidance window), host array of n floats, consumed by the
  * next agd_denoise / agd_denoise_plms / agd_denoise_dpm (n must equal its evaluation count) or agd_unet_forward (n = 1).  A scale of
  * exactly 0 skips the ControlNet for that evaluation.  n = 0 clears the schedule: the UNet runs alone. */
@@ -111,6 +116,8 @@ int agd_controlnet_set_schedule(agd_ctx* ctx, const float* scales, int n);
  * out = NULL: only the count.  The conditioning embedding must be set for batch2 rows. */
 int agd_controlnet_residuals(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float scale, int nhwc,
                              float* out, long long* n_out, void* stream);
+int agd_controlnet_residuals_hw(agd_ctx* ctx, const float* sample, int batch2, int latent_h, int latent_w, float timestep, float scale, int nhwc,
+                                float* out, long long* n_out, void* stream);
 
 /* ---- inpainting (diffusers StableDiffusionInpaintPipeline).  A 9-channel UNet (in_channels = latent + 1 + latent) reads
  * latents | mask | masked-image latents every evaluation; a UNet that takes the latent channels only is blended after every scheduler
@@ -121,12 +128,16 @@ int agd_controlnet_residuals(agd_ctx* ctx, const float* sample, int batch2, int 
  * [batch,1,L,L] with L = S / the VAE's downscale f and latent pixel (i, j) = mask pixel (f i, f j). */
 int agd_inpaint_prepare(agd_ctx* ctx, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int side,
                         float* image_out, float* masked_out, float* mask_lat_out, void* stream);
+int agd_inpaint_prepare_hw(agd_ctx* ctx, const void* image, int image_f32, const void* mask, int mask_f32, int batch, int h, int w,
+                           float* image_out, float* masked_out, float* mask_lat_out, void* stream);   /* mask_lat [batch][1][h/8][w/8] */
 /* the state, copied from device fp32 NCHW tensors of `batch` images (both CFG halves read them): mask [batch,mask_channels,L,L] and cond
  * [batch,cond_channels,L,L].  A 9-channel UNet: cond = the masked-image latents, latent + mask_channels + cond_channels must equal
  * in_channels, noise = NULL.  A UNet of latent input channels: cond = the image latents, mask_channels = 1, noise [batch,latent,L,L] (the
  * draw that started the loop), and a blend schedule must follow.  The next loop must run on `batch` images at latent side L. */
 int agd_inpaint_set(agd_ctx* ctx, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
                     int batch, int latent_side, void* stream);
+int agd_inpaint_set_hw(agd_ctx* ctx, const float* mask, int mask_channels, const float* cond, int cond_channels, const float* noise,
+                       int batch, int latent_h, int latent_w, void* stream);
 /* the blend's (sa, sb) per model evaluation, host array of 2 n floats; n must equal the next loop's evaluation count.  After the step of
  * evaluation i: x = (1 - m) (sa_i image_latents + sb_i noise) + m x. */
 int agd_inpaint_set_schedule(agd_ctx* ctx, const float* sa_sb, int n);
@@ -135,20 +146,27 @@ int agd_inpaint_clear(agd_ctx* ctx);
 /* ---- `unet(sample, t, encoder_hidden_states).sample`: sample/out fp32 NCHW [B2,4,L,L] */
 int agd_unet_forward(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float* out,
                      void* stream);
+int agd_unet_forward_hw(agd_ctx* ctx, const float* sample, int batch2, int latent_h, int latent_w, float timestep, float* out, void* stream);
 /* the same with one timestep PER IMAGE (host array of batch2 floats): the training call `unet(noisy_latents, timesteps, ehs)` of
  * finetune_sd_token.py:1027, where `timesteps` is a [bsz] tensor */
 int agd_unet_forward_ts(agd_ctx* ctx, const float* sample, int batch2, int latent_side, const float* timesteps, float* out, void* stream);
+int agd_unet_forward_ts_hw(agd_ctx* ctx, const float* sample, int batch2, int latent_h, int latent_w, const float* timesteps, float* out,
+                           void* stream);
 
 /* ---- CFG combine + DDIM (eta 0) step on fp32 NCHW latents [B,4,L,L] in place;
  * eps is [2B,4,L,L] NCHW.  (`scheduler.step` inside pipeline.__call__) */
 int agd_cfg_ddim_step(agd_ctx* ctx, const float* eps, float* latents, int batch, int latent_side, float guidance,
                       float alpha_t, float alpha_prev, void* stream);
+int agd_cfg_ddim_step_hw(agd_ctx* ctx, const float* eps, float* latents, int batch, int latent_h, int latent_w, float guidance,
+                         float alpha_t, float alpha_prev, void* stream);
 
 /* ---- the whole denoise loop of `pipeline(prompt, num_inference_steps=..)` on device:
  * latents [B,4,L,L] fp32 in/out; per-step timesteps and alpha_cumprod (t, prev) from the host
  * scheduler.  Heat-map recording follows agd_record_config. */
 int agd_denoise(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_steps, const float* timesteps,
                 const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
+int agd_denoise_hw(agd_ctx* ctx, float* latents, int batch, int latent_h, int latent_w, int n_steps, const float* timesteps,
+                   const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
 
 /* ---- the same loop under the scheduler the reference actually runs: data_generation.py:59 calls the pipeline with the
  * checkpoint's default PNDMScheduler (skip_prk_steps: PLMS) x 20.  n_evals = steps + 1 model evaluations; per evaluation the
@@ -156,6 +174,8 @@ int agd_denoise(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_
  * from the host scheduler (agenda_amd/scheduler.py PNDMScheduler); the multistep weights are applied on the device. */
 int agd_denoise_plms(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_evals, const float* timesteps,
                      const float* sample_coeff, const float* eps_coeff, float guidance, void* stream);
+int agd_denoise_plms_hw(agd_ctx* ctx, float* latents, int batch, int latent_h, int latent_w, int n_evals, const float* timesteps,
+                        const float* sample_coeff, const float* eps_coeff, float guidance, void* stream);
 
 /* ---- the same loop under DPM-Solver++ (2M) (agenda_amd/scheduler.py DPMSolverMultistepScheduler, epsilon or v-prediction, with
  * or without Karras sigmas): n_evals = steps model evaluations.  Per evaluation i the host passes the UNet timestep (fractional
@@ -163,15 +183,20 @@ int agd_denoise_plms(agd_ctx* ctx, float* latents, int batch, int latent_side, i
  * sample = a * sample + b0 * x0 + b1 * x0 of evaluation i - 1.  The previous x0 lives in a context-owned buffer. */
 int agd_denoise_dpm(agd_ctx* ctx, float* latents, int batch, int latent_side, int n_evals, const float* timesteps,
                     const float* coeffs, float guidance, void* stream);
+int agd_denoise_dpm_hw(agd_ctx* ctx, float* latents, int batch, int latent_h, int latent_w, int n_evals, const float* timesteps,
+                       const float* coeffs, float guidance, void* stream);
 
 /* ---- `vae.decode(latents / scaling_factor)` + image post-process.
  * out_u8: [B, 8L, 8L, 3] uint8 (may be NULL); out_f32: [B, 8L, 8L, 3] fp32 in [-1,1] (may be NULL) */
 int agd_vae_decode(agd_ctx* ctx, const float* latents, int batch, int latent_side, unsigned char* out_u8,
                    float* out_f32, void* stream);
+int agd_vae_decode_hw(agd_ctx* ctx, const float* latents, int batch, int latent_h, int latent_w, unsigned char* out_u8,
+                      float* out_f32, void* stream);   /* images [batch][8 latent_h][8 latent_w][3] */
 
 /* ---- `vae.encode(image).latent_dist` (img2img front end; anchors: finetune_sd.py:764-765):
  * image fp32 NCHW [B,3,S,S] in [-1,1] -> mean and logvar fp32 NCHW [B,4,S/8,S/8].  Syncs. */
 int agd_vae_encode(agd_ctx* ctx, const float* image, int batch, int side, float* mean_out, float* logvar_out, void* stream);
+int agd_vae_encode_hw(agd_ctx* ctx, const float* image, int batch, int h, int w, float* mean_out, float* logvar_out, void* stream);
 
 /* ---- per-ctx options (no environment variables steer the library).  "cfg_shared_prefix" (default 1): agd_denoise runs the
  * layers ahead of the first cross-attention once for the identical unconditional / conditional halves (bit-identical to 0).
@@ -224,6 +249,9 @@ int agd_set_option(agd_ctx* ctx, const char* name, int value);
  * next agd_record_reset, which (re)sizes the accumulators for it. */
 int agd_record_config(agd_ctx* ctx, int mode, int is_train, int rec_tokens);
 int agd_record_reset(agd_ctx* ctx, int batch, int latent_side, void* stream);   /* hooker.clear() / new trace */
+/* DAAM: layer accumulators of (latent_h / f) x (latent_w / f), f = 2^level; agd_daam_global then writes [rows][latent_h][latent_w].
+ * The hook.py recorder (mode 2) takes square latents only. */
+int agd_record_reset_hw(agd_ctx* ctx, int batch, int latent_h, int latent_w, void* stream);
 /* daam `compute_global_heat_map()` for image `img`: out [rows, S, S] fp32 (rows <= rec_tokens). Stream-ordered. */
 int agd_daam_global(agd_ctx* ctx, int img, int rows, float* out, void* stream);
 /* hook.py `compute_global_heat_map()`: out [B', T, S, S]; returns -2 if nothing was recorded. Stream-ordered. */
