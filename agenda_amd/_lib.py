@@ -60,6 +60,14 @@ class AgdControlNetConfig(C.Structure):
     ]
 
 
+class AgdGligenConfig(C.Structure):
+    """`agd_gligen_config`: the PositionNet of a GLIGEN UNet (agd_gligen_configure)."""
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("max_objs", C.c_int), ("positive_len", C.c_int), ("fourier_freqs", C.c_int),
+    ]
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -84,6 +92,12 @@ _SIGS = {
     "agd_inpaint_set": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "agd_inpaint_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "agd_inpaint_clear": (C.c_int, [_P]),
+    "agd_gligen_configure": (C.c_int, [_P, C.POINTER(AgdGligenConfig)]),
+    "agd_gligen_set": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "agd_gligen_set_schedule": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),
+    "agd_gligen_clear": (C.c_int, [_P]),
+    "agd_gligen_objs": (C.c_int, [_P, _P]),
+    "agd_gligen_fuser": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "agd_lora_add": (C.c_int, [_P, C.c_char_p, _P, _P, C.c_int, C.c_float]),
     "agd_lora_set_scale": (C.c_int, [_P, C.c_float, _P]),
     "agd_lora_clear": (C.c_int, [_P]),

@@ -47,7 +47,10 @@ template <int D> struct AttnCfg {
 // head (hook.py mode); 2 = single key tile, the block walks ALL heads of its (batch row, query tile) and adds the head SUM of the
 // probabilities into per-image rows once -- the DAAM layers at latent resolution, where the aggregation is linear in the heads
 // (bicubic to the same size is the identity and clamp(min=0) cannot fire), so 1/8 of the accumulator traffic.
-template <int D, int KB, int QB, int RECORD, int AMASK = 0>
+// EXTRA (RECORD = AMASK = 0 only): after the Nk keys of k / v, the Nk2 <= KEYS keys of the second source k2 / v2 (GLIGEN's grounding
+// tokens, per batch row) run as one more key tile through the same online softmax, keys >= Nk2 masked -- the visual rows and the
+// grounding rows are never concatenated in memory.  The production instantiations (EXTRA = 0) compile to what they were.
+template <int D, int KB, int QB, int RECORD, int AMASK = 0, int EXTRA = 0>
 #if defined(AGD_EXPERIMENTS) && defined(EXP_ATTN_LB)      // tools/: occupancy experiments on the plain flash kernels
 #define ATTN_LB(def) ((!RECORD && !AMASK) ? EXP_ATTN_LB : (def))
 #else
@@ -179,6 +182,21 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
       vreg[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrh, vvoff[it], 0, 0));
     }
   };
+  // EXTRA: the second source's single tile (its own pitches; rows >= Nk2 fall outside num_records and read as zeros)
+  auto gload_extra = [&]() {
+    const unsigned k2b = (unsigned)(((long long)(p.Nk2 - 1) * p.ldk2 + D) * 2), v2b = (unsigned)(((long long)(p.Nk2 - 1) * p.ldv2 + D) * 2);
+    const auto kr2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.k2 + b * p.sk2 + head * D), 0, k2b, 0x00020000);
+    const auto vr2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.v2 + b * p.sv2 + head * D), 0, v2b, 0x00020000);
+#pragma unroll
+    for (int it = 0; it < LD_IT; ++it) {
+      const int idx = tid + it * 256;
+      const int r = idx / CH, cc = idx - r * CH;
+      const unsigned ko = (idx < NCHUNK) ? (unsigned)((r * p.ldk2 + cc * 8) * 2) : 0x80000000u;
+      const unsigned vo = (idx < NCHUNK) ? (unsigned)((r * p.ldv2 + cc * 8) * 2) : 0x80000000u;
+      kreg[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(kr2, ko, 0, 0));
+      vreg[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vr2, vo, 0, 0));
+    }
+  };
   auto lstore = [&](int stage) {
     char* sK = smem + stage * STAGE;
     char* sV = sK + KEYS * KPITCH;
@@ -222,7 +240,8 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
       for (int j = 0; j < 16; ++j) pacc[kb][j] = 0.f;
   }
 
-  const int ntiles = RECORD ? 1 : (p.Nk + KEYS - 1) / KEYS;   // RECORD: host guarantees Nk <= KEYS
+  const int ntiles_main = RECORD ? 1 : (p.Nk + KEYS - 1) / KEYS;   // RECORD: host guarantees Nk <= KEYS
+  const int ntiles = ntiles_main + (EXTRA ? 1 : 0);                 // EXTRA: tile ntiles_main is the second source's
   const bool ragged = (p.Nk % KEYS) != 0 || p.causal || AMASK;   // causal / additive mask: every tile takes the masked path
   gload(0);
   lstore(0);
@@ -239,6 +258,7 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
     const char* sK = smem + cur * STAGE;
     const char* sV = sK + KEYS * KPITCH;
     if constexpr (RECORD == 2) { if (t + 1 < hend) { gload_head(t + 1); prefetch_q(t + 1); } }
+    else if constexpr (EXTRA) { if (t + 1 < ntiles_main) gload(t + 1); else if (t + 1 == ntiles_main) gload_extra(); }
     else if (t + 1 < ntiles) gload(t + 1);
     // ---- S^T = K . Q^T ----
     f32x16 sacc[QB][KB];
@@ -263,8 +283,8 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const int key = (RECORD ? 0 : t * KEYS) + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            if (key >= p.Nk || (p.causal && key > q0 + qb * 32 + c)) sacc[qb][kb][i] = -INFINITY;
+            const int key = (RECORD || (EXTRA && t == ntiles_main) ? 0 : t * KEYS) + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            if (key >= ((EXTRA && t == ntiles_main) ? p.Nk2 : p.Nk) || (p.causal && key > q0 + qb * 32 + c)) sacc[qb][kb][i] = -INFINITY;
             else if constexpr (AMASK) {
               // RECORD keeps raw logits (scaled below): pre-divide so that (s + a/scale)*scale = s*scale + a
               const float a = p.mask[(long long)b * p.Nk + key];
@@ -483,6 +503,10 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
       return;
     } else if constexpr (RECORD) {
       tile_body(0, T_{});                              // single (always key-masked) tile
+    } else if constexpr (EXTRA) {
+      for (int t = 0; t < ntiles_main - 1; ++t) tile_body(t, F_{});
+      if (ragged) tile_body(ntiles_main - 1, T_{}); else tile_body(ntiles_main - 1, F_{});
+      tile_body(ntiles_main, T_{});                  // the second source's tile (always key-masked)
     } else {
       if (p.causal || AMASK) { for (int t = 0; t < ntiles - 1; ++t) tile_body(t, T_{}); }
       else { for (int t = 0; t < ntiles - 1; ++t) tile_body(t, F_{}); }
@@ -493,7 +517,7 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
 }
 
 
-template <int D, int KB, int QB, int RECORD, int AMASK = 0>
+template <int D, int KB, int QB, int RECORD, int AMASK = 0, int EXTRA = 0>
 static int launch_attn_t(const AttnP& p, hipStream_t st) {
   using C = AttnCfg<D>;
   constexpr int lds = (RECORD == 1 ? 1 : 2) * KB * 32 * (C::KPITCH + C::VPITCH);
@@ -501,7 +525,7 @@ static int launch_attn_t(const AttnP& p, hipStream_t st) {
   pp.nqt = (p.Nq + 128 * QB - 1) / (128 * QB);
   const int per = (p.B * (RECORD == 2 ? p.H / p.rec_hpb : p.H) + 7) / 8;
   dim3 grid(8 * per * pp.nqt);
-  auto kfn = attn_kernel<D, KB, QB, RECORD, AMASK>;
+  auto kfn = attn_kernel<D, KB, QB, RECORD, AMASK, EXTRA>;
   if (lds > 65536) {                                   // per (instantiation, device) latch
     static std::atomic<bool> attr[AGD_MAX_DEVICES] = {};
     int dev = 0; HIP_CHECK_RET(hipGetDevice(&dev));
@@ -515,6 +539,11 @@ static int launch_attn_t(const AttnP& p, hipStream_t st) {
 
 template <int D>
 static int launch_attn_d(const AttnP& p, hipStream_t st) {
+  if (p.k2) {                                    // GLIGEN's gated self-attention: the visual keys + one tile of grounding keys
+    if (p.record_mode != 0 || p.mask || p.causal) { agd_set_error("attention: a second K/V source takes no recording, mask or causal order"); return -1; }
+    if (!p.v2 || p.Nk2 < 1 || p.Nk2 > 64 || ((p.ldk2 | p.ldv2) & 7)) { agd_set_error("attention: second K/V source of %d keys (1 .. 64, pitches multiples of 8)", p.Nk2); return -1; }
+    return launch_attn_t<D, 2, 1, 0, 0, 1>(p, st);
+  }
   if (p.record_mode != 0) {
     if (p.Nk > 96) { agd_set_error("attention: recording needs Nk <= 96 (got %d)", p.Nk); return -1; }
     if (p.record_mode == 3) {                    // head-summed rows: the block walks the heads

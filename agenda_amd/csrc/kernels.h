@@ -88,6 +88,9 @@ struct AttnP {
   int nqt;                          // set by the launcher: query tiles per (batch, head)
   int causal;                       // 1: key j attends only to queries i >= j (CLIP text encoder)
   const float* mask;                // additive fp32 [B][Nk] (broadcast over heads and queries) or NULL
+  // a second K/V source (GLIGEN's gated self-attention: the grounding tokens of each image) or NULL: Nk2 <= 64 trailing keys per batch row,
+  // attended after the Nk keys of k / v as one extra masked key tile (a separate instantiation; no recording, mask or causal)
+  const bf16_t* k2; const bf16_t* v2; int ldk2, ldv2; long long sk2, sv2; int Nk2;
 };
 int launch_attention(const AttnP& p, hipStream_t st);
 
@@ -230,6 +233,9 @@ int launch_scale(float* x, long long n, float s, hipStream_t st);
 // ControlNet (controlnet.hip): fp32 NCHW [B][3][HW] -> bf16 NHWC [B][HW][Cpad] (optionally BGR-flipped); out = s * in over n floats
 int launch_controlnet_cond_prep(const float* cond, bf16_t* out, int B, int HW, int Cpad, int bgr, hipStream_t st);
 int launch_controlnet_scale_bias(const float* in, float* out, int n, float s, hipStream_t st);
+// GLIGEN (gligen.hip): the PositionNet's input rows [rows][ld] bf16 = [m pos + (1 - m) null_pos | m fourier(box) + (1 - m) null_xyxy | 0 pad]
+int launch_gligen_posnet_input(const float* boxes, const float* pos, const float* masks, const float* null_pos, const float* null_xyxy,
+                               bf16_t* out, int rows, int P, int F, int ld, hipStream_t st);
 // Inpainting (inpaint.hip): the mask front end (image [-1,1], masked image, latent-resolution binary mask), the 9-channel UNet input
 // (latents | mask | masked-image latents | zero pad, bf16 NHWC), the 4-channel blend x = (1 - m)(sa x0img + sb n) + m x
 int launch_inpaint_front(const void* image, int image_f32, const void* mask, int mask_f32, int B, int H, int W, int f, float* image_out,

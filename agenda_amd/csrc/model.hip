@@ -82,6 +82,14 @@ struct XLayer {
   DBuf pm_kppb, pm_vppb, pm_csb; bf16_t* pm_kpp = nullptr; bf16_t* pm_vpp = nullptr; float* pm_kcs = nullptr; float* pm_kbs = nullptr;
 };
 
+// one GLIGEN GatedSelfAttentionDense ("<pre>transformer_blocks.0.fuser."): fused q/k/v and k/v, the tanh gates, the to_out / ff.net.2 biases
+// pre-scaled by them (agd_finalize), and the per-call grounding K/V [B2][max_objs][2C] bf16 (agd_gligen_set)
+struct Fuser {
+  std::string pre; int C = 0, heads = 0;
+  WMat wqkv, wkv; float ta = 0.f, td = 0.f; float* bo_s = nullptr; float* b2_s = nullptr;
+  DBuf gkvb;
+};
+
 struct ProfEv { int cls; double flops, bytes; hipEvent_t a, b; };   // algorithmic flop / HBM bytes of the launch
 
 struct agd_ctx {
@@ -161,6 +169,11 @@ struct agd_ctx {
   DBuf lora_descb; bf16_t* lora_scratch = nullptr; size_t lora_scratch_n = 0;
   float lora_scale = 0.f; bool lora_dirty = false;
   bool ctx_stale = false;                             // the raw matrices changed after agd_set_context: the projected context must be rebuilt
+  // GLIGEN (agd_gligen_configure): one Fuser per UNet transformer block (gl_idx: block prefix -> index), the PositionNet output of the call
+  // (gl_objb [gl_B2][max_objs][cross_attention_dim] bf16), one flag per model evaluation; gl_active: the forward being walked runs the fusers
+  agd_gligen_config glc{}; bool gl_on = false;
+  std::vector<Fuser> gl_f; std::unordered_map<std::string, int> gl_idx;
+  DBuf gl_objb; int gl_B2 = 0; std::vector<int> gl_sched; bool gl_active = false;
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
@@ -511,6 +524,35 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   return 0;
 }
 
+// GLIGEN's GatedSelfAttentionDense on the B x HW rows of h, in place:  h += tanh(alpha_attn) to_out(attn(norm1(h) | grounding K/V));
+// h += tanh(alpha_dense) ff.net.2(GEGLU(norm2(h))).  The attention is attention.hip's second-K/V-source form: the HW visual keys of the image,
+// then its max_objs grounding keys (norm1 and K/V of the objects were computed once per call) as one extra masked tile.  Both gates go on
+// the GEMM accumulators (alpha) with the biases pre-scaled, the residual operand = h.  qkv [B HW][3C] and att [B HW][C] are the caller's
+// scratch; last(A, K, w, o) runs the gated ff.net.2 launch (transformer(): the GEMM that also leaves norm2's row statistics).
+static int fuser_rows(agd_ctx* c, hipStream_t st, const Fuser& f, bf16_t* h, int B, int HW, bf16_t* qkv, bf16_t* att,
+                      const std::function<int(const bf16_t*, int, const WMat&, const GemmOpt&)>& last) {
+  const int C = f.C, D = C / f.heads, M = B * HW, NO = c->glc.max_objs;
+  if (B != c->gl_B2) FAIL("gligen: the grounding objects are set for %d rows, this forward has %d (agd_gligen_set)", c->gl_B2, B);
+  const std::string t = f.pre + "transformer_blocks.0.fuser.";
+  bf16_t* n = (bf16_t*)c->arena.alloc((size_t)M * C * 2); bf16_t* ff = (bf16_t*)c->arena.alloc((size_t)M * 4 * C * 2);
+  if (!n || !ff) return -1;
+  GETV(g1, t + "norm1.weight"); GETV(b1, t + "norm1.bias"); GETV(g2, t + "norm2.weight"); GETV(b2, t + "norm2.bias");
+  GETW(wo, t + "attn.to_out.0.weight"); GETW(w1, t + "ff.net.0.proj.weight"); GETV(bb1, t + "ff.net.0.proj.bias"); GETW(w2, t + "ff.net.2.weight");
+  { ProfScope ps(c, st, PC_LN, 0, 4.0 * M * (double)C); CK(launch_layernorm(h, n, g1, b1, M, C, 1e-5f, st)); }
+  { GemmOpt o; CK(run_conv(c, st, n, C, nullptr, 0, 1, 1, M, f.wqkv, 1, qkv, o, c->zero_page)); }
+  AttnP a{}; a.q = qkv; a.k = qkv + C; a.v = qkv + 2 * C; a.o = att;
+  a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.sq = a.sk = a.sv = (long long)HW * 3 * C; a.so = (long long)HW * C;
+  a.B = B; a.H = f.heads; a.D = D; a.Nq = HW; a.Nk = HW; a.scale = 1.0f / sqrtf((float)D);
+  a.k2 = f.gkvb.as<bf16_t>(); a.v2 = a.k2 + C; a.ldk2 = a.ldv2 = 2 * C; a.sk2 = a.sv2 = (long long)NO * 2 * C; a.Nk2 = NO;
+  { const double fl = 4.0 * B * f.heads * (double)HW * (HW + NO) * D, by = 2.0 * B * (double)C * (4.0 * HW + 2.0 * NO);
+    ProfScope ps(c, st, PC_ATTN_SELF, fl, by); CK(launch_attention(a, st)); }
+  { GemmOpt o; o.bias = f.bo_s; o.alpha = f.ta; o.residual = h; CK(run_conv(c, st, att, C, nullptr, 0, 1, 1, M, *wo, 1, h, o, c->zero_page)); }
+  { ProfScope ps(c, st, PC_LN, 0, 4.0 * M * (double)C); CK(launch_layernorm(h, n, g2, b2, M, C, 1e-5f, st)); }
+  { GemmOpt o; o.bias = bb1; o.geglu = 1; CK(run_conv(c, st, n, C, nullptr, 0, 1, 1, M, *w1, 1, ff, o, c->zero_page)); }
+  GemmOpt o; o.bias = f.b2_s; o.alpha = f.td; o.residual = h;
+  return last(ff, 4 * C, *w2, o);
+}
+
 // Transformer2DModel with one BasicTransformerBlock
 // the second half of a [2B'] activation := its first half (CFG: both halves saw identical inputs so far)
 static int dup_half(agd_ctx* c, hipStream_t st, bf16_t* p, long long half_elems) {
@@ -524,6 +566,11 @@ static int dup_half(agd_ctx* c, hipStream_t st, bf16_t* p, long long half_elems)
 // proj_in, norm1 and the self-attention run once on B' rows; the result is duplicated right before the first
 // cross-attention and the block returns 2B' rows.  Bit-identical to running both halves (every op here is
 // row- or image-local), at half the cost for the most expensive attention call of the forward.
+// GLIGEN (c->gl_active, a UNet block with a fuser): the fuser runs between attn1's residual add and attn2.  The CFG halves diverge there
+// (the unconditional half sees null objects only), so the shared prefix is duplicated BEFORE the fuser (the copy path: no lazy_dup) and
+// attn1.to_out stays a GEMM of its own (no chain_pre).  norm2's statistics for whatever attn2 path follows come from the fuser's last GEMM
+// (the gated ff.net.2 is a produce() launch: with the LayerNorm fold it emits the row statistics; the chain kernel takes its own).
+// Evaluations without the flag walk exactly the code above and below.
 static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const Act& x, int heads, int groups, Act& out, int dup = 0) {
   const int Bs = x.B;                                  // batch of the shared part
   int B = dup ? 2 * x.B : x.B;
@@ -656,8 +703,10 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
                           c->rec_mode != 2 && c->W.count(t + "attn2.to_q.frag") && !xpre_ready;
   // CFG-shared prefix with the fused kernels behind it: the duplication of the B' rows happens INSIDE them (the chain reads input row m % M', the feed-forward's
   // proj_out stage adds block-input row m % M'): no copy launches, and attn1.to_out joins the chain here too
-  const bool lazy_dup = dup && (c->opt_tb_fuse & 64) && chain_fuse && C == 320 && ff_fused && (c->opt_tb_fuse & 8) && c->W.count(pre + "proj_out.frag");
-  const bool chain_pre = chain_fuse && (c->opt_tb_fuse & 4) && (!dup || lazy_dup) && c->W.count(t + "attn1.to_out.frag");     // attn1.to_out + residual inside the chain launch
+  const Fuser* fu = nullptr;                             // GLIGEN: this evaluation runs the block's fuser
+  if (c->gl_active) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) fu = &c->gl_f[itf->second]; }
+  const bool lazy_dup = dup && (c->opt_tb_fuse & 64) && chain_fuse && C == 320 && ff_fused && (c->opt_tb_fuse & 8) && c->W.count(pre + "proj_out.frag") && !fu;
+  const bool chain_pre = chain_fuse && (c->opt_tb_fuse & 4) && (!dup || lazy_dup) && c->W.count(t + "attn1.to_out.frag") && !fu;     // attn1.to_out + residual inside the chain launch
   // --- self attention ---
   { if (!qkv_done) CK(consume(t + "norm1", t + "attn1.qkv", nullptr, 0, qkv));
     AttnP a{}; a.q = qkv; a.k = qkv + C; a.v = qkv + 2 * C; a.o = att;
@@ -681,6 +730,7 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
     xres = x2.p;
     M = B * HW;
   }
+  if (fu) CK(fuser_rows(c, st, *fu, h.p, B, HW, qkv, att, [&](const bf16_t* A, int K, const WMat& w, const GemmOpt& o) { return produce(A, K, w, o, h.p, false, !chain_fuse); }));
   // --- cross attention (the processor seam) ---
   bool chain_done = false;
   { auto it = c->xl_idx.find(t + "attn2");
@@ -947,9 +997,11 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
 // cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
 // tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
 // cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
+// grounded: the GLIGEN fusers run in the UNet's transformer blocks (agd_gligen_set_schedule)
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
-                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f) {
+                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f, bool grounded = false) {
   const agd_config& g = c->cfg;
+  c->gl_active = grounded;
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   const int nl = g.n_levels, G = g.norm_num_groups;
   const std::string u = "unet.";
@@ -1169,6 +1221,8 @@ AGD_API void agd_destroy(agd_ctx* c) {
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
   c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
+  for (auto& f : c->gl_f) f.gkvb.release();
+  c->gl_objb.release();
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1194,10 +1248,12 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
   if (hipMemcpy(c->stage, ptr, bytes, hipMemcpyDefault) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
   const std::string k(name);
   if (k.compare(0, 11, "controlnet.") == 0 && !c->cn_on) { agd_set_error("'%s': call agd_controlnet_configure before loading ControlNet weights", name); return fail_ctx(c); }
+  if ((k.compare(0, 18, "unet.position_net.") == 0 || k.find(".fuser.") != std::string::npos) && !c->gl_on) {
+    agd_set_error("'%s': call agd_gligen_configure before loading GLIGEN weights", name); return fail_ctx(c); }
   // the safety checker keeps everything but its encoder-layer matrices in fp32 as loaded (embeddings, the 14 x 14 patch conv, the
   // projection, the concept rows); agd_finalize checks their sizes and builds the padded patch matrix
   const bool vis_f32 = k.compare(0, 7, "safety.") == 0 && !(ndim == 2 && k.find(".encoder.layers.") != std::string::npos);
-  if (ndim == 1 || vis_f32) {
+  if (ndim == 1 || vis_f32 || (ndim == 0 && c->gl_on)) {            // (0-d: GLIGEN's alpha_attn / alpha_dense)
     float* d = dmalloc<float>(c, (size_t)n); if (!d) return fail_ctx(c);
     hipMemcpy(d, c->stage, bytes, hipMemcpyDeviceToDevice);
     c->V[k] = d; c->Vn[k] = (int)n;
@@ -1554,6 +1610,59 @@ static int derive_tblock(agd_ctx* c, const std::string& pre, int level, bool all
   return 0;
 }
 
+// GLIGEN: PositionNet linears.{0,2,4} = [512][positive_len + 8 F], [512][512], [cross_attention_dim][512] and the two null features; in every
+// UNet transformer block a fuser whose linear maps cross_attention_dim -> C, with q / k / v / to_out [C][C], GEGLU [8C][C], ff.net.2 [C][4C]
+static int finalize_gligen(agd_ctx* c) {
+  const agd_gligen_config& e = c->glc;
+  const int Dc = c->cfg.cross_attention_dim, Pin = e.positive_len + 8 * e.fourier_freqs;
+  auto want = [&](const std::string& k, int n, int cin) -> int {
+    const WMat* w = getW(c, k + ".weight"); if (!w) return -1;
+    if (w->N != n || w->Cin != cin || w->taps != 1) FAIL("'%s.weight' is [%d, %d], GLIGEN needs [%d, %d]", k.c_str(), w->N, w->Cin, n, cin);
+    return 0;
+  };
+  auto wantv = [&](const std::string& k, int n) -> int {
+    auto it = c->Vn.find(k); if (it == c->Vn.end() || it->second != n) FAIL("'%s' missing or not %d long", k.c_str(), n);
+    return 0;
+  };
+  const std::string P = "unet.position_net.";
+  CK(want(P + "linears.0", 512, Pin)); CK(wantv(P + "linears.0.bias", 512));
+  CK(want(P + "linears.2", 512, 512)); CK(wantv(P + "linears.2.bias", 512));
+  CK(want(P + "linears.4", Dc, 512)); CK(wantv(P + "linears.4.bias", Dc));
+  CK(wantv(P + "null_positive_feature", e.positive_len)); CK(wantv(P + "null_position_feature", 8 * e.fourier_freqs));
+  if (getW(c, P + "linears.0.weight")->Cpad != Pin) FAIL("gligen: positive_len + %d = %d is not a multiple of 64", 8 * e.fourier_freqs, Pin);
+  c->gl_f.clear(); c->gl_idx.clear();
+  for (auto& pr : transformer_prefixes(c)) {
+    if (pr.first.compare(0, 5, "unet.") != 0) continue;
+    const std::string t = pr.first + "transformer_blocks.0.fuser.";
+    const WMat* q = getW(c, t + "attn.to_q.weight"); if (!q) return -1;
+    Fuser f; f.pre = pr.first; f.C = q->N; f.heads = c->cfg.num_heads[pr.second];
+    const int C = f.C;
+    if (C % f.heads) FAIL("gligen: %s C %d not divisible by %d heads", t.c_str(), C, f.heads);
+    CK(want(t + "linear", C, Dc)); CK(wantv(t + "linear.bias", C));
+    CK(want(t + "attn.to_q", C, C)); CK(want(t + "attn.to_k", C, C)); CK(want(t + "attn.to_v", C, C));
+    CK(want(t + "attn.to_out.0", C, C)); CK(wantv(t + "attn.to_out.0.bias", C));
+    CK(want(t + "ff.net.0.proj", 8 * C, C)); CK(wantv(t + "ff.net.0.proj.bias", 8 * C));
+    CK(want(t + "ff.net.2", C, 4 * C)); CK(wantv(t + "ff.net.2.bias", C));
+    for (const char* n : {"norm1", "norm2"}) { CK(wantv(t + n + ".weight", C)); CK(wantv(t + n + ".bias", C)); }
+    CK(wantv(t + "alpha_attn", 1)); CK(wantv(t + "alpha_dense", 1));
+    CK(concat_rows(c, {q, getW(c, t + "attn.to_k.weight"), getW(c, t + "attn.to_v.weight")}, f.wqkv));
+    CK(concat_rows(c, {getW(c, t + "attn.to_k.weight"), getW(c, t + "attn.to_v.weight")}, f.wkv));
+    float al[2];
+    if (hipMemcpy(&al[0], c->V[t + "alpha_attn"], 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&al[1], c->V[t + "alpha_dense"], 4, hipMemcpyDeviceToHost) != hipSuccess) FAIL("gligen: gate read failed");
+    f.ta = tanhf(al[0]); f.td = tanhf(al[1]);
+    std::vector<float> bo(C), b2(C);
+    if (hipMemcpy(bo.data(), c->V[t + "attn.to_out.0.bias"], (size_t)C * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(b2.data(), c->V[t + "ff.net.2.bias"], (size_t)C * 4, hipMemcpyDeviceToHost) != hipSuccess) FAIL("gligen: bias read failed");
+    for (int i = 0; i < C; ++i) { bo[i] *= f.ta; b2[i] *= f.td; }
+    f.bo_s = dmalloc<float>(c, C); f.b2_s = dmalloc<float>(c, C); if (!f.bo_s || !f.b2_s) return -1;
+    if (hipMemcpy(f.bo_s, bo.data(), (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f.b2_s, b2.data(), (size_t)C * 4, hipMemcpyHostToDevice) != hipSuccess) FAIL("gligen: bias write failed");
+    c->gl_idx[f.pre] = (int)c->gl_f.size(); c->gl_f.push_back(f);
+  }
+  return 0;
+}
+
 AGD_API int agd_finalize(agd_ctx* c) {
   if (!c) return -1;
   hipSetDevice(c->device);
@@ -1625,6 +1734,8 @@ AGD_API int agd_finalize(agd_ctx* c) {
   if (c->vis_on) API_CK(c, finalize_safety(c));
   // ---- ControlNet: the conditioning embedding's shapes, the zero convs' biases back to back
   if (c->cn_on) API_CK(c, finalize_controlnet(c));
+  // ---- GLIGEN: the PositionNet's shapes, every fuser's fused projections, gates and pre-scaled biases
+  if (c->gl_on) API_CK(c, finalize_gligen(c));
   hipDeviceSynchronize();
   c->finalized = true;
   return 0;
@@ -1690,6 +1801,17 @@ static int cn_schedule_for(agd_ctx* c, int n, int B2, int Lh, int Lw, const floa
   *out = c->cn_sched.data();
   return 0;
 }
+// the GLIGEN schedule of a call of n model evaluations on B2 rows: nullptr = none set (no fuser runs); else its length must be n, and the
+// grounding objects must be set for exactly these rows when any flag is on (checked before anything runs)
+static int gl_schedule_for(agd_ctx* c, int n, int B2, const int** out) {
+  *out = nullptr;
+  if (c->gl_sched.empty()) return 0;
+  if ((int)c->gl_sched.size() != n) FAIL("gligen: the schedule has %zu flags, this call runs %d model evaluations (agd_gligen_set_schedule)", c->gl_sched.size(), n);
+  bool any = false; for (int v : c->gl_sched) any = any || v != 0;
+  if (any && c->gl_B2 != B2) FAIL("gligen: the grounding objects are set for %d rows, this call runs %d (agd_gligen_set)", c->gl_B2, B2);
+  *out = c->gl_sched.data();
+  return 0;
+}
 // the inpaint state of a fused loop of n model evaluations on `batch` images at latent size Lh x Lw: *blend = the (sa, sb) schedule of the
 // 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
 static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float** blend) {
@@ -1737,8 +1859,10 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   const int Cl = c->cfg.in_channels;
   const float* cs = nullptr;
   API_CK(c, cn_schedule_for(c, 1, batch2, Lh, Lw, &cs));                     // a one-element ControlNet schedule: one injected forward
+  const int* gs = nullptr;
+  API_CK(c, gl_schedule_for(c, 1, batch2, &gs));                             // a one-element GLIGEN schedule: one grounded forward
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f));
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0]));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
 }
@@ -1753,6 +1877,7 @@ AGD_API int agd_unet_forward_ts_hw(agd_ctx* c, const float* sample, int batch2, 
   API_CK(c, check_latent_hw(c, "unet_forward_ts", Lh, Lw));
   if (!timesteps || batch2 < 1) { agd_set_error("unet_forward_ts: bad arguments"); return fail_ctx(c); }
   if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
+  if (!c->gl_sched.empty()) { agd_set_error("unet_forward_ts: a GLIGEN schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
@@ -1821,13 +1946,15 @@ AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw
   if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
   const float* cs = nullptr;                                       // the ControlNet's per-step scales (none: the UNet alone)
   API_CK(c, cn_schedule_for(c, n_steps, B2, Lh, Lw, &cs));
+  const int* gs = nullptr;                                         // the GLIGEN per-step flags (none: no fuser runs)
+  API_CK(c, gl_schedule_for(c, n_steps, B2, &gs));
   const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per step (none: no blend)
   API_CK(c, inpaint_for(c, n_steps, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
   for (int s = 0; s < n_steps; ++s) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f, gs && gs[s]));
     { ProfScope ps(c, st, PC_ELEM, 0);
       API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
     if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * s));
@@ -1863,6 +1990,8 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
   float* kept = c->plmsb.as<float>() + n1 * 4;
   const float* cs = nullptr;
   API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
+  const int* gs = nullptr;
+  API_CK(c, gl_schedule_for(c, n_evals, B2, &gs));
   const float* ib = nullptr;                                       // the blend rewrites `latents` only: the kept sample stays unblended
   API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;
@@ -1870,7 +1999,7 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
   for (int i = 0; i < n_evals; ++i) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
     const float* src = latents; float* store = nullptr;
@@ -1917,13 +2046,15 @@ AGD_API int agd_denoise_dpm_hw(agd_ctx* c, float* latents, int batch, int Lh, in
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
   const float* cs = nullptr;
   API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
+  const int* gs = nullptr;
+  API_CK(c, gl_schedule_for(c, n_evals, B2, &gs));
   const float* ib = nullptr;
   API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
   const float* tp_all = nullptr;
   API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
   for (int i = 0; i < n_evals; ++i) {
     API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     { ProfScope ps(c, st, PC_ELEM, 0);
@@ -3384,3 +3515,113 @@ AGD_API int agd_lora_clear(agd_ctx* c) {
 
 AGD_API int agd_lora_count(agd_ctx* c) { return c ? (int)c->lora_d.size() : 0; }
 AGD_API float agd_lora_scale(agd_ctx* c) { return c ? c->lora_scale : 0.f; }
+
+// ---------------------------------------------------------------------------------------
+// GLIGEN (diffusers PositionNet + GatedSelfAttentionDense + StableDiffusionGLIGENPipeline): the fusers run inside transformer()
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_gligen_configure(agd_ctx* c, const agd_gligen_config* e) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (!e || e->struct_size != (int)sizeof(agd_gligen_config)) {
+    agd_set_error("agd_gligen_configure: bad config (struct_size %d != %zu)", e ? e->struct_size : -1, sizeof(agd_gligen_config)); return fail_ctx(c); }
+  if (c->finalized) { agd_set_error("agd_gligen_configure: call it before agd_finalize"); return fail_ctx(c); }
+  if (e->max_objs < 1 || e->max_objs > 64) { agd_set_error("agd_gligen_configure: max_objs %d (1 .. 64: one key tile)", e->max_objs); return fail_ctx(c); }
+  if (e->fourier_freqs < 1 || e->fourier_freqs > 64 || e->positive_len < 1 || e->positive_len > 8192) {
+    agd_set_error("agd_gligen_configure: positive_len %d / fourier_freqs %d", e->positive_len, e->fourier_freqs); return fail_ctx(c); }
+  c->glc = *e; c->gl_on = true;
+  return 0;
+}
+
+// the PositionNet (Fourier embedding + null replacement + concat in one launch, then three igemm linears with SiLU between them) and, per
+// fuser, linear -> norm1 -> K / V of the grounding rows.  Everything runs on the batch2 * max_objs object rows.
+AGD_API int agd_gligen_set(agd_ctx* c, const float* boxes, const float* pos_emb, const float* masks, int batch2, void* stream) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (!c->gl_on) { agd_set_error("gligen_set: no GLIGEN UNet loaded (agd_gligen_configure before agd_finalize)"); return fail_ctx(c); }
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!boxes || !pos_emb || !masks || batch2 < 1) { agd_set_error("gligen_set: bad arguments (batch2 %d)", batch2); return fail_ctx(c); }
+  if (c->ctx_B2 > 0 && batch2 != c->ctx_B2) { agd_set_error("gligen_set: %d rows, the context holds %d (agd_set_context)", batch2, c->ctx_B2); return fail_ctx(c); }
+  const agd_gligen_config& e = c->glc;
+  const int rows = batch2 * e.max_objs, Dc = c->cfg.cross_attention_dim, Pin = e.positive_len + 8 * e.fourier_freqs;
+  c->gl_B2 = 0;                                                    // (unset until every block's K/V is written)
+  c->arena.release(0);
+  bf16_t* in = (bf16_t*)c->arena.alloc((size_t)rows * Pin * 2);
+  bf16_t* h1 = (bf16_t*)c->arena.alloc((size_t)rows * 512 * 2); bf16_t* h2 = (bf16_t*)c->arena.alloc((size_t)rows * 512 * 2);
+  if (!in || !h1 || !h2) return fail_ctx(c);
+  API_CK(c, c->gl_objb.ensure((size_t)rows * Dc * 2));
+  bf16_t* objs = c->gl_objb.as<bf16_t>();
+  const std::string P = "unet.position_net.";
+  { const float* np_ = getV(c, P + "null_positive_feature"); const float* nx = getV(c, P + "null_position_feature");
+    if (!np_ || !nx) return fail_ctx(c);
+    ProfScope ps(c, st, PC_ELEM, 0);
+    API_CK(c, launch_gligen_posnet_input(boxes, pos_emb, masks, np_, nx, in, rows, e.positive_len, e.fourier_freqs, Pin, st)); }
+  auto lin = [&](const std::string& k, const bf16_t* A, int K, bf16_t* out, int act) -> int {
+    GETW(w, k + ".weight"); GETV(b, k + ".bias");
+    GemmOpt o; o.bias = b; o.act = act;
+    return run_conv(c, st, A, K, nullptr, 0, 1, 1, rows, *w, 1, out, o, c->zero_page);
+  };
+  API_CK(c, lin(P + "linears.0", in, Pin, h1, 1));
+  API_CK(c, lin(P + "linears.2", h1, 512, h2, 1));
+  API_CK(c, lin(P + "linears.4", h2, 512, objs, 0));
+  for (Fuser& f : c->gl_f) {
+    const size_t mk = c->arena.mark();
+    const int C = f.C;
+    const std::string t = f.pre + "transformer_blocks.0.fuser.";
+    bf16_t* o = (bf16_t*)c->arena.alloc((size_t)rows * C * 2); bf16_t* n = (bf16_t*)c->arena.alloc((size_t)rows * C * 2);
+    if (!o || !n) return fail_ctx(c);
+    API_CK(c, lin(t + "linear", objs, Dc, o, 0));
+    const float* g1 = getV(c, t + "norm1.weight"); const float* b1 = getV(c, t + "norm1.bias"); if (!g1 || !b1) return fail_ctx(c);
+    { ProfScope ps(c, st, PC_LN, 0, 4.0 * rows * (double)C); API_CK(c, launch_layernorm(o, n, g1, b1, rows, C, 1e-5f, st)); }
+    API_CK(c, f.gkvb.ensure((size_t)rows * 2 * C * 2));
+    { GemmOpt go; API_CK(c, run_conv(c, st, n, C, nullptr, 0, 1, 1, rows, f.wkv, 1, f.gkvb.p, go, c->zero_page)); }
+    c->arena.release(mk);
+  }
+  c->gl_B2 = batch2;
+  return 0;
+}
+
+AGD_API int agd_gligen_set_schedule(agd_ctx* c, const int* flags, int n) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (n < 0 || (n > 0 && !flags)) { agd_set_error("gligen_set_schedule: %d flags", n); return fail_ctx(c); }
+  if (n > 0 && !c->gl_on) { agd_set_error("gligen_set_schedule: no GLIGEN UNet loaded"); return fail_ctx(c); }
+  c->gl_sched.assign(flags, flags + n);
+  return 0;
+}
+
+AGD_API int agd_gligen_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  c->gl_sched.clear(); c->gl_B2 = 0; c->gl_active = false;
+  return 0;
+}
+
+AGD_API int agd_gligen_objs(agd_ctx* c, float* out) {
+  API_CK(c, need_final(c));
+  if (!c->gl_on || c->gl_B2 < 1) { agd_set_error("gligen_objs: no grounding objects set (agd_gligen_set)"); return fail_ctx(c); }
+  if (!out) { agd_set_error("gligen_objs: null out"); return fail_ctx(c); }
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("gligen_objs: sync failed"); return fail_ctx(c); }   // (agd_gligen_set ran on the caller's stream)
+  API_CK(c, launch_bf16_to_f32(c->gl_objb.as<bf16_t>(), out, (long long)c->gl_B2 * c->glc.max_objs * c->cfg.cross_attention_dim, 0));
+  if (hipStreamSynchronize(0) != hipSuccess) { agd_set_error("gligen_objs: sync failed"); return fail_ctx(c); }
+  return 0;
+}
+
+AGD_API int agd_gligen_fuser(agd_ctx* c, const char* block_name, const float* x, int batch2, int h, int w, float* out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->gl_on) { agd_set_error("gligen_fuser: no GLIGEN UNet loaded"); return fail_ctx(c); }
+  if (!block_name || !x || !out || batch2 < 1 || h < 1 || w < 1) { agd_set_error("gligen_fuser: bad arguments"); return fail_ctx(c); }
+  std::string pre(block_name);
+  if (pre.compare(0, 5, "unet.") != 0) pre = "unet." + pre;
+  if (pre.back() != '.') pre += ".";
+  auto it = c->gl_idx.find(pre);
+  if (it == c->gl_idx.end()) { agd_set_error("gligen_fuser: no fuser in block '%s'", block_name); return fail_ctx(c); }
+  const Fuser& f = c->gl_f[it->second];
+  const int HW = h * w, M = batch2 * HW, C = f.C;
+  c->arena.release(0);
+  bf16_t* hb = (bf16_t*)c->arena.alloc((size_t)M * C * 2); bf16_t* qkv = (bf16_t*)c->arena.alloc((size_t)M * 3 * C * 2);
+  bf16_t* att = (bf16_t*)c->arena.alloc((size_t)M * C * 2);
+  if (!hb || !qkv || !att) return fail_ctx(c);
+  API_CK(c, launch_f32_to_bf16(x, hb, (long long)M * C, st));
+  API_CK(c, fuser_rows(c, st, f, hb, batch2, HW, qkv, att, [&](const bf16_t* A, int K, const WMat& wm, const GemmOpt& o) {
+    return run_conv(c, st, A, K, nullptr, 0, 1, 1, M, wm, 1, hb, o, c->zero_page); }));
+  API_CK(c, launch_bf16_to_f32(hb, out, (long long)M * C, st));
+  return 0;
+}

@@ -6,6 +6,7 @@ batch (RCCL over xGMI on GPUs; gloo in the CPU tests)."""
 from __future__ import annotations
 
 import argparse
+import json
 import os
 from typing import List, Optional, Sequence
 
@@ -280,6 +281,13 @@ def parse_args(argv=None):
                    help="a LoRA file or directory (kohya or diffusers format) merged into the UNet / text encoder on every rank")
     p.add_argument("--lora-weight-name", type=str, default=None, help="the LoRA file inside --lora-path (default pytorch_lora_weights.safetensors, then .bin)")
     p.add_argument("--lora-scale", type=float, default=1.0, help="the LoRA's strength (cross_attention_kwargs scale)")
+    p.add_argument("--gligen-phrases", type=str, default=None, nargs="+", metavar="P",
+                   help="GLIGEN checkpoint: one phrase per box, the same layout for every seed")
+    p.add_argument("--gligen-boxes", type=float, default=None, nargs="+", metavar="V",
+                   help="GLIGEN: x0 y0 x1 y1 per phrase, normalised to [0, 1]")
+    p.add_argument("--gligen-layouts", type=str, default=None,
+                   help="GLIGEN: a JSON file holding a list of {\"phrases\": [...], \"boxes\": [[x0, y0, x1, y1], ...]}; seed s uses layout s mod n")
+    p.add_argument("--gligen-beta", type=float, default=0.3, help="GLIGEN: gligen_scheduled_sampling_beta (the grounded share of the evaluations)")
     args = p.parse_args(argv)
     if args.lora_path is None and (args.lora_weight_name is not None or args.lora_scale != 1.0):
         p.error("--lora-weight-name / --lora-scale need --lora-path")
@@ -298,11 +306,60 @@ def parse_args(argv=None):
     if len(args.image_size) not in (1, 2) or min(args.image_size) < 1:
         p.error("--image-size takes one positive value S (square) or two, H W")
     args.image_size = args.image_size[0] if len(args.image_size) == 1 else tuple(args.image_size)
+    if (args.gligen_phrases is None) != (args.gligen_boxes is None):
+        p.error("--gligen-phrases and --gligen-boxes go together")
+    if args.gligen_phrases is not None and args.gligen_layouts is not None:
+        p.error("--gligen-layouts replaces --gligen-phrases / --gligen-boxes")
+    if args.gligen_boxes is not None and len(args.gligen_boxes) != 4 * len(args.gligen_phrases):
+        p.error(f"--gligen-boxes takes four values per phrase ({len(args.gligen_phrases)} phrases, {len(args.gligen_boxes)} values)")
+    if (args.gligen_phrases is not None or args.gligen_layouts is not None) and (args.controlnet_model_path or args.init_image):
+        p.error("GLIGEN with ControlNet or inpainting is not implemented")
     for name in ("height", "width"):
         v = getattr(args, name)
         if v is not None and (v < 1 or v % 64):
             p.error(f"--{name} {v}: a positive multiple of 64")
     return args
+
+
+def gligen_layouts_from_args(args) -> Optional[List[dict]]:
+    """The GLIGEN layouts of the run: one from --gligen-phrases / --gligen-boxes, or the list of --gligen-layouts; None without either."""
+    if args.gligen_layouts is not None:
+        with open(args.gligen_layouts) as f:
+            lays = json.load(f)
+        if not isinstance(lays, list) or not lays or not all(isinstance(x, dict) and {"phrases", "boxes"} <= set(x) for x in lays):
+            raise ValueError(f"{args.gligen_layouts}: a non-empty list of {{'phrases': [...], 'boxes': [...]}} objects")
+        return [{"phrases": list(x["phrases"]), "boxes": [list(map(float, b)) for b in x["boxes"]]} for x in lays]
+    if args.gligen_phrases is None:
+        return None
+    v = args.gligen_boxes
+    return [{"phrases": list(args.gligen_phrases), "boxes": [v[4 * i: 4 * i + 4] for i in range(len(args.gligen_phrases))]}]
+
+
+def gligen_inputs_for(layouts: Sequence[dict], seeds: Sequence[int], beta: float) -> dict:
+    """The GLIGEN pipeline's keyword arguments for a batch: seed s takes layout s mod n, one layout per image (the per-image extension)."""
+    lay = [layouts[int(s) % len(layouts)] for s in seeds]
+    return {"gligen_phrases": [x["phrases"] for x in lay], "gligen_boxes": [x["boxes"] for x in lay], "gligen_scheduled_sampling_beta": beta}
+
+
+def write_gligen_layouts(save_dir: str, records: dict):
+    """gligen_layouts.json: each saved image's file name -> its phrases and boxes, normalised and in saved-image pixels."""
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "gligen_layouts.json"), "w") as f:
+        json.dump(records, f, indent=2, sort_keys=True)
+
+
+def gligen_records(seeds, layouts, image_size, images_dir: Optional[str] = None) -> dict:
+    """The gligen_layouts.json entries of the seeds whose image was written (`images_dir` given: skipped black images have no file)."""
+    sh, sw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
+    out = {}
+    for s in seeds:
+        name = f"{s}.png"
+        if images_dir is not None and not os.path.exists(os.path.join(images_dir, name)):
+            continue
+        lay = layouts[int(s) % len(layouts)]
+        out[name] = {"phrases": lay["phrases"], "boxes": lay["boxes"],
+                     "boxes_px": [[b[0] * sw, b[1] * sh, b[2] * sw, b[3] * sh] for b in lay["boxes"]]}
+    return out
 
 
 def control_image_files(path: str) -> List[str]:
@@ -348,6 +405,10 @@ def main(argv=None):
         own_group = True
     kw = {"safety_checker": None} if args.no_safety_checker else {}
     cls, cn_files = StableDiffusionPipeline, None
+    gl_layouts = gligen_layouts_from_args(args)
+    if gl_layouts is not None:
+        from .gligen import StableDiffusionGLIGENPipeline
+        cls = StableDiffusionGLIGENPipeline
     if args.controlnet_model_path:
         from .controlnet import ControlNetModel, StableDiffusionControlNetPipeline
         cls = StableDiffusionControlNetPipeline
@@ -385,6 +446,7 @@ def main(argv=None):
     per_rank = (args.num_images + world - 1) // world
     rounds = (per_rank + args.batch_size - 1) // args.batch_size if gather else (len(seeds) + args.batch_size - 1) // args.batch_size
     S = args.image_size
+    gl_done = {}
     for r in range(rounds):
         chunk = seeds[r * args.batch_size:(r + 1) * args.batch_size]
         if chunk:
@@ -394,10 +456,15 @@ def main(argv=None):
                            "control_guidance_start": args.control_guidance_start, "control_guidance_end": args.control_guidance_end}
             if ip_files:
                 control = inpaint_inputs_for(ip_files, chunk, args.strength)
+            if gl_layouts is not None:
+                control = gligen_inputs_for(gl_layouts, chunk, args.gligen_beta)
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
                                        height=args.height, width=args.width)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)
+            if gl_layouts is not None:
+                gl_done.update(gligen_records(chunk, gl_layouts, S, os.path.join(args.save_dir, "images")))
+                write_gligen_layouts(args.save_dir, gl_done)
             continue
         # export on the producing GPU (resize 512 -> S, min-max -> uint8 -> resize), then ONE gather of the finished
         # payloads (S*S*3 + S*S per word bytes per image instead of the full-size tensors); rank 0 writes the files
@@ -415,6 +482,9 @@ def main(argv=None):
         all_seeds, small, hm8 = gather_outputs(small, hm8, seeds=chunk, max_batch=args.batch_size, global_seeds=round_seeds)
         if rank == 0:
             save_outputs(args.save_dir, all_seeds, small, hm8, words, S, stack_words=args.stack, exported=True)
+            if gl_layouts is not None:
+                gl_done.update(gligen_records(all_seeds, gl_layouts, S, os.path.join(args.save_dir, "images")))
+                write_gligen_layouts(args.save_dir, gl_done)
     if world > 1:
         dist.barrier()
         if own_group:

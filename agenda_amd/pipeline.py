@@ -239,6 +239,43 @@ class Engine:
                                                           _lib.ptr(out), C.byref(n), self._stream()), "agd_controlnet_residuals_hw")
         return out
 
+    def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
+        self._glcfg = _lib.AgdGligenConfig()
+        self._glcfg.struct_size = C.sizeof(_lib.AgdGligenConfig)
+        self._glcfg.max_objs, self._glcfg.positive_len, self._glcfg.fourier_freqs = int(max_objs), int(positive_len), int(fourier_freqs)
+        self._ck(self.lib.agd_gligen_configure(self.ctx, C.byref(self._glcfg)), "agd_gligen_configure")
+
+    def gligen_set(self, boxes: torch.Tensor, pos_emb: torch.Tensor, masks: torch.Tensor):
+        """`agd_gligen_set`: boxes [B2,n,4], phrase embeddings [B2,n,D] and masks [B2,n] (fp32) -> the PositionNet output and every fuser's
+        grounding K/V, computed once for the next forwards on B2 rows."""
+        boxes, pos_emb, masks = (self._h2d(t).clone().contiguous() for t in (boxes, pos_emb, masks))
+        self._ck(self.lib.agd_gligen_set(self.ctx, _lib.ptr(boxes), _lib.ptr(pos_emb), _lib.ptr(masks), int(boxes.shape[0]), self._stream()),
+                 "agd_gligen_set")
+        self._gl_keepalive = (boxes, pos_emb, masks)
+
+    def gligen_set_schedule(self, flags):
+        """One flag per model evaluation of the next fused loop (or one: the next unet_forward); empty clears."""
+        n = len(flags)
+        arr = (C.c_int * max(n, 1))(*[int(bool(x)) for x in flags])
+        self._ck(self.lib.agd_gligen_set_schedule(self.ctx, arr, n), "agd_gligen_set_schedule")
+
+    def gligen_clear(self):
+        self._ck(self.lib.agd_gligen_clear(self.ctx), "agd_gligen_clear")
+
+    def gligen_objs(self, batch2: int) -> torch.Tensor:
+        """`agd_gligen_objs`: the PositionNet output of the current call, fp32 [B2, max_objs, cross_attention_dim] (cuda)."""
+        out = torch.empty(batch2, self._glcfg.max_objs, self.cfg.unet.cross_attention_dim, device=f"cuda:{self.device}", dtype=torch.float32)
+        self._ck(self.lib.agd_gligen_objs(self.ctx, _lib.ptr(out)), "agd_gligen_objs")
+        return out
+
+    def gligen_fuser(self, block: str, x: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """`agd_gligen_fuser`: one GatedSelfAttentionDense forward of `block` on x fp32 [B2, h*w, C]."""
+        x = x.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        self._ck(self.lib.agd_gligen_fuser(self.ctx, block.encode(), _lib.ptr(x), x.shape[0], h, w, _lib.ptr(out), self._stream()),
+                 "agd_gligen_fuser")
+        return out
+
     def inpaint_prepare(self, image: torch.Tensor, mask: torch.Tensor, want_image: bool, want_masked: bool):
         """`agd_inpaint_prepare`: image uint8 [B,H,W,3] or float [B,3,H,W] in [-1,1], mask uint8 or float [B,H,W] -> (x, mask_lat): x fp32
         [n B,3,H,W] holds the [-1,1] image rows (want_image), then the masked-image rows (want_masked), ready for one vae_encode; mask_lat
@@ -633,6 +670,7 @@ class VAEHandle:
 
 
 class StableDiffusionPipeline:
+    _gligen = False                       # StableDiffusionGLIGENPipeline loads and runs the position net and the fusers
     def __init__(self, cfg: SDConfig, unet_sd: Dict[str, torch.Tensor], vae_sd: Dict[str, torch.Tensor],
                  tokenizer=None, text_encoder=None, device: Union[int, str] = 0, workspace_bytes: int = 0,
                  text_sd: Optional[Dict[str, torch.Tensor]] = None, scheduler: str = "DDIMScheduler",
@@ -640,6 +678,9 @@ class StableDiffusionPipeline:
         self.cfg = cfg
         dev = int(str(device).split(":")[-1]) if not isinstance(device, int) and ":" in str(device) else (device if isinstance(device, int) else 0)
         self.engine = Engine(cfg, dev, workspace_bytes)
+        if not self._gligen:      # a GLIGEN (gated) UNet under the plain pipeline: diffusers never runs its fusers, so they are not loaded
+            from .gligen import is_gligen_key
+            unet_sd = {k: v for k, v in unet_sd.items() if not is_gligen_key(k)}
         self.engine.load_state_dict(unet_sd, "unet.")
         self.engine.load_state_dict(vae_sd, "vae.")
         if text_sd is not None:

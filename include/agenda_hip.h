@@ -143,6 +143,33 @@ int agd_inpaint_set_hw(agd_ctx* ctx, const float* mask, int mask_channels, const
 int agd_inpaint_set_schedule(agd_ctx* ctx, const float* sa_sb, int n);
 int agd_inpaint_clear(agd_ctx* ctx);
 
+/* ---- GLIGEN (diffusers StableDiffusionGLIGENPipeline, a UNet of attention_type "gated"): a PositionNet turns per-object phrase
+ * embeddings and boxes into grounding tokens, and a GatedSelfAttentionDense ("fuser") in every transformer block, after attn1's residual
+ * add, attends over the block's rows plus those tokens:  x += tanh(alpha_attn) attn(norm1([x; o]))[:N];  x += tanh(alpha_dense) ff(norm2(x)).
+ * Configured by agd_gligen_configure BEFORE agd_finalize; weights through agd_load_tensor under their diffusers keys ("unet.position_net.*",
+ * "unet.<block>.transformer_blocks.0.fuser.*"; the 0-d alpha_attn / alpha_dense included).  agd_finalize fuses each fuser's q/k/v and k/v
+ * and pre-scales its to_out and ff.net.2 biases by the tanh gates (the gates themselves go on the GEMM accumulators). */
+typedef struct agd_gligen_config {
+  int struct_size;                 /* sizeof(agd_gligen_config), ABI guard */
+  int max_objs;                    /* 30 */
+  int positive_len;                /* PositionNet positive_len (the UNet's cross_attention_dim) */
+  int fourier_freqs;               /* 8 */
+} agd_gligen_config;
+int agd_gligen_configure(agd_ctx* ctx, const agd_gligen_config* gcfg);
+/* the per-call objects, device fp32: boxes [batch2][max_objs][4] (x0, y0, x1, y1 in [0,1]), pos_emb [batch2][max_objs][positive_len],
+ * masks [batch2][max_objs] (1 = a real object, 0 = null; the CFG unconditional half all null).  Runs the PositionNet and, for every fuser,
+ * linear -> norm1 -> K/V of the max_objs grounding rows, kept per block ([batch2][max_objs][2C] bf16) for the next forwards on batch2 rows. */
+int agd_gligen_set(agd_ctx* ctx, const float* boxes, const float* pos_emb, const float* masks, int batch2, void* stream);
+/* one flag per model evaluation (1 = the fusers run), host array of n ints, consumed by the next agd_denoise / agd_denoise_plms /
+ * agd_denoise_dpm (n must equal its evaluation count) or agd_unet_forward (n = 1).  A flag of 0 runs exactly the plain UNet.
+ * n = 0 clears the schedule. */
+int agd_gligen_set_schedule(agd_ctx* ctx, const int* flags, int n);
+int agd_gligen_clear(agd_ctx* ctx);                  /* the schedule and the per-call objects */
+/* seams for tests: the PositionNet output of the current call, out fp32 [batch2][max_objs][cross_attention_dim] (device; syncs), and one
+ * fuser forward on rows x fp32 [batch2][h*w][C] -> out (device; the block's name as "down_blocks.0.attentions.0", "unet." optional) */
+int agd_gligen_objs(agd_ctx* ctx, float* out);
+int agd_gligen_fuser(agd_ctx* ctx, const char* block_name, const float* x, int batch2, int h, int w, float* out, void* stream);
+
 /* ---- `unet(sample, t, encoder_hidden_states).sample`: sample/out fp32 NCHW [B2,4,L,L] */
 int agd_unet_forward(agd_ctx* ctx, const float* sample, int batch2, int latent_side, float timestep, float* out,
                      void* stream);
