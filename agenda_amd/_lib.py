@@ -159,6 +159,10 @@ _SIGS = {
     "agd_op_heatmap_u8": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "agd_op_resize_u8_pil": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "agd_op_stack_heatmaps": (C.c_int, [_P, _P, _P, C.c_longlong, _P, _P, _P]),
+    "agd_op_window_gather": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P]),
+    "agd_op_window_mean": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "agd_denoise_panorama": (C.c_int, [_P, _P] + [C.c_int] * 7 + [C.POINTER(C.c_float)] * 3 + [C.c_float, _P]),
+    "agd_daam_global_panorama": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "agd_profile_begin": (C.c_int, [_P]),
     "agd_profile_end": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "agd_profile_end_ex": (C.c_int, [_P, C.c_double, C.c_double] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_longlong)]),

@@ -245,6 +245,17 @@ int launch_prep_inpaint(const float* lat, const float* mask, const float* cond, 
 int launch_inpaint_blend(float* lat, const float* x0img, const float* noise, const float* mask, int B, int C, int HW, float sa, float sb,
                          hipStream_t st);
 
+// MultiDiffusion panorama (panorama.hip): views of win x win at (i stride, j stride), view v = i nbw + j; image of (panorama p, view v) in a view
+// buffer = p * pano_stride + v * view_stride images of [C][win][win] fp32.  gather: views [v0, v0 + n) of every panorama out of the canvas
+// [B][C][Lh][Lw] (view v lands at slot v - v0); mean: canvas element = the fp32 sum of its covering views in ascending view order / their number
+int pano_view_grid(int Lh, int Lw, int win, int stride, int* nbh, int* nbw);
+int launch_window_gather(const float* canvas, float* views, int B, int C, int Lh, int Lw, int win, int stride, int v0, int n,
+                         long long pano_stride, long long view_stride, hipStream_t st);
+int launch_window_mean(const float* views, float* canvas, int B, int C, int Lh, int Lw, int win, int stride, long long pano_stride,
+                       long long view_stride, hipStream_t st);
+// dst [halves][B * reps][row_bytes] = src [halves][B][row_bytes], row r of a half reading row r % B
+int launch_tile_rows(const void* src, void* dst, int halves, int B, int reps, size_t row_bytes, hipStream_t st);
+
 // export path (bit-exact with numpy min-max/astype and PIL Image.resize BICUBIC on uint8)
 int launch_heatmap_u8(const float* hm, int n, int npix, unsigned char* out, hipStream_t st);
 int launch_pil_resample(const unsigned char* in, unsigned char* out, const int* bounds, const int* kk, int ksize,

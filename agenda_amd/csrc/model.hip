@@ -119,6 +119,13 @@ struct agd_ctx {
   std::vector<HookRec> hook_recs; size_t hook_store_used = 0;
   DBuf bwd_wsb;                                                 // attention-backward workspace
   float* hook_sum = nullptr; float* hook_scratch = nullptr; int hook_count = 0, hook_Bp = 0, hook_T = 0;
+  // DAAM states of a forward that covers only part of the rec_B images the accumulators hold (agd_denoise_panorama: one state per (panorama,
+  // view), a chunk of views per forward): recorded image j of the forward is state rec_base + j, and the forward records iff it has rec_call
+  // images.  0 / 0 = every other entry point: state j, rec_B images.
+  int rec_base = 0, rec_call = 0;
+  int pano_B = 0, pano_Lh = 0, pano_Lw = 0, pano_stride = 0;        // the last agd_denoise_panorama that recorded (agd_daam_global_panorama reads its geometry)
+  DBuf pano_ctxb;                                                // agd_denoise_panorama: the prompts' bf16 context [2 B][T][D], kept while the tiled one is in place
+  DBuf pano_viewb, pano_hmb;                                     // agd_denoise_panorama's views [V][B][C][win][win]; agd_daam_global_panorama's per-view maps
   // denoise scratch
   DBuf latb, epsb, vae_imgb, plmsb, dpmb;
   bf16_t* lat_bf16 = nullptr; float* eps_nhwc = nullptr;
@@ -180,6 +187,7 @@ struct agd_ctx {
 };
 
 static int fail_ctx(agd_ctx* c) { if (c) c->err = g_err; return -1; }
+static inline int rec_images(const agd_ctx* c) { return c->rec_call > 0 ? c->rec_call : c->rec_B; }   // images a recording forward must have
 #define API_CK(c, expr) do { if ((expr) != 0) return fail_ctx(c); } while (0)
 
 struct ProfScope {
@@ -477,9 +485,10 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   bool hook_call = false;
   if (record && c->rec_mode == 1 && !xl.mid && xl.acc) {
     // daam: factor = sqrt(latent h * w / N) = Lh / qh; recorded iff factor != 8 (mid block); conditional half only
-    if (c->rec_Lh / qh != 8 && qh == xl.acc_h && qw == xl.acc_w && B2 / 2 == c->rec_B) {
-      a.rec_b0 = B2 / 2; a.rec = xl.acc; a.rec_T = c->rec_T;
+    if (c->rec_Lh / qh != 8 && qh == xl.acc_h && qw == xl.acc_w && B2 / 2 == rec_images(c)) {
+      a.rec_b0 = B2 / 2; a.rec_T = c->rec_T;
       a.rec_head_stride = (long long)c->rec_T * N; a.rec_img_stride = a.rec_head_stride * xl.acc_heads;
+      a.rec = xl.acc + (size_t)c->rec_base * a.rec_img_stride;
       if (xl.acc_heads < xl.heads) {                 // latent-resolution layer: head-group sums (attention.hip RECORD 2)
         if (mask) FAIL("attention_mask together with daam recording at latent resolution is not supported");
         a.record_mode = 3; a.rec_hpb = xl.heads / xl.acc_heads;
@@ -696,7 +705,7 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
   { auto itx = c->xl_idx.find(t + "attn2");              // the ONE predicate of that form: the chain kernel steps aside exactly where it holds
     if (itx != c->xl_idx.end()) {
       const XLayer& xq = c->xl[itx->second];
-      xpre_rec = c->rec_mode == 1 && !xq.mid && xq.acc && c->rec_Lh / x.H != 8 && x.H == xq.acc_h && x.W == xq.acc_w && B / 2 == c->rec_B;
+      xpre_rec = c->rec_mode == 1 && !xq.mid && xq.acc && c->rec_Lh / x.H != 8 && x.H == xq.acc_h && x.W == xq.acc_w && B / 2 == rec_images(c);
       xpre_ready = xq.pm_ready && c->opt_xpre && fold && HW % 64 == 0 && c->rec_mode != 2 && c->ctx_T <= XATTN_TP && !dup && (!xpre_rec || xq.acc_heads == xq.heads);
     } }
   const bool chain_fuse = (c->opt_tb_fuse & 2) && (C == 320 || (C == 640 && (c->opt_tb_fuse & 32))) && heads == 8 && HW % (C == 320 ? 128 : 64) == 0 && c->ctx_T <= 96 &&
@@ -745,9 +754,10 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
       AttnChainP ap{}; ap.h = h.p; ap.out = h.p; ap.gamma = g2; ap.beta = b2_; ap.ln_eps = lneps; ap.wqf = fq->w; ap.wof = fo->w; ap.bo = bo;
       ap.kv = xl.kv; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)D);
       double rec_bytes = 0;
-      if (c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_Lh / x.H != 8 && x.H == xl.acc_h && x.W == xl.acc_w && B / 2 == c->rec_B) {   // daam's rule, as cross_attention()
-        ap.record = 1; ap.rec = xl.acc; ap.rec_b0 = B / 2; ap.rec_T = c->rec_T; ap.rec_hpb = heads / xl.acc_heads;
+      if (c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_Lh / x.H != 8 && x.H == xl.acc_h && x.W == xl.acc_w && B / 2 == rec_images(c)) {   // daam's rule, as cross_attention()
+        ap.record = 1; ap.rec_b0 = B / 2; ap.rec_T = c->rec_T; ap.rec_hpb = heads / xl.acc_heads;
         ap.rec_head_stride = (long long)c->rec_T * HW; ap.rec_img_stride = ap.rec_head_stride * xl.acc_heads;
+        ap.rec = xl.acc + (size_t)c->rec_base * ap.rec_img_stride;
         rec_bytes = 8.0 * (B - ap.rec_b0) * xl.acc_heads * (double)c->rec_T * HW;
       }
       if (chain_pre) {                                   // h1 = attn1.to_out(att) + h is computed (and stored) by the chain itself: into a second buffer
@@ -782,7 +792,8 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
       sp.kpp = xl.pm_kpp; sp.kcs = xl.pm_kcs; sp.kbs = xl.pm_kbs; sp.P = P; sp.M = M; sp.HW = HW; sp.C = C; sp.H = heads; sp.T = c->ctx_T;
       double rec_bytes = 0;
       if (rec_daam) {
-        sp.rec = xl.acc; sp.rec_b0 = B / 2; sp.rec_T = c->rec_T; sp.rec_head_stride = (long long)c->rec_T * HW; sp.rec_img_stride = sp.rec_head_stride * xl.acc_heads;
+        sp.rec_b0 = B / 2; sp.rec_T = c->rec_T; sp.rec_head_stride = (long long)c->rec_T * HW; sp.rec_img_stride = sp.rec_head_stride * xl.acc_heads;
+        sp.rec = xl.acc + (size_t)c->rec_base * sp.rec_img_stride;
         rec_bytes = 8.0 * (B - sp.rec_b0) * heads * (double)c->rec_T * HW;
       }
       { ProfScope ps(c, st, PC_ATTN_CROSS, 2.0 * M * (double)HT * C, 2.0 * M * (double)C + 2.0 * B * (double)HT * C + 2.0 * M * (double)HT + rec_bytes);
@@ -1218,6 +1229,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   hipDeviceSynchronize();
   for (void* p : c->owned) hipFree(p);
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
+  c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
   c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
@@ -1744,6 +1756,7 @@ AGD_API int agd_finalize(agd_ctx* c) {
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 static int need_final(agd_ctx* c) { if (!c) { agd_set_error("null ctx"); return -1; } if (!c->finalized) { agd_set_error("agd_finalize not called"); return -1; } hipSetDevice(c->device); return 0; }
 
+static int project_context(agd_ctx* c, hipStream_t st, int batch2, int tokens);
 AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int tokens, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
@@ -1755,6 +1768,14 @@ AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int to
   for (auto& xl : c->xl) { API_CK(c, xl.kvb.ensure((size_t)batch2 * tokens * 2 * xl.C * 2)); xl.kv = xl.kvb.as<bf16_t>(); }
   c->ctx_B2 = batch2; c->ctx_T = tokens;
   API_CK(c, launch_f32_to_bf16(ctx_emb, c->ctx_bf16, (long long)batch2 * tokens * Dc, st));
+  API_CK(c, project_context(c, st, batch2, tokens));
+  return 0;
+}
+// the per-layer K/V rows (and, where that form runs, the pre-multiplied attn2 products) of the bf16 context [batch2][tokens][Dc] in ctx_bf16
+static int project_context(agd_ctx* c, hipStream_t st, int batch2, int tokens) {
+  const int Dc = c->cfg.cross_attention_dim;
+  for (auto& xl : c->xl) { API_CK(c, xl.kvb.ensure((size_t)batch2 * tokens * 2 * xl.C * 2)); xl.kv = xl.kvb.as<bf16_t>(); }
+  c->ctx_B2 = batch2; c->ctx_T = tokens;
   for (auto& xl : c->xl) {
     GemmOpt o;
     API_CK(c, run_conv(c, st, c->ctx_bf16, Dc, nullptr, 0, 1, 1, batch2 * tokens, xl.wkv, 1, xl.kv, o, c->zero_page));
@@ -1964,6 +1985,108 @@ AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw
 AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_steps, const float* timesteps, const float* alpha_t,
                            const float* alpha_prev, float guidance, void* stream) {
   return agd_denoise_hw(c, latents, batch, L, L, n_steps, timesteps, alpha_t, alpha_prev, guidance, stream);
+}
+
+// ---- MultiDiffusion panorama (diffusers 0.21.2 StableDiffusionPanoramaPipeline [upstream-knowledge]; panorama.hip) ------------------
+// While agd_denoise_panorama runs, the context is the prompts' [uncond x B | cond x B] tiled to [uncond x n B | cond x n B] (UNet batch order of a
+// forward: view-major, panorama-minor) and projected ONCE per call -- exactly what agd_set_context on the tiled embeddings gives, so no step
+// projects the text again.  When the loop ends (on an error too) the prompts' own context is put back and projected again: the engine is
+// left as agd_set_context left it.
+struct PanoCtx {
+  agd_ctx* c; hipStream_t st; int B2, n = 0; bool tiled = false;
+  PanoCtx(agd_ctx* c_, hipStream_t st_) : c(c_), st(st_), B2(c_->ctx_B2) {}
+  int tile(int B, int n_) {
+    const size_t row = (size_t)c->ctx_T * c->cfg.cross_attention_dim * 2;
+    CK(c->pano_ctxb.ensure((size_t)B2 * row));
+    if (hipMemcpyAsync(c->pano_ctxb.p, c->ctx_bf16, (size_t)B2 * row, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("denoise_panorama: context copy failed");
+    tiled = true; n = n_;
+    CK(c->ctxb.ensure((size_t)2 * B * n * row)); c->ctx_bf16 = c->ctxb.as<bf16_t>();
+    { ProfScope ps(c, st, PC_ELEM, 0); CK(launch_tile_rows(c->pano_ctxb.p, c->ctx_bf16, 2, B, n, row, st)); }
+    return project_context(c, st, 2 * B * n, c->ctx_T);
+  }
+  // a forward of m <= n views per panorama: rows [(n - m) B, (n + m) B) of the tiled context are [uncond x m B | cond x m B] (the tiles of a half are equal)
+  void point(int B, int m) {
+    const size_t R = (size_t)2 * B * n, off = (size_t)(n - m) * B;
+    for (auto& xl : c->xl) {
+      xl.kv = xl.kvb.as<bf16_t>() + off * c->ctx_T * 2 * xl.C;
+      if (!xl.pm_ready) continue;
+      const size_t HT = (size_t)xl.heads * XATTN_TP;
+      xl.pm_kpp = xl.pm_kppb.as<bf16_t>() + off * HT * xl.C; xl.pm_vpp = xl.pm_vppb.as<bf16_t>() + off * HT * xl.C;
+      xl.pm_kcs = xl.pm_csb.as<float>() + off * HT; xl.pm_kbs = xl.pm_csb.as<float>() + R * HT + off * HT;
+    }
+    c->ctx_B2 = 2 * B * m;
+  }
+  ~PanoCtx() {
+    c->rec_base = 0; c->rec_call = 0;
+    if (!tiled) return;
+    const size_t row = (size_t)c->ctx_T * c->cfg.cross_attention_dim * 2;
+    (void)hipMemcpyAsync(c->ctx_bf16, c->pano_ctxb.p, (size_t)B2 * row, hipMemcpyDeviceToDevice, st);
+    const std::string keep = g_err;                               // an error of the loop stays the one reported
+    if (project_context(c, st, B2, c->ctx_T) != 0) c->ctx_stale = true;
+    else agd_set_error("%s", keep.c_str());
+  }
+};
+// accepted panorama sizes: each latent side a multiple of the stride and at least the window, the window itself on the stride grid (every
+// canvas element is then covered: count > 0 everywhere) and a latent size the UNet takes
+static int check_panorama(agd_ctx* c, const char* what, int Lh, int Lw, int window, int stride, int* nbh, int* nbw) {
+  if (window < 1 || stride < 1 || window % stride || Lh < window || Lw < window || Lh % stride || Lw % stride)
+    FAIL("%s: latent size %d x %d with window %d and stride %d (each side a multiple of the stride and at least the window)", what, Lh, Lw, window, stride);
+  CK(check_latent_hw(c, what, window, window));
+  return pano_view_grid(Lh, Lw, window, stride, nbh, nbw);
+}
+
+// The DDIM loop of a panorama: canvas [batch][4][Lh][Lw] fp32 in place.  Per step every view (window x window at (i stride, j stride), view
+// v = i nbw + j) is gathered, run through the CFG UNet and stepped on its own, `view_batch` views per panorama per forward (<= 0: all of
+// them); then every canvas element becomes the mean of the stepped views that cover it, summed in view order.  The context set by
+// agd_set_context is the [2 batch, T, D] of the prompts; it is tiled per view here, once.  With the DAAM recorder on, the state of
+// (panorama p, view v) is image v * batch + p of an agd_record_reset_hw(ctx, batch * views, window, window).
+AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, int Lw, int window, int stride, int view_batch, int n_steps,
+                                 const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  int nbh = 0, nbw = 0;
+  API_CK(c, check_panorama(c, "denoise_panorama", Lh, Lw, window, stride, &nbh, &nbw));
+  if (batch < 1 || n_steps < 1 || !canvas || !timesteps || !alpha_t || !alpha_prev) { agd_set_error("denoise_panorama: batch %d, steps %d or a null argument", batch, n_steps); return fail_ctx(c); }
+  if (!c->cn_sched.empty()) { agd_set_error("denoise_panorama: a ControlNet schedule is set; ControlNet on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
+  if (!c->gl_sched.empty()) { agd_set_error("denoise_panorama: a GLIGEN schedule is set; GLIGEN on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
+  if (c->ip_mode != 0) { agd_set_error("denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)"); return fail_ctx(c); }
+  if (c->cfg.in_channels != c->cfg.out_channels) { agd_set_error("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels); return fail_ctx(c); }
+  if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
+  const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
+  const int Cl = c->cfg.out_channels, HW = window * window;
+  if (c->ctx_B2 != 2 * batch) { agd_set_error("denoise_panorama: context batch %d != 2*batch %d", c->ctx_B2, 2 * batch); return fail_ctx(c); }
+  if (c->rec_mode == 1 && (c->rec_B != batch * V || c->rec_Lh != window || c->rec_Lw != window)) {
+    agd_set_error("denoise_panorama: the recorder holds %d images at %d x %d, this call records %d panoramas x %d views at %d x %d (agd_record_reset_hw(ctx, batch * views, window, window))",
+                  c->rec_B, c->rec_Lh, c->rec_Lw, batch, V, window, window);
+    return fail_ctx(c);
+  }
+  c->pano_B = 0;
+  if (c->rec_mode == 1) { c->pano_B = batch; c->pano_Lh = Lh; c->pano_Lw = Lw; c->pano_stride = stride; }
+  API_CK(c, ensure_lat(c, 2 * batch * n, window, window));
+  const size_t img = (size_t)Cl * HW;
+  API_CK(c, c->pano_viewb.ensure((size_t)batch * V * img * sizeof(float)));
+  float* views = c->pano_viewb.as<float>();                         // [V][batch][Cl][window][window]
+  const float* tp_all = nullptr;
+  API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
+  PanoCtx pc(c, st);
+  API_CK(c, pc.tile(batch, n));
+  for (int s = 0; s < n_steps; ++s) {
+    for (int v0 = 0; v0 < V; v0 += n) {
+      const int m = V - v0 < n ? V - v0 : n;
+      float* vb = views + (size_t)v0 * batch * img;
+      { ProfScope ps(c, st, PC_ELEM, 0, 8.0 * batch * m * (double)img);
+        API_CK(c, launch_window_gather(canvas, vb, batch, Cl, Lh, Lw, window, stride, v0, m, 1, batch, st)); }
+      pc.point(batch, m);
+      c->rec_base = v0 * batch; c->rec_call = m * batch;
+      API_CK(c, prep_unet_input(c, st, vb, batch * m, HW));
+      API_CK(c, unet_walk(c, st, c->lat_bf16, 2 * batch * m, window, window, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true));
+      { ProfScope ps(c, st, PC_ELEM, 0);
+        API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, vb, batch * m, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
+    }
+    ProfScope ps(c, st, PC_ELEM, 0, 4.0 * batch * (double)img * V + 4.0 * batch * (double)Cl * Lh * Lw);
+    API_CK(c, launch_window_mean(views, canvas, batch, Cl, Lh, Lw, window, stride, 1, batch, st));
+  }
+  return 0;
 }
 
 // The denoise loop under the reference's ACTUAL scheduler: `pipeline(prompt, num_inference_steps=20)` at
@@ -2177,7 +2300,7 @@ AGD_API int agd_record_reset_hw(agd_ctx* c, int batch, int Lh, int Lw, void* str
   } else if (c->rec_mode == 2) {
     API_CK(c, hook_reset_rows(c, c->rec_is_train ? 2 * batch : batch, Lh, st));   // `batch` = images; UNet batch is 2*batch under CFG
   }
-  c->rec_B = batch; c->rec_L = Lh; c->rec_Lh = Lh; c->rec_Lw = Lw;
+  c->rec_B = batch; c->rec_L = Lh; c->rec_Lh = Lh; c->rec_Lw = Lw; c->pano_B = 0;
   return 0;
 }
 AGD_API int agd_record_reset(agd_ctx* c, int batch, int L, void* stream) {
@@ -2197,6 +2320,34 @@ AGD_API int agd_daam_global(agd_ctx* c, int img, int rows, float* out, void* str
   if (hl.empty() || c->rec_mode != 1) { agd_set_error("No heat maps found. Did you forget to call `with trace(...)`?"); c->err = g_err; return -2; }
   if (rows > c->rec_T || img >= c->rec_B) { agd_set_error("daam_global: rows %d > recorded %d or img %d >= %d", rows, c->rec_T, img, c->rec_B); return fail_ctx(c); }
   { ProfScope ps(c, st, PC_HEAT, 0); API_CK(c, launch_daam_global(hl.data(), (int)hl.size(), total, rows, c->rec_Lh, c->rec_Lw, img, out, st)); }
+  return 0;
+}
+
+// The heat map of a whole panorama (this project's definition; daam has no panorama support): the per-view global map of each of panorama
+// `img`'s views -- launch_daam_global at window x window, unchanged -- then the overlap mean of the views, exactly as the latents are fused.
+// out [rows][Lh][Lw] at the canvas size of the last agd_denoise_panorama, whose recorder state it reads: batch * views images, (panorama p,
+// view v) at v * batch + p.
+AGD_API int agd_daam_global_panorama(agd_ctx* c, int img, int rows, float* out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  const int win = c->rec_Lh, batch = c->pano_B, Lh = c->pano_Lh, Lw = c->pano_Lw, stride = c->pano_stride;
+  if (c->rec_mode != 1 || win < 1 || c->rec_Lw != win || batch < 1) { agd_set_error("No heat maps found. Did you forget to call `with trace(...)`?"); c->err = g_err; return -2; }
+  int nbh = 0, nbw = 0;
+  API_CK(c, check_panorama(c, "daam_global_panorama", Lh, Lw, win, stride, &nbh, &nbw));
+  const int V = nbh * nbw;
+  if (batch < 1 || c->rec_B != batch * V || img < 0 || img >= batch || rows < 1 || rows > c->rec_T) {
+    agd_set_error("daam_global_panorama: panorama %d of %d with %d views and %d rows, the recorder holds %d images and %d rows", img, batch, V, rows, c->rec_B, c->rec_T);
+    return fail_ctx(c);
+  }
+  const size_t per = (size_t)rows * win * win;
+  API_CK(c, c->pano_hmb.ensure((size_t)V * per * sizeof(float)));
+  float* hm = c->pano_hmb.as<float>();                              // [V][rows][win][win]
+  for (int v = 0; v < V; ++v) {
+    const int rc = agd_daam_global(c, v * batch + img, rows, hm + (size_t)v * per, stream);
+    if (rc != 0) return rc;
+  }
+  ProfScope ps(c, st, PC_HEAT, 0, 4.0 * V * (double)per + 4.0 * rows * (double)Lh * Lw);
+  API_CK(c, launch_window_mean(hm, out, 1, rows, Lh, Lw, win, stride, V, 1, st));
   return 0;
 }
 
@@ -2692,6 +2843,21 @@ AGD_API int agd_op_bicubic_clamp_mean(const float* maps, int n_maps, int T, int 
   CK(launch_daam_global(&h, 1, n_maps, T, S_, S_, 0, out, st));
   hipStreamSynchronize(st);
   return 0;
+}
+
+// panorama.hip in isolation: canvas [B][C][Lh][Lw] -> views [v0, v0 + n) of every panorama as [B * n][C][win][win] (view-major within a
+// panorama), and views [B * V][C][win][win] -> canvas as the overlap mean (sum in ascending view order / number of covering views)
+AGD_API int agd_op_window_gather(const float* canvas, float* views, int B, int C, int Lh, int Lw, int window, int stride, int v0, int n, void* stream) {
+  int nbh = 0, nbw = 0;
+  if (pano_view_grid(Lh, Lw, window, stride, &nbh, &nbw)) return -1;
+  if (!canvas || !views) { agd_set_error("op_window_gather: null argument"); return -1; }
+  return launch_window_gather(canvas, views, B, C, Lh, Lw, window, stride, v0, n, n, 1, S(stream));
+}
+AGD_API int agd_op_window_mean(const float* views, float* canvas, int B, int C, int Lh, int Lw, int window, int stride, void* stream) {
+  int nbh = 0, nbw = 0;
+  if (pano_view_grid(Lh, Lw, window, stride, &nbh, &nbw)) return -1;
+  if (!canvas || !views) { agd_set_error("op_window_mean: null argument"); return -1; }
+  return launch_window_mean(views, canvas, B, C, Lh, Lw, window, stride, (long long)nbh * nbw, 1, S(stream));
 }
 
 #ifdef AGD_EXPERIMENTS   // the micro-benchmark entry points exist only in the experiments library (make exp): tools/kb*.py

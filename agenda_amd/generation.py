@@ -287,6 +287,10 @@ def parse_args(argv=None):
                    help="GLIGEN: x0 y0 x1 y1 per phrase, normalised to [0, 1]")
     p.add_argument("--gligen-layouts", type=str, default=None,
                    help="GLIGEN: a JSON file holding a list of {\"phrases\": [...], \"boxes\": [[x0, y0, x1, y1], ...]}; seed s uses layout s mod n")
+    p.add_argument("--panorama", action="store_true",
+                   help="MultiDiffusion panorama txt2img (StableDiffusionPanoramaPipeline): --height / --width give the canvas, each a multiple of 64 "
+                        "and at least the checkpoint's size (default: that size x 4 times it); DDIM only")
+    p.add_argument("--view-batch-size", type=int, default=None, help="panorama: views per UNet call (default: all views of a step at once)")
     p.add_argument("--gligen-beta", type=float, default=0.3, help="GLIGEN: gligen_scheduled_sampling_beta (the grounded share of the evaluations)")
     args = p.parse_args(argv)
     if args.lora_path is None and (args.lora_weight_name is not None or args.lora_scale != 1.0):
@@ -318,7 +322,32 @@ def parse_args(argv=None):
         v = getattr(args, name)
         if v is not None and (v < 1 or v % 64):
             p.error(f"--{name} {v}: a positive multiple of 64")
+    if args.view_batch_size is not None and not args.panorama:
+        p.error("--view-batch-size needs --panorama")
+    if args.panorama:
+        # everything StableDiffusionPanoramaPipeline refuses is refused here, before a device is touched
+        if args.controlnet_model_path or args.init_image or args.gligen_phrases is not None or args.gligen_layouts is not None:
+            p.error("--panorama with ControlNet, inpainting or GLIGEN is not implemented")
+        if args.scheduler is None:
+            args.scheduler = "DDIMScheduler"
+        from .panorama import check_panorama_args
+        window = panorama_window(args)
+        args.height = args.height or 8 * window
+        args.width = args.width or 4 * args.height
+        try:
+            check_panorama_args(args.scheduler, args.height, args.width, window, args.view_batch_size)
+        except ValueError as e:
+            p.error(f"--panorama: {e}")
     return args
+
+
+def panorama_window(args) -> int:
+    """The view side in latent pixels of the model the arguments name: the checkpoint's UNet `sample_size`, or the synthetic config's."""
+    if args.pretrained_model_path:
+        with open(os.path.join(args.pretrained_model_path, "unet", "config.json")) as f:
+            return int(json.load(f).get("sample_size", 64))
+    from .config import CONFIGS
+    return int(CONFIGS[args.synthetic_config]().default_sample_size)
 
 
 def gligen_layouts_from_args(args) -> Optional[List[dict]]:
@@ -421,6 +450,9 @@ def main(argv=None):
         ip_files = list(zip(control_image_files(args.init_image), control_image_files(args.mask_image)))
         if len(ip_files) != len(control_image_files(args.init_image)) or len(ip_files) != len(control_image_files(args.mask_image)):
             raise ValueError(f"{args.init_image} and {args.mask_image} hold different numbers of images")
+    if args.panorama:
+        from .panorama import StableDiffusionPanoramaPipeline
+        cls = StableDiffusionPanoramaPipeline
     pipe = (cls.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
             cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
@@ -458,6 +490,8 @@ def main(argv=None):
                 control = inpaint_inputs_for(ip_files, chunk, args.strength)
             if gl_layouts is not None:
                 control = gligen_inputs_for(gl_layouts, chunk, args.gligen_beta)
+            if args.panorama:
+                control = {"view_batch_size": args.view_batch_size}
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
                                        height=args.height, width=args.width)
         if not gather:

@@ -189,3 +189,32 @@ def conv_groupnorm(x, w, bias, gamma, beta, groups=32, eps=1e-5, silu=True, fuse
     _lib.check(lib.agd_op_conv_groupnorm(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(ga), _lib.ptr(be), _lib.ptr(y), B, Cin, H, W, Cout,
                                          groups, float(eps), int(silu), int(fused) | _P8[p8], _lib.current_stream_ptr()), None, "agd_op_conv_groupnorm")
     return y
+
+
+def window_gather(canvas, window, stride=8, v0=0, n=None):
+    """MultiDiffusion views of a canvas [B, C, Lh, Lw]: views [v0, v0 + n) of every panorama as [B * n, C, window, window]
+    (view-major within a panorama; diffusers get_views order)."""
+    lib = _lib.load()
+    canvas = _f32c(canvas)
+    B, Cc, Lh, Lw = canvas.shape
+    V = max((Lh - window) // stride + 1, 0) * max((Lw - window) // stride + 1, 0)
+    n = max(V - v0, 0) if n is None else n
+    out = torch.empty(B * n, Cc, window, window, device=canvas.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_window_gather(_lib.ptr(canvas), _lib.ptr(out), B, Cc, Lh, Lw, window, stride, v0, n, _lib.current_stream_ptr()), None,
+               "agd_op_window_gather")
+    return out
+
+
+def window_mean(views, batch, Lh, Lw, stride=8):
+    """The overlap mean: views [B * V, C, window, window] -> canvas [B, C, Lh, Lw], each element the sum of its covering views in view
+    order divided by their number."""
+    lib = _lib.load()
+    views = _f32c(views)
+    _, Cc, window, _ = views.shape
+    out = torch.empty(batch, Cc, Lh, Lw, device=views.device, dtype=torch.float32)
+    V = ((Lh - window) // stride + 1) * ((Lw - window) // stride + 1)
+    if views.shape[0] != batch * V:
+        raise ValueError(f"window_mean: {views.shape[0]} views for {batch} canvases of {V} views")
+    _lib.check(lib.agd_op_window_mean(_lib.ptr(views), _lib.ptr(out), batch, Cc, Lh, Lw, window, stride, _lib.current_stream_ptr()), None,
+               "agd_op_window_mean")
+    return out

@@ -383,6 +383,29 @@ class Engine:
             self._ck(self.lib.agd_denoise_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, at, ap, float(guidance), self._stream()), "agd_denoise_hw")
         return latents
 
+    def denoise_panorama(self, canvas: torch.Tensor, window: int, stride: int, view_batch: Optional[int], timesteps, a_t, a_p, guidance: float):
+        """The fused MultiDiffusion DDIM loop (`agd_denoise_panorama`) on a canvas [B,4,Lh,Lw] in place: per step every window x window
+        view is run and stepped on its own, `view_batch` views of every panorama per UNet call (None: all), then overlap-averaged."""
+        assert canvas.is_cuda and canvas.dtype == torch.float32 and canvas.is_contiguous()
+        n = len(timesteps)
+        ts = (C.c_float * n)(*[float(t) for t in timesteps])
+        at = (C.c_float * n)(*[float(x) for x in a_t])
+        ap = (C.c_float * n)(*[float(x) for x in a_p])
+        b, _, Lh, Lw = canvas.shape
+        self._ck(self.lib.agd_denoise_panorama(self.ctx, _lib.ptr(canvas), b, Lh, Lw, int(window), int(stride), int(view_batch or 0), n, ts, at, ap,
+                                               float(guidance), self._stream()), "agd_denoise_panorama")
+        return canvas
+
+    def daam_global_panorama(self, img: int, rows: int, S) -> torch.Tensor:
+        """[rows, Lh, Lw] over the canvas of the last denoise_panorama: the overlap mean of the views' global maps (`S`: its (Lh, Lw))."""
+        Sh, Sw = _hw(S)
+        out = torch.empty(rows, Sh, Sw, device=f"cuda:{self.device}", dtype=torch.float32)
+        rc = self.lib.agd_daam_global_panorama(self.ctx, img, rows, _lib.ptr(out), self._stream())
+        if rc == -2:
+            raise RuntimeError(self.lib.agd_last_error(self.ctx).decode())
+        self._ck(rc, "agd_daam_global_panorama")
+        return out
+
     def cfg_ddim_step(self, eps: torch.Tensor, latents: torch.Tensor, guidance: float, alpha_t: float, alpha_prev: float):
         """`scheduler.step` of the call-by-call loop: CFG combine of eps [2B,4,L,L] (rows [0,B) unconditional) + one DDIM
         (eta 0) update of `latents` [B,4,L,L] in place (`agd_cfg_ddim_step`; the fused loop is `denoise`)."""

@@ -6,7 +6,11 @@ bicubic -> clamp -> mean, rows truncated to len(tokenize(prompt)) + 2.
 Rectangular generates (height != width) give maps of [rows, Lh, Lw].  daam itself is square-only (its `_unravel_attn` takes
 h = w = sqrt(N)); here a layer's maps are (Lh / f) x (Lw / f) with daam's own factor f = sqrt(Lh * Lw / N), resized by bicubic with
 separate y and x scales (torch `F.interpolate(size=(Lh, Lw), mode="bicubic", align_corners=False)`).  That is the direct
-generalisation of daam's formula, not a behaviour daam has: parity-unpinned.  Square generates are exactly daam's."""
+generalisation of daam's formula, not a behaviour daam has: parity-unpinned.  Square generates are exactly daam's.
+
+A panorama (StableDiffusionPanoramaPipeline) gives maps [rows, Lh, Lw] over the whole canvas: every view's global map, computed exactly as
+for a square generate of the window size, then the mean over the views that cover each latent pixel (the rule that fuses the latents).
+daam has no panorama support; this definition is this project's (parity-unpinned)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -77,8 +81,9 @@ class trace:
         self.pipe._apply_record_mode()
         return False
 
-    def _on_generate(self, batch: int, latent_side, prompt: Optional[str]):
+    def _on_generate(self, batch: int, latent_side, prompt: Optional[str], panorama: bool = False):
         self.batch, self.latent_side, self.last_prompt, self._ran = batch, latent_side, prompt, True
+        self.panorama = panorama             # a StableDiffusionPanoramaPipeline call: latent_side is the canvas (Lh, Lw)
 
     def compute_global_heat_map(self, prompt: Optional[str] = None, image_index: int = 0, normalize: bool = False) -> GlobalHeatMap:
         """Heat maps [rows, Lh, Lw] of image `image_index` (word maps from it are [Lh, Lw])."""
@@ -88,7 +93,10 @@ class trace:
         rows = self.rec_tokens
         if prompt is not None:
             rows = min(rows, len(self.pipe.tokenizer.tokenize(prompt)) + 2)   # 1 for SOS and 1 for padding
-        maps = self.pipe.engine.daam_global(image_index, rows, self.latent_side)
+        if getattr(self, "panorama", False):
+            maps = self.pipe.engine.daam_global_panorama(image_index, rows, self.latent_side)
+        else:
+            maps = self.pipe.engine.daam_global(image_index, rows, self.latent_side)
         if normalize:
             maps = maps / (maps[1:-1].sum(0, keepdim=True) + 1e-6)
         return GlobalHeatMap(self.pipe.tokenizer, prompt or "", maps)

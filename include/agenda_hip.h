@@ -394,6 +394,27 @@ int agd_lora_clear(agd_ctx* ctx);
 int agd_lora_count(agd_ctx* ctx);                    /* targets staged */
 float agd_lora_scale(agd_ctx* ctx);                  /* the scale the weights hold now */
 
+/* ---- MultiDiffusion panorama (diffusers 0.21.2 StableDiffusionPanoramaPipeline [upstream-knowledge]; csrc/panorama.hip)
+ * Views of a latent canvas Lh x Lw: nbh x nbw windows of `window` x `window` at (i stride, j stride), nbh = (Lh - window) / stride + 1,
+ * view v = i * nbw + j (diffusers get_views order).
+ * agd_op_window_gather: canvas fp32 [B][C][Lh][Lw] -> views [v0, v0 + n) of every panorama, fp32 [B * n][C][window][window], view-major
+ *   within a panorama.  agd_op_window_mean: views [B * V][C][window][window] -> canvas, every element the fp32 sum of the views that cover it
+ *   in ascending view order divided by their number (0 where no view covers it): a gather, deterministic, no atomics.  Both take any
+ *   window / stride with each side at least the window.
+ * agd_denoise_panorama: the DDIM loop on a canvas [batch][4][Lh][Lw] in place.  Per step every view is gathered, run through the CFG UNet
+ *   and stepped on its own, view_batch views of every panorama per UNet call (<= 0: all views); then one overlap mean writes the canvas.
+ *   Sizes: Lh, Lw multiples of `stride` and at least `window`, `window` a multiple of `stride`.  The context (agd_set_context) is the
+ *   [2 * batch, T, D] of the prompts; the loop tiles its projections per view once per call.  A ControlNet schedule, a GLIGEN schedule or an
+ *   inpainting state being set is an error.  DAAM: after agd_record_reset_hw(ctx, batch * views, window, window) the loop records one state
+ *   per (panorama p, view v), image v * batch + p, for any view_batch (agd_daam_global reads one view's map).
+ * agd_daam_global_panorama: out [rows][Lh][Lw] of panorama `img` of the last agd_denoise_panorama = the overlap mean of its views' global
+ *   maps (each the agd_daam_global map at window x window).  This definition is this project's: daam has no panorama support. */
+int agd_op_window_gather(const float* canvas, float* views, int B, int C, int Lh, int Lw, int window, int stride, int v0, int n, void* stream);
+int agd_op_window_mean(const float* views, float* canvas, int B, int C, int Lh, int Lw, int window, int stride, void* stream);
+int agd_denoise_panorama(agd_ctx* ctx, float* canvas, int batch, int Lh, int Lw, int window, int stride, int view_batch, int n_steps,
+                         const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
+int agd_daam_global_panorama(agd_ctx* ctx, int img, int rows, float* out, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
