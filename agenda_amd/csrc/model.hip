@@ -1957,29 +1957,42 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
   return 0;
 }
 
+// The CFG evaluation loop of every fused denoise call: n model evaluations on `batch` images at Lh x Lw, `latents` updated in place.  Per
+// evaluation i: the UNet input from the latents, the walk under that evaluation's time embedding, ControlNet scale and GLIGEN flag, then
+// step(i) -- the scheduler's kernel, c->eps_nhwc -> latents -- then the inpainting blend when a blend schedule is set.  Every refusal comes
+// before the first launch.
+template <class Step>
+static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, int Lh, int Lw, int n, const float* timesteps, Step&& step) {
+  const int B2 = 2 * batch, HW = Lh * Lw;
+  CK(ensure_lat(c, B2, Lh, Lw));
+  if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
+  const float* cs = nullptr;                                       // the ControlNet's per-evaluation scales (none: the UNet alone)
+  CK(cn_schedule_for(c, n, B2, Lh, Lw, &cs));
+  const int* gs = nullptr;                                         // the GLIGEN per-evaluation flags (none: no fuser runs)
+  CK(gl_schedule_for(c, n, B2, &gs));
+  const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per evaluation (none: no blend)
+  CK(inpaint_for(c, n, batch, Lh, Lw, &ib));
+  const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
+  CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
+  for (int i = 0; i < n; ++i) {
+    CK(prep_unet_input(c, st, latents, batch, HW));
+    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
+    CK(step(i));
+    if (ib) CK(inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
+  }
+  return 0;
+}
+
 AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw, int n_steps, const float* timesteps, const float* alpha_t,
                            const float* alpha_prev, float guidance, void* stream) {
   API_CK(c, need_final(c));
   API_CK(c, check_latent_hw(c, "denoise", Lh, Lw));
   hipStream_t st = S(stream);
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;          // Cl: the latent channels (a 9-channel UNet's input has more)
-  API_CK(c, ensure_lat(c, B2, Lh, Lw));
-  if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
-  const float* cs = nullptr;                                       // the ControlNet's per-step scales (none: the UNet alone)
-  API_CK(c, cn_schedule_for(c, n_steps, B2, Lh, Lw, &cs));
-  const int* gs = nullptr;                                         // the GLIGEN per-step flags (none: no fuser runs)
-  API_CK(c, gl_schedule_for(c, n_steps, B2, &gs));
-  const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per step (none: no blend)
-  API_CK(c, inpaint_for(c, n_steps, batch, Lh, Lw, &ib));
-  const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
-  API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
-  for (int s = 0; s < n_steps; ++s) {
-    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true, 0, cs ? cs[s] : 0.f, gs && gs[s]));
-    { ProfScope ps(c, st, PC_ELEM, 0);
-      API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
-    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * s));
-  }
+  const int Cl = c->cfg.out_channels, HW = Lh * Lw;                          // Cl: the latent channels (a 9-channel UNet's input has more)
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_steps, timesteps, [&](int s) {
+    ProfScope ps(c, st, PC_ELEM, 0);
+    return launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st);
+  }));
   return 0;
 }
 AGD_API int agd_denoise(agd_ctx* c, float* latents, int batch, int L, int n_steps, const float* timesteps, const float* alpha_t,
@@ -2104,44 +2117,32 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
   hipStream_t st = S(stream);
   if (c->cfg.prediction_type != 0) { agd_set_error("denoise_plms: epsilon prediction only"); return fail_ctx(c); }
   if (n_evals < 2) { agd_set_error("denoise_plms: needs >= 2 model evaluations (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;
-  API_CK(c, ensure_lat(c, B2, Lh, Lw));
-  if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
+  const int Cl = c->cfg.out_channels, HW = Lh * Lw;
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->plmsb.ensure(n1 * 5 * sizeof(float)));            // 4 history slots + the kept sample
   float* hist[4]; for (int k = 0; k < 4; ++k) hist[k] = c->plmsb.as<float>() + n1 * k;
-  float* kept = c->plmsb.as<float>() + n1 * 4;
-  const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
-  const int* gs = nullptr;
-  API_CK(c, gl_schedule_for(c, n_evals, B2, &gs));
-  const float* ib = nullptr;                                       // the blend rewrites `latents` only: the kept sample stays unblended
-  API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
-  const float* tp_all = nullptr;
-  API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
+  float* kept = c->plmsb.as<float>() + n1 * 4;                    // the blend rewrites `latents` only: the kept sample stays unblended
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
-  for (int i = 0; i < n_evals; ++i) {
-    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i) {
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
     const float* src = latents; float* store = nullptr;
     if (i == 1) {                                                 // PLMS second call: average with e0, restart from the kept sample
       w[0] = 0.5f; w[1] = 0.5f; h[0] = hist[(head - 1) & 3]; src = kept;
     } else {
-      if (i == 0 && hipMemcpyAsync(kept, latents, n1 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("plms: keep sample"); return fail_ctx(c); }
+      if (i == 0 && hipMemcpyAsync(kept, latents, n1 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("plms: keep sample");
       store = hist[head & 3];
       for (int k = 0; k < 3 && k < n_hist; ++k) h[k] = hist[(head - 1 - k) & 3];
       if (n_hist == 1) { w[0] = 1.5f; w[1] = -0.5f; }
       else if (n_hist == 2) { w[0] = 23.f / 12.f; w[1] = -16.f / 12.f; w[2] = 5.f / 12.f; }
       else if (n_hist >= 3) { w[0] = 55.f / 24.f; w[1] = -59.f / 24.f; w[2] = 37.f / 24.f; w[3] = -9.f / 24.f; }
     }
-    { ProfScope ps(c, st, PC_ELEM, 0);
-      API_CK(c, launch_cfg_plms(c->eps_nhwc, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w,
-                                sample_coeff[i], eps_coeff[i], st)); }
-    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
+    ProfScope ps(c, st, PC_ELEM, 0);
+    CK(launch_cfg_plms(c->eps_nhwc, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w, sample_coeff[i],
+                       eps_coeff[i], st));
     if (store) { ++head; if (n_hist < 3) ++n_hist; }
-  }
+    return 0;
+  }));
   return 0;
 }
 AGD_API int agd_denoise_plms(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* sample_coeff,
@@ -2161,29 +2162,16 @@ AGD_API int agd_denoise_dpm_hw(agd_ctx* c, float* latents, int batch, int Lh, in
   API_CK(c, check_latent_hw(c, "denoise_dpm", Lh, Lw));
   hipStream_t st = S(stream);
   if (n_evals < 1 || !timesteps || !coeffs) { agd_set_error("denoise_dpm: needs >= 1 model evaluation and host timesteps / coeffs (got %d)", n_evals); return fail_ctx(c); }
-  const int B2 = 2 * batch, Cl = c->cfg.out_channels, HW = Lh * Lw;
-  API_CK(c, ensure_lat(c, B2, Lh, Lw));
-  if (c->ctx_B2 != B2) { agd_set_error("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2); return fail_ctx(c); }
+  const int Cl = c->cfg.out_channels, HW = Lh * Lw;
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
-  const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, n_evals, B2, Lh, Lw, &cs));
-  const int* gs = nullptr;
-  API_CK(c, gl_schedule_for(c, n_evals, B2, &gs));
-  const float* ib = nullptr;
-  API_CK(c, inpaint_for(c, n_evals, batch, Lh, Lw, &ib));
-  const float* tp_all = nullptr;
-  API_CK(c, embed_all_timesteps(c, st, timesteps, n_evals, &tp_all));
-  for (int i = 0; i < n_evals; ++i) {
-    API_CK(c, prep_unet_input(c, st, latents, batch, HW));
-    API_CK(c, unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i) {
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
-    { ProfScope ps(c, st, PC_ELEM, 0);
-      API_CK(c, launch_cfg_dpm(c->eps_nhwc, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st)); }
-    if (ib) API_CK(c, inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
-  }
+    ProfScope ps(c, st, PC_ELEM, 0);
+    return launch_cfg_dpm(c->eps_nhwc, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st);
+  }));
   return 0;
 }
 AGD_API int agd_denoise_dpm(agd_ctx* c, float* latents, int batch, int L, int n_evals, const float* timesteps, const float* coeffs,

@@ -206,14 +206,7 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
         self._apply_lora_scale(cross_attention_kwargs)
         L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
         img, mask = prepare_mask_and_image(image, mask_image, height, width)
-        if prompt_embeds is None:
-            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
-            pb, per = len(prompts), num_images_per_prompt
-            prompts = [p for p in prompts for _ in range(per)]
-            negs = None if negative_prompt is None else ([negative_prompt] * len(prompts) if isinstance(negative_prompt, str) else list(negative_prompt))
-            prompt_embeds = self.encode_prompt(prompts, negs)
-        else:
-            pb, per = prompt_embeds.shape[0] // 2, 1
+        prompt_embeds, pb, per = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)
         B = prompt_embeds.shape[0] // 2
         n = img.shape[0]
         if n != 1 and n != pb:
@@ -255,14 +248,7 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
             else:
                 eng.inpaint_set(mask_lat, image_lat, nz)
                 eng.inpaint_set_schedule(blend_schedule(self.scheduler, evaluation_timesteps(self.scheduler, num_inference_steps, strength)))
-            eng.set_context(prompt_embeds)
-            self._apply_record_mode()
-            if self._trace is not None or self._hooker is not None:
-                eng.record_reset(B, L)
-                if self._trace is not None:
-                    self._trace._on_generate(B, L, self._last_prompt)
-                if self._hooker is not None:
-                    self._hooker._on_generate(B, L, prompt_embeds.shape[1])
+            self._begin_recording(prompt_embeds, B, L)
             if strength < 1.0:
                 eng.denoise(lat, ts[t0:], a_t[t0:], a_p[t0:], guidance_scale)
             else:

@@ -87,27 +87,9 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
         self._apply_lora_scale(cross_attention_kwargs)
         Lh, Lw = height // f, width // f
         n_views = len(get_views(height, width, win, STRIDE))
-        if prompt_embeds is None:
-            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
-            prompts = [p for p in prompts for _ in range(num_images_per_prompt)]
-            negs = None if negative_prompt is None else ([negative_prompt] * len(prompts) if isinstance(negative_prompt, str) else list(negative_prompt))
-            prompt_embeds = self.encode_prompt(prompts, negs)
+        prompt_embeds = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)[0]
         B = prompt_embeds.shape[0] // 2
-        Cl = self.cfg.unet.out_channels
-        if latents is None:                                    # ONE latent of the canvas size, drawn exactly as for txt2img
-            if isinstance(generator, (list, tuple)):
-                if len(generator) != B:
-                    raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {B}.")
-                parts = [torch.randn(1, Cl, Lh, Lw, generator=g, device=g.device if g is not None else "cpu") for g in generator]
-                if len({p_.device for p_ in parts}) > 1:
-                    parts = [p_.cpu() for p_ in parts]
-                latents = torch.cat(parts, 0)
-            else:
-                latents = torch.randn(B, Cl, Lh, Lw, generator=generator, device=generator.device if generator is not None else "cpu")
-        expect = (B, Cl, Lh, Lw)
-        if tuple(latents.shape) != expect:
-            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
-        lat = self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
+        lat = self._draw_latents(B, Lh, Lw, generator, latents)       # ONE latent of the canvas size, drawn exactly as for txt2img
         self.engine.set_context(prompt_embeds)                 # the [2B, T, D] of the prompts; the loop tiles its projections per view
         self._apply_record_mode()
         if self._trace is not None:

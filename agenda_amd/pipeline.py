@@ -61,6 +61,12 @@ def check_image_size(height: int, width: int, multiple: int = 64) -> None:
         raise ValueError(f"height and width must each be a positive multiple of {multiple}, got height={height}, width={width}")
 
 
+def _floats(xs):
+    """A sequence of numbers as a ctypes float array (one element when empty: the engine is given a valid pointer and a length of 0)."""
+    xs = [float(x) for x in xs]
+    return (C.c_float * max(len(xs), 1))(*xs)
+
+
 def _make_cfg(cfg: SDConfig, workspace_bytes: int) -> _lib.AgdConfig:
     a = _lib.AgdConfig()
     a.struct_size = C.sizeof(_lib.AgdConfig)
@@ -186,12 +192,8 @@ class Engine:
         b, h, w = img.shape[0], img.shape[1], img.shape[2]
         cos = torch.empty(b, s.n_special + s.n_concepts, device=img.device, dtype=torch.float32)
         pix = torch.empty(b, 3, s.image_size, s.image_size, device=img.device, dtype=torch.float32) if want_pixels else None
-        if h == w:
-            self._ck(self.lib.agd_safety_scores(self.ctx, _lib.ptr(img), b, h, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
-                     "agd_safety_scores")
-        else:
-            self._ck(self.lib.agd_safety_scores_hw(self.ctx, _lib.ptr(img), b, h, w, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
-                     "agd_safety_scores_hw")
+        self._ck(self.lib.agd_safety_scores_hw(self.ctx, _lib.ptr(img), b, h, w, _lib.ptr(cos), _lib.ptr(pix), self._stream()),
+                 "agd_safety_scores_hw")
         return (cos, pix) if want_pixels else cos
 
     def controlnet_configure(self, cncfg):
@@ -211,17 +213,12 @@ class Engine:
         b, c, h, w = cond.shape
         if c != 3:
             raise ValueError(f"control image must be [B,3,H,W], got {tuple(cond.shape)}")
-        if h == w:
-            self._ck(self.lib.agd_controlnet_set_cond(self.ctx, _lib.ptr(cond), b, h, int(repeat), self._stream()), "agd_controlnet_set_cond")
-        else:
-            self._ck(self.lib.agd_controlnet_set_cond_hw(self.ctx, _lib.ptr(cond), b, h, w, int(repeat), self._stream()), "agd_controlnet_set_cond_hw")
+        self._ck(self.lib.agd_controlnet_set_cond_hw(self.ctx, _lib.ptr(cond), b, h, w, int(repeat), self._stream()), "agd_controlnet_set_cond_hw")
         self._cond_keepalive = cond
 
     def controlnet_set_schedule(self, scales):
         """Per-model-evaluation conditioning scales of the next fused loop (or one-element: the next unet_forward); empty clears."""
-        n = len(scales)
-        arr = (C.c_float * max(n, 1))(*[float(x) for x in scales])
-        self._ck(self.lib.agd_controlnet_set_schedule(self.ctx, arr, n), "agd_controlnet_set_schedule")
+        self._ck(self.lib.agd_controlnet_set_schedule(self.ctx, _floats(scales), len(scales)), "agd_controlnet_set_schedule")
 
     def controlnet_residuals(self, sample: torch.Tensor, timestep: float, scale: float = 1.0, nhwc: bool = False) -> torch.Tensor:
         """`agd_controlnet_residuals`: the scaled ControlNet residuals of one forward, back to back in one fp32 vector (down residuals in
@@ -231,12 +228,8 @@ class Engine:
         n = C.c_longlong(0)
         self._ck(self.lib.agd_controlnet_residuals_hw(self.ctx, None, b2, Lh, Lw, 0.0, 0.0, int(nhwc), None, C.byref(n), None), "agd_controlnet_residuals")
         out = torch.empty(n.value, device=sample.device, dtype=torch.float32)
-        if Lh == Lw:
-            self._ck(self.lib.agd_controlnet_residuals(self.ctx, _lib.ptr(sample), b2, Lh, float(timestep), float(scale), int(nhwc), _lib.ptr(out),
-                                                       C.byref(n), self._stream()), "agd_controlnet_residuals")
-        else:
-            self._ck(self.lib.agd_controlnet_residuals_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(timestep), float(scale), int(nhwc),
-                                                          _lib.ptr(out), C.byref(n), self._stream()), "agd_controlnet_residuals_hw")
+        self._ck(self.lib.agd_controlnet_residuals_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(timestep), float(scale), int(nhwc),
+                                                      _lib.ptr(out), C.byref(n), self._stream()), "agd_controlnet_residuals_hw")
         return out
 
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
@@ -293,12 +286,8 @@ class Engine:
         xi = _lib.ptr(x) if want_image else None
         xm = C.c_void_p(x.data_ptr() + (b * 3 * H * W * 4 if want_image else 0)) if want_masked else None
         img_p, mask_p = C.c_void_p(image.data_ptr()), C.c_void_p(mask.data_ptr())
-        if H == W:
-            self._ck(self.lib.agd_inpaint_prepare(self.ctx, img_p, int(img_f32), mask_p, int(mask_f32), b, H, xi, xm, _lib.ptr(m), self._stream()),
-                     "agd_inpaint_prepare")
-        else:
-            self._ck(self.lib.agd_inpaint_prepare_hw(self.ctx, img_p, int(img_f32), mask_p, int(mask_f32), b, H, W, xi, xm, _lib.ptr(m),
-                                                     self._stream()), "agd_inpaint_prepare_hw")
+        self._ck(self.lib.agd_inpaint_prepare_hw(self.ctx, img_p, int(img_f32), mask_p, int(mask_f32), b, H, W, xi, xm, _lib.ptr(m),
+                                                 self._stream()), "agd_inpaint_prepare_hw")
         self._inpaint_keep = (image, mask)
         return x, m
 
@@ -311,19 +300,13 @@ class Engine:
         if cond.shape[0] != b or tuple(cond.shape[2:]) != (Lh, Lw) or (noise is not None and noise.shape != cond.shape):
             raise ValueError(f"inpaint state shapes disagree: mask {tuple(mask.shape)}, cond {tuple(cond.shape)}, "
                              f"noise {None if noise is None else tuple(noise.shape)}")
-        if Lh == Lw:
-            self._ck(self.lib.agd_inpaint_set(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, Lh, self._stream()),
-                     "agd_inpaint_set")
-        else:
-            self._ck(self.lib.agd_inpaint_set_hw(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, Lh, Lw,
-                                                 self._stream()), "agd_inpaint_set_hw")
+        self._ck(self.lib.agd_inpaint_set_hw(self.ctx, _lib.ptr(mask), cm, _lib.ptr(cond), cond.shape[1], _lib.ptr(noise), b, Lh, Lw,
+                                             self._stream()), "agd_inpaint_set_hw")
         self._inpaint_state = (mask, cond, noise)
 
     def inpaint_set_schedule(self, sa_sb):
         """The blend's (sa, sb) per model evaluation of the next fused loop."""
-        n = len(sa_sb)
-        arr = (C.c_float * max(2 * n, 1))(*[float(v) for pair in sa_sb for v in pair])
-        self._ck(self.lib.agd_inpaint_set_schedule(self.ctx, arr, n), "agd_inpaint_set_schedule")
+        self._ck(self.lib.agd_inpaint_set_schedule(self.ctx, _floats(v for pair in sa_sb for v in pair), len(sa_sb)), "agd_inpaint_set_schedule")
 
     def inpaint_clear(self):
         self._ck(self.lib.agd_inpaint_clear(self.ctx), "agd_inpaint_clear")
@@ -353,47 +336,29 @@ class Engine:
         b2, _, Lh, Lw = sample.shape
         ts = timestep.detach().flatten().tolist() if torch.is_tensor(timestep) else (list(timestep) if isinstance(timestep, (list, tuple)) else [timestep])
         if len(ts) == 1:
-            if Lh == Lw:
-                self._ck(self.lib.agd_unet_forward(self.ctx, _lib.ptr(sample), b2, Lh, float(ts[0]), _lib.ptr(out), self._stream()),
-                         "agd_unet_forward")
-            else:
-                self._ck(self.lib.agd_unet_forward_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(ts[0]), _lib.ptr(out), self._stream()),
-                         "agd_unet_forward_hw")
+            self._ck(self.lib.agd_unet_forward_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(ts[0]), _lib.ptr(out), self._stream()),
+                     "agd_unet_forward_hw")
         else:
             if len(ts) != b2:
                 raise ValueError(f"timestep has {len(ts)} entries for a batch of {b2}")
-            arr = (C.c_float * b2)(*[float(t) for t in ts])
-            if Lh == Lw:
-                self._ck(self.lib.agd_unet_forward_ts(self.ctx, _lib.ptr(sample), b2, Lh, arr, _lib.ptr(out), self._stream()), "agd_unet_forward_ts")
-            else:
-                self._ck(self.lib.agd_unet_forward_ts_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, arr, _lib.ptr(out), self._stream()),
-                         "agd_unet_forward_ts_hw")
+            self._ck(self.lib.agd_unet_forward_ts_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, _floats(ts), _lib.ptr(out), self._stream()),
+                     "agd_unet_forward_ts_hw")
         return out
 
     def denoise(self, latents: torch.Tensor, timesteps, a_t, a_p, guidance: float):
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
-        n = len(timesteps)
-        ts = (C.c_float * n)(*[float(t) for t in timesteps])
-        at = (C.c_float * n)(*[float(x) for x in a_t])
-        ap = (C.c_float * n)(*[float(x) for x in a_p])
         b, _, Lh, Lw = latents.shape
-        if Lh == Lw:
-            self._ck(self.lib.agd_denoise(self.ctx, _lib.ptr(latents), b, Lh, n, ts, at, ap, float(guidance), self._stream()), "agd_denoise")
-        else:
-            self._ck(self.lib.agd_denoise_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, at, ap, float(guidance), self._stream()), "agd_denoise_hw")
+        self._ck(self.lib.agd_denoise_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, len(timesteps), _floats(timesteps), _floats(a_t), _floats(a_p),
+                                         float(guidance), self._stream()), "agd_denoise_hw")
         return latents
 
     def denoise_panorama(self, canvas: torch.Tensor, window: int, stride: int, view_batch: Optional[int], timesteps, a_t, a_p, guidance: float):
         """The fused MultiDiffusion DDIM loop (`agd_denoise_panorama`) on a canvas [B,4,Lh,Lw] in place: per step every window x window
         view is run and stepped on its own, `view_batch` views of every panorama per UNet call (None: all), then overlap-averaged."""
         assert canvas.is_cuda and canvas.dtype == torch.float32 and canvas.is_contiguous()
-        n = len(timesteps)
-        ts = (C.c_float * n)(*[float(t) for t in timesteps])
-        at = (C.c_float * n)(*[float(x) for x in a_t])
-        ap = (C.c_float * n)(*[float(x) for x in a_p])
         b, _, Lh, Lw = canvas.shape
-        self._ck(self.lib.agd_denoise_panorama(self.ctx, _lib.ptr(canvas), b, Lh, Lw, int(window), int(stride), int(view_batch or 0), n, ts, at, ap,
-                                               float(guidance), self._stream()), "agd_denoise_panorama")
+        self._ck(self.lib.agd_denoise_panorama(self.ctx, _lib.ptr(canvas), b, Lh, Lw, int(window), int(stride), int(view_batch or 0), len(timesteps),
+                                               _floats(timesteps), _floats(a_t), _floats(a_p), float(guidance), self._stream()), "agd_denoise_panorama")
         return canvas
 
     def daam_global_panorama(self, img: int, rows: int, S) -> torch.Tensor:
@@ -414,28 +379,16 @@ class Engine:
         b, _, Lh, Lw = latents.shape
         if eps.shape[0] != 2 * b:
             raise ValueError(f"eps batch {eps.shape[0]} != 2 x latents batch {b}")
-        if Lh == Lw:
-            self._ck(self.lib.agd_cfg_ddim_step(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, Lh, float(guidance), float(alpha_t),
-                                                float(alpha_prev), self._stream()), "agd_cfg_ddim_step")
-        else:
-            self._ck(self.lib.agd_cfg_ddim_step_hw(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, Lh, Lw, float(guidance), float(alpha_t),
-                                                   float(alpha_prev), self._stream()), "agd_cfg_ddim_step_hw")
+        self._ck(self.lib.agd_cfg_ddim_step_hw(self.ctx, _lib.ptr(eps), _lib.ptr(latents), b, Lh, Lw, float(guidance), float(alpha_t),
+                                               float(alpha_prev), self._stream()), "agd_cfg_ddim_step_hw")
         return latents
 
     def denoise_plms(self, latents: torch.Tensor, timesteps, sample_coeff, eps_coeff, guidance: float):
         """The fused loop under PNDM/PLMS (`agd_denoise_plms`): len(timesteps) = num_inference_steps + 1 model evaluations."""
         assert latents.is_cuda and latents.dtype == torch.float32 and latents.is_contiguous()
-        n = len(timesteps)
-        ts = (C.c_float * n)(*[float(t) for t in timesteps])
-        ca = (C.c_float * n)(*[float(x) for x in sample_coeff])
-        cb = (C.c_float * n)(*[float(x) for x in eps_coeff])
         b, _, Lh, Lw = latents.shape
-        if Lh == Lw:
-            self._ck(self.lib.agd_denoise_plms(self.ctx, _lib.ptr(latents), b, Lh, n, ts, ca, cb, float(guidance), self._stream()),
-                     "agd_denoise_plms")
-        else:
-            self._ck(self.lib.agd_denoise_plms_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, ca, cb, float(guidance), self._stream()),
-                     "agd_denoise_plms_hw")
+        self._ck(self.lib.agd_denoise_plms_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, len(timesteps), _floats(timesteps), _floats(sample_coeff),
+                                              _floats(eps_coeff), float(guidance), self._stream()), "agd_denoise_plms_hw")
         return latents
 
     def denoise_dpm(self, latents: torch.Tensor, timesteps, cx, ce, a, b0, b1, guidance: float):
@@ -445,14 +398,10 @@ class Engine:
         n = len(timesteps)
         if not all(len(x) == n for x in (cx, ce, a, b0, b1)):
             raise ValueError("denoise_dpm: one (cx, ce, a, b0, b1) per timestep")
-        ts = (C.c_float * n)(*[float(t) for t in timesteps])
-        co = (C.c_float * (5 * n))(*[float(v) for row in zip(cx, ce, a, b0, b1) for v in row])
+        co = _floats(v for row in zip(cx, ce, a, b0, b1) for v in row)
         b, _, Lh, Lw = latents.shape
-        if Lh == Lw:
-            self._ck(self.lib.agd_denoise_dpm(self.ctx, _lib.ptr(latents), b, Lh, n, ts, co, float(guidance), self._stream()), "agd_denoise_dpm")
-        else:
-            self._ck(self.lib.agd_denoise_dpm_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, ts, co, float(guidance), self._stream()),
-                     "agd_denoise_dpm_hw")
+        self._ck(self.lib.agd_denoise_dpm_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, n, _floats(timesteps), co, float(guidance), self._stream()),
+                 "agd_denoise_dpm_hw")
         return latents
 
     def vae_decode(self, latents: torch.Tensor, want_f32: bool = False):
@@ -461,11 +410,7 @@ class Engine:
         f = 2 ** (len(self.cfg.vae.block_out_channels) - 1)
         u8 = torch.empty(b, Lh * f, Lw * f, 3, device=latents.device, dtype=torch.uint8)
         f32 = torch.empty(b, Lh * f, Lw * f, 3, device=latents.device, dtype=torch.float32) if want_f32 else None
-        if Lh == Lw:
-            self._ck(self.lib.agd_vae_decode(self.ctx, _lib.ptr(latents), b, Lh, _lib.ptr(u8), _lib.ptr(f32), self._stream()), "agd_vae_decode")
-        else:
-            self._ck(self.lib.agd_vae_decode_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, _lib.ptr(u8), _lib.ptr(f32), self._stream()),
-                     "agd_vae_decode_hw")
+        self._ck(self.lib.agd_vae_decode_hw(self.ctx, _lib.ptr(latents), b, Lh, Lw, _lib.ptr(u8), _lib.ptr(f32), self._stream()), "agd_vae_decode_hw")
         return (u8, f32) if want_f32 else u8
 
     def vae_encode(self, image: torch.Tensor):
@@ -475,11 +420,7 @@ class Engine:
         f = 2 ** (len(self.cfg.vae.block_out_channels) - 1)
         mean = torch.empty(b, self.cfg.vae.latent_channels, H // f, W // f, device=image.device, dtype=torch.float32)
         logvar = torch.empty_like(mean)
-        if H == W:
-            self._ck(self.lib.agd_vae_encode(self.ctx, _lib.ptr(image), b, H, _lib.ptr(mean), _lib.ptr(logvar), self._stream()), "agd_vae_encode")
-        else:
-            self._ck(self.lib.agd_vae_encode_hw(self.ctx, _lib.ptr(image), b, H, W, _lib.ptr(mean), _lib.ptr(logvar), self._stream()),
-                     "agd_vae_encode_hw")
+        self._ck(self.lib.agd_vae_encode_hw(self.ctx, _lib.ptr(image), b, H, W, _lib.ptr(mean), _lib.ptr(logvar), self._stream()), "agd_vae_encode_hw")
         return mean, logvar.clamp_(-30.0, 20.0)
 
     def set_option(self, name: str, value: int):
@@ -492,10 +433,7 @@ class Engine:
     def record_reset(self, batch: int, L):
         """`L`: the latent side, or an (Lh, Lw) pair."""
         Lh, Lw = _hw(L)
-        if Lh == Lw:
-            self._ck(self.lib.agd_record_reset(self.ctx, batch, Lh, self._stream()), "agd_record_reset")
-        else:
-            self._ck(self.lib.agd_record_reset_hw(self.ctx, batch, Lh, Lw, self._stream()), "agd_record_reset_hw")
+        self._ck(self.lib.agd_record_reset_hw(self.ctx, batch, Lh, Lw, self._stream()), "agd_record_reset_hw")
 
     def daam_global(self, img: int, rows: int, S) -> torch.Tensor:
         """[rows, Lh, Lw] at the size the last record_reset stored; `S`: the latent side, or an (Lh, Lw) pair."""
@@ -1004,6 +942,49 @@ class StableDiffusionPipeline:
         self._last_prompt = prompts[0]
         return torch.cat([self.text_encoder(neg), self.text_encoder(prompts)], 0)
 
+    def _expand_prompts(self, prompt, negative_prompt, num_images_per_prompt: int, prompt_embeds: Optional[torch.Tensor]):
+        """The call's context and how it was batched: (prompt_embeds, prompt batch, images per prompt).  `prompt` is a string or a list,
+        every entry repeated num_images_per_prompt times; `negative_prompt` a string (for every row) or one entry per row.  Given
+        `prompt_embeds` are taken as they are, one image per row."""
+        if prompt_embeds is not None:
+            return prompt_embeds, prompt_embeds.shape[0] // 2, 1
+        prompts = [prompt] if isinstance(prompt, str) else list(prompt)
+        pb = len(prompts)
+        prompts = [p for p in prompts for _ in range(num_images_per_prompt)]
+        negs = None if negative_prompt is None else ([negative_prompt] * len(prompts) if isinstance(negative_prompt, str) else list(negative_prompt))
+        return self.encode_prompt(prompts, negs), pb, num_images_per_prompt
+
+    def _draw_latents(self, B: int, Lh: int, Lw: int, generator, latents: Optional[torch.Tensor]) -> torch.Tensor:
+        """The initial latents [B, C, Lh, Lw] on the device, scaled by the scheduler's init_noise_sigma: `latents` when given, else drawn."""
+        Cl = self.cfg.unet.out_channels
+        if latents is None:
+            # data_generation.py:58 seeds `torch.Generator(device="cuda")`: accepted (torch's device Philox stream; whether it is
+            # bit-identical to an NVIDIA run of the reference is not verifiable here).  CPU generators give host-reproducible latents.
+            if isinstance(generator, (list, tuple)):           # diffusers randn_tensor: one (1, C, Lh, Lw) draw per generator
+                if len(generator) != B:
+                    raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {B}.")
+                parts = [torch.randn(1, Cl, Lh, Lw, generator=g, device=g.device if g is not None else "cpu") for g in generator]
+                if len({p_.device for p_ in parts}) > 1:
+                    parts = [p_.cpu() for p_ in parts]
+                latents = torch.cat(parts, 0)
+            else:                                              # ONE (B, C, Lh, Lw) draw, kept on the generator's device (no host round trip)
+                latents = torch.randn(B, Cl, Lh, Lw, generator=generator, device=generator.device if generator is not None else "cpu")
+        expect = (B, Cl, Lh, Lw)
+        if tuple(latents.shape) != expect:                 # diffusers prepare_latents raises the same way
+            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
+        return self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
+
+    def _begin_recording(self, prompt_embeds: torch.Tensor, B: int, L):
+        """Sets the call's context and, with a tracer or a hooker installed, starts their recording of B images at latent size L."""
+        self.engine.set_context(prompt_embeds)
+        self._apply_record_mode()
+        if self._trace is not None or self._hooker is not None:
+            self.engine.record_reset(B, L)
+            if self._trace is not None:
+                self._trace._on_generate(B, L, self._last_prompt)
+            if self._hooker is not None:
+                self._hooker._on_generate(B, L, prompt_embeds.shape[1])
+
     # ---- txt2img ------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, height: Optional[int] = None, width: Optional[int] = None,
@@ -1019,37 +1000,10 @@ class StableDiffusionPipeline:
         Lh, Lw = height // self.vae_scale_factor, width // self.vae_scale_factor
         self._refuse_rectangular_hook(Lh, Lw)
         L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
-        if prompt_embeds is None:
-            prompts = [prompt] if isinstance(prompt, str) else list(prompt)
-            prompts = [p for p in prompts for _ in range(num_images_per_prompt)]
-            negs = None if negative_prompt is None else ([negative_prompt] * len(prompts) if isinstance(negative_prompt, str) else list(negative_prompt))
-            prompt_embeds = self.encode_prompt(prompts, negs)
+        prompt_embeds = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)[0]
         B = prompt_embeds.shape[0] // 2
-        if latents is None:
-            # data_generation.py:58 seeds `torch.Generator(device="cuda")`: accepted (torch's device Philox stream; whether it is
-            # bit-identical to an NVIDIA run of the reference is not verifiable here).  CPU generators give host-reproducible latents.
-            Cl = self.cfg.unet.out_channels
-            if isinstance(generator, (list, tuple)):           # diffusers randn_tensor: one (1, C, Lh, Lw) draw per generator
-                if len(generator) != B:
-                    raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {B}.")
-                parts = [torch.randn(1, Cl, Lh, Lw, generator=g, device=g.device if g is not None else "cpu") for g in generator]
-                if len({p_.device for p_ in parts}) > 1:
-                    parts = [p_.cpu() for p_ in parts]
-                latents = torch.cat(parts, 0)
-            else:                                              # ONE (B, C, Lh, Lw) draw, kept on the generator's device (no host round trip)
-                latents = torch.randn(B, Cl, Lh, Lw, generator=generator, device=generator.device if generator is not None else "cpu")
-        expect = (B, self.cfg.unet.out_channels, Lh, Lw)
-        if tuple(latents.shape) != expect:                 # diffusers prepare_latents raises the same way
-            raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
-        lat = self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
-        self.engine.set_context(prompt_embeds)
-        self._apply_record_mode()
-        if self._trace is not None or self._hooker is not None:
-            self.engine.record_reset(B, L)
-            if self._trace is not None:
-                self._trace._on_generate(B, L, self._last_prompt)
-            if self._hooker is not None:
-                self._hooker._on_generate(B, L, prompt_embeds.shape[1])
+        lat = self._draw_latents(B, Lh, Lw, generator, latents)
+        self._begin_recording(prompt_embeds, B, L)
         self._denoise(lat, num_inference_steps, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
@@ -1135,14 +1089,7 @@ class StableDiffusionPipeline:
         x0 = (mean + torch.exp(0.5 * logvar) * noise_enc.to(mean.device)) * self.cfg.vae.scaling_factor
         a = float(sched.alphas_cumprod[int(ts[0])])
         lat = (a ** 0.5 * x0 + (1 - a) ** 0.5 * noise.to(mean.device)).contiguous()
-        self.engine.set_context(prompt_embeds)
-        self._apply_record_mode()
-        if self._trace is not None or self._hooker is not None:
-            self.engine.record_reset(B, L)
-            if self._trace is not None:
-                self._trace._on_generate(B, L, self._last_prompt)
-            if self._hooker is not None:
-                self._hooker._on_generate(B, L, prompt_embeds.shape[1])
+        self._begin_recording(prompt_embeds, B, L)
         self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
