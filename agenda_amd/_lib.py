@@ -92,6 +92,9 @@ _SIGS = {
     "agd_inpaint_set": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "agd_inpaint_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "agd_inpaint_clear": (C.c_int, [_P]),
+    "agd_ip2p_prepare_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "agd_ip2p_set_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "agd_ip2p_clear": (C.c_int, [_P]),
     "agd_gligen_configure": (C.c_int, [_P, C.POINTER(AgdGligenConfig)]),
     "agd_gligen_set": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "agd_gligen_set_schedule": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),

@@ -230,6 +230,15 @@ def inpaint_variant(cfg: SDConfig) -> SDConfig:
     return out
 
 
+def ip2p_variant(cfg: SDConfig) -> SDConfig:
+    """`cfg` with an InstructPix2Pix UNet: in_channels = latents + image latents (8 for SD); everything else unchanged."""
+    import copy
+    out = copy.deepcopy(cfg)
+    out.unet.in_channels = out.unet.out_channels + out.vae.latent_channels
+    out.name = cfg.name + "-ip2p"
+    return out
+
+
 def inpaint_flavour(cfg: SDConfig) -> str:
     """How a UNet inpaints [upstream-knowledge: diffusers 0.21.2 StableDiffusionInpaintPipeline]: "concat" when it takes latents + mask +
     masked-image latents (in_channels = out_channels + 1 + the VAE's latent channels: 9 for SD), "blend" when it takes the latents only

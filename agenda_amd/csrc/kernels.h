@@ -244,6 +244,12 @@ int launch_prep_inpaint(const float* lat, const float* mask, const float* cond, 
                         int dup, hipStream_t st);
 int launch_inpaint_blend(float* lat, const float* x0img, const float* noise, const float* mask, int B, int C, int HW, float sa, float sb,
                          hipStream_t st);
+// InstructPix2Pix (ip2p.hip): the image front end (uint8 NHWC or float NCHW -> fp32 NCHW in [-1,1]), the 8-channel UNet input of the three
+// guidance branches (rows [0,B) latents | 0, rows [B,3B) latents | image latents, bf16 NHWC), and the in-place fold of eps [3][n]
+// (uncond | image | text) into lo = e_u + s_i (e_i - e_u), hi = lo + (e_t - e_i) for the two-way step kernels
+int launch_ip2p_front(const void* image, int image_f32, int B, int H, int W, float* out, hipStream_t st);
+int launch_prep_ip2p(const float* lat, const float* img, bf16_t* out, int B, int Cl, int Cc, int HW, int Cpad, hipStream_t st);
+int launch_ip2p_fold(float* eps, long long n, float image_guidance, hipStream_t st);
 
 // MultiDiffusion panorama (panorama.hip): views of win x win at (i stride, j stride), view v = i nbw + j; image of (panorama p, view v) in a view
 // buffer = p * pano_stride + v * view_stride images of [C][win][win] fp32.  gather: views [v0, v0 + n) of every panorama out of the canvas

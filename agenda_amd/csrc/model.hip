@@ -170,6 +170,11 @@ struct agd_ctx {
   int ip_mode = 0, ip_B = 0, ip_Lh = 0, ip_Lw = 0, ip_Cm = 0, ip_Cc = 0;
   DBuf ip_maskb, ip_condb, ip_noiseb;
   std::vector<float> ip_sched;
+  // InstructPix2Pix (agd_ip2p_set_hw): the image latents fp32 NCHW [i2_B][vae latent channels][i2_Lh][i2_Lw] in i2_latb, unscaled, and the
+  // image guidance scale; i2_prep_*: the shape agd_ip2p_prepare_hw left there (agd_ip2p_set_hw with a null pointer installs those)
+  bool i2_on = false; int i2_B = 0, i2_Lh = 0, i2_Lw = 0; float i2_scale = 1.f;
+  int i2_prep_B = 0, i2_prep_Lh = 0, i2_prep_Lw = 0;
+  DBuf i2_latb;
   // LoRA (agd_lora_add / agd_lora_set_scale / agd_lora_clear): per target its fp32 factors and a bf16 copy of its base matrix (merge descriptors
   // on the host and in lora_descb), merged into the raw matrices and re-derived in place; lora_scratch: 8 C C bf16 for derive_tblock
   std::vector<std::string> lora_keys; std::vector<LoraMergeD> lora_d; int lora_tiles = 0;
@@ -1229,7 +1234,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   hipDeviceSynchronize();
   for (void* p : c->owned) hipFree(p);
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
-  c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release();
+  c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release(); c->i2_latb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
   c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
@@ -1839,7 +1844,8 @@ static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float
   *blend = nullptr;
   if (c->ip_mode == 0) {
     if (c->cfg.in_channels != c->cfg.out_channels)
-      FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first", c->cfg.in_channels, c->cfg.out_channels);
+      FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first, an InstructPix2Pix UNet agd_ip2p_set_hw",
+           c->cfg.in_channels, c->cfg.out_channels);
     return 0;
   }
   if (c->ip_B != batch || c->ip_Lh != Lh || c->ip_Lw != Lw)
@@ -1957,12 +1963,65 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
   return 0;
 }
 
+// an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
+static int ip2p_check_unet(agd_ctx* c, const char* what) {
+  const agd_config& g = c->cfg;
+  if (g.in_channels != g.out_channels + g.vae_latent_channels || g.in_channels > 64)
+    FAIL("%s: the UNet takes %d input channels, InstructPix2Pix needs %d latent + %d image-latent channels", what, g.in_channels, g.out_channels, g.vae_latent_channels);
+  return 0;
+}
+// The InstructPix2Pix state of a fused loop of n model evaluations on `batch` images at Lh x Lw; every refusal names its cause
+static int ip2p_for(agd_ctx* c, int batch, int Lh, int Lw) {
+  CK(ip2p_check_unet(c, "ip2p"));
+  if (c->i2_B != batch || c->i2_Lh != Lh || c->i2_Lw != Lw)
+    FAIL("ip2p: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->i2_B, c->i2_Lh, c->i2_Lw, batch, Lh, Lw);
+  if (!c->cn_sched.empty()) FAIL("ip2p: a ControlNet schedule is set; ControlNet with InstructPix2Pix is not implemented (clear it first)");
+  if (!c->gl_sched.empty()) FAIL("ip2p: a GLIGEN schedule is set; GLIGEN with InstructPix2Pix is not implemented (clear it first)");
+  if (c->ip_mode != 0) FAIL("ip2p: an inpainting state is set; inpainting with InstructPix2Pix is not implemented (agd_inpaint_clear first)");
+  return 0;
+}
+// The uncond walk of an InstructPix2Pix evaluation runs `rows` images against the first `rows` context rows -- the [uncond x B] half of the
+// [uncond x B | cond x B] agd_set_context projected -- and records nothing.  The engine is put back as it was when the walk ends, on an error too.
+struct Ip2pUncond {
+  agd_ctx* c; int B2, mode;
+  Ip2pUncond(agd_ctx* c_, int rows) : c(c_), B2(c_->ctx_B2), mode(c_->rec_mode) { c->ctx_B2 = rows; c->rec_mode = 0; }
+  ~Ip2pUncond() { c->ctx_B2 = B2; c->rec_mode = mode; }
+};
+// The InstructPix2Pix evaluation loop (ip2p.hip): per evaluation the 8-channel input of the three branches, walk A on rows [0, B) (uncond:
+// zero image latents, the negative prompt), walk B on rows [B, 3 B) (the usual [uncond | cond] pair, both with the image latents: the
+// shared prefix and the recorders' conditional half apply unchanged), the fold of the three outputs into rows [B, 3 B), then step(i, eps)
+// on those rows with the text scale.
+template <class Step>
+static int run_ip2p_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, int Lh, int Lw, int n, const float* timesteps, Step&& step) {
+  const int B2 = 2 * batch, HW = Lh * Lw, oc = c->cfg.out_channels;
+  CK(ip2p_for(c, batch, Lh, Lw));
+  if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
+  CK(ensure_lat(c, 3 * batch, Lh, Lw));
+  const float* tp_all = nullptr;
+  CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
+  const long long ne = (long long)batch * HW * oc;                 // one branch of eps
+  bf16_t* xin_b = c->lat_bf16 + (size_t)batch * HW * 64;
+  float* eps_b = c->eps_nhwc + ne;
+  for (int i = 0; i < n; ++i) {
+    const float* tp = tp_all + (size_t)i * c->tproj_total;
+    { ProfScope ps(c, st, PC_ELEM, 0);
+      CK(launch_prep_ip2p(latents, c->i2_latb.as<float>(), c->lat_bf16, batch, oc, c->cfg.vae_latent_channels, HW, 64, st)); }
+    { Ip2pUncond un(c, batch);
+      CK(unet_walk(c, st, c->lat_bf16, batch, Lh, Lw, timesteps[i], c->eps_nhwc, tp, false)); }
+    CK(unet_walk(c, st, xin_b, B2, Lh, Lw, timesteps[i], eps_b, tp, true));
+    { ProfScope ps(c, st, PC_ELEM, 0); CK(launch_ip2p_fold(c->eps_nhwc, ne, c->i2_scale, st)); }
+    CK(step(i, eps_b));
+  }
+  return 0;
+}
+
 // The CFG evaluation loop of every fused denoise call: n model evaluations on `batch` images at Lh x Lw, `latents` updated in place.  Per
 // evaluation i: the UNet input from the latents, the walk under that evaluation's time embedding, ControlNet scale and GLIGEN flag, then
-// step(i) -- the scheduler's kernel, c->eps_nhwc -> latents -- then the inpainting blend when a blend schedule is set.  Every refusal comes
-// before the first launch.
+// step(i, eps) -- the scheduler's kernel, eps [uncond | cond] -> latents -- then the inpainting blend when a blend schedule is set.  With an
+// InstructPix2Pix state the three-branch loop above runs instead.  Every refusal comes before the first launch.
 template <class Step>
 static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, int Lh, int Lw, int n, const float* timesteps, Step&& step) {
+  if (c->i2_on) return run_ip2p_loop(c, st, latents, batch, Lh, Lw, n, timesteps, step);
   const int B2 = 2 * batch, HW = Lh * Lw;
   CK(ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
@@ -1977,7 +2036,7 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
     CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
-    CK(step(i));
+    CK(step(i, c->eps_nhwc));
     if (ib) CK(inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
   }
   return 0;
@@ -1989,9 +2048,9 @@ AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw
   API_CK(c, check_latent_hw(c, "denoise", Lh, Lw));
   hipStream_t st = S(stream);
   const int Cl = c->cfg.out_channels, HW = Lh * Lw;                          // Cl: the latent channels (a 9-channel UNet's input has more)
-  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_steps, timesteps, [&](int s) {
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_steps, timesteps, [&](int s, const float* eps) {
     ProfScope ps(c, st, PC_ELEM, 0);
-    return launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st);
+    return launch_cfg_ddim(eps, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st);
   }));
   return 0;
 }
@@ -2063,6 +2122,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
   if (!c->cn_sched.empty()) { agd_set_error("denoise_panorama: a ControlNet schedule is set; ControlNet on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
   if (!c->gl_sched.empty()) { agd_set_error("denoise_panorama: a GLIGEN schedule is set; GLIGEN on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
   if (c->ip_mode != 0) { agd_set_error("denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)"); return fail_ctx(c); }
+  if (c->i2_on) { agd_set_error("denoise_panorama: an InstructPix2Pix state is set; InstructPix2Pix on a panorama is not implemented (agd_ip2p_clear first)"); return fail_ctx(c); }
   if (c->cfg.in_channels != c->cfg.out_channels) { agd_set_error("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels); return fail_ctx(c); }
   if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
   const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
@@ -2123,7 +2183,7 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
   float* hist[4]; for (int k = 0; k < 4; ++k) hist[k] = c->plmsb.as<float>() + n1 * k;
   float* kept = c->plmsb.as<float>() + n1 * 4;                    // the blend rewrites `latents` only: the kept sample stays unblended
   int n_hist = 0, head = 0;                                       // hist[(head - 1 - k) & 3] = k-th newest stored eps
-  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i) {
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i, const float* eps) {
     float w[4] = {1.f, 0.f, 0.f, 0.f};
     const float* h[3] = {nullptr, nullptr, nullptr};
     const float* src = latents; float* store = nullptr;
@@ -2138,7 +2198,7 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
       else if (n_hist >= 3) { w[0] = 55.f / 24.f; w[1] = -59.f / 24.f; w[2] = 37.f / 24.f; w[3] = -9.f / 24.f; }
     }
     ProfScope ps(c, st, PC_ELEM, 0);
-    CK(launch_cfg_plms(c->eps_nhwc, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w, sample_coeff[i],
+    CK(launch_cfg_plms(eps, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w, sample_coeff[i],
                        eps_coeff[i], st));
     if (store) { ++head; if (n_hist < 3) ++n_hist; }
     return 0;
@@ -2166,11 +2226,11 @@ AGD_API int agd_denoise_dpm_hw(agd_ctx* c, float* latents, int batch, int Lh, in
   const size_t n1 = (size_t)batch * Cl * HW;
   API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
-  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i) {
+  API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i, const float* eps) {
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     ProfScope ps(c, st, PC_ELEM, 0);
-    return launch_cfg_dpm(c->eps_nhwc, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st);
+    return launch_cfg_dpm(eps, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st);
   }));
   return 0;
 }
@@ -3547,6 +3607,56 @@ AGD_API int agd_inpaint_set_schedule(agd_ctx* c, const float* sa_sb, int n) {
 AGD_API int agd_inpaint_clear(agd_ctx* c) {
   if (!c) { agd_set_error("null ctx"); return -1; }
   c->ip_mode = 0; c->ip_B = c->ip_Lh = c->ip_Lw = c->ip_Cm = c->ip_Cc = 0; c->ip_sched.clear();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// InstructPix2Pix (diffusers StableDiffusionInstructPix2PixPipeline): the image front end and VAE encode once per call, then a state the
+// three fused loops read (run_ip2p_loop)
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_ip2p_prepare_hw(agd_ctx* c, const void* image, int image_f32, int batch, int h, int w, float* latents_out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  const int lc = c->cfg.vae_latent_channels, f = 1 << (c->cfg.vae_n_levels - 1);
+  if (!image || batch < 1) { agd_set_error("ip2p_prepare: null image or batch %d", batch); return fail_ctx(c); }
+  if (h < 1 || w < 1 || h % f || h % 8 || w % f || w % 8) { agd_set_error("ip2p_prepare: size %d x %d (each side a positive multiple of %d)", h, w, f > 8 ? f : 8); return fail_ctx(c); }
+  const int Lh = h / f, Lw = w / f;
+  const size_t nl = (size_t)batch * lc * Lh * Lw;
+  c->i2_on = false; c->i2_prep_B = 0;                              // the buffer below is the state's: a state set earlier ends here
+  Tmp tmp;
+  float* x = tmp.get<float>((size_t)batch * 3 * h * w); float* logvar = tmp.get<float>(nl);
+  if (!x || !logvar) return fail_ctx(c);
+  API_CK(c, c->i2_latb.ensure(nl * 4));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_ip2p_front(image, image_f32 != 0, batch, h, w, x, st)); }
+  if (agd_vae_encode_hw(c, x, batch, h, w, c->i2_latb.as<float>(), logvar, stream) != 0) return -1;      // synchronizes the stream
+  if (latents_out && hipMemcpyAsync(latents_out, c->i2_latb.p, nl * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("ip2p_prepare: copy failed"); return fail_ctx(c); }
+  c->i2_prep_B = batch; c->i2_prep_Lh = Lh; c->i2_prep_Lw = Lw;
+  return 0;
+}
+
+AGD_API int agd_ip2p_set_hw(agd_ctx* c, const float* image_latents, int batch, int Lh, int Lw, float image_guidance, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  API_CK(c, ip2p_check_unet(c, "ip2p_set"));
+  if (batch < 1 || Lh < 1 || Lw < 1) { agd_set_error("ip2p_set: batch %d latent size %d x %d", batch, Lh, Lw); return fail_ctx(c); }
+  if (!std::isfinite(image_guidance)) { agd_set_error("ip2p_set: image guidance scale %g", image_guidance); return fail_ctx(c); }
+  c->i2_on = false;
+  if (!image_latents) {
+    if (c->i2_prep_B != batch || c->i2_prep_Lh != Lh || c->i2_prep_Lw != Lw)
+      { agd_set_error("ip2p_set: no image latents given and agd_ip2p_prepare_hw left %d images at %d x %d, not %d at %d x %d", c->i2_prep_B, c->i2_prep_Lh, c->i2_prep_Lw, batch, Lh, Lw); return fail_ctx(c); }
+  } else {
+    const size_t nl = (size_t)batch * c->cfg.vae_latent_channels * Lh * Lw;
+    c->i2_prep_B = 0;
+    API_CK(c, c->i2_latb.ensure(nl * 4));
+    if (hipMemcpyAsync(c->i2_latb.p, image_latents, nl * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("ip2p_set: copy failed"); return fail_ctx(c); }
+  }
+  c->i2_on = true; c->i2_B = batch; c->i2_Lh = Lh; c->i2_Lw = Lw; c->i2_scale = image_guidance;
+  return 0;
+}
+
+AGD_API int agd_ip2p_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  c->i2_on = false; c->i2_B = c->i2_Lh = c->i2_Lw = 0; c->i2_scale = 1.f; c->i2_prep_B = 0;
   return 0;
 }
 

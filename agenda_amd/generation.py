@@ -64,8 +64,8 @@ def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Opt
                    guidance_scale: float = 7.5, height: Optional[int] = None, rec_tokens: Optional[int] = None,
                    word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None, width: Optional[int] = None):
     """One hot-path pass: len(seeds) images + per-word DAAM maps.  control: extra keyword arguments of a ControlNet pipeline's call
-    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`) or of an inpainting one
-    (`inpaint_inputs_for`).
+    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`), of an inpainting one
+    (`inpaint_inputs_for`) or of an InstructPix2Pix one (`ip2p_inputs_for`, with height and width the image's).
     Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, H/8, W/8] on GPU)."""
     from .trace import trace
     from . import synthetic
@@ -277,6 +277,10 @@ def parse_args(argv=None):
     p.add_argument("--mask-image", type=str, default=None,
                    help="inpainting: the mask, white = repaint (file or directory, paired with --init-image by sorted name)")
     p.add_argument("--strength", type=float, default=1.0, help="inpainting: 1 starts from noise; < 1 (DDIM only) from the noised image")
+    p.add_argument("--instruct-image", type=str, default=None,
+                   help="InstructPix2Pix checkpoint: the image the prompt edits (a file for every seed, or a directory: seed s uses its sorted "
+                        "file s mod n); the output has the image's size")
+    p.add_argument("--image-guidance-scale", type=float, default=None, help="InstructPix2Pix: image_guidance_scale (default 1.5, at least 1)")
     p.add_argument("--lora-path", type=str, default=None,
                    help="a LoRA file or directory (kohya or diffusers format) merged into the UNet / text encoder on every rank")
     p.add_argument("--lora-weight-name", type=str, default=None, help="the LoRA file inside --lora-path (default pytorch_lora_weights.safetensors, then .bin)")
@@ -301,6 +305,18 @@ def parse_args(argv=None):
         p.error("ControlNet inpainting is not implemented (--init-image with --controlnet-model-path)")
     if args.init_image is None and args.strength != 1.0:
         p.error("--strength needs --init-image / --mask-image")
+    if args.instruct_image is None and args.image_guidance_scale is not None:
+        p.error("--image-guidance-scale needs --instruct-image")
+    if args.instruct_image is not None:
+        # everything StableDiffusionInstructPix2PixPipeline refuses is refused here, before a device is touched
+        if args.controlnet_model_path or args.control_image or args.init_image or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama:
+            p.error("--instruct-image with ControlNet, inpainting, GLIGEN or --panorama is not implemented")
+        if args.height is not None or args.width is not None:
+            p.error("--instruct-image takes its size from the image: --height / --width cannot be given (nothing is resized)")
+        if args.image_guidance_scale is None:
+            args.image_guidance_scale = 1.5
+        if not args.image_guidance_scale >= 1.0:
+            p.error(f"--image-guidance-scale {args.image_guidance_scale}: at least 1 (the no-guidance mode is not implemented)")
     if (args.controlnet_model_path is None) != (args.control_image is None):
         p.error("--controlnet-model-path and --control-image go together")
     if not 0.0 <= args.control_guidance_start < args.control_guidance_end <= 1.0:
@@ -418,6 +434,18 @@ def inpaint_inputs_for(pairs: Sequence, seeds: Sequence[int], strength: float) -
             "strength": strength, "generator": torch.Generator().manual_seed(int(seeds[0]))}
 
 
+def ip2p_inputs_for(files: Sequence[str], seeds: Sequence[int], image_guidance_scale: float) -> dict:
+    """The InstructPix2Pix call's image of every seed (seed s takes file s mod n), the image guidance scale and the images' size (the
+    call's height and width; the images of one batch must share it)."""
+    from PIL import Image
+    ims = [Image.open(files[s % len(files)]).convert("RGB") for s in seeds]
+    sizes = {i.size for i in ims}
+    if len(sizes) != 1:
+        raise ValueError(f"the --instruct-image files of one batch must share one size, got {sorted(sizes)}")
+    w, h = ims[0].size
+    return {"image": ims, "image_guidance_scale": image_guidance_scale, "height": h, "width": w}
+
+
 def main(argv=None):
     import torch.distributed as dist
     from . import StableDiffusionPipeline
@@ -453,6 +481,11 @@ def main(argv=None):
     if args.panorama:
         from .panorama import StableDiffusionPanoramaPipeline
         cls = StableDiffusionPanoramaPipeline
+    i2_files = None
+    if args.instruct_image:
+        from .ip2p import StableDiffusionInstructPix2PixPipeline
+        cls = StableDiffusionInstructPix2PixPipeline
+        i2_files = control_image_files(args.instruct_image)
     pipe = (cls.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
             cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
@@ -492,8 +525,12 @@ def main(argv=None):
                 control = gligen_inputs_for(gl_layouts, chunk, args.gligen_beta)
             if args.panorama:
                 control = {"view_batch_size": args.view_batch_size}
+            height, width = args.height, args.width
+            if i2_files:                                                             # (parse_args refused --height / --width: both are None)
+                control = ip2p_inputs_for(i2_files, chunk, args.image_guidance_scale)
+                height, width = control.pop("height"), control.pop("width")          # the image's size is the call's
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
-                                       height=args.height, width=args.width)
+                                       height=height, width=width)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)
             if gl_layouts is not None:

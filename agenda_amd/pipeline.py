@@ -312,6 +312,31 @@ class Engine:
         self._ck(self.lib.agd_inpaint_clear(self.ctx), "agd_inpaint_clear")
         self._inpaint_state = None
 
+    def ip2p_prepare(self, image: torch.Tensor) -> torch.Tensor:
+        """`agd_ip2p_prepare_hw`: image uint8 [B,H,W,3] or float [B,3,H,W] in [-1,1] -> the image latents fp32 [B,c,H/8,W/8]: the VAE
+        posterior's mean, not multiplied by the scaling factor."""
+        dev = f"cuda:{self.device}"
+        img_f32 = image.dtype != torch.uint8
+        image = image.to(device=dev, dtype=torch.float32 if img_f32 else torch.uint8).contiguous()
+        b = image.shape[0]
+        H, W = tuple(image.shape[2:4]) if img_f32 else tuple(image.shape[1:3])
+        f = self.cfg.vae_scale_factor
+        out = torch.empty(b, self.cfg.vae.latent_channels, H // f, W // f, device=dev, dtype=torch.float32)
+        self._ck(self.lib.agd_ip2p_prepare_hw(self.ctx, C.c_void_p(image.data_ptr()), int(img_f32), b, H, W, _lib.ptr(out), self._stream()),
+                 "agd_ip2p_prepare_hw")
+        return out
+
+    def ip2p_set(self, image_latents: torch.Tensor, image_guidance: float):
+        """`agd_ip2p_set_hw`: image latents [B,c,Lh,Lw] (unscaled) and the image guidance scale of the next fused loop."""
+        lat = image_latents.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        b, _, Lh, Lw = lat.shape
+        if lat.shape[1] != self.cfg.vae.latent_channels:
+            raise ValueError(f"image latents have {lat.shape[1]} channels, the VAE's latents {self.cfg.vae.latent_channels}")
+        self._ck(self.lib.agd_ip2p_set_hw(self.ctx, _lib.ptr(lat), b, Lh, Lw, float(image_guidance), self._stream()), "agd_ip2p_set_hw")
+
+    def ip2p_clear(self):
+        self._ck(self.lib.agd_ip2p_clear(self.ctx), "agd_ip2p_clear")
+
     def lora_add(self, key: str, down: torch.Tensor, up: torch.Tensor, alpha: float):
         """Stages one target's fp32 factors (down [r, in], up [out, r]) and a copy of its base matrix; the weights stay at the base."""
         d, u = down.detach().to("cpu", torch.float32).contiguous(), up.detach().to("cpu", torch.float32).contiguous()
@@ -332,8 +357,8 @@ class Engine:
     def unet_forward(self, sample: torch.Tensor, timestep) -> torch.Tensor:
         """`timestep`: a number (one timestep for the batch) or a [B] tensor / sequence (one per image, the training call)."""
         sample = sample.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
-        out = torch.empty_like(sample)
         b2, _, Lh, Lw = sample.shape
+        out = torch.empty(b2, self.cfg.unet.out_channels, Lh, Lw, device=sample.device, dtype=torch.float32)   # an inpainting or ip2p sample is wider
         ts = timestep.detach().flatten().tolist() if torch.is_tensor(timestep) else (list(timestep) if isinstance(timestep, (list, tuple)) else [timestep])
         if len(ts) == 1:
             self._ck(self.lib.agd_unet_forward_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(ts[0]), _lib.ptr(out), self._stream()),
@@ -1016,9 +1041,13 @@ class StableDiffusionPipeline:
                              f"got a {Lh * self.vae_scale_factor} x {Lw * self.vae_scale_factor} generate")
 
     def _refuse_inpainting_unet(self):
-        if self.cfg.unet.in_channels != self.cfg.unet.out_channels:
-            raise ValueError(f"this UNet takes {self.cfg.unet.in_channels} input channels (an inpainting checkpoint): txt2img and img2img need "
-                             f"{self.cfg.unet.out_channels}; use StableDiffusionInpaintPipeline")
+        u = self.cfg.unet
+        if u.in_channels == u.out_channels + self.cfg.vae.latent_channels:
+            raise ValueError(f"this UNet takes {u.in_channels} input channels (an InstructPix2Pix checkpoint): txt2img and img2img need "
+                             f"{u.out_channels}; use StableDiffusionInstructPix2PixPipeline")
+        if u.in_channels != u.out_channels:
+            raise ValueError(f"this UNet takes {u.in_channels} input channels (an inpainting checkpoint): txt2img and img2img need "
+                             f"{u.out_channels}; use StableDiffusionInpaintPipeline")
 
     def _denoise(self, lat, num_inference_steps, guidance_scale):
         """`for t in scheduler.timesteps: unet -> CFG -> scheduler.step`, fused on the device, under the pipeline's scheduler."""

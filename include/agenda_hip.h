@@ -143,6 +143,22 @@ int agd_inpaint_set_hw(agd_ctx* ctx, const float* mask, int mask_channels, const
 int agd_inpaint_set_schedule(agd_ctx* ctx, const float* sa_sb, int n);
 int agd_inpaint_clear(agd_ctx* ctx);
 
+/* ---- InstructPix2Pix (diffusers StableDiffusionInstructPix2PixPipeline).  An 8-channel UNet (in_channels = latent + the VAE's latent
+ * channels) reads latents | image latents.  With a state set, every evaluation of agd_denoise_hw / agd_denoise_plms_hw / agd_denoise_dpm_hw
+ * runs three branches against the [uncond | cond] context of agd_set_context -- uncond: negative prompt, zero image latents; image: negative
+ * prompt, image latents; text: prompt, image latents -- and combines them on the device as
+ *   e = e_uncond + guidance (e_text - e_image) + image_guidance (e_image - e_uncond)
+ * before the scheduler's step; `guidance` of those calls is the text scale.  The recorders see the text branch only.  ControlNet and GLIGEN
+ * schedules, an inpainting state and agd_denoise_panorama are refused while the state is set; without it every loop runs as before. */
+/* the front end, once per call, device pointers: image uint8 NHWC [batch,h,w,3] (image_f32 = 0: x / 255, then 2 x - 1) or fp32 NCHW
+ * [batch,3,h,w] already in [-1,1] (image_f32 = 1).  Runs the VAE encoder and keeps the posterior mean (`latent_dist.mode()`, NOT multiplied
+ * by the scaling factor) on the device; also written to latents_out fp32 NCHW [batch,lc,h/f,w/f] when that is non-NULL.  Ends a state set earlier. */
+int agd_ip2p_prepare_hw(agd_ctx* ctx, const void* image, int image_f32, int batch, int h, int w, float* latents_out, void* stream);
+/* the state: image latents fp32 NCHW [batch,lc,Lh,Lw] (device; copied), or NULL for the ones agd_ip2p_prepare_hw left (same batch and
+ * size).  The next loop must run `batch` images at Lh x Lw. */
+int agd_ip2p_set_hw(agd_ctx* ctx, const float* image_latents, int batch, int latent_h, int latent_w, float image_guidance, void* stream);
+int agd_ip2p_clear(agd_ctx* ctx);
+
 /* ---- GLIGEN (diffusers StableDiffusionGLIGENPipeline, a UNet of attention_type "gated"): a PositionNet turns per-object phrase
  * embeddings and boxes into grounding tokens, and a GatedSelfAttentionDense ("fuser") in every transformer block, after attn1's residual
  * add, attends over the block's rows plus those tokens:  x += tanh(alpha_attn) attn(norm1([x; o]))[:N];  x += tanh(alpha_dense) ff(norm2(x)).
