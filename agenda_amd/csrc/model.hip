@@ -90,6 +90,24 @@ struct Fuser {
   DBuf gkvb;
 };
 
+// agd_set_option("tblock_fuse"): the fused row-panel kernels of the transformer blocks (tblock.hip).  Read by tblock_plan() alone.
+enum : int {
+  TBF_FF            = 1 << 0,    // C = 320: norm3 -> GEGLU -> ff.net.2 + residual in one launch
+  TBF_ATTN2         = 1 << 1,    // C = 320: the attn2 chain, norm2 -> to_q -> attention (+ DAAM record) -> to_out + residual in one launch
+  TBF_ATTN1_OUT     = 1 << 2,    // attn1.to_out + residual in front of the attn2 chain, same launch
+  TBF_FF_PROJ       = 1 << 3,    // proj_out + residual behind the fused feed-forward, same launch
+  TBF_QKV           = 1 << 4,    // C = 320: proj_in -> norm1 -> q / k / v in one launch (the qkv chain)
+  TBF_ATTN2_640     = 1 << 5,    // the attn2 chain for the C = 640 blocks too
+  TBF_LAZY_DUP      = 1 << 6,    // the CFG-shared prefix's duplication inside the fused kernels (no copy launches)
+  TBF_QKV_GN        = 1 << 7,    // the GroupNorm applied inside the qkv chain (no fold launch)
+  TBF_QKV_640       = 1 << 8,    // the qkv chain with the GroupNorm inside for the C = 640 blocks too (off: measured slower than the three launches it replaces)
+  TBF_FF_PREMUL     = 1 << 9,    // ff.net.2 / proj_out pre-multiplied inside the feed-forward launch
+  TBF_ATTN2_ROWS32  = 1 << 10,   // 32-row panels for the C = 640 attn2 chain where 64-row panels would fill half the chip
+  TBF_QKV_ROWS64    = 1 << 11,   // the C = 320 qkv chain on 64-row panels (two co-resident four-wave workgroups per CU)
+  TBF_QKV_SCHED2    = 1 << 12,   // the qkv chain on qkv_chain2_kernel's schedule (same results bit for bit)
+  TBF_DEFAULT       = 0x1fff & ~TBF_QKV_640,   // 7935
+};
+
 struct ProfEv { int cls; double flops, bytes; hipEvent_t a, b; };   // algorithmic flop / HBM bytes of the launch
 
 struct agd_ctx {
@@ -137,9 +155,7 @@ struct agd_ctx {
   int opt_gn_proj_fold = 1;                           // agd_set_option("gn_proj_fold"): the transformers' GroupNorm folded into per-image proj_in matrices (1: C <= 320, 2: C <= 640)
   int opt_p8 = 1;                                     // agd_set_option("igemm8p"): 256-row 8-wave / 8-phase igemm for launches with enough tiles (igemm8p.h)
   int opt_halo = 1;                                   // agd_set_option("conv_halo"): 3x3 stride-1 convs through the row-halo kernel (igemm_halo.h)
-  int opt_tb_fuse = 255 | 512 | 1024 | 2048 | 4096;                 // agd_set_option("tblock_fuse"): fused row-panel kernels of the C = 320 transformer blocks (tblock.hip): bit 0 = feed-forward (bit 3: + proj_out),
-                                                      // bit 1 = attn2 chain (bit 2: + attn1.to_out in front of it), bit 4 = proj_in -> norm1 -> qkv, bit 5 = the attn2 chain for the C = 640 blocks too, bit 6 = the CFG-shared prefix's duplication inside the fused kernels, bit 7 = the GroupNorm applied inside the bit-4 launch (no fold launch), bit 8 (off) = the bit-4 launch with the GroupNorm inside for the C = 640 blocks too, bit 9 = ff.net.2 / proj_out pre-multiplied inside the feed-forward launch, bit 10 = 32-row panels for the C = 640 attn2 chain,
-                                                      // round 6: bit 11 = the bit-4 launch on 64-row panels (two co-resident four-wave workgroups per CU), bit 12 = on qkv_chain2_kernel's schedule for the C = 640 blocks, bit 9 = ff.net.2 / proj_out pre-multiplied inside the feed-forward kernel, bit 10 = 32-row panels for the C = 640 attn2 chain where 64-row panels would fill half the chip
+  int opt_tb_fuse = TBF_DEFAULT;                       // agd_set_option("tblock_fuse"): the TBF_* bits above
   int opt_ups4 = 7; /* see agd_set_option */                                   // agd_set_option("upsample_phases"): the UNet's nearest-2x upsampling convs as four 2x2 phase convs on the un-upsampled map (one launch, 4/9 of the MACs)
   int opt_ffproj = 1;                                 // agd_set_option("ff_proj_fuse"): ff.net.2 and proj_out as ONE GEMM with the pre-multiplied matrix [Wp W2 | Wp] over [hidden | h] (blocks whose feed-forward is not the fused row-panel kernel)
   int opt_sc_fuse = 3;                                // agd_set_option("shortcut_fuse"): a UNet resnet's 1x1 conv_shortcut runs as extra K of its conv2 launch where that is an unsplit row-halo launch
@@ -475,6 +491,13 @@ static int run_attention(agd_ctx* c, hipStream_t st, int cls, AttnP& a) {
   return launch_attention(a, st);
 }
 
+// DAAM's recording rule, for an attn2 call of B2 images (a CFG pair per recorded image) on a qh x qw query map: the recorder is on, the layer
+// is not the mid block's and has accumulators of this map's size, and the images are the ones they were sized for.  factor = sqrt(latent
+// h * w / N) = Lh / qh; recorded iff factor != 8; the conditional half only.
+static inline bool daam_records(const agd_ctx* c, const XLayer& xl, int B2, int qh, int qw) {
+  return c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_Lh / qh != 8 && qh == xl.acc_h && qw == xl.acc_w && B2 / 2 == rec_images(c);
+}
+
 // cross-attention attn2 body shared by the UNet walk and the agd_cross_attn seam
 // qh x qw: the query map (N = qh * qw); the seam passes the square side of its token count
 static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t* q, int B2, int N, int qh, int qw, bf16_t* out, bool record,
@@ -488,17 +511,14 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   a.record_mode = 0; a.mask = mask;
   const int side = qh;                                 // (hook.py mode: square maps only)
   bool hook_call = false;
-  if (record && c->rec_mode == 1 && !xl.mid && xl.acc) {
-    // daam: factor = sqrt(latent h * w / N) = Lh / qh; recorded iff factor != 8 (mid block); conditional half only
-    if (c->rec_Lh / qh != 8 && qh == xl.acc_h && qw == xl.acc_w && B2 / 2 == rec_images(c)) {
-      a.rec_b0 = B2 / 2; a.rec_T = c->rec_T;
-      a.rec_head_stride = (long long)c->rec_T * N; a.rec_img_stride = a.rec_head_stride * xl.acc_heads;
-      a.rec = xl.acc + (size_t)c->rec_base * a.rec_img_stride;
-      if (xl.acc_heads < xl.heads) {                 // latent-resolution layer: head-group sums (attention.hip RECORD 2)
-        if (mask) FAIL("attention_mask together with daam recording at latent resolution is not supported");
-        a.record_mode = 3; a.rec_hpb = xl.heads / xl.acc_heads;
-      } else a.record_mode = 1;
-    }
+  if (record && daam_records(c, xl, B2, qh, qw)) {
+    a.rec_b0 = B2 / 2; a.rec_T = c->rec_T;
+    a.rec_head_stride = (long long)c->rec_T * N; a.rec_img_stride = a.rec_head_stride * xl.acc_heads;
+    a.rec = xl.acc + (size_t)c->rec_base * a.rec_img_stride;
+    if (xl.acc_heads < xl.heads) {                   // latent-resolution layer: head-group sums (attention.hip RECORD 2)
+      if (mask) FAIL("attention_mask together with daam recording at latent resolution is not supported");
+      a.record_mode = 3; a.rec_hpb = xl.heads / xl.acc_heads;
+    } else a.record_mode = 1;
   } else if (record && c->rec_mode == 2 && c->hook_scratch) {
     const int b0 = c->rec_is_train ? 0 : B2 / 2;
     if (B2 - b0 == c->hook_Bp) {
@@ -567,7 +587,6 @@ static int fuser_rows(agd_ctx* c, hipStream_t st, const Fuser& f, bf16_t* h, int
   return last(ff, 4 * C, *w2, o);
 }
 
-// Transformer2DModel with one BasicTransformerBlock
 // the second half of a [2B'] activation := its first half (CFG: both halves saw identical inputs so far)
 static int dup_half(agd_ctx* c, hipStream_t st, bf16_t* p, long long half_elems) {
   ProfScope ps(c, st, PC_ELEM, 0);
@@ -575,289 +594,373 @@ static int dup_half(agd_ctx* c, hipStream_t st, bf16_t* p, long long half_elems)
   return 0;
 }
 
+// Transformer2DModel with one BasicTransformerBlock: transformer() allocates, tblock_plan() decides which form every stage takes,
+// the tb_*() stages launch what the plan says and decide nothing themselves
+enum TbHead  { HEAD_GN,            // GroupNorm pass (or the producing resnet's normalised copy), proj_in GEMM
+               HEAD_FOLD,          // fold launch (the GroupNorm into per-image proj_in matrices), proj_in GEMM on the raw x
+               HEAD_QKV,           // fold launch, then proj_in -> h -> norm1 -> q / k / v in one launch (the qkv chain, tblock.hip)
+               HEAD_QKV_GN };      // the qkv chain alone, applying the GroupNorm itself (C = 320; C = 640 under TBF_QKV_640)
+enum TbDup   { DUP_NONE, DUP_COPY,   // copy launches behind attn1.to_out
+               DUP_LAZY };         // inside the fused kernels (the chain reads input row m % M', the feed-forward's proj_out stage adds block-input row m % M')
+enum TbAttn2 { ATTN2_CHAIN,        // norm2 -> to_q -> attention (+ DAAM record) -> to_out + residual in one launch (tblock.hip)
+               ATTN2_PREMUL,       // the C = 1280 blocks: S GEMM + softmax + recorder, then the output GEMM, against per-image pre-multiplied context matrices (xattn_pre.hip)
+               ATTN2_KERNELS };    // to_q, cross_attention() (the processor seam), to_out
+enum TbFf    { FF_FUSED,           // norm3 (folded) -> GEGLU -> ff.net.2 + residual in one launch, the 4C-wide hidden activation stays in LDS (tblock.hip); proj_out a GEMM
+               FF_FUSED_PROJ,      // ... with proj_out + residual (+ the next GroupNorm's partial sums) behind it, same launch
+               FF_FUSED_PREMUL,    // ... with ff.net.2 and proj_out pre-multiplied (as FF_FFPROJ does for the other blocks): no intermediate h3
+               FF_FFPROJ,          // GEGLU GEMM, then ff.net.2 and proj_out as ONE GEMM (opt "ff_proj_fuse")
+               FF_PLAIN };         // GEGLU, ff.net.2 and proj_out GEMMs
+
+struct TBlockPlan {
+  // LayerNorm folded into the GEMMs around it (opt "ln_fold"): the GEMM that writes h also emits per-row (sum, sum of squares) of its bf16
+  // outputs per N tile; the GEMM that would read LayerNorm(h) reads h itself with W diag(gamma) and finishes  rstd (acc - mean colsum) +
+  // (bias + W beta)  in its epilogue.  The three LayerNorm launches (and their read + write of the activation) per block disappear; h is
+  // still rounded to bf16 exactly once.
+  bool fold;
+  bool x_normed;                   // the producing resnet's slab pass already applied this block's GroupNorm (x.normed)
+  bool gfold;                      // the GroupNorm goes into per-image proj_in matrices: every head but HEAD_GN and C = 640's HEAD_QKV_GN
+  TbHead head; int qkv_rows64, qkv_sched2;      // (QkvChainP::rows64 / sched2)
+  bool attn1_in_chain;             // attn1.to_out + residual run inside the attn2 chain launch, not as a GEMM of their own
+  TbDup dup;
+  const Fuser* fuser;              // GLIGEN: this evaluation runs the block's fuser (between the duplication and attn2)
+  XLayer* xl;                      // the block's attn2 layer (null: not registered -- the attn2 stage refuses)
+  TbAttn2 attn2; int chain_rows32;              // (AttnChainP::rows32)
+  bool daam;                       // attn2 records into the DAAM accumulators (the chain and pre-multiplied forms; cross_attention() asks daam_records() itself)
+  TbFf ff;
+  bool wreg_proj;                  // proj_in / proj_out GEMMs through the weight-streaming kernel (opt "wreg_mask" bit 1)
+  // the GEMM that writes h leaves the row statistics its reader folds a LayerNorm with: proj_in for norm1; attn1.to_out, or the fuser's last
+  // GEMM, for norm2 (the attn2 chain takes its own); attn2's last launch for norm3 (the fused feed-forward takes its own)
+  bool stats_head, stats_attn1, stats_attn2;
+  // Not here, because they shape one launch and choose no path: consume()'s weight-streaming form of the C = 1280 GEGLU (opt "wreg_mask" bit 0,
+  // by M) and the fused feed-forward's partial sums for the next GroupNorm (where `out` has room for them)
+};
+
+static const float kTbLnEps = 1e-5f;
+
+// one block's walk: its inputs, its buffers and where the residual stream stands
+struct TBlock {
+  agd_ctx* c; hipStream_t st; const std::string& pre; const std::string t; const Act& x; Act& out; int heads, groups;
+  int C, HW, Bs, B;                 // Bs: batch of the shared part (B / 2 under dup)
+  const float* gn_g = nullptr; const float* gn_b = nullptr; const WMat* w_in = nullptr; const float* b_in = nullptr;     // norm, proj_in
+  bf16_t* ln = nullptr;             // [M][C] normalised rows: the GroupNorm's output, then the unfolded LayerNorms'
+  bf16_t* h = nullptr; bf16_t* qkv = nullptr; bf16_t* att = nullptr;
+  const bf16_t* xres;               // residual of proj_out
+  int M; const int Mshared;         // rows until the duplication point (Mshared), B * HW after it
+  float* stats = nullptr; int slots = 0;        // row statistics of the current h
+  TBlock(agd_ctx* c_, hipStream_t st_, const std::string& pre_, const Act& x_, Act& out_, int heads_, int groups_, int dup)
+    : c(c_), st(st_), pre(pre_), t(pre_ + "transformer_blocks.0."), x(x_), out(out_), heads(heads_), groups(groups_), C(x_.C), HW(x_.H * x_.W),
+      Bs(x_.B), B(dup ? 2 * x_.B : x_.B), xres(x_.p), M(x_.B * x_.H * x_.W), Mshared(M) {}
+
+  // h = A . W^T (+ bias, + residual), and with want_stats its row statistics
+  // (shaped: launched as [images][H][W] instead of one row of M pixels -- the per-image forms of the epilogue need the image of a row)
+  int produce(const bf16_t* A, int K, const WMat& w, GemmOpt o, bool shaped, bool want_stats) {
+    const int gb_ = shaped ? M / HW : 1, gh_ = shaped ? x.H : 1, gw_ = shaped ? x.W : M;
+    stats = nullptr; slots = 0;
+    if (want_stats) {
+      int cfg[3] = {0, 0, 0}; GemmOpt qo = o; qo.query_cfg = cfg; qo.want_rowstat = 1;
+      CK(run_conv(c, st, A, K, nullptr, 0, gb_, gh_, gw_, w, 1, h, qo, c->zero_page));
+      slots = (w.N + cfg[1] - 1) / cfg[1];
+      stats = (float*)c->arena.alloc((size_t)B * HW * slots * 2 * sizeof(float)); if (!stats) return -1;   // B*HW rows: room for the CFG duplicate
+      o.rowstat_out = stats; o.rowstat_slots = slots;
+    }
+    return run_conv(c, st, A, K, nullptr, 0, gb_, gh_, gw_, w, 1, h, o, c->zero_page);
+  }
+  // outp = LayerNorm(h) . W^T (+ bias) [GEGLU]: folded, or the LayerNorm kernel followed by the plain GEMM
+  int consume(bool fold, const std::string& lnkey, const std::string& wkey, const float* bias, int geglu, bf16_t* outp) {
+    if (fold) {
+      const std::string k = wkey + ".lnfold";
+      GETW(wf, k); GETV(cs, k + ".cs"); GETV(bf, k + ".bias");
+      GemmOpt o; o.bias = bf; o.geglu = geglu; o.ln_stats = stats; o.ln_slots = slots; o.ln_cs = cs; o.ln_invC = 1.0f / (float)C; o.ln_eps = kTbLnEps;
+      if (geglu && C == 1280 && M >= 1024 && M <= 4096 && (c->opt_wreg & 1) && wf->wfrag) o.wreg = 2;
+      return run_conv(c, st, h, C, nullptr, 0, 1, 1, M, *wf, 1, outp, o, c->zero_page);
+    }
+    GETV(g, lnkey + ".weight"); GETV(b, lnkey + ".bias");
+    { ProfScope ps(c, st, PC_LN, 0, 4.0 * M * (double)C); CK(launch_layernorm(h, ln, g, b, M, C, kTbLnEps, st)); }
+    GETW(w, wkey); GemmOpt o; o.bias = bias; o.geglu = geglu;
+    return run_conv(c, st, ln, C, nullptr, 0, 1, 1, M, *w, 1, outp, o, c->zero_page);
+  }
+};
+
 // dup != 0 (first transformer of a CFG forward, agd_denoise only): x holds B' = batch/2 images whose unconditional and
 // conditional rows are still IDENTICAL (same latents, same timestep; the text context enters at attn2).  GroupNorm,
 // proj_in, norm1 and the self-attention run once on B' rows; the result is duplicated right before the first
 // cross-attention and the block returns 2B' rows.  Bit-identical to running both halves (every op here is
 // row- or image-local), at half the cost for the most expensive attention call of the forward.
 // GLIGEN (c->gl_active, a UNet block with a fuser): the fuser runs between attn1's residual add and attn2.  The CFG halves diverge there
-// (the unconditional half sees null objects only), so the shared prefix is duplicated BEFORE the fuser (the copy path: no lazy_dup) and
-// attn1.to_out stays a GEMM of its own (no chain_pre).  norm2's statistics for whatever attn2 path follows come from the fuser's last GEMM
-// (the gated ff.net.2 is a produce() launch: with the LayerNorm fold it emits the row statistics; the chain kernel takes its own).
-// Evaluations without the flag walk exactly the code above and below.
-static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const Act& x, int heads, int groups, Act& out, int dup = 0) {
-  const int Bs = x.B;                                  // batch of the shared part
-  int B = dup ? 2 * x.B : x.B;
-  const int HW = x.H * x.W, C = x.C;
-  int M = Bs * HW;                                     // rows until the duplication point, B*HW after it
-  out = alloc_act(c, B, x.H, x.W, C, true); if (!out.p) return -1;
-  const size_t mk = c->arena.mark();
-  const std::string t = pre + "transformer_blocks.0.";
-  Act n = alloc_act(c, B, x.H, x.W, C); if (!n.p) return -1;
-  GETV(gg, pre + "norm.weight"); GETV(gb, pre + "norm.bias");
+// (the unconditional half sees null objects only), so the shared prefix is duplicated BEFORE the fuser (DUP_COPY) and attn1.to_out stays a
+// GEMM of its own.  norm2's statistics for whatever attn2 form follows come from the fuser's last GEMM (the gated ff.net.2 is a produce()
+// launch).  Evaluations without the flag take the same plan as a model without fusers.
+static TBlockPlan tblock_plan(const TBlock& s, int dup) {
+  agd_ctx* c = s.c; const Act& x = s.x; const std::string& pre = s.pre; const std::string& t = s.t;
+  const int C = s.C, HW = s.HW, heads = s.heads, groups = s.groups;
+  auto tb = [c](int bit) { return (c->opt_tb_fuse & bit) != 0; };
+  auto has = [c](const std::string& key) { return c->W.count(key) != 0; };
+  TBlockPlan p{};
+  p.fold = c->opt_ln_fold == 1 || (c->opt_ln_fold == 2 && C <= 320) || (c->opt_ln_fold == 3 && C <= 640);
+  p.x_normed = x.normed && x.normed_gamma == s.gn_g;
+  p.wreg_proj = C == 640 && (c->opt_wreg & 2);
+  // --- head ---
   // The transformer's GroupNorm has no activation behind it: where the producer of x left its per-tile channel sums, the norm is folded
   // into per-image proj_in matrices (norm.hip gn_fold_weight_kernel) and proj_in reads the raw x -- no read + write of the activation by
   // a GroupNorm kernel.  Default C <= 320 (the 64 x 64 maps: the fold launch takes 8.5 us against the 17 us apply pass; in situ 522.4 -> 521.3 ms
   // per batch, tools/ab_option.py); at C = 640 the fold (16.8 us, 6.5 MB of matrices) costs more than the 10.8 us pass it replaces.
-  const bool gfold = c->opt_gn_proj_fold && c->opt_gn_fused && C <= (c->opt_gn_proj_fold >= 2 ? 640 : 320) && x.cpart && x.cpart_bm > 0 && HW % 128 == 0 && HW % x.cpart_bm == 0;
-  // C = 640 (the 32 x 32 maps): no fold, but the qkv chain kernel (tblock.hip) takes the raw rows and applies the GroupNorm itself -- the apply launch disappears
-  // (bit 8, default off: measured 71 us against 65 for the three launches it replaces -- 128 workgroups each streaming 3.3 MB of weights)
-  const bool qkv640 = !gfold && C == 640 && (c->opt_tb_fuse & 16) && (c->opt_tb_fuse & 256) && (c->opt_tb_fuse & 128) && c->opt_gn_fused && x.cpart && x.cpart_bm > 0 &&
-                      HW % 64 == 0 && HW % x.cpart_bm == 0 && groups <= 32 && !(x.normed && x.normed_gamma == gg) && !dup &&
-                      c->W.count(pre + "proj_in.frag") && c->W.count(t + "attn1.qkv.frag");
-  if (!gfold && !qkv640) {
-    if (x.normed && x.normed_gamma == gg) n.p = x.normed;          // the producing resnet's slab pass already applied this norm
-    else CK(run_gn(c, st, x.p, C, nullptr, 0, Bs, HW, gg, gb, groups, 1e-6f, 0, n.p, &x));
-  }
-  Act h = alloc_act(c, B, x.H, x.W, C); if (!h.p) return -1;
-  Act ln = n;  // reuse (only the unfolded path normalises into it)
-  bf16_t* qkv = (bf16_t*)c->arena.alloc((size_t)B * HW * 3 * C * 2); if (!qkv) return -1;
-  bf16_t* att = (bf16_t*)c->arena.alloc((size_t)B * HW * C * 2); if (!att) return -1;
-  const bf16_t* xres = x.p;                            // residual of proj_out
-  // LayerNorm folded into the GEMMs around it (opt "ln_fold"): the GEMM that writes h also emits per-row (sum, sum of
-  // squares) of its bf16 outputs per N tile; the GEMM that would read LayerNorm(h) reads h itself with W diag(gamma) and
-  // finishes  rstd (acc - mean colsum) + (bias + W beta)  in its epilogue.  The three LayerNorm launches (and their
-  // read + write of the activation) per block disappear; h is still rounded to bf16 exactly once.
-  const bool fold = c->opt_ln_fold == 1 || (c->opt_ln_fold == 2 && C <= 320) || (c->opt_ln_fold == 3 && C <= 640);
-  const float lneps = 1e-5f;
-  float* stats = nullptr; int slots = 0;               // row statistics of the current h
-  // h_out = A . W^T (+ bias, + residual): writes h and, when folding, its row statistics
-  // (shaped: launched as [images][H][W] instead of one row of M pixels -- the per-image forms of the epilogue need the image of a row)
-  auto produce = [&](const bf16_t* A, int K, const WMat& w, GemmOpt o, bf16_t* hout, bool shaped = false, bool want_stats = true) -> int {
-    const int gb_ = shaped ? M / HW : 1, gh_ = shaped ? x.H : 1, gw_ = shaped ? x.W : M;
-    stats = nullptr; slots = 0;
-    if (fold && want_stats) {
-      int cfg[3] = {0, 0, 0}; GemmOpt qo = o; qo.query_cfg = cfg; qo.want_rowstat = 1;
-      CK(run_conv(c, st, A, K, nullptr, 0, gb_, gh_, gw_, w, 1, hout, qo, c->zero_page));
-      slots = (w.N + cfg[1] - 1) / cfg[1];
-      stats = (float*)c->arena.alloc((size_t)B * HW * slots * 2 * sizeof(float)); if (!stats) return -1;   // B*HW rows: room for the CFG duplicate
-      o.rowstat_out = stats; o.rowstat_slots = slots;
-    }
-    return run_conv(c, st, A, K, nullptr, 0, gb_, gh_, gw_, w, 1, hout, o, c->zero_page);
-  };
-  // out = LayerNorm(h) . W^T (+ bias) [GEGLU]: folded, or the LayerNorm kernel followed by the plain GEMM
-  auto consume = [&](const std::string& lnkey, const std::string& wkey, const float* bias, int geglu, bf16_t* outp) -> int {
-    if (fold) {
-      const std::string k = wkey + ".lnfold";
-      GETW(wf, k); GETV(cs, k + ".cs"); GETV(bf, k + ".bias");
-      GemmOpt o; o.bias = bf; o.geglu = geglu; o.ln_stats = stats; o.ln_slots = slots; o.ln_cs = cs; o.ln_invC = 1.0f / (float)C; o.ln_eps = lneps;
-      if (geglu && C == 1280 && M >= 1024 && M <= 4096 && (c->opt_wreg & 1) && wf->wfrag) o.wreg = 2;
-      return run_conv(c, st, h.p, C, nullptr, 0, 1, 1, M, *wf, 1, outp, o, c->zero_page);
-    }
-    GETV(g, lnkey + ".weight"); GETV(b, lnkey + ".bias");
-    { ProfScope ps(c, st, PC_LN, 0, 4.0 * M * (double)C); CK(launch_layernorm(h.p, ln.p, g, b, M, C, lneps, st)); }
-    GETW(w, wkey); GemmOpt o; o.bias = bias; o.geglu = geglu;
-    return run_conv(c, st, ln.p, C, nullptr, 0, 1, 1, M, *w, 1, outp, o, c->zero_page);
-  };
-  bool qkv_done = false;
-  { GETW(w, pre + "proj_in.weight"); GETV(b, pre + "proj_in.bias");
-    if (gfold) {
-      if (w->taps != 1 || w->Cpad != C) FAIL("gn_proj_fold: proj_in weight [N=%d taps=%d Cpad=%d] is not a 1x1 over %d channels", w->N, w->taps, w->Cpad, C);
-      const bool qkv_fuse = (c->opt_tb_fuse & 16) && C == 320 && w->N == C && c->W.count(t + "attn1.qkv.frag");
-      // bit 7: the qkv chain kernel applies the GroupNorm itself (statistics from the partial sums, rows normalised in its LDS panel): no fold launch
-      const bool gn_inside = qkv_fuse && (c->opt_tb_fuse & 128) && groups <= 32 && c->W.count(pre + "proj_in.frag");
-      bf16_t* wb = nullptr; float* radd = nullptr;
-      if (!gn_inside) {
-        wb = (bf16_t*)c->arena.alloc((size_t)Bs * w->N * C * 2);
-        radd = (float*)c->arena.alloc((size_t)Bs * w->N * sizeof(float));
-        if (!wb || !radd) return -1;
-        ProfScope ps(c, st, PC_GN, 0, 2.0 * Bs * (double)w->N * C * 2);
-        CK(launch_gn_fold_weight(x.cpart, x.cpart_bm, Bs, HW, C, groups, 1e-6f, gg, gb, w->w, b, w->N, wb, radd, st, qkv_fuse ? C / 64 : 0));
-      }
-      if (qkv_fuse) {      // proj_in -> h -> norm1 -> q / k / v in one launch (tblock.hip); norm1's statistics come from the rows themselves
-        GETW(fqkv, t + "attn1.qkv.frag"); GETV(g1, t + "norm1.weight"); GETV(b1_, t + "norm1.bias");
-        QkvChainP qp{}; qp.x = x.p; qp.wbf = wb; qp.wb_stride = (long long)w->N * C; qp.rowadd = radd; qp.rowadd_stride = C; qp.h = h.p; qp.gamma = g1; qp.beta = b1_; qp.ln_eps = lneps;
-        qp.wqkvf = fqkv->w; qp.qkv = qkv; qp.M = M; qp.HW = HW;
-        qp.rows64 = (c->opt_tb_fuse & 2048) && HW % 64 == 0 ? 1 : 0;
-        qp.sched2 = (c->opt_tb_fuse & 4096) ? 1 : 0;
-        if (gn_inside) {
-          GETW(fpi, pre + "proj_in.frag");
-          if (!b) FAIL("proj_in without bias");
-          qp.wbf = fpi->w; qp.wb_stride = 0; qp.rowadd = b; qp.rowadd_stride = 0;
-          qp.gn_part = x.cpart; qp.gn_bm = x.cpart_bm; qp.gn_groups = groups; qp.gn_eps = 1e-6f; qp.gn_gamma = gg; qp.gn_beta = gb;
-        }
-        stats = nullptr; slots = 0;
-        ProfScope ps(c, st, PC_GEMM, 8.0 * M * (double)C * C, 2.0 * M * (double)C * 5.0 + 2.0 * (Bs + 3.0) * C * (double)C);
-        CK(launch_qkv_chain(qp, C, st));
-        qkv_done = true;
-      } else {
-      WMat wi = *w; wi.w = wb;
-      GemmOpt o; o.rowadd = radd; o.rowadd_ld = w->N; o.w_per_image = 1;
-      CK(produce(x.p, C, wi, o, h.p, true));
-      }
-    } else if (qkv640) {
-      if (w->taps != 1 || w->Cpad != C || w->N != C || !b) FAIL("qkv chain: proj_in weight [N=%d taps=%d Cpad=%d] is not a biased 1x1 over %d channels", w->N, w->taps, w->Cpad, C);
-      GETW(fpi, pre + "proj_in.frag"); GETW(fqkv, t + "attn1.qkv.frag"); GETV(g1, t + "norm1.weight"); GETV(b1_, t + "norm1.bias");
-      QkvChainP qp{}; qp.x = x.p; qp.wbf = fpi->w; qp.wb_stride = 0; qp.rowadd = b; qp.rowadd_stride = 0; qp.h = h.p; qp.gamma = g1; qp.beta = b1_; qp.ln_eps = lneps;
-      qp.wqkvf = fqkv->w; qp.qkv = qkv; qp.M = M; qp.HW = HW;
-      qp.gn_part = x.cpart; qp.gn_bm = x.cpart_bm; qp.gn_groups = groups; qp.gn_eps = 1e-6f; qp.gn_gamma = gg; qp.gn_beta = gb;
-      qp.sched2 = (c->opt_tb_fuse & 4096) ? 1 : 0;
-      stats = nullptr; slots = 0;
-      ProfScope ps(c, st, PC_GEMM, 8.0 * M * (double)C * C, 2.0 * M * (double)C * 5.0 + 2.0 * 4.0 * C * (double)C);
-      CK(launch_qkv_chain(qp, C, st));
-      qkv_done = true;
-    } else {
-      GemmOpt o; o.bias = b;
-      if (C == 640 && (c->opt_wreg & 2)) o.wreg = 1;
-      CK(produce(n.p, C, *w, o, h.p));
-    }
-  }
-  // fused row-panel kernels of this block (tblock.hip), where their shape is built: C = 320, 8 heads, <= 96 keys, whole 128-row tiles per
-  // image; the hook.py recorder (per-head maps of every call) keeps the kernel chain
-  const bool ff_fused = (c->opt_tb_fuse & 1) && fold && C == 320 && c->W.count(t + "ff.w1.frag");
-  bool xpre_ready = false;                               // the pre-multiplied attn2 form is ready for this block (agd_set_context built its products)
-  bool xpre_rec = false;                                 // ... and it records into the DAAM accumulators (daam's rule, as cross_attention())
-  { auto itx = c->xl_idx.find(t + "attn2");              // the ONE predicate of that form: the chain kernel steps aside exactly where it holds
-    if (itx != c->xl_idx.end()) {
-      const XLayer& xq = c->xl[itx->second];
-      xpre_rec = c->rec_mode == 1 && !xq.mid && xq.acc && c->rec_Lh / x.H != 8 && x.H == xq.acc_h && x.W == xq.acc_w && B / 2 == rec_images(c);
-      xpre_ready = xq.pm_ready && c->opt_xpre && fold && HW % 64 == 0 && c->rec_mode != 2 && c->ctx_T <= XATTN_TP && !dup && (!xpre_rec || xq.acc_heads == xq.heads);
-    } }
-  const bool chain_fuse = (c->opt_tb_fuse & 2) && (C == 320 || (C == 640 && (c->opt_tb_fuse & 32))) && heads == 8 && HW % (C == 320 ? 128 : 64) == 0 && c->ctx_T <= 96 &&
-                          c->rec_mode != 2 && c->W.count(t + "attn2.to_q.frag") && !xpre_ready;
-  // CFG-shared prefix with the fused kernels behind it: the duplication of the B' rows happens INSIDE them (the chain reads input row m % M', the feed-forward's
-  // proj_out stage adds block-input row m % M'): no copy launches, and attn1.to_out joins the chain here too
-  const Fuser* fu = nullptr;                             // GLIGEN: this evaluation runs the block's fuser
-  if (c->gl_active) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) fu = &c->gl_f[itf->second]; }
-  const bool lazy_dup = dup && (c->opt_tb_fuse & 64) && chain_fuse && C == 320 && ff_fused && (c->opt_tb_fuse & 8) && c->W.count(pre + "proj_out.frag") && !fu;
-  const bool chain_pre = chain_fuse && (c->opt_tb_fuse & 4) && (!dup || lazy_dup) && c->W.count(t + "attn1.to_out.frag") && !fu;     // attn1.to_out + residual inside the chain launch
-  // --- self attention ---
-  { if (!qkv_done) CK(consume(t + "norm1", t + "attn1.qkv", nullptr, 0, qkv));
-    AttnP a{}; a.q = qkv; a.k = qkv + C; a.v = qkv + 2 * C; a.o = att;
-    a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.sq = a.sk = a.sv = (long long)HW * 3 * C; a.so = (long long)HW * C;
-    a.B = Bs; a.H = heads; a.D = C / heads; a.Nq = HW; a.Nk = HW; a.scale = 1.0f / sqrtf((float)(C / heads));
-    CK(run_attention(c, st, PC_ATTN_SELF, a));
-    GETW(wo, t + "attn1.to_out.0.weight"); GETV(bo, t + "attn1.to_out.0.bias");
-    GemmOpt oo; oo.bias = bo; oo.residual = h.p;
-    // (the fused attn2 chain takes norm2's statistics from the rows themselves; with bit 2 it also starts at this very GEMM)
-    if (!chain_pre) CK(produce(att, C, *wo, oo, h.p, false, !chain_fuse)); }
-  const int Mshared = M;                               // rows of the shared part
-  if (dup && lazy_dup) M = B * HW;
-  else if (dup) {                                      // the halves diverge from here on (text context)
-    CK(dup_half(c, st, h.p, (long long)M * C));
-    if (fold && stats) { ProfScope ps(c, st, PC_ELEM, 0);
-      if (hipMemcpyAsync(stats + (size_t)M * slots * 2, stats, (size_t)M * slots * 2 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup stats copy failed"); }
-    Act x2 = alloc_act(c, B, x.H, x.W, C); if (!x2.p) return -1;
-    { ProfScope ps(c, st, PC_ELEM, 0);
-      if (hipMemcpyAsync(x2.p, x.p, (size_t)M * C * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup copy failed"); }
-    CK(dup_half(c, st, x2.p, (long long)M * C));
-    xres = x2.p;
-    M = B * HW;
-  }
-  if (fu) CK(fuser_rows(c, st, *fu, h.p, B, HW, qkv, att, [&](const bf16_t* A, int K, const WMat& w, const GemmOpt& o) { return produce(A, K, w, o, h.p, false, !chain_fuse); }));
-  // --- cross attention (the processor seam) ---
-  bool chain_done = false;
-  { auto it = c->xl_idx.find(t + "attn2");
-    if (it == c->xl_idx.end()) FAIL("cross-attn layer %s not registered", (t + "attn2").c_str());
-    if (c->ctx_B2 != B) FAIL("context batch %d != unet batch %d (call agd_set_context)", c->ctx_B2, B);
-    XLayer& xl = c->xl[it->second];
-    // one launch for norm2 -> to_q -> attention (+ DAAM record) -> to_out + residual (tblock.hip)
-    if (chain_fuse) {
-      GETW(fq, t + "attn2.to_q.frag"); GETW(fo, t + "attn2.to_out.frag");
-      GETV(g2, t + "norm2.weight"); GETV(b2_, t + "norm2.bias"); GETV(bo, t + "attn2.to_out.0.bias");
-      const int T = c->ctx_T, D = C / heads;
-      AttnChainP ap{}; ap.h = h.p; ap.out = h.p; ap.gamma = g2; ap.beta = b2_; ap.ln_eps = lneps; ap.wqf = fq->w; ap.wof = fo->w; ap.bo = bo;
-      ap.kv = xl.kv; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)D);
-      double rec_bytes = 0;
-      if (c->rec_mode == 1 && !xl.mid && xl.acc && c->rec_Lh / x.H != 8 && x.H == xl.acc_h && x.W == xl.acc_w && B / 2 == rec_images(c)) {   // daam's rule, as cross_attention()
-        ap.record = 1; ap.rec_b0 = B / 2; ap.rec_T = c->rec_T; ap.rec_hpb = heads / xl.acc_heads;
-        ap.rec_head_stride = (long long)c->rec_T * HW; ap.rec_img_stride = ap.rec_head_stride * xl.acc_heads;
-        ap.rec = xl.acc + (size_t)c->rec_base * ap.rec_img_stride;
-        rec_bytes = 8.0 * (B - ap.rec_b0) * xl.acc_heads * (double)c->rec_T * HW;
-      }
-      if (chain_pre) {                                   // h1 = attn1.to_out(att) + h is computed (and stored) by the chain itself: into a second buffer
-        GETW(f1o, t + "attn1.to_out.frag"); GETV(bo1, t + "attn1.to_out.0.bias");
-        bf16_t* h2 = (bf16_t*)c->arena.alloc((size_t)M * C * 2); if (!h2) return -1;
-        ap.o1 = att; ap.wo1f = f1o->w; ap.bo1 = bo1; ap.out = h2;
-      } else if (lazy_dup) { bf16_t* h2 = (bf16_t*)c->arena.alloc((size_t)M * C * 2); if (!h2) return -1; ap.out = h2; }
-      if (lazy_dup) ap.src_rows = Mshared;
-      ap.rows32 = (c->opt_tb_fuse & 1024) ? 1 : 0;       // bit 10: 32-row panels for the C = 640 chain where 64-row panels fill half the chip
-      if (fold && !ff_fused) {                           // the GEGLU consumer of the LayerNorm fold reads one slot of row statistics
-        slots = 1; stats = (float*)c->arena.alloc((size_t)M * 2 * sizeof(float)); if (!stats) return -1;
-        ap.rowstat_out = stats;
-      }
-      ProfScope ps(c, st, PC_ATTN_CROSS, (chain_pre ? 6.0 : 4.0) * M * (double)C * C + 4.0 * B * heads * (double)HW * T * D,
-                   (chain_pre ? 6.0 : 4.0) * M * (double)C + (chain_pre ? 6.0 : 4.0) * C * (double)C + 4.0 * B * (double)T * C + rec_bytes);
-      CK(launch_attn_chain(ap, C, heads, st));
-      if (ap.out != ap.h) h.p = ap.out;                  // the residual stream continues in the second buffer
-      chain_done = true;
-    }
-  }
-  // attn2 of the C = 1280 blocks against the per-image pre-multiplied context matrices (xattn_pre.hip): S GEMM + softmax + recorder, then the output GEMM
-  // with per-image weights -- two launches instead of to_q, the attention kernel and to_out; the hook.py recorder (per-call head means) keeps the kernel chain
-  bool xpre_done = false;
-  if (!chain_done) {
-    auto it = c->xl_idx.find(t + "attn2"); XLayer& xl = c->xl[it->second];
-    const bool rec_daam = xpre_rec;
-    if (xpre_ready && stats && slots > 0) {               // (norm2's row statistics come from attn1.to_out's epilogue: the chain kernel was not chosen, so it wrote them)
-      GETV(bo, t + "attn2.to_out.0.bias");
-      const int HT = heads * XATTN_TP;
-      bf16_t* P = (bf16_t*)c->arena.alloc((size_t)M * HT * 2); if (!P) return -1;
-      XattnSP sp{}; sp.x = h.p; sp.ln_stats = stats; sp.ln_slots = slots; sp.ln_invC = 1.0f / (float)C; sp.ln_eps = lneps;
-      sp.kpp = xl.pm_kpp; sp.kcs = xl.pm_kcs; sp.kbs = xl.pm_kbs; sp.P = P; sp.M = M; sp.HW = HW; sp.C = C; sp.H = heads; sp.T = c->ctx_T;
-      double rec_bytes = 0;
-      if (rec_daam) {
-        sp.rec_b0 = B / 2; sp.rec_T = c->rec_T; sp.rec_head_stride = (long long)c->rec_T * HW; sp.rec_img_stride = sp.rec_head_stride * xl.acc_heads;
-        sp.rec = xl.acc + (size_t)c->rec_base * sp.rec_img_stride;
-        rec_bytes = 8.0 * (B - sp.rec_b0) * heads * (double)c->rec_T * HW;
-      }
-      { ProfScope ps(c, st, PC_ATTN_CROSS, 2.0 * M * (double)HT * C, 2.0 * M * (double)C + 2.0 * B * (double)HT * C + 2.0 * M * (double)HT + rec_bytes);
-        CK(launch_xattn_s(sp, st)); }
-      WMat wv; wv.w = xl.pm_vpp; wv.N = C; wv.Cin = HT; wv.Cpad = HT; wv.taps = 1;
-      GemmOpt oo; oo.bias = bo; oo.residual = h.p; oo.w_per_image = 1;
-      CK(produce(P, HT, wv, oo, h.p, true, !ff_fused));
-      xpre_done = true;
-    }
-  }
-  if (!chain_done && !xpre_done)
-  { bf16_t* q = qkv;
-    CK(consume(t + "norm2", t + "attn2.to_q.weight", nullptr, 0, q));
-    auto it = c->xl_idx.find(t + "attn2");
-    CK(cross_attention(c, st, c->xl[it->second], q, B, HW, x.H, x.W, att, true));
-    GETW(wo, t + "attn2.to_out.0.weight"); GETV(bo, t + "attn2.to_out.0.bias");
-    GemmOpt oo; oo.bias = bo; oo.residual = h.p;
-    CK(produce(att, C, *wo, oo, h.p, false, !ff_fused)); }
-  // --- GEGLU feed-forward ---
-  bool proj_done = false;
+  const bool sums = c->opt_gn_fused && x.cpart && x.cpart_bm > 0 && HW % x.cpart_bm == 0;
+  p.gfold = c->opt_gn_proj_fold && sums && C <= (c->opt_gn_proj_fold >= 2 ? 640 : 320) && HW % 128 == 0;
+  if (p.gfold) {
+    const bool qkv = tb(TBF_QKV) && C == 320 && s.w_in->N == C && has(t + "attn1.qkv.frag");
+    // the chain takes the GroupNorm's statistics from the partial sums and normalises the rows in its LDS panel: no fold launch either
+    const bool gn_inside = qkv && tb(TBF_QKV_GN) && groups <= 32 && has(pre + "proj_in.frag");
+    p.head = gn_inside ? HEAD_QKV_GN : qkv ? HEAD_QKV : HEAD_FOLD;
+    p.qkv_rows64 = qkv && tb(TBF_QKV_ROWS64) && HW % 64 == 0;
+  } else if (C == 640 && tb(TBF_QKV) && tb(TBF_QKV_640) && tb(TBF_QKV_GN) && sums && HW % 64 == 0 && groups <= 32 && !p.x_normed && !dup &&
+             has(pre + "proj_in.frag") && has(t + "attn1.qkv.frag")) {
+    // C = 640 (the 32 x 32 maps): no fold, the chain takes the raw rows (measured 71 us against 65 for the three launches it replaces --
+    // 128 workgroups each streaming 3.3 MB of weights)
+    p.head = HEAD_QKV_GN;
+  } else p.head = HEAD_GN;
+  p.qkv_sched2 = tb(TBF_QKV_SCHED2);
+  // --- feed-forward: the row-panel kernel where its shape is built (C = 320) ---
+  const bool ff_fused = tb(TBF_FF) && p.fold && C == 320 && has(t + "ff.w1.frag");
   if (ff_fused) {
-    // one launch: norm3 (folded) -> GEGLU -> ff.net.2 + residual; the 4C-wide hidden activation stays in LDS (tblock.hip)
-    GETW(f1, t + "ff.w1.frag"); GETW(f2, t + "ff.w2.frag");
-    const std::string k = t + "ff.net.0.proj.weight.lnfold";
-    GETV(cs, k + ".cs"); GETV(bf, k + ".bias"); GETV(b2, t + "ff.net.2.bias");
-    FFusedP fp{}; fp.h = h.p; fp.out = h.p; fp.w1f = f1->w; fp.cs1 = cs; fp.b1 = bf; fp.w2f = f2->w; fp.b2 = b2; fp.M = M; fp.ln_eps = lneps;
-    if ((c->opt_tb_fuse & 8) && c->W.count(pre + "proj_out.frag")) {      // proj_out + residual (+ the next GroupNorm's partial sums) behind it, same launch
-      GETW(fpw, pre + "proj_out.frag"); GETV(bp, pre + "proj_out.bias");
-      fp.wpf = fpw->w; fp.bp = bp; fp.xres = xres; fp.pout = out.p;
-      if ((c->opt_tb_fuse & 512) && c->W.count(t + "ff.w2p.frag")) {      // ff.net.2 and proj_out pre-multiplied (as ff_proj_fuse does for the other blocks): no intermediate h3
-        GETW(f2p, t + "ff.w2p.frag"); GETV(bcp, pre + "ffproj.bias");
-        fp.w2f = f2p->w; fp.bp = bcp; fp.premul = 1;
-      }
-      if (lazy_dup) fp.xres_rows = Mshared;             // xres is still the B'-row block input
-      out.cpart_bm = 0;
-      if (out.cpart && c->opt_gn_fused && HW % 128 == 0) { fp.colstat = out.cpart; out.cpart_bm = 128; }
-      proj_done = true;
+    const bool proj = tb(TBF_FF_PROJ) && has(pre + "proj_out.frag");
+    p.ff = !proj ? FF_FUSED : tb(TBF_FF_PREMUL) && has(t + "ff.w2p.frag") ? FF_FUSED_PREMUL : FF_FUSED_PROJ;
+  } else p.ff = c->opt_ffproj && has(pre + "ffproj.weight") ? FF_FFPROJ : FF_PLAIN;
+  // --- attn2: the pre-multiplied form where agd_set_context built its products; the chain steps aside exactly there.  The chain's shape: 8 heads,
+  // <= 96 keys, whole 128-row (C = 640: 64-row) tiles per image.  The hook.py recorder (per-head maps of every call) keeps the kernels. ---
+  auto itx = c->xl_idx.find(t + "attn2");
+  p.xl = itx == c->xl_idx.end() ? nullptr : &c->xl[itx->second];
+  p.daam = p.xl && daam_records(c, *p.xl, s.B, x.H, x.W);
+  const bool premul = p.xl && p.xl->pm_ready && c->opt_xpre && p.fold && HW % 64 == 0 && c->rec_mode != 2 && c->ctx_T <= XATTN_TP && !dup &&
+                      (!p.daam || p.xl->acc_heads == p.xl->heads);
+  const bool chain = !premul && tb(TBF_ATTN2) && (C == 320 || (C == 640 && tb(TBF_ATTN2_640))) && heads == 8 && HW % (C == 320 ? 128 : 64) == 0 &&
+                     c->ctx_T <= 96 && c->rec_mode != 2 && has(t + "attn2.to_q.frag");
+  p.attn2 = premul ? ATTN2_PREMUL : chain ? ATTN2_CHAIN : ATTN2_KERNELS;
+  p.chain_rows32 = tb(TBF_ATTN2_ROWS32);
+  // --- between them: the duplication of the CFG-shared prefix, the fuser, and where attn1.to_out runs ---
+  if (c->gl_active) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) p.fuser = &c->gl_f[itf->second]; }
+  const bool lazy = dup && tb(TBF_LAZY_DUP) && chain && C == 320 && (p.ff == FF_FUSED_PROJ || p.ff == FF_FUSED_PREMUL) && !p.fuser;
+  p.dup = !dup ? DUP_NONE : lazy ? DUP_LAZY : DUP_COPY;
+  p.attn1_in_chain = chain && tb(TBF_ATTN1_OUT) && p.dup != DUP_COPY && has(t + "attn1.to_out.frag") && !p.fuser;
+  p.stats_head = p.fold; p.stats_attn1 = p.fold && !chain; p.stats_attn2 = p.fold && !ff_fused;
+  return p;
+}
+
+// launch parameters of the qkv chain; wb / radd: the fold launch's per-image matrices and rows (HEAD_QKV)
+static int qkv_chain_params(const TBlock& s, const TBlockPlan& p, const bf16_t* wb, const float* radd, QkvChainP& qp) {
+  agd_ctx* c = s.c; const Act& x = s.x; const int C = s.C;
+  GETW(fqkv, s.t + "attn1.qkv.frag"); GETV(g1, s.t + "norm1.weight"); GETV(b1, s.t + "norm1.bias");
+  qp.x = x.p; qp.wbf = wb; qp.wb_stride = (long long)s.w_in->N * C; qp.rowadd = radd; qp.rowadd_stride = C; qp.h = s.h; qp.gamma = g1; qp.beta = b1; qp.ln_eps = kTbLnEps;
+  qp.wqkvf = fqkv->w; qp.qkv = s.qkv; qp.M = s.M; qp.HW = s.HW; qp.rows64 = p.qkv_rows64; qp.sched2 = p.qkv_sched2;
+  if (p.head == HEAD_QKV_GN) {
+    GETW(fpi, s.pre + "proj_in.frag");
+    if (!s.b_in) FAIL("proj_in without bias");
+    qp.wbf = fpi->w; qp.wb_stride = 0; qp.rowadd = s.b_in; qp.rowadd_stride = 0;
+    qp.gn_part = x.cpart; qp.gn_bm = x.cpart_bm; qp.gn_groups = s.groups; qp.gn_eps = 1e-6f; qp.gn_gamma = s.gn_g; qp.gn_beta = s.gn_b;
+  }
+  return 0;
+}
+
+// GroupNorm + proj_in -> h (HEAD_QKV / HEAD_QKV_GN: + norm1 and attn1's q / k / v)
+static int tb_head(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; hipStream_t st = s.st; const Act& x = s.x; const WMat* w = s.w_in; const int C = s.C;
+  if (p.head == HEAD_GN) {
+    if (p.x_normed) s.ln = x.normed;
+    else CK(run_gn(c, st, x.p, C, nullptr, 0, s.Bs, s.HW, s.gn_g, s.gn_b, s.groups, 1e-6f, 0, s.ln, &x));
+    GemmOpt o; o.bias = s.b_in;
+    if (p.wreg_proj) o.wreg = 1;
+    return s.produce(s.ln, C, *w, o, false, p.stats_head);
+  }
+  if (p.gfold) { if (w->taps != 1 || w->Cpad != C) FAIL("gn_proj_fold: proj_in weight [N=%d taps=%d Cpad=%d] is not a 1x1 over %d channels", w->N, w->taps, w->Cpad, C); }
+  else if (w->taps != 1 || w->Cpad != C || w->N != C || !s.b_in) FAIL("qkv chain: proj_in weight [N=%d taps=%d Cpad=%d] is not a biased 1x1 over %d channels", w->N, w->taps, w->Cpad, C);
+  bf16_t* wb = nullptr; float* radd = nullptr;
+  if (p.head != HEAD_QKV_GN) {
+    wb = (bf16_t*)c->arena.alloc((size_t)s.Bs * w->N * C * 2);
+    radd = (float*)c->arena.alloc((size_t)s.Bs * w->N * sizeof(float));
+    if (!wb || !radd) return -1;
+    ProfScope ps(c, st, PC_GN, 0, 2.0 * s.Bs * (double)w->N * C * 2);
+    CK(launch_gn_fold_weight(x.cpart, x.cpart_bm, s.Bs, s.HW, C, s.groups, 1e-6f, s.gn_g, s.gn_b, w->w, s.b_in, w->N, wb, radd, st, p.head == HEAD_QKV ? C / 64 : 0));
+  }
+  if (p.head == HEAD_FOLD) {
+    WMat wi = *w; wi.w = wb;
+    GemmOpt o; o.rowadd = radd; o.rowadd_ld = w->N; o.w_per_image = 1;
+    return s.produce(x.p, C, wi, o, true, p.stats_head);
+  }
+  QkvChainP qp{}; CK(qkv_chain_params(s, p, wb, radd, qp));
+  s.stats = nullptr; s.slots = 0;                        // norm1's statistics come from the rows themselves
+  ProfScope ps(c, st, PC_GEMM, 8.0 * s.M * (double)C * C, 2.0 * s.M * (double)C * 5.0 + 2.0 * (p.gfold ? s.Bs + 3.0 : 4.0) * C * (double)C);
+  return launch_qkv_chain(qp, C, st);
+}
+
+static int tb_self_attention(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; const std::string& t = s.t; const int C = s.C, HW = s.HW, D = C / s.heads;
+  if (p.head == HEAD_GN || p.head == HEAD_FOLD) CK(s.consume(p.fold, t + "norm1", t + "attn1.qkv", nullptr, 0, s.qkv));
+  AttnP a{}; a.q = s.qkv; a.k = s.qkv + C; a.v = s.qkv + 2 * C; a.o = s.att;
+  a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.sq = a.sk = a.sv = (long long)HW * 3 * C; a.so = (long long)HW * C;
+  a.B = s.Bs; a.H = s.heads; a.D = D; a.Nq = HW; a.Nk = HW; a.scale = 1.0f / sqrtf((float)D);
+  CK(run_attention(c, s.st, PC_ATTN_SELF, a));
+  if (p.attn1_in_chain) return 0;
+  GETW(wo, t + "attn1.to_out.0.weight"); GETV(bo, t + "attn1.to_out.0.bias");
+  GemmOpt oo; oo.bias = bo; oo.residual = s.h;
+  return s.produce(s.att, C, *wo, oo, false, p.stats_attn1);
+}
+
+// the halves of a CFG-shared prefix diverge from here on (text context)
+static int tb_duplicate(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; hipStream_t st = s.st; const int C = s.C, M = s.Mshared;
+  if (p.dup == DUP_NONE) return 0;
+  s.M = s.B * s.HW;
+  if (p.dup == DUP_LAZY) return 0;
+  CK(dup_half(c, st, s.h, (long long)M * C));
+  if (p.stats_attn1) { ProfScope ps(c, st, PC_ELEM, 0);
+    if (hipMemcpyAsync(s.stats + (size_t)M * s.slots * 2, s.stats, (size_t)M * s.slots * 2 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup stats copy failed"); }
+  Act x2 = alloc_act(c, s.B, s.x.H, s.x.W, C); if (!x2.p) return -1;
+  { ProfScope ps(c, st, PC_ELEM, 0);
+    if (hipMemcpyAsync(x2.p, s.x.p, (size_t)M * C * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("dup copy failed"); }
+  CK(dup_half(c, st, x2.p, (long long)M * C));
+  s.xres = x2.p;
+  return 0;
+}
+
+static int tb_fuser(TBlock& s, const TBlockPlan& p) {
+  return fuser_rows(s.c, s.st, *p.fuser, s.h, s.B, s.HW, s.qkv, s.att,
+                    [&](const bf16_t* A, int K, const WMat& w, const GemmOpt& o) { return s.produce(A, K, w, o, false, p.stats_attn1); });
+}
+
+static int tb_attn2_chain(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; const std::string& t = s.t; const XLayer& xl = *p.xl; const int C = s.C, HW = s.HW, B = s.B, M = s.M, heads = s.heads;
+  GETW(fq, t + "attn2.to_q.frag"); GETW(fo, t + "attn2.to_out.frag");
+  GETV(g2, t + "norm2.weight"); GETV(b2, t + "norm2.bias"); GETV(bo, t + "attn2.to_out.0.bias");
+  const int T = c->ctx_T, D = C / heads;
+  AttnChainP ap{}; ap.h = s.h; ap.out = s.h; ap.gamma = g2; ap.beta = b2; ap.ln_eps = kTbLnEps; ap.wqf = fq->w; ap.wof = fo->w; ap.bo = bo;
+  ap.kv = xl.kv; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)D);
+  double rec_bytes = 0;
+  if (p.daam) {
+    ap.record = 1; ap.rec_b0 = B / 2; ap.rec_T = c->rec_T; ap.rec_hpb = heads / xl.acc_heads;
+    ap.rec_head_stride = (long long)c->rec_T * HW; ap.rec_img_stride = ap.rec_head_stride * xl.acc_heads;
+    ap.rec = xl.acc + (size_t)c->rec_base * ap.rec_img_stride;
+    rec_bytes = 8.0 * (B - ap.rec_b0) * xl.acc_heads * (double)c->rec_T * HW;
+  }
+  if (p.attn1_in_chain || p.dup == DUP_LAZY) {           // the chain's input is not its output: the residual stream continues in a second buffer
+    ap.out = (bf16_t*)c->arena.alloc((size_t)M * C * 2); if (!ap.out) return -1;
+  }
+  if (p.attn1_in_chain) {                                // h1 = attn1.to_out(att) + h is computed (and stored) by the chain itself
+    GETW(f1o, t + "attn1.to_out.frag"); GETV(bo1, t + "attn1.to_out.0.bias");
+    ap.o1 = s.att; ap.wo1f = f1o->w; ap.bo1 = bo1;
+  }
+  if (p.dup == DUP_LAZY) ap.src_rows = s.Mshared;
+  ap.rows32 = p.chain_rows32;
+  if (p.stats_attn2) {                                   // the GEGLU consumer of the LayerNorm fold reads one slot of row statistics
+    s.slots = 1; s.stats = (float*)c->arena.alloc((size_t)M * 2 * sizeof(float)); if (!s.stats) return -1;
+    ap.rowstat_out = s.stats;
+  }
+  const double gemms = p.attn1_in_chain ? 6.0 : 4.0;
+  ProfScope ps(c, s.st, PC_ATTN_CROSS, gemms * M * (double)C * C + 4.0 * B * heads * (double)HW * T * D, gemms * M * (double)C + gemms * C * (double)C + 4.0 * B * (double)T * C + rec_bytes);
+  CK(launch_attn_chain(ap, C, heads, s.st));
+  s.h = ap.out;
+  return 0;
+}
+
+static int tb_attn2_premul(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; const XLayer& xl = *p.xl; const int C = s.C, HW = s.HW, B = s.B, M = s.M, heads = s.heads;
+  if (!s.stats || s.slots <= 0) FAIL("attn2_premul: the GEMM in front of attn2 left no row statistics for norm2");
+  GETV(bo, s.t + "attn2.to_out.0.bias");
+  const int HT = heads * XATTN_TP;
+  bf16_t* P = (bf16_t*)c->arena.alloc((size_t)M * HT * 2); if (!P) return -1;
+  XattnSP sp{}; sp.x = s.h; sp.ln_stats = s.stats; sp.ln_slots = s.slots; sp.ln_invC = 1.0f / (float)C; sp.ln_eps = kTbLnEps;
+  sp.kpp = xl.pm_kpp; sp.kcs = xl.pm_kcs; sp.kbs = xl.pm_kbs; sp.P = P; sp.M = M; sp.HW = HW; sp.C = C; sp.H = heads; sp.T = c->ctx_T;
+  double rec_bytes = 0;
+  if (p.daam) {
+    sp.rec_b0 = B / 2; sp.rec_T = c->rec_T; sp.rec_head_stride = (long long)c->rec_T * HW; sp.rec_img_stride = sp.rec_head_stride * xl.acc_heads;
+    sp.rec = xl.acc + (size_t)c->rec_base * sp.rec_img_stride;
+    rec_bytes = 8.0 * (B - sp.rec_b0) * heads * (double)c->rec_T * HW;
+  }
+  { ProfScope ps(c, s.st, PC_ATTN_CROSS, 2.0 * M * (double)HT * C, 2.0 * M * (double)C + 2.0 * B * (double)HT * C + 2.0 * M * (double)HT + rec_bytes);
+    CK(launch_xattn_s(sp, s.st)); }
+  WMat wv; wv.w = xl.pm_vpp; wv.N = C; wv.Cin = HT; wv.Cpad = HT; wv.taps = 1;
+  GemmOpt oo; oo.bias = bo; oo.residual = s.h; oo.w_per_image = 1;
+  return s.produce(P, HT, wv, oo, true, p.stats_attn2);
+}
+
+static int tb_attn2(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; const std::string& t = s.t;
+  if (!p.xl) FAIL("cross-attn layer %s not registered", (t + "attn2").c_str());
+  if (c->ctx_B2 != s.B) FAIL("context batch %d != unet batch %d (call agd_set_context)", c->ctx_B2, s.B);
+  if (p.attn2 == ATTN2_CHAIN) return tb_attn2_chain(s, p);
+  if (p.attn2 == ATTN2_PREMUL) return tb_attn2_premul(s, p);
+  CK(s.consume(p.fold, t + "norm2", t + "attn2.to_q.weight", nullptr, 0, s.qkv));
+  CK(cross_attention(c, s.st, *p.xl, s.qkv, s.B, s.HW, s.x.H, s.x.W, s.att, true));
+  GETW(wo, t + "attn2.to_out.0.weight"); GETV(bo, t + "attn2.to_out.0.bias");
+  GemmOpt oo; oo.bias = bo; oo.residual = s.h;
+  return s.produce(s.att, s.C, *wo, oo, false, p.stats_attn2);
+}
+
+static int tb_ff_fused(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; const std::string& t = s.t; Act& out = s.out; const int C = s.C, M = s.M;
+  GETW(f1, t + "ff.w1.frag"); GETW(f2, t + "ff.w2.frag");
+  const std::string k = t + "ff.net.0.proj.weight.lnfold";
+  GETV(cs, k + ".cs"); GETV(bf, k + ".bias"); GETV(b2, t + "ff.net.2.bias");
+  FFusedP fp{}; fp.h = s.h; fp.out = s.h; fp.w1f = f1->w; fp.cs1 = cs; fp.b1 = bf; fp.w2f = f2->w; fp.b2 = b2; fp.M = M; fp.ln_eps = kTbLnEps;
+  const bool proj = p.ff != FF_FUSED;
+  if (proj) {
+    GETW(fpw, s.pre + "proj_out.frag"); GETV(bp, s.pre + "proj_out.bias");
+    fp.wpf = fpw->w; fp.bp = bp; fp.xres = s.xres; fp.pout = out.p;
+    if (p.ff == FF_FUSED_PREMUL) {
+      GETW(f2p, t + "ff.w2p.frag"); GETV(bcp, s.pre + "ffproj.bias");
+      fp.w2f = f2p->w; fp.bp = bcp; fp.premul = 1;
     }
-    ProfScope ps(c, st, PC_GEMM, 2.0 * M * (double)C * (proj_done ? 13.0 : 12.0) * C, (proj_done ? 8.0 : 4.0) * M * (double)C + 2.0 * (proj_done ? 13.0 : 12.0) * C * (double)C);
-    CK(launch_ff_fused(fp, C, st));
-  } else
-  { bf16_t* ff = (bf16_t*)c->arena.alloc((size_t)M * 4 * C * 2); if (!ff) return -1;
+    if (p.dup == DUP_LAZY) fp.xres_rows = s.Mshared;     // xres is still the B'-row block input
+    out.cpart_bm = 0;
+    if (out.cpart && c->opt_gn_fused && s.HW % 128 == 0) { fp.colstat = out.cpart; out.cpart_bm = 128; }
+  }
+  ProfScope ps(c, s.st, PC_GEMM, 2.0 * M * (double)C * (proj ? 13.0 : 12.0) * C, (proj ? 8.0 : 4.0) * M * (double)C + 2.0 * (proj ? 13.0 : 12.0) * C * (double)C);
+  return launch_ff_fused(fp, C, s.st);
+}
+
+// GEGLU feed-forward and proj_out
+static int tb_feed_forward(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c; hipStream_t st = s.st; const std::string& t = s.t; const int C = s.C, M = s.M;
+  if (p.ff == FF_FUSED || p.ff == FF_FUSED_PROJ || p.ff == FF_FUSED_PREMUL) CK(tb_ff_fused(s, p));
+  else {
+    bf16_t* ff = (bf16_t*)c->arena.alloc((size_t)M * 4 * C * 2); if (!ff) return -1;
     GETV(b1, t + "ff.net.0.proj.bias");
-    CK(consume(t + "norm3", t + "ff.net.0.proj.weight", b1, 1, ff));
-    if (c->opt_ffproj && c->W.count(pre + "ffproj.weight")) {
+    CK(s.consume(p.fold, t + "norm3", t + "ff.net.0.proj.weight", b1, 1, ff));
+    if (p.ff == FF_FFPROJ) {
       // proj_out(ff.net.2(g) + h) + x = [Wp W2 | Wp] . [g | h] + (Wp b2 + bp) + x: one launch over the channel concat of the hidden activation and the residual stream
       // with the matrix pre-multiplied at load time -- h3 is never formed, the proj_out launch (its 5 - 10 MB output pass and epilogue) disappears
-      GETW(wc, pre + "ffproj.weight"); GETV(bc, pre + "ffproj.bias");
-      GemmOpt o; o.bias = bc; o.residual = xres; o.out_act = &out; o.rows_per_image = HW;
-      CK(run_conv(c, st, ff, 4 * C, h.p, C, 1, 1, M, *wc, 1, out.p, o, c->zero_page));
-      proj_done = true;
-    } else {
+      GETW(wc, s.pre + "ffproj.weight"); GETV(bc, s.pre + "ffproj.bias");
+      GemmOpt o; o.bias = bc; o.residual = s.xres; o.out_act = &s.out; o.rows_per_image = s.HW;
+      return run_conv(c, st, ff, 4 * C, s.h, C, 1, 1, M, *wc, 1, s.out.p, o, c->zero_page);
+    }
     GETW(w2, t + "ff.net.2.weight"); GETV(b2, t + "ff.net.2.bias");
-    GemmOpt o2; o2.bias = b2; o2.residual = h.p;
-    CK(run_conv(c, st, ff, 4 * C, nullptr, 0, 1, 1, M, *w2, 1, h.p, o2, c->zero_page)); } }
-  if (!proj_done)
-  { GETW(w, pre + "proj_out.weight"); GETV(b, pre + "proj_out.bias"); GemmOpt o; o.bias = b; o.residual = xres; o.out_act = &out; o.rows_per_image = HW;
-    if (C == 640 && (c->opt_wreg & 2)) o.wreg = 1;
-    CK(run_conv(c, st, h.p, C, nullptr, 0, 1, 1, M, *w, 1, out.p, o, c->zero_page)); }
+    GemmOpt o2; o2.bias = b2; o2.residual = s.h;
+    CK(run_conv(c, st, ff, 4 * C, nullptr, 0, 1, 1, M, *w2, 1, s.h, o2, c->zero_page));
+  }
+  if (p.ff != FF_FUSED && p.ff != FF_PLAIN) return 0;    // proj_out ran inside the feed-forward's last launch
+  GETW(w, s.pre + "proj_out.weight"); GETV(b, s.pre + "proj_out.bias");
+  GemmOpt o; o.bias = b; o.residual = s.xres; o.out_act = &s.out; o.rows_per_image = s.HW;
+  if (p.wreg_proj) o.wreg = 1;
+  return run_conv(c, st, s.h, C, nullptr, 0, 1, 1, M, *w, 1, s.out.p, o, c->zero_page);
+}
+
+static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const Act& x, int heads, int groups, Act& out, int dup = 0) {
+  TBlock s(c, st, pre, x, out, heads, groups, dup);
+  const int B = s.B, HW = s.HW, C = s.C;
+  out = alloc_act(c, B, x.H, x.W, C, true); if (!out.p) return -1;
+  const size_t mk = c->arena.mark();
+  Act n = alloc_act(c, B, x.H, x.W, C); if (!n.p) return -1;
+  Act h = alloc_act(c, B, x.H, x.W, C); if (!h.p) return -1;
+  s.ln = n.p; s.h = h.p;
+  s.qkv = (bf16_t*)c->arena.alloc((size_t)B * HW * 3 * C * 2); if (!s.qkv) return -1;
+  s.att = (bf16_t*)c->arena.alloc((size_t)B * HW * C * 2); if (!s.att) return -1;
+  GETV(gg, pre + "norm.weight"); GETV(gb, pre + "norm.bias"); GETW(w_in, pre + "proj_in.weight"); GETV(b_in, pre + "proj_in.bias");
+  s.gn_g = gg; s.gn_b = gb; s.w_in = w_in; s.b_in = b_in;
+  const TBlockPlan p = tblock_plan(s, dup);
+  CK(tb_head(s, p));
+  CK(tb_self_attention(s, p));
+  CK(tb_duplicate(s, p));
+  if (p.fuser) CK(tb_fuser(s, p));
+  CK(tb_attn2(s, p));
+  CK(tb_feed_forward(s, p));
   c->arena.release(mk);
   return 0;
 }
@@ -2272,7 +2375,7 @@ AGD_API int agd_set_option(agd_ctx* c, const char* name, int value) {
   if (!strcmp(name, "weight_warm")) { c->opt_warm = value; return 0; }
   if (!strcmp(name, "conv_halo")) { c->opt_halo = value != 0; return 0; }
   if (!strcmp(name, "gn_proj_fold")) { c->opt_gn_proj_fold = value < 0 ? 0 : value; return 0; }   // 0 off, 1: blocks with C <= 320, 2: C <= 640 (A/B)
-  if (!strcmp(name, "tblock_fuse")) { c->opt_tb_fuse = value < 0 ? 0 : value; return 0; }   // bit 0: fused feed-forward, bit 1: fused attn2 chain (C = 320 blocks)
+  if (!strcmp(name, "tblock_fuse")) { c->opt_tb_fuse = value < 0 ? 0 : value; return 0; }   // the TBF_* bits
   if (!strcmp(name, "reduce_gn")) { c->opt_reduce_gn = value != 0; return 0; }
   if (!strcmp(name, "xcd_block")) { c->opt_xcd_block = value != 0; return 0; }
   if (!strcmp(name, "igemm_pc")) { c->opt_pc = value < 0 ? 0 : value; return 0; }
