@@ -8,6 +8,7 @@ from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indice
 from .hook import UNetCrossAttentionHooker  # noqa: F401
 from .scheduler import DDIMScheduler  # noqa: F401
 from .controlnet import ControlNetModel, StableDiffusionControlNetPipeline  # noqa: F401
+from .adapter import T2IAdapter, StableDiffusionAdapterPipeline  # noqa: F401
 from .inpaint import StableDiffusionInpaintPipeline  # noqa: F401
 from .ip2p import StableDiffusionInstructPix2PixPipeline  # noqa: F401
 from .gligen import StableDiffusionGLIGENPipeline  # noqa: F401
@@ -15,6 +16,7 @@ from .panorama import StableDiffusionPanoramaPipeline, get_views  # noqa: F401
 
 __all__ = ["StableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
            "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic",
-           "ControlNetModel", "StableDiffusionControlNetPipeline", "StableDiffusionInpaintPipeline",
+           "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
+           "StableDiffusionInpaintPipeline",
            "StableDiffusionInstructPix2PixPipeline",
            "StableDiffusionGLIGENPipeline", "StableDiffusionPanoramaPipeline", "get_views"]

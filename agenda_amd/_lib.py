@@ -60,6 +60,15 @@ class AgdControlNetConfig(C.Structure):
     ]
 
 
+class AgdAdapterConfig(C.Structure):
+    """`agd_adapter_config`: a T2I-Adapter "full_adapter" (agd_adapter_configure)."""
+    _fields_ = [
+        ("struct_size", C.c_int),
+        ("in_channels", C.c_int), ("n_channels", C.c_int), ("channels", C.c_int * AGD_MAX_LEVELS),
+        ("num_res_blocks", C.c_int), ("downscale_factor", C.c_int),
+    ]
+
+
 class AgdGligenConfig(C.Structure):
     """`agd_gligen_config`: the PositionNet of a GLIGEN UNet (agd_gligen_configure)."""
     _fields_ = [
@@ -95,6 +104,12 @@ _SIGS = {
     "agd_ip2p_prepare_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "agd_ip2p_set_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "agd_ip2p_clear": (C.c_int, [_P]),
+    "agd_adapter_configure": (C.c_int, [_P, C.POINTER(AgdAdapterConfig)]),
+    "agd_adapter_set_cond_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "agd_adapter_features": (C.c_int, [_P, _P]),
+    "agd_adapter_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "agd_adapter_clear": (C.c_int, [_P]),
+    "agd_adapter_add_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
     "agd_gligen_configure": (C.c_int, [_P, C.POINTER(AgdGligenConfig)]),
     "agd_gligen_set": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "agd_gligen_set_schedule": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),

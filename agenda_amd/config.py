@@ -589,3 +589,71 @@ def controlnet_keep_schedule(n: int, start: float = 0.0, end: float = 1.0) -> Li
     if not 0.0 <= start < end <= 1.0:
         raise ValueError(f"control guidance window [{start}, {end}] must satisfy 0 <= start < end <= 1")
     return [1.0 - float(i / n < start or (i + 1) / n > end) for i in range(n)]
+
+
+# ==========================================================================================
+# T2I-Adapter (diffusers T2IAdapter, "full_adapter") [upstream-knowledge: diffusers 0.21.2]
+# ==========================================================================================
+@dataclass
+class AdapterConfig:
+    """A diffusers T2IAdapter `config.json`: `T2IAdapter(in_channels, channels, num_res_blocks, downscale_factor, adapter_type)`.  The
+    defaults are the published SD-1.5 full adapters (canny / sketch take in_channels=1, depth / seg / pose 3)."""
+    in_channels: int = 3
+    channels: Tuple[int, ...] = (320, 640, 1280, 1280)
+    num_res_blocks: int = 2
+    downscale_factor: int = 8
+    adapter_type: str = "full_adapter"
+
+    def to_json(self) -> dict:
+        return {"_class_name": "T2IAdapter", "in_channels": self.in_channels, "channels": list(self.channels),
+                "num_res_blocks": self.num_res_blocks, "downscale_factor": self.downscale_factor, "adapter_type": self.adapter_type}
+
+
+def adapter_config_from_json(cj: dict) -> AdapterConfig:
+    """`T2IAdapter.from_pretrained(dir).config` -> AdapterConfig.  Only "full_adapter" is implemented ("light_adapter" and the SDXL
+    "full_adapter_xl" raise NotImplementedError)."""
+    kind = cj.get("adapter_type", "full_adapter")
+    if kind != "full_adapter":
+        raise NotImplementedError(f"T2IAdapter adapter_type={kind!r} is not implemented (only 'full_adapter')")
+    ch = tuple(int(c) for c in cj.get("channels", (320, 640, 1280, 1280)))
+    if not ch or any(c < 1 for c in ch):
+        raise ValueError(f"T2IAdapter channels={cj.get('channels')!r}")
+    return AdapterConfig(in_channels=int(cj.get("in_channels", 3)), channels=ch, num_res_blocks=int(cj.get("num_res_blocks", 2)),
+                         downscale_factor=int(cj.get("downscale_factor", 8)), adapter_type=kind)
+
+
+def adapter_config_for(unet: UNetConfig, in_channels: int = 3) -> AdapterConfig:
+    """The full adapter that fits `unet`: one block per UNet level at that level's width."""
+    return AdapterConfig(in_channels=in_channels, channels=tuple(unet.block_out_channels))
+
+
+def adapter_param_shapes(unet: UNetConfig, acfg: AdapterConfig) -> Dict[str, tuple]:
+    """diffusers T2IAdapter (FullAdapter) state-dict keys and shapes: `adapter.conv_in` (3x3 on the pixel-unshuffled image), per entry
+    of `channels` an AdapterBlock `adapter.body.{i}` -- `in_conv` (1x1) only where the width changes, then `num_res_blocks` resnets of
+    `block1` (3x3) and `block2` (1x1).  `unet` only has to agree with it (the engine checks channels[i] == block_out_channels[i])."""
+    del unet
+    p: Dict[str, tuple] = {}
+    ch = acfg.channels
+    p["adapter.conv_in.weight"] = (ch[0], acfg.in_channels * acfg.downscale_factor ** 2, 3, 3)
+    p["adapter.conv_in.bias"] = (ch[0],)
+    for i, co in enumerate(ch):
+        cin = ch[i - 1] if i else ch[0]
+        b = f"adapter.body.{i}."
+        if cin != co:
+            p[b + "in_conv.weight"] = (co, cin, 1, 1)
+            p[b + "in_conv.bias"] = (co,)
+        for j in range(acfg.num_res_blocks):
+            p[b + f"resnets.{j}.block1.weight"] = (co, co, 3, 3)
+            p[b + f"resnets.{j}.block1.bias"] = (co,)
+            p[b + f"resnets.{j}.block2.weight"] = (co, co, 1, 1)
+            p[b + f"resnets.{j}.block2.bias"] = (co,)
+    return p
+
+
+def adapter_schedule(n: int, scale: float = 1.0, factor: float = 1.0) -> List[float]:
+    """One scale per model evaluation: `adapter_conditioning_scale` on evaluations i < int(adapter_conditioning_factor * n), 0 (the plain
+    UNet) on the rest.  n counts evaluations, so PNDM's repeated one counts."""
+    if not 0.0 <= factor <= 1.0:
+        raise ValueError(f"adapter_conditioning_factor {factor} must lie in [0, 1]")
+    k = int(factor * n)
+    return [float(scale) if i < k else 0.0 for i in range(n)]

@@ -251,6 +251,15 @@ int launch_ip2p_front(const void* image, int image_f32, int B, int H, int W, flo
 int launch_prep_ip2p(const float* lat, const float* img, bf16_t* out, int B, int Cl, int Cc, int HW, int Cpad, hipStream_t st);
 int launch_ip2p_fold(float* eps, long long n, float image_guidance, hipStream_t st);
 
+// T2I-Adapter (adapter.hip): the front end (uint8 NHWC or fp32 NCHW in [0,1] -> the pixel-unshuffled model input, bf16 NHWC [B][H/r * W/r][Cpad]),
+// the 2x2 average pool and the in-place ReLU of the adapter network (bf16 NHWC), and the per-evaluation add y = bf16(h + s f) of a feature
+// f fp32 [Bf][HW][C] (row image b reads feature image b % Bf) into a fresh activation; part != nullptr: it also leaves the GroupNorm partial
+// sums [B2 HW / bm][C] float2 of the bf16-rounded outputs (the igemm epilogue's colstat_out layout; HW % bm == 0), reduced in a fixed order
+int launch_adapter_front(const void* image, int image_f32, int B, int H, int W, int C, int r, int Cpad, bf16_t* out, hipStream_t st);
+int launch_adapter_avgpool(const bf16_t* x, bf16_t* y, int B, int H, int W, int C, hipStream_t st);
+int launch_adapter_relu(bf16_t* x, long long n, hipStream_t st);
+int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, int bm, int B2, int HW, int C, int Bf, float s, hipStream_t st);
+
 // MultiDiffusion panorama (panorama.hip): views of win x win at (i stride, j stride), view v = i nbw + j; image of (panorama p, view v) in a view
 // buffer = p * pano_stride + v * view_stride images of [C][win][win] fp32.  gather: views [v0, v0 + n) of every panorama out of the canvas
 // [B][C][Lh][Lw] (view v lands at slot v - v0); mean: canvas element = the fp32 sum of its covering views in ascending view order / their number

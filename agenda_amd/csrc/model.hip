@@ -202,6 +202,12 @@ struct agd_ctx {
   agd_gligen_config glc{}; bool gl_on = false;
   std::vector<Fuser> gl_f; std::unordered_map<std::string, int> gl_idx;
   DBuf gl_objb; int gl_B2 = 0; std::vector<int> gl_sched; bool gl_active = false;
+  // T2I-Adapter (agd_adapter_configure): weights "adapter.*"; the per-call UNSCALED features fp32 NHWC [ad_B][Lh >> i][Lw >> i][channels[i]]
+  // (agd_adapter_set_cond_hw), one scale per model evaluation; ad_cur: the scale of the forward being walked (0: the plain UNet);
+  // ad_adds: adds launched with / without GroupNorm partial sums
+  agd_adapter_config adc{}; bool ad_on = false;
+  DBuf ad_featb[AGD_MAX_LEVELS]; int ad_B = 0, ad_Lh = 0, ad_Lw = 0;
+  std::vector<float> ad_sched; float ad_cur = 0.f; long long ad_adds[2] = {0, 0};
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
@@ -987,11 +993,15 @@ static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float*
 // every res sample in order (conv_in, each resnet / transformer output, each downsampler: the UNet's skips); h = the mid block's output.
 // conv_in_res: added in conv_in's epilogue (the ControlNet's conditioning embedding).  shared: rows [0,B2/2) and [B2/2,B2) of xin (and of
 // conv_in_res) are identical -- everything ahead of the first attn2 runs on B2/2 rows.
+// T2I-Adapter (the UNet's walk with ad_cur != 0): after the last layer of level i and before on_sample sees it, h becomes h + ad_cur * feature i
+// in a fresh activation (adapter_add) -- the sum is the level's last skip and the input of the downsampler / the mid block.
+static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act& out);
 static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int Lh, int Lw, bool shared,
                          const bf16_t* conv_in_res, const std::function<int(const Act&)>& on_sample, Act& h) {
   const agd_config& g = c->cfg;
   const int nl = g.n_levels, G = g.norm_num_groups;
   const int Bh = shared ? B2 / 2 : B2;
+  const bool inject = c->ad_cur != 0.f && u == "unet.";
   h = alloc_act(c, B2, Lh, Lw, g.block_out_channels[0], true); if (!h.p) return -1;
   { GETW(w, u + "conv_in.weight"); GETV(b, u + "conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h; o.residual = conv_in_res;
     CK(run_conv(c, st, xin, 64, nullptr, 0, Bh, Lh, Lw, *w, 3, h.p, o, c->zero_page)); }
@@ -1007,6 +1017,7 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
     const int co = g.block_out_channels[i];
     for (int j = 0; j < g.layers_per_block; ++j) {
       const bool first = shared && i == 0 && j == 0;
+      const bool add_here = inject && j + 1 == g.layers_per_block;       // the adapter's feature i lands on this layer's output
       Act hin = h; if (first) hin.B = Bh;
       // the GroupNorm that reads this resnet's output alone: the block's transformer, the next resnet of an attention-free level, or mid_block
       NextGn ng; std::string nk; 
@@ -1014,12 +1025,15 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
       else if (j + 1 < g.layers_per_block) { nk = u + "down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j + 1) + ".norm1."; ng.eps = 1e-5f; ng.silu = 1; }
       else if (i == nl - 1) { nk = u + "mid_block.resnets.0.norm1."; ng.eps = 1e-5f; ng.silu = 1; }
       if (!nk.empty()) { auto ig = c->V.find(nk + "weight"), ib = c->V.find(nk + "bias"); if (ig != c->V.end() && ib != c->V.end()) { ng.gamma = ig->second; ng.beta = ib->second; } }
-      Act r; CK(resnet(c, st, u + "down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", hin, nullptr, co, 1e-5f, true, G, r, first ? nullptr : &ng));
+      // (no NextGn where the add follows the resnet directly -- the attention-free level: a normalised copy of the un-added tensor would be stale)
+      const bool no_ng = first || (add_here && !g.down_cross[i]);
+      Act r; CK(resnet(c, st, u + "down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", hin, nullptr, co, 1e-5f, true, G, r, no_ng ? nullptr : &ng));
       h = r;
       if (g.down_cross[i]) {
         Act a; CK(transformer(c, st, u + "down_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", h, g.num_heads[i], G, a, first ? 1 : 0));
         h = a;
       }
+      if (add_here) { Act s; CK(adapter_add(c, st, i, h, s)); h = s; }
       CK(on_sample(h));
     }
     if (i != nl - 1) {
@@ -1037,6 +1051,23 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
     Act r; CK(resnet(c, st, u + "mid_block.resnets.0.", h, nullptr, cm, 1e-5f, true, G, r, &ngm)); h = r;
     Act a; CK(transformer(c, st, u + "mid_block.attentions.0.", h, g.num_heads[nl - 1], G, a)); h = a;
     Act r2; CK(resnet(c, st, u + "mid_block.resnets.1.", h, nullptr, cm, 1e-5f, true, G, r2)); h = r2; }
+  return 0;
+}
+
+// h + ad_cur * feature `level` into a fresh activation, with the GroupNorm partial sums of the sum on 64-row tiles where the consumer takes
+// them (norm.hip gn_part_ok: HW % bm == 0, C % 8 == 0, the 65536 index bound) and cpart_bm = 0 -- the norm's own statistics pass -- elsewhere
+static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act& out) {
+  const int HW = h.H * h.W;
+  if (level >= c->adc.n_channels || h.C != c->adc.channels[level] || h.H != (c->ad_Lh >> level) || h.W != (c->ad_Lw >> level) || c->ad_B < 1 || h.B % c->ad_B)
+    FAIL("adapter: feature %d is set for %d images at %d x %d x %d, down block %d gives %d rows of %d x %d x %d", level, c->ad_B, c->ad_Lh >> level, c->ad_Lw >> level,
+         level < c->adc.n_channels ? c->adc.channels[level] : 0, level, h.B, h.H, h.W, h.C);
+  out = alloc_act(c, h.B, h.H, h.W, h.C, true); if (!out.p) return -1;
+  const int bm = (out.cpart && HW % 64 == 0 && (long long)(h.C / c->cfg.norm_num_groups) * (HW / 64) < 65536) ? 64 : 0;
+  out.cpart_bm = bm;
+  const double rows = (double)h.B * HW;
+  ProfScope ps(c, st, PC_ELEM, 0, rows * h.C * (2.0 + 4.0 + 2.0) + (bm ? rows / bm * h.C * 8.0 : 0.0));
+  CK(launch_adapter_add(h.p, c->ad_featb[level].as<float>(), out.p, bm ? out.cpart : nullptr, bm, h.B, HW, h.C, c->ad_B, c->ad_cur, st));
+  c->ad_adds[bm ? 0 : 1]++;
   return 0;
 }
 
@@ -1117,10 +1148,13 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
 // tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
 // cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
 // grounded: the GLIGEN fusers run in the UNet's transformer blocks (agd_gligen_set_schedule)
+// ad_scale != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs (agd_adapter_set_schedule)
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
-                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f, bool grounded = false) {
+                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f, bool grounded = false,
+                     float ad_scale = 0.f) {
   const agd_config& g = c->cfg;
   c->gl_active = grounded;
+  c->ad_cur = ad_scale;
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   const int nl = g.n_levels, G = g.norm_num_groups;
   const std::string u = "unet.";
@@ -1343,6 +1377,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
   for (auto& f : c->gl_f) f.gkvb.release();
   c->gl_objb.release();
+  for (auto& b : c->ad_featb) b.release();
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1368,6 +1403,7 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
   if (hipMemcpy(c->stage, ptr, bytes, hipMemcpyDefault) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
   const std::string k(name);
   if (k.compare(0, 11, "controlnet.") == 0 && !c->cn_on) { agd_set_error("'%s': call agd_controlnet_configure before loading ControlNet weights", name); return fail_ctx(c); }
+  if (k.compare(0, 8, "adapter.") == 0 && !c->ad_on) { agd_set_error("'%s': call agd_adapter_configure before loading T2I-Adapter weights", name); return fail_ctx(c); }
   if ((k.compare(0, 18, "unet.position_net.") == 0 || k.find(".fuser.") != std::string::npos) && !c->gl_on) {
     agd_set_error("'%s': call agd_gligen_configure before loading GLIGEN weights", name); return fail_ctx(c); }
   // the safety checker keeps everything but its encoder-layer matrices in fp32 as loaded (embeddings, the 14 x 14 patch conv, the
@@ -1525,6 +1561,36 @@ static int finalize_controlnet(agd_ctx* c) {
   for (size_t k = 0; k < keys.size(); ++k)
     if (hipMemcpy(c->cn_zb + c->cn_zb_off[k], c->V[keys[k] + ".bias"], (size_t)n_of[k] * 4, hipMemcpyDeviceToDevice) != hipSuccess) FAIL("controlnet: bias copy failed");
   c->cn_zb_total = total; c->cn_zscale = NAN;
+  return 0;
+}
+
+// T2I-Adapter "full_adapter": the config must fit the UNet it feeds, and every matrix of adapter.conv_in / adapter.body.{i}.in_conv /
+// adapter.body.{i}.resnets.{j}.block1 (3x3) / block2 (1x1) must be present with the config's shape
+static int finalize_adapter(agd_ctx* c) {
+  const agd_config& g = c->cfg;
+  const agd_adapter_config& e = c->adc;
+  if (e.n_channels != g.n_levels) FAIL("adapter: channels has %d entries, the UNet has %d levels", e.n_channels, g.n_levels);
+  for (int i = 0; i < e.n_channels; ++i)
+    if (e.channels[i] != g.block_out_channels[i]) FAIL("adapter: channels[%d] = %d, the UNet's block_out_channels[%d] = %d", i, e.channels[i], i, g.block_out_channels[i]);
+  const int vf = 1 << (g.vae_n_levels - 1);
+  if (e.downscale_factor != vf) FAIL("adapter: downscale_factor = %d, the VAE's scale factor is %d", e.downscale_factor, vf);
+  auto want = [&](const std::string& k, int n, int cin, int taps) -> int {
+    const WMat* w = getW(c, k + ".weight"); if (!w) return -1;
+    if (w->N != n || w->Cin != cin || w->taps != taps) FAIL("'%s.weight' is [%d, %d, %d taps], the adapter config needs [%d, %d, %d taps]", k.c_str(), w->N, w->Cin, w->taps, n, cin, taps);
+    auto b = c->Vn.find(k + ".bias"); if (b == c->Vn.end() || b->second != n) FAIL("'%s.bias' missing or not %d long", k.c_str(), n);
+    return 0;
+  };
+  const std::string A = "adapter.adapter.";
+  CK(want(A + "conv_in", e.channels[0], e.in_channels * e.downscale_factor * e.downscale_factor, 9));
+  for (int i = 0; i < e.n_channels; ++i) {
+    const std::string Bk = A + "body." + std::to_string(i) + ".";
+    const int cin = i ? e.channels[i - 1] : e.channels[0], co = e.channels[i];
+    if (cin != co) CK(want(Bk + "in_conv", co, cin, 1));
+    for (int j = 0; j < e.num_res_blocks; ++j) {
+      CK(want(Bk + "resnets." + std::to_string(j) + ".block1", co, co, 9));
+      CK(want(Bk + "resnets." + std::to_string(j) + ".block2", co, co, 1));
+    }
+  }
   return 0;
 }
 
@@ -1856,6 +1922,8 @@ AGD_API int agd_finalize(agd_ctx* c) {
   if (c->cn_on) API_CK(c, finalize_controlnet(c));
   // ---- GLIGEN: the PositionNet's shapes, every fuser's fused projections, gates and pre-scaled biases
   if (c->gl_on) API_CK(c, finalize_gligen(c));
+  // ---- T2I-Adapter: the config against the UNet's, every matrix's shape
+  if (c->ad_on) API_CK(c, finalize_adapter(c));
   hipDeviceSynchronize();
   c->finalized = true;
   return 0;
@@ -1941,6 +2009,24 @@ static int gl_schedule_for(agd_ctx* c, int n, int B2, const int** out) {
   *out = c->gl_sched.data();
   return 0;
 }
+// the T2I-Adapter schedule of a call of n model evaluations on `rows` images (a fused loop: its batch; agd_unet_forward: its rows) at latent
+// size Lh x Lw: nullptr = none set (the plain UNet); else its length must be n, nothing else that changes the walk may be set, and features
+// for these sizes must exist when any scale is non-zero -- for ad_B images with rows a multiple of ad_B (row image b reads feature image b % ad_B)
+static int adapter_for(agd_ctx* c, int n, int rows, int Lh, int Lw, const float** out) {
+  *out = nullptr;
+  if (c->ad_sched.empty()) return 0;
+  if ((int)c->ad_sched.size() != n) FAIL("adapter: the schedule has %zu scales, this call runs %d model evaluations (agd_adapter_set_schedule)", c->ad_sched.size(), n);
+  if (!c->cn_sched.empty()) FAIL("adapter: a ControlNet schedule is set; the T2I-Adapter with a ControlNet is not implemented (clear one of them)");
+  if (!c->gl_sched.empty()) FAIL("adapter: a GLIGEN schedule is set; the T2I-Adapter with GLIGEN is not implemented (clear one of them)");
+  if (c->ip_mode != 0) FAIL("adapter: an inpainting state is set; the T2I-Adapter with inpainting is not implemented (agd_inpaint_clear first)");
+  if (c->i2_on) FAIL("adapter: an InstructPix2Pix state is set; the T2I-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)");
+  bool any = false; for (float v : c->ad_sched) any = any || v != 0.f;
+  if (any && (c->ad_B < 1 || rows % c->ad_B || c->ad_Lh != Lh || c->ad_Lw != Lw))
+    FAIL("adapter: the features are set for %d images at latent sides %d x %d, this call runs %d rows at %d x %d (agd_adapter_set_cond_hw)", c->ad_B, c->ad_Lh, c->ad_Lw,
+         rows, Lh, Lw);
+  *out = c->ad_sched.data();
+  return 0;
+}
 // the inpaint state of a fused loop of n model evaluations on `batch` images at latent size Lh x Lw: *blend = the (sa, sb) schedule of the
 // 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
 static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float** blend) {
@@ -1991,8 +2077,10 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   API_CK(c, cn_schedule_for(c, 1, batch2, Lh, Lw, &cs));                     // a one-element ControlNet schedule: one injected forward
   const int* gs = nullptr;
   API_CK(c, gl_schedule_for(c, 1, batch2, &gs));                             // a one-element GLIGEN schedule: one grounded forward
+  const float* as = nullptr;
+  API_CK(c, adapter_for(c, 1, batch2, Lh, Lw, &as));                         // a one-element T2I-Adapter schedule: one forward with the features added
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0]));
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0], as ? as[0] : 0.f));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
 }
@@ -2008,6 +2096,7 @@ AGD_API int agd_unet_forward_ts_hw(agd_ctx* c, const float* sample, int batch2, 
   if (!timesteps || batch2 < 1) { agd_set_error("unet_forward_ts: bad arguments"); return fail_ctx(c); }
   if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   if (!c->gl_sched.empty()) { agd_set_error("unet_forward_ts: a GLIGEN schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
+  if (!c->ad_sched.empty()) { agd_set_error("unet_forward_ts: a T2I-Adapter schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
@@ -2081,6 +2170,7 @@ static int ip2p_for(agd_ctx* c, int batch, int Lh, int Lw) {
   if (!c->cn_sched.empty()) FAIL("ip2p: a ControlNet schedule is set; ControlNet with InstructPix2Pix is not implemented (clear it first)");
   if (!c->gl_sched.empty()) FAIL("ip2p: a GLIGEN schedule is set; GLIGEN with InstructPix2Pix is not implemented (clear it first)");
   if (c->ip_mode != 0) FAIL("ip2p: an inpainting state is set; inpainting with InstructPix2Pix is not implemented (agd_inpaint_clear first)");
+  if (!c->ad_sched.empty()) FAIL("ip2p: a T2I-Adapter schedule is set; the T2I-Adapter with InstructPix2Pix is not implemented (clear it first)");
   return 0;
 }
 // The uncond walk of an InstructPix2Pix evaluation runs `rows` images against the first `rows` context rows -- the [uncond x B] half of the
@@ -2134,11 +2224,13 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   CK(gl_schedule_for(c, n, B2, &gs));
   const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per evaluation (none: no blend)
   CK(inpaint_for(c, n, batch, Lh, Lw, &ib));
+  const float* as = nullptr;                                       // the T2I-Adapter's per-evaluation scales (none: no feature is added)
+  CK(adapter_for(c, n, batch, Lh, Lw, &as));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
-    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i]));
+    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i], as ? as[i] : 0.f));
     CK(step(i, c->eps_nhwc));
     if (ib) CK(inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
   }
@@ -2226,6 +2318,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
   if (!c->gl_sched.empty()) { agd_set_error("denoise_panorama: a GLIGEN schedule is set; GLIGEN on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
   if (c->ip_mode != 0) { agd_set_error("denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)"); return fail_ctx(c); }
   if (c->i2_on) { agd_set_error("denoise_panorama: an InstructPix2Pix state is set; InstructPix2Pix on a panorama is not implemented (agd_ip2p_clear first)"); return fail_ctx(c); }
+  if (!c->ad_sched.empty()) { agd_set_error("denoise_panorama: a T2I-Adapter schedule is set; the T2I-Adapter on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
   if (c->cfg.in_channels != c->cfg.out_channels) { agd_set_error("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels); return fail_ctx(c); }
   if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
   const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
@@ -3644,6 +3737,119 @@ AGD_API int agd_controlnet_residuals_hw(agd_ctx* c, const float* sample, int bat
 AGD_API int agd_controlnet_residuals(agd_ctx* c, const float* sample, int batch2, int L, float timestep, float scale, int nhwc,
                                      float* out, long long* n_out, void* stream) {
   return agd_controlnet_residuals_hw(c, sample, batch2, L, L, timestep, scale, nhwc, out, n_out, stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// T2I-Adapter (diffusers T2IAdapter "full_adapter" + StableDiffusionAdapterPipeline): the network runs once per call here; the per-evaluation
+// adds are adapter_add inside down_mid_walk
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_adapter_configure(agd_ctx* c, const agd_adapter_config* e) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (!e || e->struct_size != (int)sizeof(agd_adapter_config)) {
+    agd_set_error("agd_adapter_configure: bad config (struct_size %d != %zu)", e ? e->struct_size : -1, sizeof(agd_adapter_config)); return fail_ctx(c); }
+  if (c->finalized) { agd_set_error("agd_adapter_configure: call it before agd_finalize"); return fail_ctx(c); }
+  if (e->n_channels < 1 || e->n_channels > AGD_MAX_LEVELS) { agd_set_error("agd_adapter_configure: %d channel counts (1 .. %d)", e->n_channels, AGD_MAX_LEVELS); return fail_ctx(c); }
+  for (int i = 0; i < e->n_channels; ++i)
+    if (e->channels[i] < 64 || e->channels[i] % 64 || e->channels[i] > 4096) { agd_set_error("agd_adapter_configure: channels[%d] = %d (a multiple of 64)", i, e->channels[i]); return fail_ctx(c); }
+  if (e->in_channels < 1 || e->in_channels > 4 || e->num_res_blocks < 1 || e->num_res_blocks > 16 || e->downscale_factor < 1 || e->downscale_factor > 16) {
+    agd_set_error("agd_adapter_configure: in_channels %d, num_res_blocks %d, downscale_factor %d", e->in_channels, e->num_res_blocks, e->downscale_factor); return fail_ctx(c); }
+  c->adc = *e; c->ad_on = true;
+  return 0;
+}
+
+// The adapter, once per call, on the arena: front end (pixel unshuffle, channels zero-padded to a 64-multiple), conv_in, then per block the 2x2
+// average pool, the 1x1 in_conv and the resnets x + block2(relu(block1(x))) -- block2 takes x as its residual operand, and the block's last
+// block2 writes the feature as fp32 (the bf16 copy the next block reads is rounded from it).
+AGD_API int agd_adapter_set_cond_hw(agd_ctx* c, const void* image, int image_f32, int batch, int ih, int iw, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->ad_on) { agd_set_error("adapter_set_cond: no T2I-Adapter loaded (agd_adapter_configure before agd_finalize)"); return fail_ctx(c); }
+  const agd_adapter_config& e = c->adc;
+  const int r = e.downscale_factor, f = r << (e.n_channels - 1);
+  if (!image || batch < 1 || ih < f || iw < f || ih % f || iw % f) {
+    agd_set_error("adapter_set_cond: batch %d / size %d x %d (each side a positive multiple of %d)", batch, ih, iw, f); return fail_ctx(c); }
+  const int Lh = ih / r, Lw = iw / r;
+  c->ad_B = 0; c->ad_Lh = c->ad_Lw = 0;                            // (unset until every feature below is complete)
+  c->arena.release(0);
+  const int Cpad = (e.in_channels * r * r + 63) / 64 * 64;
+  bf16_t* x0 = (bf16_t*)c->arena.alloc((size_t)batch * Lh * Lw * Cpad * 2); if (!x0) return fail_ctx(c);
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_adapter_front(image, image_f32, batch, ih, iw, e.in_channels, r, Cpad, x0, st)); }
+  const std::string A = "adapter.adapter.";
+  auto conv = [&](const std::string& k, const bf16_t* src, int Cin, int H, int W, int ks, const bf16_t* residual, void* out, int out_f32) -> int {
+    GETW(w, A + k + ".weight"); GETV(b, A + k + ".bias");
+    GemmOpt o; o.bias = b; o.residual = residual; o.out_f32 = out_f32;
+    return run_conv(c, st, src, Cin, nullptr, 0, batch, H, W, *w, ks, out, o, c->zero_page);
+  };
+  int H = Lh, W = Lw;
+  Act a = alloc_act(c, batch, H, W, e.channels[0]); if (!a.p) return fail_ctx(c);
+  API_CK(c, conv("conv_in", x0, Cpad, H, W, 3, nullptr, a.p, 0));
+  for (int i = 0; i < e.n_channels; ++i) {
+    const std::string Bk = "body." + std::to_string(i) + ".";
+    const int co = e.channels[i];
+    if (i > 0) {
+      Act d = alloc_act(c, batch, H / 2, W / 2, a.C); if (!d.p) return fail_ctx(c);
+      { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_adapter_avgpool(a.p, d.p, batch, H, W, a.C, st)); }
+      a = d; H /= 2; W /= 2;
+    }
+    if (a.C != co) {
+      Act d = alloc_act(c, batch, H, W, co); if (!d.p) return fail_ctx(c);
+      API_CK(c, conv(Bk + "in_conv", a.p, a.C, H, W, 1, nullptr, d.p, 0));
+      a = d;
+    }
+    const size_t n = (size_t)batch * H * W * co;
+    API_CK(c, c->ad_featb[i].ensure(n * 4));
+    for (int j = 0; j < e.num_res_blocks; ++j) {
+      const std::string R = Bk + "resnets." + std::to_string(j) + ".";
+      const bool last = j + 1 == e.num_res_blocks;
+      Act t = alloc_act(c, batch, H, W, co), y = alloc_act(c, batch, H, W, co); if (!t.p || !y.p) return fail_ctx(c);
+      API_CK(c, conv(R + "block1", a.p, co, H, W, 3, nullptr, t.p, 0));
+      { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_adapter_relu(t.p, (long long)n, st)); }
+      if (!last) API_CK(c, conv(R + "block2", t.p, co, H, W, 1, a.p, y.p, 0));
+      else {
+        API_CK(c, conv(R + "block2", t.p, co, H, W, 1, a.p, c->ad_featb[i].p, 1));
+        if (i + 1 < e.n_channels) { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_f32_to_bf16(c->ad_featb[i].as<float>(), y.p, (long long)n, st)); }
+      }
+      a = y;
+    }
+  }
+  c->ad_B = batch; c->ad_Lh = Lh; c->ad_Lw = Lw;
+  return 0;
+}
+
+AGD_API int agd_adapter_features(agd_ctx* c, float* out) {
+  API_CK(c, need_final(c));
+  if (!c->ad_on || c->ad_B < 1) { agd_set_error("adapter_features: no features set (agd_adapter_set_cond_hw)"); return fail_ctx(c); }
+  if (!out) { agd_set_error("adapter_features: null out"); return fail_ctx(c); }
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("adapter_features: sync failed"); return fail_ctx(c); }   // (agd_adapter_set_cond_hw ran on the caller's stream)
+  size_t off = 0;
+  for (int i = 0; i < c->adc.n_channels; ++i) {
+    const int C = c->adc.channels[i], hw = (c->ad_Lh >> i) * (c->ad_Lw >> i);
+    API_CK(c, launch_nchw_from_nhwc_f32(c->ad_featb[i].as<float>(), C, out + off, c->ad_B, C, hw, 0));
+    off += (size_t)c->ad_B * C * hw;
+  }
+  if (hipStreamSynchronize(0) != hipSuccess) { agd_set_error("adapter_features: sync failed"); return fail_ctx(c); }
+  return 0;
+}
+
+AGD_API int agd_adapter_set_schedule(agd_ctx* c, const float* scales, int n) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  if (n < 0 || (n > 0 && !scales)) { agd_set_error("adapter_set_schedule: %d scales", n); return fail_ctx(c); }
+  if (n > 0 && !c->ad_on) { agd_set_error("adapter_set_schedule: no T2I-Adapter loaded"); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i) if (!std::isfinite(scales[i])) { agd_set_error("adapter_set_schedule: scale %d is %g", i, scales[i]); return fail_ctx(c); }
+  c->ad_sched.assign(scales, scales + n);
+  return 0;
+}
+
+AGD_API int agd_adapter_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  c->ad_sched.clear(); c->ad_B = 0; c->ad_Lh = c->ad_Lw = 0; c->ad_cur = 0.f;
+  return 0;
+}
+
+AGD_API int agd_adapter_add_counts(agd_ctx* c, long long* counts) {
+  if (!c || !counts) { agd_set_error("adapter_add_counts: null argument"); return fail_ctx(c); }
+  counts[0] = c->ad_adds[0]; counts[1] = c->ad_adds[1];
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------

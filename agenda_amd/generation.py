@@ -64,7 +64,8 @@ def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Opt
                    guidance_scale: float = 7.5, height: Optional[int] = None, rec_tokens: Optional[int] = None,
                    word_rows: Optional[Sequence[Sequence[int]]] = None, control: Optional[dict] = None, width: Optional[int] = None):
     """One hot-path pass: len(seeds) images + per-word DAAM maps.  control: extra keyword arguments of a ControlNet pipeline's call
-    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`), of an inpainting one
+    (`image`, `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end`), of a T2I-Adapter one (`image`,
+    `adapter_conditioning_scale`, `adapter_conditioning_factor`), of an inpainting one
     (`inpaint_inputs_for`) or of an InstructPix2Pix one (`ip2p_inputs_for`, with height and width the image's).
     Returns (uint8 images [B,H,W,3] on GPU, fp32 heat maps [B, n_words, H/8, W/8] on GPU)."""
     from .trace import trace
@@ -272,6 +273,12 @@ def parse_args(argv=None):
     p.add_argument("--controlnet-conditioning-scale", type=float, default=1.0)
     p.add_argument("--control-guidance-start", type=float, default=0.0)
     p.add_argument("--control-guidance-end", type=float, default=1.0)
+    p.add_argument("--adapter-model-path", type=str, default=None, help="a diffusers T2IAdapter directory: T2I-Adapter conditioned txt2img")
+    p.add_argument("--adapter-image", type=str, default=None,
+                   help="adapter conditioning image file (every seed), or a directory: seed s uses its sorted file s mod n")
+    p.add_argument("--adapter-conditioning-scale", type=float, default=1.0)
+    p.add_argument("--adapter-conditioning-factor", type=float, default=1.0,
+                   help="the share of the model evaluations, from the first on, that get the adapter's features")
     p.add_argument("--init-image", type=str, default=None,
                    help="inpainting: the image to paint into (a file for every seed, or a directory: seed s uses its sorted file s mod n)")
     p.add_argument("--mask-image", type=str, default=None,
@@ -319,6 +326,15 @@ def parse_args(argv=None):
             p.error(f"--image-guidance-scale {args.image_guidance_scale}: at least 1 (the no-guidance mode is not implemented)")
     if (args.controlnet_model_path is None) != (args.control_image is None):
         p.error("--controlnet-model-path and --control-image go together")
+    if (args.adapter_model_path is None) != (args.adapter_image is None):
+        p.error("--adapter-model-path and --adapter-image go together")
+    if args.adapter_model_path is None and (args.adapter_conditioning_scale != 1.0 or args.adapter_conditioning_factor != 1.0):
+        p.error("--adapter-conditioning-scale / --adapter-conditioning-factor need --adapter-model-path")
+    if not 0.0 <= args.adapter_conditioning_factor <= 1.0:
+        p.error("--adapter-conditioning-factor: 0 <= factor <= 1")
+    if args.adapter_model_path and (args.controlnet_model_path or args.init_image or args.instruct_image or args.gligen_phrases is not None
+                                    or args.gligen_layouts is not None or args.panorama):
+        p.error("--adapter-model-path with ControlNet, inpainting, InstructPix2Pix, GLIGEN or --panorama is not implemented")
     if not 0.0 <= args.control_guidance_start < args.control_guidance_end <= 1.0:
         p.error("--control-guidance-start / --control-guidance-end: 0 <= start < end <= 1")
     if args.use_karras_sigmas and args.scheduler != "DPMSolverMultistepScheduler":
@@ -424,6 +440,12 @@ def control_images_for(files: Sequence[str], seeds: Sequence[int]):
     return [Image.open(files[s % len(files)]).convert("RGB") for s in seeds]
 
 
+def adapter_images_for(files: Sequence[str], seeds: Sequence[int], in_channels: int = 3):
+    """The adapter's conditioning image of every seed (seed s takes file s mod n): "L" for a 1-channel adapter, else RGB."""
+    from PIL import Image
+    return [Image.open(files[s % len(files)]).convert("L" if in_channels == 1 else "RGB") for s in seeds]
+
+
 def inpaint_inputs_for(pairs: Sequence, seeds: Sequence[int], strength: float) -> dict:
     """The inpainting call's image / mask_image of every seed (seed s takes pair s mod n) and strength.  The start noise is the seeds'
     latents (generate_batch passes them); the VAE posterior draws come from a CPU generator seeded with the batch's first seed, so a
@@ -471,6 +493,12 @@ def main(argv=None):
         cls = StableDiffusionControlNetPipeline
         kw["controlnet"] = ControlNetModel.from_pretrained(args.controlnet_model_path)
         cn_files = control_image_files(args.control_image)
+    ad_files = None
+    if args.adapter_model_path:
+        from .adapter import StableDiffusionAdapterPipeline, T2IAdapter
+        cls = StableDiffusionAdapterPipeline
+        kw["adapter"] = T2IAdapter.from_pretrained(args.adapter_model_path)
+        ad_files = control_image_files(args.adapter_image)
     ip_files = None
     if args.init_image:
         from .inpaint import StableDiffusionInpaintPipeline
@@ -489,7 +517,7 @@ def main(argv=None):
     pipe = (cls.from_pretrained(args.pretrained_model_path, device=local, scheduler=args.scheduler, **kw)
             if args.pretrained_model_path else
             cls.from_synthetic(args.synthetic_config, device=local, scheduler=args.scheduler or "DDIMScheduler",
-                               **({"controlnet": kw["controlnet"]} if cn_files else {})))
+                               **({"controlnet": kw["controlnet"]} if cn_files else {}), **({"adapter": kw["adapter"]} if ad_files else {})))
     if args.lora_path:
         pipe.load_lora_weights(args.lora_path, weight_name=args.lora_weight_name)
         pipe.fuse_lora(lora_scale=args.lora_scale)
@@ -519,6 +547,9 @@ def main(argv=None):
             if cn_files:
                 control = {"image": control_images_for(cn_files, chunk), "controlnet_conditioning_scale": args.controlnet_conditioning_scale,
                            "control_guidance_start": args.control_guidance_start, "control_guidance_end": args.control_guidance_end}
+            if ad_files:
+                control = {"image": adapter_images_for(ad_files, chunk, pipe.adapter_cfg.in_channels),
+                           "adapter_conditioning_scale": args.adapter_conditioning_scale, "adapter_conditioning_factor": args.adapter_conditioning_factor}
             if ip_files:
                 control = inpaint_inputs_for(ip_files, chunk, args.strength)
             if gl_layouts is not None:

@@ -232,6 +232,62 @@ class Engine:
                                                       _lib.ptr(out), C.byref(n), self._stream()), "agd_controlnet_residuals_hw")
         return out
 
+    def adapter_configure(self, acfg):
+        self._adcfg = _lib.AgdAdapterConfig()
+        self._adcfg.struct_size = C.sizeof(_lib.AgdAdapterConfig)
+        if len(acfg.channels) > _lib.AGD_MAX_LEVELS:
+            raise ValueError(f"T2IAdapter channels has {len(acfg.channels)} entries (at most {_lib.AGD_MAX_LEVELS})")
+        self._adcfg.in_channels, self._adcfg.n_channels = int(acfg.in_channels), len(acfg.channels)
+        for i, c in enumerate(acfg.channels):
+            self._adcfg.channels[i] = int(c)
+        self._adcfg.num_res_blocks, self._adcfg.downscale_factor = int(acfg.num_res_blocks), int(acfg.downscale_factor)
+        self._ck(self.lib.agd_adapter_configure(self.ctx, C.byref(self._adcfg)), "agd_adapter_configure")
+
+    def adapter_set_cond(self, image: torch.Tensor):
+        """`agd_adapter_set_cond_hw`: the conditioning image uint8 [B,H,W,C] or float [B,C,H,W] in [0,1] -> the adapter's features, computed
+        once and kept for B images (UNet row image b reads feature image b % B)."""
+        f32 = image.dtype != torch.uint8
+        image = image.to(device=f"cuda:{self.device}", dtype=torch.float32 if f32 else torch.uint8).contiguous()
+        if image.ndim != 4:
+            raise ValueError(f"adapter image must be uint8 [B,H,W,C] or float [B,C,H,W], got {tuple(image.shape)}")
+        b = image.shape[0]
+        (c, h, w) = tuple(image.shape[1:]) if f32 else (image.shape[3], image.shape[1], image.shape[2])
+        if c != self._adcfg.in_channels:
+            raise ValueError(f"adapter image has {c} channels, the adapter takes {self._adcfg.in_channels}")
+        self._ck(self.lib.agd_adapter_set_cond_hw(self.ctx, C.c_void_p(image.data_ptr()), int(f32), b, h, w, self._stream()), "agd_adapter_set_cond_hw")
+        self._adapter_keepalive = image
+        r = self._adcfg.downscale_factor
+        self._adapter_shape = (b, h // r, w // r)
+
+    def adapter_features(self) -> List[torch.Tensor]:
+        """`agd_adapter_features`: the unscaled features of the last adapter_set_cond, fp32 [B, channels[i], Lh >> i, Lw >> i] (cuda)."""
+        if getattr(self, "_adapter_shape", None) is None:      # nothing set through this object: the engine says so
+            self._ck(self.lib.agd_adapter_features(self.ctx, None), "agd_adapter_features")
+        b, Lh, Lw = self._adapter_shape
+        shapes = [(b, self._adcfg.channels[i], Lh >> i, Lw >> i) for i in range(self._adcfg.n_channels)]
+        flat = torch.empty(sum(s[0] * s[1] * s[2] * s[3] for s in shapes), device=f"cuda:{self.device}", dtype=torch.float32)
+        self._ck(self.lib.agd_adapter_features(self.ctx, _lib.ptr(flat)), "agd_adapter_features")
+        out, off = [], 0
+        for s in shapes:
+            n = s[0] * s[1] * s[2] * s[3]
+            out.append(flat[off:off + n].view(s))
+            off += n
+        return out
+
+    def adapter_set_schedule(self, scales):
+        """Per-model-evaluation adapter scales of the next fused loop (or one-element: the next unet_forward); empty clears."""
+        self._ck(self.lib.agd_adapter_set_schedule(self.ctx, _floats(scales), len(scales)), "agd_adapter_set_schedule")
+
+    def adapter_clear(self):
+        self._ck(self.lib.agd_adapter_clear(self.ctx), "agd_adapter_clear")
+        self._adapter_shape = None
+
+    def adapter_add_counts(self):
+        """(adds that left GroupNorm partial sums, adds that did not) since the engine was created."""
+        n = (C.c_longlong * 2)()
+        self._ck(self.lib.agd_adapter_add_counts(self.ctx, n), "agd_adapter_add_counts")
+        return int(n[0]), int(n[1])
+
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
         self._glcfg = _lib.AgdGligenConfig()
         self._glcfg.struct_size = C.sizeof(_lib.AgdGligenConfig)

@@ -129,3 +129,12 @@ def make_controlnet_weights(cfg: SDConfig, cncfg=None, seed: int = 555, gain: fl
     from .config import ControlNetConfig, controlnet_param_shapes
     g = torch.Generator(device).manual_seed(seed)
     return _fill(controlnet_param_shapes(cfg.unet, cncfg or ControlNetConfig()), g, gain, bias_std, perturb_norm)
+
+
+def make_adapter_weights(cfg: SDConfig, acfg=None, seed: int = 777, gain: float = 1.0, bias_std: float = 0.0,
+                         device: str = "cpu") -> Dict[str, torch.Tensor]:
+    """Random T2I-Adapter weights (diffusers T2IAdapter key names) for `cfg.unet`: N(0, gain^2 / fan_in) matrices, biases N(0, bias_std^2)
+    (the adapter has no normalisation layers); bf16-representable."""
+    from .config import adapter_config_for, adapter_param_shapes
+    g = torch.Generator(device).manual_seed(seed)
+    return _fill(adapter_param_shapes(cfg.unet, acfg or adapter_config_for(cfg.unet)), g, gain, bias_std, 0.0)

@@ -159,6 +159,39 @@ int agd_ip2p_prepare_hw(agd_ctx* ctx, const void* image, int image_f32, int batc
 int agd_ip2p_set_hw(agd_ctx* ctx, const float* image_latents, int batch, int latent_h, int latent_w, float image_guidance, void* stream);
 int agd_ip2p_clear(agd_ctx* ctx);
 
+/* ---- T2I-Adapter (diffusers T2IAdapter "full_adapter" + StableDiffusionAdapterPipeline): a small convolutional network runs ONCE per call
+ * on the conditioning image -- PixelUnshuffle(downscale_factor), conv_in 3x3, then per entry of channels[] an AdapterBlock (2x2 average pool
+ * from the second block on, a 1x1 in_conv where the width changes, num_res_blocks x [x + conv1x1(relu(conv3x3(x)))]) -- and the output of
+ * block i, independent of the timestep, is added to the output of UNet down block i at every evaluation: after the block's last resnet /
+ * transformer, before that state becomes a skip and before the downsampler (the last, attention-free block: after the block, the same tensor
+ * being its last skip and the mid block's input).  Configured by agd_adapter_configure BEFORE agd_finalize; weights through agd_load_tensor
+ * as "adapter." + diffusers state-dict key ("adapter.adapter.conv_in.weight", "adapter.adapter.body.1.in_conv.weight", ...).  agd_finalize
+ * needs len(channels) == n_levels, channels[i] == block_out_channels[i] and downscale_factor == the VAE's downscale. */
+typedef struct agd_adapter_config {
+  int struct_size;                 /* sizeof(agd_adapter_config), ABI guard */
+  int in_channels;                 /* channels of the conditioning image (3, or 1 for sketch-style adapters) */
+  int n_channels;                  /* len(channels), 1 .. AGD_MAX_LEVELS */
+  int channels[AGD_MAX_LEVELS];
+  int num_res_blocks;
+  int downscale_factor;
+} agd_adapter_config;
+int agd_adapter_configure(agd_ctx* ctx, const agd_adapter_config* acfg);
+/* the conditioning image, device pointer: uint8 NHWC [batch,h,w,in_channels] (image_f32 = 0: x / 255) or fp32 NCHW [batch,in_channels,h,w]
+ * already in [0,1] (image_f32 = 1).  Runs the adapter once and keeps its UNSCALED features as fp32 for `batch` images at latent size
+ * h / downscale_factor x w / downscale_factor; UNet row image b reads feature image b % batch (both CFG halves the same features). */
+int agd_adapter_set_cond_hw(agd_ctx* ctx, const void* image, int image_f32, int batch, int h, int w, void* stream);
+/* the features of the last agd_adapter_set_cond_hw, back to back, each fp32 NCHW [batch][channels[i]][Lh >> i][Lw >> i] (device; syncs) */
+int agd_adapter_features(agd_ctx* ctx, float* out);
+/* per-model-evaluation scales (adapter_conditioning_scale where the features are added, 0 where they are not), host array of n floats,
+ * consumed by the next agd_denoise_hw / agd_denoise_plms_hw / agd_denoise_dpm_hw (n must equal its evaluation count) or agd_unet_forward
+ * (n = 1).  A scale of exactly 0 runs the plain UNet for that evaluation; n = 0 clears the schedule.  While a schedule is set, ControlNet and
+ * GLIGEN schedules, inpainting and InstructPix2Pix states, agd_denoise_panorama and agd_unet_forward_ts are refused. */
+int agd_adapter_set_schedule(agd_ctx* ctx, const float* scales, int n);
+int agd_adapter_clear(agd_ctx* ctx);                 /* the schedule and the per-call features */
+/* seam for tests: the adds launched since agd_create -- counts[0] with GroupNorm partial sums left for the next norm, counts[1] without
+ * (maps with no legal statistics tile, or "gn_fused_stats" off: the norm runs its own statistics pass) */
+int agd_adapter_add_counts(agd_ctx* ctx, long long* counts);
+
 /* ---- GLIGEN (diffusers StableDiffusionGLIGENPipeline, a UNet of attention_type "gated"): a PositionNet turns per-object phrase
  * embeddings and boxes into grounding tokens, and a GatedSelfAttentionDense ("fuser") in every transformer block, after attn1's residual
  * add, attends over the block's rows plus those tokens:  x += tanh(alpha_attn) attn(norm1([x; o]))[:N];  x += tanh(alpha_dense) ff(norm2(x)).
