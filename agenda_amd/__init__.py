@@ -2,7 +2,7 @@
 Stable-Diffusion UNet denoise loop + DAAM cross-attention heat maps + VAE decode, as hand-written
 HIP kernels behind a C ABI (include/agenda_hip.h), with the Python call surfaces the reference
 scripts use (StableDiffusionPipeline, daam.trace, the attention-processor hooker)."""
-from . import config, synthetic  # noqa: F401
+from . import config, synthetic, ip_adapter  # noqa: F401
 from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine  # noqa: F401
 from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indices  # noqa: F401
 from .hook import UNetCrossAttentionHooker  # noqa: F401
@@ -15,7 +15,7 @@ from .gligen import StableDiffusionGLIGENPipeline  # noqa: F401
 from .panorama import StableDiffusionPanoramaPipeline, get_views  # noqa: F401
 
 __all__ = ["StableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
-           "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic",
+           "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic", "ip_adapter",
            "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
            "StableDiffusionInpaintPipeline",
            "StableDiffusionInstructPix2PixPipeline",

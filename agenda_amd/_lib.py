@@ -110,6 +110,20 @@ _SIGS = {
     "agd_adapter_set_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "agd_adapter_clear": (C.c_int, [_P]),
     "agd_adapter_add_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "agd_ip_adapter_begin": (C.c_int, [_P, C.c_int, C.c_int]),
+    "agd_ip_adapter_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "agd_ip_adapter_commit": (C.c_int, [_P]),
+    "agd_ip_adapter_unload": (C.c_int, [_P]),
+    "agd_ip_adapter_set": (C.c_int, [_P, _P, C.c_int, C.c_float, _P]),
+    "agd_ip_adapter_clear": (C.c_int, [_P]),
+    "agd_ip_adapter_tokens": (C.c_int, [_P, _P]),
+    "agd_ip_adapter_block": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "agd_ip_adapter_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "agd_image_encoder_begin": (C.c_int, [_P, C.POINTER(AgdVisionConfig)]),
+    "agd_image_encoder_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "agd_image_encoder_commit": (C.c_int, [_P]),
+    "agd_image_encoder_unload": (C.c_int, [_P]),
+    "agd_image_embeds": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "agd_gligen_configure": (C.c_int, [_P, C.POINTER(AgdGligenConfig)]),
     "agd_gligen_set": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "agd_gligen_set_schedule": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),

@@ -260,6 +260,27 @@ int launch_adapter_avgpool(const bf16_t* x, bf16_t* y, int B, int H, int W, int 
 int launch_adapter_relu(bf16_t* x, long long n, hipStream_t st);
 int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, int bm, int B2, int HW, int C, int Bf, float s, hipStream_t st);
 
+// IP-Adapter (ipadapter.hip): the once-per-call pieces (fp32 rows against bf16 matrices: y = x W^T + bias, an in-place fp32 LayerNorm, the
+// pre-multiplied per-image matrices of one attn2 layer) and the two per-forward stages.  col = (head, token); colsP = heads * nt padded to 16.
+#define IPA_MAX_COLS 80
+int launch_ipa_linear(const float* x, const bf16_t* W, const float* bias, float* y, int R, int N, int K, hipStream_t st);
+int launch_ipa_layernorm(float* x, const float* g, const float* b, int rows, int C, float eps, hipStream_t st);
+struct IpaPremulP {
+  const float* kip; const float* vip;               // to_k_ip / to_v_ip of the tokens, fp32 [B][nt][C]
+  const bf16_t* wq; const bf16_t* wo;               // attn2.to_q / attn2.to_out.0, raw [C][C]
+  const float* gamma; const float* wqb;             // norm2.weight [C]; Wq . norm2.bias [C]
+  int B, C, H, nt, colsP; float scale;              // scale = 1 / sqrt(C / H)
+  bf16_t* kpp; float* cs; float* bs; bf16_t* vpp;   // [B][colsP][C], [B][colsP], [B][colsP], [B][C][colsP]
+};
+int launch_ipa_premul(const IpaPremulP& p, hipStream_t st);
+// P[b HW + r][col] = softmax over each head's nt columns of rstd_r (h[r] . K''[b][col] - mu_r cs[b][col]) + bs[b][col] (bf16, padded columns zero);
+// mean / rstd from the row itself
+struct IpaScoreP { const bf16_t* h; const bf16_t* kpp; const float* cs; const float* bs; bf16_t* P; int B, HW, C, H, nt, colsP; float eps; };
+int launch_ipa_scores(const IpaScoreP& p, hipStream_t st);
+// h[b HW + r][n] += s sum_col P[b HW + r][col] V''[b][n][col], in place
+struct IpaAddP { bf16_t* h; const bf16_t* P; const bf16_t* vpp; int B, HW, C, colsP; float s; };
+int launch_ipa_add(const IpaAddP& p, hipStream_t st);
+
 // MultiDiffusion panorama (panorama.hip): views of win x win at (i stride, j stride), view v = i nbw + j; image of (panorama p, view v) in a view
 // buffer = p * pano_stride + v * view_stride images of [C][win][win] fp32.  gather: views [v0, v0 + n) of every panorama out of the canvas
 // [B][C][Lh][Lw] (view v lands at slot v - v0); mean: canvas element = the fp32 sum of its covering views in ascending view order / their number
@@ -295,7 +316,7 @@ int launch_vis_patchify(const unsigned char* img, int B, int S, int ps, int Kpad
 int launch_vis_embed_ln(const float* pe, const float* cls, const float* pos, const float* gamma, const float* beta, int B, int np, int H,
                         float eps, bf16_t* x, hipStream_t st);
 int launch_vis_pooled_head(const bf16_t* x, int B, int T, int H, const float* gamma, const float* beta, float eps, const float* Wp, int P,
-                           const float* E, int n, float* cos_out, hipStream_t st);
+                           const float* E, int n, float* cos_out, float* emb_out, hipStream_t st);   // emb_out (optional): the projected embeddings [B][P]; n = 0: no cosines
 
 // ---------------------------------------------------------------------------------------
 // LoRA merge (lora.hip): one descriptor per target matrix, its 64 x 64 output tiles numbered from tile0 (ascending across descriptors)

@@ -90,6 +90,13 @@ struct Fuser {
   DBuf gkvb;
 };
 
+// one attn2 layer's IP-Adapter parts ("<pre>transformer_blocks.0.attn2.to_k_ip / to_v_ip.weight" bf16 [C][cross_attention_dim]) and its per-call
+// pre-multiplied matrices K'' [B2][cols][C], V'' [B2][C][cols] (bf16), cs | bs [2][B2][cols] (ipadapter.hip)
+struct IpaLayer {
+  std::string pre; int C = 0, heads = 0, cols = 0;
+  DBuf wk, wv, kppb, vppb, csbsb;
+};
+
 // agd_set_option("tblock_fuse"): the fused row-panel kernels of the transformer blocks (tblock.hip).  Read by tblock_plan() alone.
 enum : int {
   TBF_FF            = 1 << 0,    // C = 320: norm3 -> GEGLU -> ff.net.2 + residual in one launch
@@ -171,6 +178,8 @@ struct agd_ctx {
                                                       // bit 5: the 1x1 launches of one 128 x 160 tile per CU (M = 8192, N = 640) on igemm_pc.h's 128-row form
   // safety checker (agd_safety_configure): the CLIP vision tower's config, its fp32 concept rows (special-care rows first, L2-normalised at finalize)
   agd_vision_config vis{}; bool vis_on = false; float* vis_concepts = nullptr;
+  // the IP-Adapter's image encoder (agd_image_encoder_begin .. commit, after agd_finalize): weights "image_encoder.*"; ienc_state 0 none, 1 loading, 2 ready
+  agd_vision_config ienc{}; int ienc_state = 0;
   int opt_xpre = 1;                                   // agd_set_option("attn2_premul"): attn2 of the C = 1280 blocks as two GEMMs against per-image pre-multiplied context matrices (xattn_pre.hip)
   int opt_touch = 3;                                  // agd_set_option("weight_touch"): n > 0 = stream 1x1 weight matrices of >= n MB through the caches right before their launch
   unsigned* touch_sink = nullptr;
@@ -208,12 +217,30 @@ struct agd_ctx {
   agd_adapter_config adc{}; bool ad_on = false;
   DBuf ad_featb[AGD_MAX_LEVELS]; int ad_B = 0, ad_Lh = 0, ad_Lw = 0;
   std::vector<float> ad_sched; float ad_cur = 0.f; long long ad_adds[2] = {0, 0};
+  // IP-Adapter (agd_ip_adapter_begin .. commit, after agd_finalize): the image projection and, per UNet attn2 layer (ipa_idx: block prefix ->
+  // index), to_k_ip / to_v_ip; ipa_t: what agd_ip_adapter_tensor has received so far (name -> shape).  Per call (agd_ip_adapter_set): the
+  // projected tokens fp32 [ipa_B2][ipa_nt][cross_attention_dim], every layer's pre-multiplied matrices and the scale; ipa_stale: a LoRA scale
+  // change rewrote to_q / to_out after they were built; ipa_active: the forward being walked runs the two stages; ipa_counts: score / add launches
+  bool ipa_loading = false, ipa_on = false; int ipa_E = 0, ipa_nt = 0;
+  DBuf ipa_projw, ipa_projb, ipa_ng, ipa_nb;
+  std::unordered_map<std::string, std::vector<long long>> ipa_t;
+  std::vector<IpaLayer> ipa_l; std::unordered_map<std::string, int> ipa_idx;
+  DBuf ipa_embb, ipa_tokb, ipa_kipb, ipa_vipb, ipa_wqbb;
+  int ipa_B2 = 0; float ipa_scale = 0.f; bool ipa_stale = false, ipa_active = false; long long ipa_counts[2] = {0, 0};
   // profiling
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
 };
 
 static int fail_ctx(agd_ctx* c) { if (c) c->err = g_err; return -1; }
+// frees everything an IP-Adapter holds (weights and per-call state); the caller has synchronised
+static void ipa_release(agd_ctx* c) {
+  for (auto& l : c->ipa_l) { l.wk.release(); l.wv.release(); l.kppb.release(); l.vppb.release(); l.csbsb.release(); }
+  c->ipa_l.clear(); c->ipa_idx.clear(); c->ipa_t.clear();
+  for (DBuf* b : {&c->ipa_projw, &c->ipa_projb, &c->ipa_ng, &c->ipa_nb, &c->ipa_embb, &c->ipa_tokb, &c->ipa_kipb, &c->ipa_vipb, &c->ipa_wqbb}) b->release();
+  c->ipa_loading = c->ipa_on = false; c->ipa_E = c->ipa_nt = 0;
+  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->ipa_active = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
+}
 static inline int rec_images(const agd_ctx* c) { return c->rec_call > 0 ? c->rec_call : c->rec_B; }   // images a recording forward must have
 #define API_CK(c, expr) do { if ((expr) != 0) return fail_ctx(c); } while (0)
 
@@ -629,6 +656,7 @@ struct TBlockPlan {
   bool attn1_in_chain;             // attn1.to_out + residual run inside the attn2 chain launch, not as a GEMM of their own
   TbDup dup;
   const Fuser* fuser;              // GLIGEN: this evaluation runs the block's fuser (between the duplication and attn2)
+  const IpaLayer* ipa;             // IP-Adapter: this forward runs the block's image branch (scores on attn2's input, the add on its output)
   XLayer* xl;                      // the block's attn2 layer (null: not registered -- the attn2 stage refuses)
   TbAttn2 attn2; int chain_rows32;              // (AttnChainP::rows32)
   bool daam;                       // attn2 records into the DAAM accumulators (the chain and pre-multiplied forms; cross_attention() asks daam_records() itself)
@@ -637,6 +665,7 @@ struct TBlockPlan {
   // the GEMM that writes h leaves the row statistics its reader folds a LayerNorm with: proj_in for norm1; attn1.to_out, or the fuser's last
   // GEMM, for norm2 (the attn2 chain takes its own); attn2's last launch for norm3 (the fused feed-forward takes its own)
   bool stats_head, stats_attn1, stats_attn2;
+  bool stats_ipa;                  // IP-Adapter: the add stage takes norm3's statistics from the rows (in place of stats_attn2)
   // Not here, because they shape one launch and choose no path: consume()'s weight-streaming form of the C = 1280 GEGLU (opt "wreg_mask" bit 0,
   // by M) and the fused feed-forward's partial sums for the next GroupNorm (where `out` has room for them)
 };
@@ -653,6 +682,7 @@ struct TBlock {
   const bf16_t* xres;               // residual of proj_out
   int M; const int Mshared;         // rows until the duplication point (Mshared), B * HW after it
   float* stats = nullptr; int slots = 0;        // row statistics of the current h
+  bf16_t* ipaP = nullptr;           // IP-Adapter: the image branch's probabilities [M][cols] between its two stages
   TBlock(agd_ctx* c_, hipStream_t st_, const std::string& pre_, const Act& x_, Act& out_, int heads_, int groups_, int dup)
     : c(c_), st(st_), pre(pre_), t(pre_ + "transformer_blocks.0."), x(x_), out(out_), heads(heads_), groups(groups_), C(x_.C), HW(x_.H * x_.W),
       Bs(x_.B), B(dup ? 2 * x_.B : x_.B), xres(x_.p), M(x_.B * x_.H * x_.W), Mshared(M) {}
@@ -744,13 +774,19 @@ static TBlockPlan tblock_plan(const TBlock& s, int dup) {
   p.chain_rows32 = tb(TBF_ATTN2_ROWS32);
   // --- between them: the duplication of the CFG-shared prefix, the fuser, and where attn1.to_out runs ---
   if (c->gl_active) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) p.fuser = &c->gl_f[itf->second]; }
-  const bool lazy = dup && tb(TBF_LAZY_DUP) && chain && C == 320 && (p.ff == FF_FUSED_PROJ || p.ff == FF_FUSED_PREMUL) && !p.fuser;
+  if (c->ipa_active) { auto iti = c->ipa_idx.find(pre); if (iti != c->ipa_idx.end()) p.ipa = &c->ipa_l[iti->second]; }
+  const bool lazy = dup && tb(TBF_LAZY_DUP) && chain && C == 320 && (p.ff == FF_FUSED_PROJ || p.ff == FF_FUSED_PREMUL) && !p.fuser && !p.ipa;
   p.dup = !dup ? DUP_NONE : lazy ? DUP_LAZY : DUP_COPY;
-  p.attn1_in_chain = chain && tb(TBF_ATTN1_OUT) && p.dup != DUP_COPY && has(t + "attn1.to_out.frag") && !p.fuser;
-  p.stats_head = p.fold; p.stats_attn1 = p.fold && !chain; p.stats_attn2 = p.fold && !ff_fused;
+  p.attn1_in_chain = chain && tb(TBF_ATTN1_OUT) && p.dup != DUP_COPY && has(t + "attn1.to_out.frag") && !p.fuser && !p.ipa;
+  // (with the image branch the add stage takes norm3's statistics itself, from the rows as they are after the add: attn2's last launch leaves none)
+  p.stats_head = p.fold; p.stats_attn1 = p.fold && !chain; p.stats_attn2 = p.fold && !ff_fused && !p.ipa; p.stats_ipa = p.fold && !ff_fused && p.ipa;
   return p;
 }
 
+// IP-Adapter (c->ipa_active, a UNet block): the image branch reads attn2's INPUT rows, so -- as with the fuser -- that input must exist in
+// memory with all B rows: attn1.to_out stays a GEMM of its own and a CFG-shared prefix is duplicated by copies.  Whatever attn2 form the plan
+// picked then runs unchanged and in place, and the add lands on its output.  norm3's row statistics must describe h AFTER the add, so attn2's
+// last launch leaves none (stats_attn2 off) and tb_ip_adapter_add takes them from the rows (stats_ipa: one slot, launch_rowstat_bf16).
 // launch parameters of the qkv chain; wb / radd: the fold launch's per-image matrices and rows (HEAD_QKV)
 static int qkv_chain_params(const TBlock& s, const TBlockPlan& p, const bf16_t* wb, const float* radd, QkvChainP& qp) {
   agd_ctx* c = s.c; const Act& x = s.x; const int C = s.C;
@@ -830,6 +866,41 @@ static int tb_duplicate(TBlock& s, const TBlockPlan& p) {
 static int tb_fuser(TBlock& s, const TBlockPlan& p) {
   return fuser_rows(s.c, s.st, *p.fuser, s.h, s.B, s.HW, s.qkv, s.att,
                     [&](const bf16_t* A, int K, const WMat& w, const GemmOpt& o) { return s.produce(A, K, w, o, false, p.stats_attn1); });
+}
+
+// the two IP-Adapter stages on B images of HW rows (transformer() and agd_ip_adapter_block)
+static int ipa_scores_rows(agd_ctx* c, hipStream_t st, const IpaLayer& l, const bf16_t* h, int B, int HW, bf16_t* P) {
+  if (B != c->ipa_B2) FAIL("ip_adapter: the image tokens are set for %d rows, this forward has %d (agd_ip_adapter_set)", c->ipa_B2, B);
+  IpaScoreP sp{}; sp.h = h; sp.kpp = l.kppb.as<bf16_t>(); sp.cs = l.csbsb.as<float>(); sp.bs = sp.cs + (size_t)B * l.cols; sp.P = P;
+  sp.B = B; sp.HW = HW; sp.C = l.C; sp.H = l.heads; sp.nt = c->ipa_nt; sp.colsP = l.cols; sp.eps = 1e-5f;
+  const double M = (double)B * HW;
+  ProfScope ps(c, st, PC_ATTN_CROSS, 2.0 * M * l.cols * l.C, 2.0 * M * l.C + 2.0 * B * (double)l.cols * l.C + 2.0 * M * l.cols);
+  return launch_ipa_scores(sp, st);
+}
+static int ipa_add_rows(agd_ctx* c, hipStream_t st, const IpaLayer& l, bf16_t* h, int B, int HW, const bf16_t* P) {
+  IpaAddP ap{}; ap.h = h; ap.P = P; ap.vpp = l.vppb.as<bf16_t>(); ap.B = B; ap.HW = HW; ap.C = l.C; ap.colsP = l.cols; ap.s = c->ipa_scale;
+  const double M = (double)B * HW;
+  ProfScope ps(c, st, PC_ATTN_CROSS, 2.0 * M * l.cols * l.C, 4.0 * M * l.C + 2.0 * B * (double)l.cols * l.C + 2.0 * M * l.cols);
+  return launch_ipa_add(ap, st);
+}
+static int tb_ip_adapter_scores(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c;
+  if (s.C != p.ipa->C) FAIL("ip_adapter: %s has %d channels, its to_k_ip / to_v_ip were loaded for %d", s.pre.c_str(), s.C, p.ipa->C);
+  s.ipaP = (bf16_t*)c->arena.alloc((size_t)s.M * p.ipa->cols * 2); if (!s.ipaP) return -1;
+  CK(ipa_scores_rows(c, s.st, *p.ipa, s.h, s.B, s.HW, s.ipaP));
+  c->ipa_counts[0]++;
+  return 0;
+}
+static int tb_ip_adapter_add(TBlock& s, const TBlockPlan& p) {
+  agd_ctx* c = s.c;
+  CK(ipa_add_rows(c, s.st, *p.ipa, s.h, s.B, s.HW, s.ipaP));
+  c->ipa_counts[1]++;
+  if (p.stats_ipa) {                                     // norm3's folded consumer reads statistics of the rows as they are NOW
+    s.slots = 1; s.stats = (float*)c->arena.alloc((size_t)s.M * 2 * sizeof(float)); if (!s.stats) return -1;
+    ProfScope ps(c, s.st, PC_LN, 0, 2.0 * s.M * (double)s.C);
+    CK(launch_rowstat_bf16(s.h, s.stats, s.M, s.C, s.st));
+  }
+  return 0;
 }
 
 static int tb_attn2_chain(TBlock& s, const TBlockPlan& p) {
@@ -965,7 +1036,9 @@ static int transformer(agd_ctx* c, hipStream_t st, const std::string& pre, const
   CK(tb_self_attention(s, p));
   CK(tb_duplicate(s, p));
   if (p.fuser) CK(tb_fuser(s, p));
+  if (p.ipa) CK(tb_ip_adapter_scores(s, p));
   CK(tb_attn2(s, p));
+  if (p.ipa) CK(tb_ip_adapter_add(s, p));
   CK(tb_feed_forward(s, p));
   c->arena.release(mk);
   return 0;
@@ -1149,12 +1222,14 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
 // cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
 // grounded: the GLIGEN fusers run in the UNet's transformer blocks (agd_gligen_set_schedule)
 // ad_scale != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs (agd_adapter_set_schedule)
+// ipa: the IP-Adapter's image branch runs beside every UNet attn2 (agd_ip_adapter_set with a non-zero scale)
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
                      const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f, bool grounded = false,
-                     float ad_scale = 0.f) {
+                     float ad_scale = 0.f, bool ipa = false) {
   const agd_config& g = c->cfg;
   c->gl_active = grounded;
   c->ad_cur = ad_scale;
+  c->ipa_active = ipa;
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   const int nl = g.n_levels, G = g.norm_num_groups;
   const std::string u = "unet.";
@@ -1378,6 +1453,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   for (auto& f : c->gl_f) f.gkvb.release();
   c->gl_objb.release();
   for (auto& b : c->ad_featb) b.release();
+  ipa_release(c);
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
   if (c->splitk.p) hipFree(c->splitk.p);
   if (c->arena.base) hipFree(c->arena.base);
@@ -1408,7 +1484,7 @@ AGD_API int agd_load_tensor(agd_ctx* c, const char* name, const void* ptr, int d
     agd_set_error("'%s': call agd_gligen_configure before loading GLIGEN weights", name); return fail_ctx(c); }
   // the safety checker keeps everything but its encoder-layer matrices in fp32 as loaded (embeddings, the 14 x 14 patch conv, the
   // projection, the concept rows); agd_finalize checks their sizes and builds the padded patch matrix
-  const bool vis_f32 = k.compare(0, 7, "safety.") == 0 && !(ndim == 2 && k.find(".encoder.layers.") != std::string::npos);
+  const bool vis_f32 = (k.compare(0, 7, "safety.") == 0 || k.compare(0, 14, "image_encoder.") == 0) && !(ndim == 2 && k.find(".encoder.layers.") != std::string::npos);
   if (ndim == 1 || vis_f32 || (ndim == 0 && c->gl_on)) {            // (0-d: GLIGEN's alpha_attn / alpha_dense)
     float* d = dmalloc<float>(c, (size_t)n); if (!d) return fail_ctx(c);
     hipMemcpy(d, c->stage, bytes, hipMemcpyDeviceToDevice);
@@ -1466,43 +1542,56 @@ static int fuse_clip_qkv(agd_ctx* c, const std::string& prefix, int layers, bool
   return 0;
 }
 
-static const char* kVisPre = "safety.vision_model.vision_model.";
-// an fp32 safety tensor of exactly n elements
-static const float* getV_n(agd_ctx* c, const std::string& k, long long n) {
+// A CLIP vision tower with its projection (transformers CLIPVisionModelWithProjection), under the weight names of its owner: the safety
+// checker's ("safety.vision_model.vision_model.", config c->vis) or the IP-Adapter's image encoder ("image_encoder.vision_model.", c->ienc)
+struct VisTower { const agd_vision_config* v; std::string pre, proj, patch; const char* what; };
+static VisTower safety_tower(agd_ctx* c) { return {&c->vis, "safety.vision_model.vision_model.", "safety.visual_projection.weight", "safety.patch_matrix", "safety"}; }
+static VisTower image_tower(agd_ctx* c) { return {&c->ienc, "image_encoder.vision_model.", "image_encoder.visual_projection.weight", "image_encoder.patch_matrix", "image encoder"}; }
+// an fp32 vision tensor of exactly n elements
+static const float* getV_n(agd_ctx* c, const std::string& k, long long n, const char* what = "safety") {
   const float* p = getV(c, k); if (!p) return nullptr;
-  if (c->Vn[k] != n) { agd_set_error("'%s' has %d elements, the safety config needs %lld", k.c_str(), c->Vn[k], n); return nullptr; }
+  if (c->Vn[k] != n) { agd_set_error("'%s' has %d elements, the %s config needs %lld", k.c_str(), c->Vn[k], what, n); return nullptr; }
   return p;
 }
 
-static int finalize_safety(agd_ctx* c) {
-  const agd_vision_config& v = c->vis;
-  const std::string E = std::string(kVisPre) + "embeddings.";
-  const int H = v.hidden, ps = v.patch_size, g = v.image_size / ps, K = 3 * ps * ps, P = v.projection_dim, n = v.n_special + v.n_concepts;
-  const float* pw = getV_n(c, E + "patch_embedding.weight", (long long)H * K); if (!pw) return -1;
-  if (!getV_n(c, E + "class_embedding", H) || !getV_n(c, E + "position_embedding.weight", (long long)(g * g + 1) * H)) return -1;
+// checks every tensor of the tower against its config, fuses q/k/v per layer and builds the zero-padded patch matrix
+static int finalize_vision(agd_ctx* c, const VisTower& t) {
+  const agd_vision_config& v = *t.v;
+  const char* kVisPre = t.pre.c_str(); const char* what = t.what;
+  const std::string E = t.pre + "embeddings.";
+  const int H = v.hidden, ps = v.patch_size, g = v.image_size / ps, K = 3 * ps * ps, P = v.projection_dim;
+  const float* pw = getV_n(c, E + "patch_embedding.weight", (long long)H * K, what); if (!pw) return -1;
+  if (!getV_n(c, E + "class_embedding", H, what) || !getV_n(c, E + "position_embedding.weight", (long long)(g * g + 1) * H, what)) return -1;
   for (const char* ln : {"pre_layrnorm.", "post_layernorm."})
-    for (const char* wb : {"weight", "bias"}) if (!getV_n(c, std::string(kVisPre) + ln + wb, H)) return -1;
-  if (!getV_n(c, "safety.visual_projection.weight", (long long)P * H)) return -1;
-  const float* sp = getV_n(c, "safety.special_care_embeds", (long long)v.n_special * P); if (!sp) return -1;
-  const float* cp = getV_n(c, "safety.concept_embeds", (long long)v.n_concepts * P); if (!cp) return -1;
+    for (const char* wb : {"weight", "bias"}) if (!getV_n(c, std::string(kVisPre) + ln + wb, H, what)) return -1;
+  if (!getV_n(c, t.proj, (long long)P * H, what)) return -1;
   for (int l = 0; l < v.layers; ++l) {
     const std::string L = std::string(kVisPre) + "encoder.layers." + std::to_string(l) + ".";
     for (const char* m : {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "mlp.fc1", "mlp.fc2"}) {
       const WMat* w = getW(c, L + m + ".weight"); if (!w) return -1;
       const bool fc1 = !strcmp(m, "mlp.fc1"), fc2 = !strcmp(m, "mlp.fc2");
       const int want_n = fc1 ? v.intermediate : H, want_k = fc2 ? v.intermediate : H;
-      if (w->N != want_n || w->Cin != want_k) FAIL("'%s%s.weight' is [%d, %d], the safety config needs [%d, %d]", L.c_str(), m, w->N, w->Cin, want_n, want_k);
-      if (!getV_n(c, L + m + ".bias", want_n)) return -1;
+      if (w->N != want_n || w->Cin != want_k) FAIL("'%s%s.weight' is [%d, %d], the %s config needs [%d, %d]", L.c_str(), m, w->N, w->Cin, what, want_n, want_k);
+      if (!getV_n(c, L + m + ".bias", want_n, what)) return -1;
     }
     for (const char* ln : {"layer_norm1.", "layer_norm2."})
-      for (const char* wb : {"weight", "bias"}) if (!getV_n(c, L + ln + wb, H)) return -1;
+      for (const char* wb : {"weight", "bias"}) if (!getV_n(c, L + ln + wb, H, what)) return -1;
   }
   if (fuse_clip_qkv(c, std::string(kVisPre) + "encoder.layers.", v.layers)) return -1;
   // the 14 x 14 / 14 conv as a [H][Kpad] GEMM matrix, K = 3 ps ps zero-padded to the 64-multiple the implicit GEMM steps in
   { WMat w; w.N = H; w.Cin = K; w.taps = 1; w.Cpad = (K + 63) / 64 * 64;
     w.w = dmalloc<bf16_t>(c, (size_t)w.N * w.Cpad); if (!w.w) return -1;
     if (launch_convert_weight(pw, w.w, w.N, K, 1, w.Cpad, 0, 0)) return -1;
-    c->W["safety.patch_matrix"] = w; }
+    c->W[t.patch] = w; }
+  return 0;
+}
+
+static int finalize_safety(agd_ctx* c) {
+  const agd_vision_config& v = c->vis;
+  const int P = v.projection_dim, n = v.n_special + v.n_concepts;
+  if (finalize_vision(c, safety_tower(c))) return -1;
+  const float* sp = getV_n(c, "safety.special_care_embeds", (long long)v.n_special * P); if (!sp) return -1;
+  const float* cp = getV_n(c, "safety.concept_embeds", (long long)v.n_concepts * P); if (!cp) return -1;
   // concept rows, L2-normalised once (cosine_distance normalises both sides; the image side is normalised per call)
   std::vector<float> rows((size_t)n * P);
   if (hipMemcpy(rows.data(), sp, (size_t)v.n_special * P * 4, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -2027,6 +2116,26 @@ static int adapter_for(agd_ctx* c, int n, int rows, int Lh, int Lw, const float*
   *out = c->ad_sched.data();
   return 0;
 }
+// The IP-Adapter state of a call on B2 rows: *on = the image branch runs.  Nothing set, or scale 0: the plain UNet, whatever else is set.
+// Otherwise nothing else that changes the walk may be set, the products must be current and built for exactly these rows.
+static int ipa_for(agd_ctx* c, int B2, bool* on) {
+  *on = false;
+  if (c->ipa_B2 < 1 || c->ipa_scale == 0.f) return 0;
+  if (!c->cn_sched.empty()) FAIL("ip_adapter: a ControlNet schedule is set; the IP-Adapter with a ControlNet is not implemented (clear one of them)");
+  if (!c->gl_sched.empty()) FAIL("ip_adapter: a GLIGEN schedule is set; the IP-Adapter with GLIGEN is not implemented (clear one of them)");
+  if (!c->ad_sched.empty()) FAIL("ip_adapter: a T2I-Adapter schedule is set; the IP-Adapter with a T2I-Adapter is not implemented (clear one of them)");
+  if (c->ip_mode != 0) FAIL("ip_adapter: an inpainting state is set; the IP-Adapter with inpainting is not implemented (agd_inpaint_clear first)");
+  if (c->i2_on) FAIL("ip_adapter: an InstructPix2Pix state is set; the IP-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)");
+  if (c->ipa_stale) FAIL("ip_adapter: a LoRA scale change rewrote to_q / to_out after the image products were built (call agd_ip_adapter_set again)");
+  if (c->ipa_B2 != B2) FAIL("ip_adapter: the image tokens are set for %d rows, this call runs %d (agd_ip_adapter_set)", c->ipa_B2, B2);
+  *on = true;
+  return 0;
+}
+// an entry point that runs the UNet alone
+static int ipa_refuse(agd_ctx* c, const char* what) {
+  if (c->ipa_B2 > 0 && c->ipa_scale != 0.f) FAIL("%s: an IP-Adapter image is set; %s runs without it (agd_ip_adapter_clear first)", what, what);
+  return 0;
+}
 // the inpaint state of a fused loop of n model evaluations on `batch` images at latent size Lh x Lw: *blend = the (sa, sb) schedule of the
 // 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
 static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float** blend) {
@@ -2079,8 +2188,10 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   API_CK(c, gl_schedule_for(c, 1, batch2, &gs));                             // a one-element GLIGEN schedule: one grounded forward
   const float* as = nullptr;
   API_CK(c, adapter_for(c, 1, batch2, Lh, Lw, &as));                         // a one-element T2I-Adapter schedule: one forward with the features added
+  bool ipa = false;
+  API_CK(c, ipa_for(c, batch2, &ipa));                                       // the IP-Adapter's image branch (agd_ip_adapter_set)
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0], as ? as[0] : 0.f));
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0], as ? as[0] : 0.f, ipa));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
 }
@@ -2097,6 +2208,7 @@ AGD_API int agd_unet_forward_ts_hw(agd_ctx* c, const float* sample, int batch2, 
   if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   if (!c->gl_sched.empty()) { agd_set_error("unet_forward_ts: a GLIGEN schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
   if (!c->ad_sched.empty()) { agd_set_error("unet_forward_ts: a T2I-Adapter schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
+  API_CK(c, ipa_refuse(c, "unet_forward_ts"));
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
@@ -2171,6 +2283,7 @@ static int ip2p_for(agd_ctx* c, int batch, int Lh, int Lw) {
   if (!c->gl_sched.empty()) FAIL("ip2p: a GLIGEN schedule is set; GLIGEN with InstructPix2Pix is not implemented (clear it first)");
   if (c->ip_mode != 0) FAIL("ip2p: an inpainting state is set; inpainting with InstructPix2Pix is not implemented (agd_inpaint_clear first)");
   if (!c->ad_sched.empty()) FAIL("ip2p: a T2I-Adapter schedule is set; the T2I-Adapter with InstructPix2Pix is not implemented (clear it first)");
+  CK(ipa_refuse(c, "ip2p"));
   return 0;
 }
 // The uncond walk of an InstructPix2Pix evaluation runs `rows` images against the first `rows` context rows -- the [uncond x B] half of the
@@ -2226,11 +2339,13 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   CK(inpaint_for(c, n, batch, Lh, Lw, &ib));
   const float* as = nullptr;                                       // the T2I-Adapter's per-evaluation scales (none: no feature is added)
   CK(adapter_for(c, n, batch, Lh, Lw, &as));
+  bool ipa = false;                                                // the IP-Adapter's image branch in every evaluation (none: the plain UNet)
+  CK(ipa_for(c, B2, &ipa));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
-    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i], as ? as[i] : 0.f));
+    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i], as ? as[i] : 0.f, ipa));
     CK(step(i, c->eps_nhwc));
     if (ib) CK(inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
   }
@@ -2319,6 +2434,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
   if (c->ip_mode != 0) { agd_set_error("denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)"); return fail_ctx(c); }
   if (c->i2_on) { agd_set_error("denoise_panorama: an InstructPix2Pix state is set; InstructPix2Pix on a panorama is not implemented (agd_ip2p_clear first)"); return fail_ctx(c); }
   if (!c->ad_sched.empty()) { agd_set_error("denoise_panorama: a T2I-Adapter schedule is set; the T2I-Adapter on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
+  API_CK(c, ipa_refuse(c, "denoise_panorama"));
   if (c->cfg.in_channels != c->cfg.out_channels) { agd_set_error("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels); return fail_ctx(c); }
   if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
   const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
@@ -3506,38 +3622,48 @@ AGD_API int agd_text_encode(agd_ctx* c, const int* input_ids, int B, int T, floa
 // ---------------------------------------------------------------------------------------
 // Safety checker (`pipeline.safety_checker`, data_generation.py:59-62): StableDiffusionSafetyChecker's CLIP vision tower + cosines
 // ---------------------------------------------------------------------------------------
+// what both towers need of their config; the head dim (64, or 80 for the image encoder) is the caller's check
+static int check_vision_config(const agd_vision_config* v, const char* who) {
+  if (v->hidden < 64 || v->hidden > 2048 || v->hidden % 64 || v->heads < 1 || v->hidden % v->heads)
+    FAIL("%s: hidden %d / heads %d unsupported (hidden a multiple of 64 up to 2048, head dim 64)", who, v->hidden, v->heads);
+  if (v->layers < 1 || v->intermediate < 64 || v->intermediate % 64 || v->act < 0 || v->act > 1)
+    FAIL("%s: layers %d / intermediate %d / act %d unsupported", who, v->layers, v->intermediate, v->act);
+  if (v->patch_size < 1 || v->image_size < v->patch_size || v->image_size % v->patch_size || v->image_size > 4096)
+    FAIL("%s: image_size %d / patch_size %d unsupported", who, v->image_size, v->patch_size);
+  if (v->projection_dim < 1 || v->hidden + v->projection_dim + 4 > 16384 || v->n_special < 0 || v->n_concepts < 0)
+    FAIL("%s: projection_dim %d / %d special / %d concepts unsupported", who, v->projection_dim, v->n_special, v->n_concepts);
+  for (int i = 0; i < 3; ++i) if (!(v->std[i] > 0.f)) FAIL("%s: image_std[%d] = %g", who, i, v->std[i]);
+  return 0;
+}
+
 AGD_API int agd_safety_configure(agd_ctx* c, const agd_vision_config* v) {
   if (!c) { agd_set_error("null ctx"); return -1; }
   if (!v || v->struct_size != (int)sizeof(agd_vision_config)) {
     agd_set_error("agd_safety_configure: bad config (struct_size %d != %zu)", v ? v->struct_size : -1, sizeof(agd_vision_config)); return fail_ctx(c); }
   if (c->finalized) { agd_set_error("agd_safety_configure: call it before agd_finalize"); return fail_ctx(c); }
-  if (v->hidden < 64 || v->hidden > 2048 || v->hidden % 64 || v->heads < 1 || v->hidden % v->heads || v->hidden / v->heads != 64)
+  API_CK(c, check_vision_config(v, "agd_safety_configure"));
+  if (v->hidden / v->heads != 64)
     { agd_set_error("agd_safety_configure: hidden %d / heads %d unsupported (hidden a multiple of 64 up to 2048, head dim 64)", v->hidden, v->heads); return fail_ctx(c); }
-  if (v->layers < 1 || v->intermediate < 64 || v->intermediate % 64 || v->act < 0 || v->act > 1)
-    { agd_set_error("agd_safety_configure: layers %d / intermediate %d / act %d unsupported", v->layers, v->intermediate, v->act); return fail_ctx(c); }
-  if (v->patch_size < 1 || v->image_size < v->patch_size || v->image_size % v->patch_size || v->image_size > 4096)
-    { agd_set_error("agd_safety_configure: image_size %d / patch_size %d unsupported", v->image_size, v->patch_size); return fail_ctx(c); }
-  if (v->projection_dim < 1 || v->hidden + v->projection_dim + 4 > 16384 || v->n_special < 0 || v->n_concepts < 0 || v->n_special + v->n_concepts < 1)
+  if (v->n_special + v->n_concepts < 1)
     { agd_set_error("agd_safety_configure: projection_dim %d / %d special / %d concepts unsupported", v->projection_dim, v->n_special, v->n_concepts); return fail_ctx(c); }
-  for (int i = 0; i < 3; ++i) if (!(v->std[i] > 0.f)) { agd_set_error("agd_safety_configure: image_std[%d] = %g", i, v->std[i]); return fail_ctx(c); }
   c->vis = *v; c->vis_on = true;
   return 0;
 }
 
-AGD_API int agd_safety_scores_hw(agd_ctx* c, const unsigned char* images, int B, int ih, int iw, float* cos_out, float* pixels_out, void* stream) {
-  API_CK(c, need_final(c));
-  hipStream_t st = S(stream);
-  if (!c->vis_on) { agd_set_error("safety checker not configured (agd_safety_configure before agd_finalize)"); return fail_ctx(c); }
-  const agd_vision_config& v = c->vis;
-  if (B < 1 || ih < 1 || iw < 1 || !images || !cos_out) { agd_set_error("safety_scores: batch %d size %d x %d / null buffer", B, ih, iw); return fail_ctx(c); }
+// The vision path shared by agd_safety_scores_hw and agd_image_embeds: CLIPImageProcessor on uint8 NHWC images (device), the patch
+// embedding, class / position embeddings + pre_layrnorm, the encoder layers, then the pooled head -- post_layernorm(CLS),
+// visual_projection, and either the cosines against `concepts` (n rows) or the projected embeddings themselves (emb_out), or both.
+static int vision_embed(agd_ctx* c, hipStream_t st, const VisTower& tw, const unsigned char* images, int B, int ih, int iw, float* pixels_out,
+                        const float* concepts, int n, float* cos_out, float* emb_out) {
+  const agd_vision_config& v = *tw.v;
+  const char* kVisPre = tw.pre.c_str();
   const int R = v.image_size, ps = v.patch_size, g = R / ps, np = g * g, T = np + 1, H = v.hidden, M = B * T;
-  const int n = v.n_special + v.n_concepts;
-  const std::string E = std::string(kVisPre) + "embeddings.";
-  const WMat* pw = getW(c, "safety.patch_matrix");
+  const std::string E = tw.pre + "embeddings.";
+  const WMat* pw = getW(c, tw.patch);
   const float* cls = getV(c, E + "class_embedding"); const float* pos = getV(c, E + "position_embedding.weight");
   const float* g0 = getV(c, std::string(kVisPre) + "pre_layrnorm.weight"); const float* b0 = getV(c, std::string(kVisPre) + "pre_layrnorm.bias");
   const float* gp = getV(c, std::string(kVisPre) + "post_layernorm.weight"); const float* bp = getV(c, std::string(kVisPre) + "post_layernorm.bias");
-  const float* wp = getV(c, "safety.visual_projection.weight");
+  const float* wp = getV(c, tw.proj);
   if (!pw || !cls || !pos || !g0 || !b0 || !gp || !bp || !wp) return fail_ctx(c);
   // scratch from the activation arena only (like agd_text_encode): the recorder accumulators, the cached context and the scheduler's
   // buffers are context-owned allocations this call never touches
@@ -3592,8 +3718,15 @@ AGD_API int agd_safety_scores_hw(agd_ctx* c, const unsigned char* images, int B,
   const ClipEnc enc{std::string(kVisPre) + "encoder.layers.", v.layers, H, v.heads, v.intermediate, v.act, v.eps, 0, PC_OTHER};
   API_CK(c, clip_encoder_layers(c, st, enc, B, T, x, h, qkv, att, ff));
   { ProfScope ps_(c, st, PC_OTHER, 2.0 * B * (double)v.projection_dim * (H + n), 4.0 * (double)v.projection_dim * (H + n));
-    API_CK(c, launch_vis_pooled_head(x, B, T, H, gp, bp, v.eps, wp, v.projection_dim, c->vis_concepts, n, cos_out, st)); }
+    API_CK(c, launch_vis_pooled_head(x, B, T, H, gp, bp, v.eps, wp, v.projection_dim, concepts, n, cos_out, emb_out, st)); }
   return 0;
+}
+
+AGD_API int agd_safety_scores_hw(agd_ctx* c, const unsigned char* images, int B, int ih, int iw, float* cos_out, float* pixels_out, void* stream) {
+  API_CK(c, need_final(c));
+  if (!c->vis_on) { agd_set_error("safety checker not configured (agd_safety_configure before agd_finalize)"); return fail_ctx(c); }
+  if (B < 1 || ih < 1 || iw < 1 || !images || !cos_out) { agd_set_error("safety_scores: batch %d size %d x %d / null buffer", B, ih, iw); return fail_ctx(c); }
+  return vision_embed(c, S(stream), safety_tower(c), images, B, ih, iw, pixels_out, c->vis_concepts, c->vis.n_special + c->vis.n_concepts, cos_out, nullptr);
 }
 AGD_API int agd_safety_scores(agd_ctx* c, const unsigned char* images, int B, int side, float* cos_out, float* pixels_out, void* stream) {
   return agd_safety_scores_hw(c, images, B, side, side, cos_out, pixels_out, stream);
@@ -4063,6 +4196,7 @@ static int lora_apply(agd_ctx* c, float s, hipStream_t st) {
   CK(lora_rederive(c));
   if (hipDeviceSynchronize() != hipSuccess) FAIL("lora: merge failed");
   c->lora_scale = s; c->lora_dirty = false; c->ctx_stale = true;
+  if (c->ipa_B2 > 0) c->ipa_stale = true;               // K'' / V'' of the image tokens were built from the old to_q / to_out
   return 0;
 }
 
@@ -4197,4 +4331,236 @@ AGD_API int agd_gligen_fuser(agd_ctx* c, const char* block_name, const float* x,
     return run_conv(c, st, A, K, nullptr, 0, 1, 1, M, wm, 1, hb, o, c->zero_page); }));
   API_CK(c, launch_bf16_to_f32(hb, out, (long long)M * C, st));
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// IP-Adapter (diffusers >= 0.24 load_ip_adapter / ip_adapter_image [upstream-knowledge]; ipadapter.hip): loaded into a finalised context like
+// a LoRA; once per call the image projection and every attn2 layer's pre-multiplied image matrices, then two stages per transformer block
+// (tb_ip_adapter_scores / tb_ip_adapter_add).  agd_attn_processor and agd_cross_attn (the seam) stay text-only.
+// ---------------------------------------------------------------------------------------
+static const char* kIpaProj[4] = {"image_proj.proj.weight", "image_proj.proj.bias", "image_proj.norm.weight", "image_proj.norm.bias"};
+static const char* kIpaK = "transformer_blocks.0.attn2.to_k_ip.weight";
+static const char* kIpaV = "transformer_blocks.0.attn2.to_v_ip.weight";
+
+AGD_API int agd_ip_adapter_begin(agd_ctx* c, int embed_dim, int n_tokens) {
+  API_CK(c, need_final(c));
+  if (c->ipa_on || c->ipa_loading) { agd_set_error("agd_ip_adapter_begin: an IP-Adapter is already loaded (one adapter at a time: agd_ip_adapter_unload first)"); return fail_ctx(c); }
+  if (embed_dim < 1 || embed_dim > 8192 || n_tokens < 1 || n_tokens > 16) { agd_set_error("agd_ip_adapter_begin: embed_dim %d (1 .. 8192) / n_tokens %d (1 .. 16)", embed_dim, n_tokens); return fail_ctx(c); }
+  for (auto& pr : transformer_prefixes(c)) {
+    if (pr.first.compare(0, 5, "unet.") != 0) continue;            // the ControlNet's attn2 layers take no image branch
+    auto it = c->xl_idx.find(pr.first + "transformer_blocks.0.attn2");
+    if (it == c->xl_idx.end()) { agd_set_error("agd_ip_adapter_begin: cross-attn layer of %s not registered", pr.first.c_str()); ipa_release(c); return fail_ctx(c); }
+    const XLayer& xl = c->xl[it->second];
+    IpaLayer l; l.pre = pr.first; l.C = xl.C; l.heads = xl.heads; l.cols = (xl.heads * n_tokens + 15) / 16 * 16;
+    if (l.cols > IPA_MAX_COLS || l.C % 8) {
+      agd_set_error("agd_ip_adapter_begin: %s: %d heads x %d tokens (at most %d columns) / C %d", pr.first.c_str(), xl.heads, n_tokens, IPA_MAX_COLS, l.C); ipa_release(c); return fail_ctx(c); }
+    c->ipa_idx[l.pre] = (int)c->ipa_l.size(); c->ipa_l.push_back(l);
+  }
+  c->ipa_E = embed_dim; c->ipa_nt = n_tokens; c->ipa_loading = true;
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_tensor(agd_ctx* c, const char* name, const void* ptr, int dtype, int ndim, const long long* shape) {
+  API_CK(c, need_final(c));
+  if (!c->ipa_loading) { agd_set_error("agd_ip_adapter_tensor: call agd_ip_adapter_begin first"); return fail_ctx(c); }
+  if (!name || !ptr || !shape) { agd_set_error("agd_ip_adapter_tensor: null argument"); return fail_ctx(c); }
+  if (dtype != 0) { agd_set_error("agd_ip_adapter_tensor: only float32 (dtype 0) supported"); return fail_ctx(c); }
+  if (ndim < 1 || ndim > 2) { agd_set_error("agd_ip_adapter_tensor: '%s': ndim %d (1 or 2)", name, ndim); return fail_ctx(c); }
+  std::string k(name);
+  DBuf* dst = nullptr; bool mat = false;
+  for (int i = 0; i < 4; ++i) if (k == kIpaProj[i]) { dst = i == 0 ? &c->ipa_projw : i == 1 ? &c->ipa_projb : i == 2 ? &c->ipa_ng : &c->ipa_nb; mat = i == 0; }
+  if (!dst) {
+    if (k.compare(0, 5, "unet.") != 0) k = "unet." + k;
+    for (auto& l : c->ipa_l) {
+      if (k == l.pre + kIpaK) { dst = &l.wk; mat = true; }
+      else if (k == l.pre + kIpaV) { dst = &l.wv; mat = true; }
+    }
+  }
+  if (!dst) { agd_set_error("agd_ip_adapter_tensor: '%s' is not an IP-Adapter tensor (image_proj.proj / norm, <unet block>.transformer_blocks.0.attn2.to_k_ip / to_v_ip.weight)", name); return fail_ctx(c); }
+  if ((ndim == 2) != mat) { agd_set_error("agd_ip_adapter_tensor: '%s': ndim %d", name, ndim); return fail_ctx(c); }
+  long long n = 1; for (int i = 0; i < ndim; ++i) { if (shape[i] < 1 || shape[i] > (1 << 24)) { agd_set_error("agd_ip_adapter_tensor: '%s': bad shape", name); return fail_ctx(c); } n *= shape[i]; }
+  if (n > (1ll << 28)) { agd_set_error("agd_ip_adapter_tensor: '%s': %lld elements", name, n); return fail_ctx(c); }
+  const size_t bytes = (size_t)n * 4;
+  if (bytes > c->stage_bytes) {
+    if (c->stage) hipFree(c->stage);
+    if (hipMalloc((void**)&c->stage, bytes) != hipSuccess) { c->stage = nullptr; c->stage_bytes = 0; agd_set_error("stage alloc failed"); return fail_ctx(c); }
+    c->stage_bytes = bytes;
+  }
+  if (hipMemcpy(c->stage, ptr, bytes, hipMemcpyDefault) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
+  API_CK(c, dst->ensure(mat ? (size_t)n * 2 : bytes));
+  if (mat) API_CK(c, launch_f32_to_bf16(c->stage, dst->as<bf16_t>(), n, 0));
+  else if (hipMemcpy(dst->p, c->stage, bytes, hipMemcpyDeviceToDevice) != hipSuccess) { agd_set_error("copy of '%s' failed", name); return fail_ctx(c); }
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("agd_ip_adapter_tensor: '%s': upload failed", name); return fail_ctx(c); }
+  c->ipa_t[k] = std::vector<long long>(shape, shape + ndim);
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_commit(agd_ctx* c) {
+  API_CK(c, need_final(c));
+  if (!c->ipa_loading) { agd_set_error("agd_ip_adapter_commit: call agd_ip_adapter_begin first"); return fail_ctx(c); }
+  const long long Dc = c->cfg.cross_attention_dim, E = c->ipa_E, nt = c->ipa_nt;
+  std::string bad;
+  auto want = [&](const std::string& k, std::vector<long long> shp) {
+    auto it = c->ipa_t.find(k);
+    if (it == c->ipa_t.end()) { bad += (bad.empty() ? "" : ", ") + k + " (missing)"; return; }
+    if (it->second != shp) {
+      std::string g, w; for (long long v : it->second) g += (g.empty() ? "" : ", ") + std::to_string(v); for (long long v : shp) w += (w.empty() ? "" : ", ") + std::to_string(v);
+      bad += (bad.empty() ? "" : ", ") + k + " ([" + g + "], expected [" + w + "])";
+    }
+  };
+  want(kIpaProj[0], {nt * Dc, E}); want(kIpaProj[1], {nt * Dc}); want(kIpaProj[2], {Dc}); want(kIpaProj[3], {Dc});
+  for (auto& l : c->ipa_l) { want(l.pre + kIpaK, {l.C, Dc}); want(l.pre + kIpaV, {l.C, Dc}); }
+  if (!bad.empty()) { agd_set_error("agd_ip_adapter_commit: %s", bad.c_str()); return fail_ctx(c); }
+  c->ipa_loading = false; c->ipa_on = true;
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_unload(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  hipSetDevice(c->device);
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("agd_ip_adapter_unload: sync failed"); return fail_ctx(c); }
+  ipa_release(c);
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_set(agd_ctx* c, const float* image_embeds, int batch2, float scale, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->ipa_on) { agd_set_error("ip_adapter_set: no IP-Adapter loaded (agd_ip_adapter_begin .. agd_ip_adapter_commit)"); return fail_ctx(c); }
+  if (!image_embeds || batch2 < 1 || batch2 > 4096) { agd_set_error("ip_adapter_set: bad arguments (batch2 %d)", batch2); return fail_ctx(c); }
+  if (!std::isfinite(scale)) { agd_set_error("ip_adapter_set: scale %g", (double)scale); return fail_ctx(c); }
+  if (c->lora_dirty) { agd_set_error("ip_adapter_set: a LoRA was added and not merged yet (agd_lora_set_scale first)"); return fail_ctx(c); }
+  const int Dc = c->cfg.cross_attention_dim, E = c->ipa_E, nt = c->ipa_nt, rows = batch2 * nt;
+  c->ipa_B2 = 0;                                                   // (unset until every layer's matrices are written)
+  int Cmax = 0; for (auto& l : c->ipa_l) Cmax = std::max(Cmax, l.C);
+  API_CK(c, c->ipa_embb.ensure((size_t)batch2 * E * 4)); API_CK(c, c->ipa_tokb.ensure((size_t)rows * Dc * 4));
+  API_CK(c, c->ipa_kipb.ensure((size_t)rows * Cmax * 4)); API_CK(c, c->ipa_vipb.ensure((size_t)rows * Cmax * 4)); API_CK(c, c->ipa_wqbb.ensure((size_t)Cmax * 4));
+  if (hipMemcpyAsync(c->ipa_embb.p, image_embeds, (size_t)batch2 * E * 4, hipMemcpyDefault, st) != hipSuccess) { agd_set_error("ip_adapter_set: copy of the embeddings failed"); return fail_ctx(c); }
+  float* tok = c->ipa_tokb.as<float>();
+  { ProfScope ps(c, st, PC_OTHER, 2.0 * batch2 * (double)nt * Dc * E);
+    API_CK(c, launch_ipa_linear(c->ipa_embb.as<float>(), c->ipa_projw.as<bf16_t>(), c->ipa_projb.as<float>(), tok, batch2, nt * Dc, E, st));
+    API_CK(c, launch_ipa_layernorm(tok, c->ipa_ng.as<float>(), c->ipa_nb.as<float>(), rows, Dc, 1e-5f, st)); }
+  for (auto& l : c->ipa_l) {
+    const std::string t = l.pre + "transformer_blocks.0.";
+    const WMat* wq = getW(c, t + "attn2.to_q.weight"); const WMat* wo = getW(c, t + "attn2.to_out.0.weight");
+    const float* g2 = getV(c, t + "norm2.weight"); const float* b2 = getV(c, t + "norm2.bias");
+    if (!wq || !wo || !g2 || !b2) return fail_ctx(c);
+    const int C = l.C;
+    if (wq->taps != 1 || wq->N != C || wq->Cpad != C || wo->taps != 1 || wo->N != C || wo->Cpad != C) {
+      agd_set_error("ip_adapter_set: %s: to_q / to_out are not [%d][%d]", t.c_str(), C, C); return fail_ctx(c); }
+    API_CK(c, l.kppb.ensure((size_t)batch2 * l.cols * C * 2)); API_CK(c, l.vppb.ensure((size_t)batch2 * l.cols * C * 2)); API_CK(c, l.csbsb.ensure((size_t)2 * batch2 * l.cols * 4));
+    ProfScope ps(c, st, PC_OTHER, 4.0 * rows * (double)C * Dc + 4.0 * batch2 * (double)l.cols * C * (C / l.heads));
+    API_CK(c, launch_ipa_linear(tok, l.wk.as<bf16_t>(), nullptr, c->ipa_kipb.as<float>(), rows, C, Dc, st));
+    API_CK(c, launch_ipa_linear(tok, l.wv.as<bf16_t>(), nullptr, c->ipa_vipb.as<float>(), rows, C, Dc, st));
+    API_CK(c, launch_matvec_bf16(wq->w, b2, c->ipa_wqbb.as<float>(), C, C, st));           // (Wq beta2)[(h,d)] from the merged to_q
+    IpaPremulP pm{}; pm.kip = c->ipa_kipb.as<float>(); pm.vip = c->ipa_vipb.as<float>(); pm.wq = wq->w; pm.wo = wo->w; pm.gamma = g2; pm.wqb = c->ipa_wqbb.as<float>();
+    pm.B = batch2; pm.C = C; pm.H = l.heads; pm.nt = nt; pm.colsP = l.cols; pm.scale = 1.0f / sqrtf((float)(C / l.heads));
+    pm.kpp = l.kppb.as<bf16_t>(); pm.cs = l.csbsb.as<float>(); pm.bs = pm.cs + (size_t)batch2 * l.cols; pm.vpp = l.vppb.as<bf16_t>();
+    API_CK(c, launch_ipa_premul(pm, st));
+  }
+  c->ipa_B2 = batch2; c->ipa_scale = scale; c->ipa_stale = false;
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->ipa_active = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_tokens(agd_ctx* c, float* out) {
+  API_CK(c, need_final(c));
+  if (!c->ipa_on || c->ipa_B2 < 1) { agd_set_error("ip_adapter_tokens: no image tokens set (agd_ip_adapter_set)"); return fail_ctx(c); }
+  if (!out) { agd_set_error("ip_adapter_tokens: null out"); return fail_ctx(c); }
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("ip_adapter_tokens: sync failed"); return fail_ctx(c); }   // (agd_ip_adapter_set ran on the caller's stream)
+  if (hipMemcpy(out, c->ipa_tokb.p, (size_t)c->ipa_B2 * c->ipa_nt * c->cfg.cross_attention_dim * 4, hipMemcpyDefault) != hipSuccess) {
+    agd_set_error("ip_adapter_tokens: copy failed"); return fail_ctx(c); }
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_block(agd_ctx* c, const char* block_name, const float* x, int batch2, int h, int w, float* out, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  if (!c->ipa_on || c->ipa_B2 < 1) { agd_set_error("ip_adapter_block: no image tokens set (agd_ip_adapter_set)"); return fail_ctx(c); }
+  if (!block_name || !x || !out || batch2 < 1 || h < 1 || w < 1) { agd_set_error("ip_adapter_block: bad arguments"); return fail_ctx(c); }
+  if (c->ipa_stale) { agd_set_error("ip_adapter_block: a LoRA scale change rewrote to_q / to_out after the image products were built (call agd_ip_adapter_set again)"); return fail_ctx(c); }
+  std::string pre(block_name);
+  if (pre.compare(0, 5, "unet.") != 0) pre = "unet." + pre;
+  if (pre.back() != '.') pre += ".";
+  auto it = c->ipa_idx.find(pre);
+  if (it == c->ipa_idx.end()) { agd_set_error("ip_adapter_block: no attn2 layer in block '%s'", block_name); return fail_ctx(c); }
+  const IpaLayer& l = c->ipa_l[it->second];
+  const long long HW = (long long)h * w, M = batch2 * HW;
+  if (M >= (1ll << 28)) { agd_set_error("ip_adapter_block: %d rows of %d x %d", batch2, h, w); return fail_ctx(c); }
+  c->arena.release(0);
+  bf16_t* hb = (bf16_t*)c->arena.alloc((size_t)M * l.C * 2); bf16_t* P = (bf16_t*)c->arena.alloc((size_t)M * l.cols * 2);
+  if (!hb || !P) return fail_ctx(c);
+  API_CK(c, launch_f32_to_bf16(x, hb, M * l.C, st));
+  API_CK(c, ipa_scores_rows(c, st, l, hb, batch2, (int)HW, P));
+  API_CK(c, ipa_add_rows(c, st, l, hb, batch2, (int)HW, P));
+  API_CK(c, launch_bf16_to_f32(hb, out, M * l.C, st));
+  return 0;
+}
+
+AGD_API int agd_ip_adapter_counts(agd_ctx* c, long long* counts) {
+  if (!c || !counts) { agd_set_error("ip_adapter_counts: null argument"); return fail_ctx(c); }
+  counts[0] = c->ipa_counts[0]; counts[1] = c->ipa_counts[1];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// The IP-Adapter's image encoder (transformers CLIPVisionModelWithProjection: image_embeds = visual_projection(post_layernorm(CLS))):
+// the safety checker's vision path (vision_embed) under its own weights, loaded after agd_finalize.  Head dim 64 or 80 (OpenCLIP ViT-H/14).
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_image_encoder_begin(agd_ctx* c, const agd_vision_config* v) {
+  API_CK(c, need_final(c));
+  if (!v || v->struct_size != (int)sizeof(agd_vision_config)) {
+    agd_set_error("agd_image_encoder_begin: bad config (struct_size %d != %zu)", v ? v->struct_size : -1, sizeof(agd_vision_config)); return fail_ctx(c); }
+  if (c->ienc_state != 0) { agd_set_error("agd_image_encoder_begin: an image encoder is already loaded or half loaded (one per context: agd_image_encoder_unload first)"); return fail_ctx(c); }
+  API_CK(c, check_vision_config(v, "agd_image_encoder_begin"));
+  const int d = v->hidden / v->heads;
+  if (d != 64 && d != 80) { agd_set_error("agd_image_encoder_begin: hidden %d / heads %d: head dim %d unsupported (64 or 80)", v->hidden, v->heads, d); return fail_ctx(c); }
+  if (v->n_special != 0 || v->n_concepts != 0) { agd_set_error("agd_image_encoder_begin: an image encoder has no concept rows (n_special = n_concepts = 0)"); return fail_ctx(c); }
+  c->ienc = *v; c->ienc_state = 1;
+  return 0;
+}
+AGD_API int agd_image_encoder_tensor(agd_ctx* c, const char* name, const void* ptr, int dtype, int ndim, const long long* shape) {
+  API_CK(c, need_final(c));
+  if (c->ienc_state != 1) { agd_set_error("agd_image_encoder_tensor: call agd_image_encoder_begin first (and not after agd_image_encoder_commit)"); return fail_ctx(c); }
+  if (!name || strncmp(name, "image_encoder.", 14) != 0) { agd_set_error("agd_image_encoder_tensor: '%s' does not start with \"image_encoder.\"", name ? name : "(null)"); return fail_ctx(c); }
+  if (ndim < 1 || ndim > 4) { agd_set_error("agd_image_encoder_tensor: '%s': ndim %d", name, ndim); return fail_ctx(c); }
+  if (c->W.count(name) || c->V.count(name)) { agd_set_error("agd_image_encoder_tensor: '%s' was loaded already", name); return fail_ctx(c); }
+  return agd_load_tensor(c, name, ptr, dtype, ndim, shape);
+}
+AGD_API int agd_image_encoder_commit(agd_ctx* c) {
+  API_CK(c, need_final(c));
+  if (c->ienc_state != 1) { agd_set_error("agd_image_encoder_commit: call agd_image_encoder_begin first"); return fail_ctx(c); }
+  API_CK(c, finalize_vision(c, image_tower(c)));
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("agd_image_encoder_commit: sync failed"); return fail_ctx(c); }
+  c->ienc_state = 2;
+  return 0;
+}
+// frees every "image_encoder.*" tensor (the loaded ones, the fused q/k/v and the patch matrix): after a failed load, so that it can be tried
+// again, or to drop a committed encoder
+AGD_API int agd_image_encoder_unload(agd_ctx* c) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  hipSetDevice(c->device);
+  if (hipDeviceSynchronize() != hipSuccess) { agd_set_error("agd_image_encoder_unload: sync failed"); return fail_ctx(c); }
+  std::vector<void*> gone;
+  for (auto it = c->W.begin(); it != c->W.end();)
+    if (it->first.compare(0, 14, "image_encoder.") == 0) { gone.push_back(it->second.w); gone.push_back(it->second.wfrag); it = c->W.erase(it); } else ++it;
+  for (auto it = c->V.begin(); it != c->V.end();)
+    if (it->first.compare(0, 14, "image_encoder.") == 0) { gone.push_back(it->second); c->Vn.erase(it->first); it = c->V.erase(it); } else ++it;
+  for (void* p : gone) {
+    auto o = std::find(c->owned.begin(), c->owned.end(), p);
+    if (o != c->owned.end()) { hipFree(p); c->owned.erase(o); }
+  }
+  c->ienc = agd_vision_config{}; c->ienc_state = 0;
+  return 0;
+}
+AGD_API int agd_image_embeds(agd_ctx* c, const unsigned char* images, int batch, int h, int w, float* out, void* stream) {
+  API_CK(c, need_final(c));
+  if (c->ienc_state != 2) { agd_set_error("image_embeds: no image encoder loaded (agd_image_encoder_begin .. agd_image_encoder_commit)"); return fail_ctx(c); }
+  if (batch < 1 || h < 1 || w < 1 || !images || !out) { agd_set_error("image_embeds: batch %d size %d x %d / null buffer", batch, h, w); return fail_ctx(c); }
+  return vision_embed(c, S(stream), image_tower(c), images, batch, h, w, nullptr, nullptr, 0, nullptr, out);
 }

@@ -94,7 +94,8 @@ int launch_vis_embed_ln(const float* pe, const float* cls, const float* pos, con
 // (cosine_distance(image_embeds, concept_embeds) of the checker; the concept side was normalised at finalize).
 __global__ __launch_bounds__(256) void vis_pooled_head_kernel(const bf16_t* __restrict__ x, int T, int H, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, const float* __restrict__ Wp, int P,
-                                                               const float* __restrict__ E, int n, float* __restrict__ cos_out) {
+                                                               const float* __restrict__ E, int n, float* __restrict__ cos_out,
+                                                               float* __restrict__ emb_out) {
   extern __shared__ float sm[];                    // [H] y, [P] e, [4] reduction slots
   float* y = sm; float* e = sm + H; float* red = e + P;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(256) void vis_pooled_head_kernel(const bf16_t* __re
     if (lane == 0) e[j] = a;
   }
   __syncthreads();
+  if (emb_out) for (int j = tid; j < P; j += 256) emb_out[(long long)b * P + j] = e[j];      // image_embeds as projected (not normalised)
   float ss = 0.f;
   for (int j = tid; j < P; j += 256) ss += e[j] * e[j];
   const float inv = 1.0f / fmaxf(sqrtf(vis_block_sum(ss, red)), 1e-12f);
@@ -127,10 +129,10 @@ __global__ __launch_bounds__(256) void vis_pooled_head_kernel(const bf16_t* __re
   }
 }
 int launch_vis_pooled_head(const bf16_t* x, int B, int T, int H, const float* gamma, const float* beta, float eps, const float* Wp, int P,
-                           const float* E, int n, float* cos_out, hipStream_t st) {
+                           const float* E, int n, float* cos_out, float* emb_out, hipStream_t st) {
   const size_t lds = (size_t)(H + P + 4) * sizeof(float);
   if (lds > 65536) { agd_set_error("vision: pooled head of hidden %d + projection %d exceeds the LDS", H, P); return -1; }
-  hipLaunchKernelGGL(vis_pooled_head_kernel, dim3(B), dim3(256), lds, st, x, T, H, gamma, beta, eps, Wp, P, E, n, cos_out);
+  hipLaunchKernelGGL(vis_pooled_head_kernel, dim3(B), dim3(256), lds, st, x, T, H, gamma, beta, eps, Wp, P, E, n, cos_out, emb_out);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

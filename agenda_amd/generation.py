@@ -279,6 +279,13 @@ def parse_args(argv=None):
     p.add_argument("--adapter-conditioning-scale", type=float, default=1.0)
     p.add_argument("--adapter-conditioning-factor", type=float, default=1.0,
                    help="the share of the model evaluations, from the first on, that get the adapter's features")
+    p.add_argument("--ip-adapter-path", type=str, default=None,
+                   help="an IP-Adapter weight file (.safetensors / .bin) or a local directory holding one: image-prompted txt2img")
+    p.add_argument("--ip-adapter-image", type=str, default=None,
+                   help="the image prompt (every seed), or a directory: seed s uses its sorted file s mod n")
+    p.add_argument("--ip-adapter-scale", type=float, default=1.0)
+    p.add_argument("--image-encoder-path", type=str, default=None,
+                   help="the adapter's CLIPVisionModelWithProjection directory (default: image_encoder/ beside the adapter weights)")
     p.add_argument("--init-image", type=str, default=None,
                    help="inpainting: the image to paint into (a file for every seed, or a directory: seed s uses its sorted file s mod n)")
     p.add_argument("--mask-image", type=str, default=None,
@@ -335,6 +342,13 @@ def parse_args(argv=None):
     if args.adapter_model_path and (args.controlnet_model_path or args.init_image or args.instruct_image or args.gligen_phrases is not None
                                     or args.gligen_layouts is not None or args.panorama):
         p.error("--adapter-model-path with ControlNet, inpainting, InstructPix2Pix, GLIGEN or --panorama is not implemented")
+    if (args.ip_adapter_path is None) != (args.ip_adapter_image is None):
+        p.error("--ip-adapter-path and --ip-adapter-image go together")
+    if args.ip_adapter_path is None and (args.ip_adapter_scale != 1.0 or args.image_encoder_path is not None):
+        p.error("--ip-adapter-scale / --image-encoder-path need --ip-adapter-path")
+    if args.ip_adapter_path and (args.controlnet_model_path or args.adapter_model_path or args.init_image or args.instruct_image
+                                 or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama):
+        p.error("--ip-adapter-path with ControlNet, a T2I-Adapter, inpainting, InstructPix2Pix, GLIGEN or --panorama is not implemented")
     if not 0.0 <= args.control_guidance_start < args.control_guidance_end <= 1.0:
         p.error("--control-guidance-start / --control-guidance-end: 0 <= start < end <= 1")
     if args.use_karras_sigmas and args.scheduler != "DPMSolverMultistepScheduler":
@@ -440,6 +454,14 @@ def control_images_for(files: Sequence[str], seeds: Sequence[int]):
     return [Image.open(files[s % len(files)]).convert("RGB") for s in seeds]
 
 
+def ip_adapter_images_for(files: Sequence[str], seeds: Sequence[int]):
+    """The image prompt of every seed (seed s takes file s mod n), as RGB PIL images resized to the first one's size (the encoder's own
+    front end then resizes and crops to its input)."""
+    from PIL import Image
+    ims = [Image.open(files[int(s) % len(files)]).convert("RGB") for s in seeds]
+    return [im if im.size == ims[0].size else im.resize(ims[0].size, Image.BICUBIC) for im in ims]
+
+
 def adapter_images_for(files: Sequence[str], seeds: Sequence[int], in_channels: int = 3):
     """The adapter's conditioning image of every seed (seed s takes file s mod n): "L" for a 1-channel adapter, else RGB."""
     from PIL import Image
@@ -521,6 +543,11 @@ def main(argv=None):
     if args.lora_path:
         pipe.load_lora_weights(args.lora_path, weight_name=args.lora_weight_name)
         pipe.fuse_lora(lora_scale=args.lora_scale)
+    ipa_files = None
+    if args.ip_adapter_path:
+        pipe.load_ip_adapter(args.ip_adapter_path, image_encoder_folder=args.image_encoder_path or "image_encoder")
+        pipe.set_ip_adapter_scale(args.ip_adapter_scale)
+        ipa_files = control_image_files(args.ip_adapter_image)
     if args.use_karras_sigmas:
         from .scheduler import DPMSolverMultistepScheduler
         pipe.cfg.sched.use_karras_sigmas = True
@@ -556,6 +583,8 @@ def main(argv=None):
                 control = gligen_inputs_for(gl_layouts, chunk, args.gligen_beta)
             if args.panorama:
                 control = {"view_batch_size": args.view_batch_size}
+            if ipa_files is not None:
+                control = {"ip_adapter_image": ip_adapter_images_for(ipa_files, chunk)}
             height, width = args.height, args.width
             if i2_files:                                                             # (parse_args refused --height / --width: both are None)
                 control = ip2p_inputs_for(i2_files, chunk, args.image_guidance_scale)

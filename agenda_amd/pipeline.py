@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -109,6 +110,11 @@ class Engine:
         if not self.ctx:
             raise _lib.AgendaHipError("agd_create failed: " + self.lib.agd_last_error(None).decode())
         self.finalized = False
+        # IP-Adapter: (embed_dim, n_tokens) of the loaded adapter, the rows of the last ip_adapter_set and its embeddings, the image encoder's config
+        self._ipa_dims: Optional[Tuple[int, int]] = None
+        self._ipa_rows = 0
+        self._ipa_keepalive = None
+        self._ienc_cfg = None
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -286,6 +292,97 @@ class Engine:
         """(adds that left GroupNorm partial sums, adds that did not) since the engine was created."""
         n = (C.c_longlong * 2)()
         self._ck(self.lib.agd_adapter_add_counts(self.ctx, n), "agd_adapter_add_counts")
+        return int(n[0]), int(n[1])
+
+    def ip_adapter_load(self, tensors: Dict[str, torch.Tensor], embed_dim: int, n_tokens: int):
+        """`agd_ip_adapter_begin` .. `agd_ip_adapter_commit`: `tensors` under the engine's names (ip_adapter.to_engine_names)."""
+        self._ck(self.lib.agd_ip_adapter_begin(self.ctx, int(embed_dim), int(n_tokens)), "agd_ip_adapter_begin")
+        try:
+            for k, t in tensors.items():
+                t = t.detach().to(torch.float32).contiguous()
+                shape = (C.c_longlong * max(t.ndim, 1))(*t.shape)
+                self._ck(self.lib.agd_ip_adapter_tensor(self.ctx, k.encode(), C.c_void_p(t.data_ptr()), 0, t.ndim, shape), f"agd_ip_adapter_tensor({k})")
+            self._ck(self.lib.agd_ip_adapter_commit(self.ctx), "agd_ip_adapter_commit")
+        except Exception:
+            self.lib.agd_ip_adapter_unload(self.ctx)
+            raise
+        self._ipa_dims = (int(embed_dim), int(n_tokens))
+
+    def ip_adapter_unload(self):
+        self._ck(self.lib.agd_ip_adapter_unload(self.ctx), "agd_ip_adapter_unload")
+        self._ipa_dims = None
+        self._ipa_rows = 0
+
+    def ip_adapter_set(self, image_embeds: torch.Tensor, scale: float = 1.0):
+        """`agd_ip_adapter_set`: image embeddings fp32 [B2, embed_dim] ([negative; positive]) -> the projected tokens and every attn2
+        layer's pre-multiplied image matrices, for the next forwards on B2 rows."""
+        emb = self._h2d(image_embeds.to(torch.float32)).clone().contiguous()
+        dims = self._ipa_dims                                  # (None: nothing loaded -- the engine says so by name)
+        if emb.ndim != 2 or (dims is not None and emb.shape[1] != dims[0]):
+            raise ValueError(f"ip_adapter_set: image_embeds {tuple(emb.shape)}, the adapter takes [rows, {dims[0] if dims else 'embed_dim'}]")
+        self._ck(self.lib.agd_ip_adapter_set(self.ctx, _lib.ptr(emb), int(emb.shape[0]), float(scale), self._stream()), "agd_ip_adapter_set")
+        self._ipa_keepalive = emb
+        self._ipa_rows = int(emb.shape[0])
+
+    def ip_adapter_clear(self):
+        self._ck(self.lib.agd_ip_adapter_clear(self.ctx), "agd_ip_adapter_clear")
+        self._ipa_rows = 0
+
+    def ip_adapter_tokens(self) -> torch.Tensor:
+        """`agd_ip_adapter_tokens`: the projected tokens of the last ip_adapter_set, fp32 [B2, n_tokens, cross_attention_dim] (cuda)."""
+        if not self._ipa_rows or self._ipa_dims is None:
+            raise _lib.AgendaHipError("ip_adapter_tokens: no image tokens set (ip_adapter_set first)")
+        out = torch.empty(self._ipa_rows, self._ipa_dims[1], self.cfg.unet.cross_attention_dim, device=f"cuda:{self.device}", dtype=torch.float32)
+        self._ck(self.lib.agd_ip_adapter_tokens(self.ctx, _lib.ptr(out)), "agd_ip_adapter_tokens")
+        return out
+
+    def ip_adapter_block(self, block: str, x: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """`agd_ip_adapter_block`: x + scale * to_out_weight . attn_ip(norm2(x)) of `block` on x fp32 [B2, h*w, C]."""
+        x = x.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        self._ck(self.lib.agd_ip_adapter_block(self.ctx, block.encode(), _lib.ptr(x), x.shape[0], h, w, _lib.ptr(out), self._stream()),
+                 "agd_ip_adapter_block")
+        return out
+
+    def image_encoder_load(self, scfg, tensors: Dict[str, torch.Tensor]):
+        """`agd_image_encoder_begin` .. `agd_image_encoder_commit`: the IP-Adapter's CLIP image encoder (scfg: ip_adapter.image_encoder_config;
+        tensors under the transformers CLIPVisionModelWithProjection keys).  One per engine, until image_encoder_unload; a load that fails
+        part way unloads itself, so it can be tried again."""
+        from .safety import vision_config
+        vcfg = vision_config(scfg)
+        self._ck(self.lib.agd_image_encoder_begin(self.ctx, C.byref(vcfg)), "agd_image_encoder_begin")
+        try:
+            for k, t in tensors.items():
+                t = t.detach().to(torch.float32).contiguous()
+                shape = (C.c_longlong * max(t.ndim, 1))(*t.shape)
+                self._ck(self.lib.agd_image_encoder_tensor(self.ctx, ("image_encoder." + k).encode(), C.c_void_p(t.data_ptr()), 0, t.ndim, shape),
+                         f"agd_image_encoder_tensor({k})")
+            self._ck(self.lib.agd_image_encoder_commit(self.ctx), "agd_image_encoder_commit")
+        except Exception:
+            self.lib.agd_image_encoder_unload(self.ctx)
+            raise
+        self._ienc_cfg = scfg
+
+    def image_encoder_unload(self):
+        self._ck(self.lib.agd_image_encoder_unload(self.ctx), "agd_image_encoder_unload")
+        self._ienc_cfg = None
+
+    def image_embeds(self, images_u8: torch.Tensor) -> torch.Tensor:
+        """`agd_image_embeds`: uint8 [B,H,W,3] -> CLIP image embeddings fp32 [B, projection_dim] (cuda)."""
+        img = images_u8.to(device=f"cuda:{self.device}", dtype=torch.uint8).contiguous()
+        if img.ndim != 4 or img.shape[3] != 3:
+            raise ValueError(f"the image encoder takes uint8 [B,H,W,3] images, got {tuple(img.shape)}")
+        if self._ienc_cfg is None:
+            raise _lib.AgendaHipError("image_embeds: no image encoder loaded (image_encoder_load first)")
+        out = torch.empty(img.shape[0], self._ienc_cfg.projection_dim, device=img.device, dtype=torch.float32)
+        self._ck(self.lib.agd_image_embeds(self.ctx, _lib.ptr(img), img.shape[0], img.shape[1], img.shape[2], _lib.ptr(out), self._stream()),
+                 "agd_image_embeds")
+        return out
+
+    def ip_adapter_counts(self):
+        """`agd_ip_adapter_counts`: (score launches, add launches) of the block walk since the last ip_adapter_clear."""
+        n = (C.c_longlong * 2)()
+        self._ck(self.lib.agd_ip_adapter_counts(self.ctx, n), "agd_ip_adapter_counts")
         return int(n[0]), int(n[1])
 
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
@@ -754,6 +851,8 @@ class StableDiffusionPipeline:
         self._last_prompt = None
         self._progress = {}
         self._lora = None                 # load_lora_weights: {"targets": n, "fused": scale or None}
+        self._ip_adapter = None           # load_ip_adapter: {"embed_dim": E, "n_tokens": n, "scale": s}
+        self._image_encoder = None        # the IP-Adapter's image encoder config once loaded (load_ip_adapter / load_image_encoder)
         self._source_path = None          # from_pretrained: the checkpoint directory (save_pretrained re-exports from it)
         # diffusers' `pipeline.safety_checker` slot: None (no checker weights ship with this repo) or a callable
         # images uint8 [B,H,W,3] (cuda tensor) -> sequence of B bools; flagged images are returned black, which the generation
@@ -923,6 +1022,101 @@ class StableDiffusionPipeline:
         s = st["fused"] if st["fused"] is not None else float((cross_attention_kwargs or {}).get("scale", 1.0))
         self.engine.lora_set_scale(s)
 
+    # ---- IP-Adapter (diffusers >= 0.24 IPAdapterMixin surface; ip_adapter.py / agd_ip_adapter_*) -------------------------------------
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None,
+                        image_encoder_folder: Optional[str] = "image_encoder"):
+        """Loads one plain IP-Adapter (4 image tokens; `.safetensors` or `.bin`) from a state dict, a local file, or `weight_name` under
+        `subfolder` of a local directory.  The image branch then runs in every call that passes `ip_adapter_image` or
+        `ip_adapter_image_embeds`, at set_ip_adapter_scale's strength.  `image_encoder_folder`: a transformers
+        CLIPVisionModelWithProjection directory (config.json + model.safetensors), itself a path or a folder beside the weights; the
+        default name is optional (without it only embeddings are taken), any other name that is not found raises.  The call's image
+        state stays set in the engine until the next call of this pipeline (a direct engine forward on the same rows runs it too)."""
+        from . import ip_adapter as ipa
+        for k in type(self).__mro__:
+            if k.__name__ in ipa.REFUSED_PIPELINES:
+                raise ValueError(f"load_ip_adapter: the IP-Adapter with {k.__name__} is not implemented (StableDiffusionPipeline only)")
+        if getattr(self, "_ip_adapter", None) is not None:
+            raise ValueError("load_ip_adapter: an IP-Adapter is already loaded; more than one adapter is not supported (unload_ip_adapter first)")
+        sd = ipa.load_ip_adapter_state_dict(pretrained_model_name_or_path_or_dict, subfolder, weight_name)
+        tensors, embed_dim, n_tokens = ipa.to_engine_tensors(sd, self.cfg)
+        enc = ipa.find_image_encoder(pretrained_model_name_or_path_or_dict, subfolder, image_encoder_folder)
+        if enc is None and image_encoder_folder not in (None, "image_encoder"):
+            raise FileNotFoundError(f"load_ip_adapter: image_encoder_folder '{image_encoder_folder}' holds no config.json (a local transformers "
+                                    "CLIPVisionModelWithProjection directory)")
+        scfg = esd = None
+        if enc is not None and not getattr(self, "_image_encoder", None):
+            scfg, esd = ipa.load_image_encoder(enc)
+            if scfg.projection_dim != embed_dim:
+                raise ValueError(f"load_ip_adapter: the image encoder in {enc} projects to {scfg.projection_dim}, the adapter takes {embed_dim}")
+        # everything is read and checked on the host before the engine changes; the adapter goes first, and an encoder the engine
+        # refuses takes it out again: a failed call leaves the pipeline as it found it
+        self.engine.ip_adapter_load(tensors, embed_dim, n_tokens)
+        if scfg is not None:
+            try:
+                self.engine.image_encoder_load(scfg, esd)
+            except Exception:
+                self.engine.ip_adapter_unload()
+                raise
+            self._image_encoder = scfg
+        self._ip_adapter = {"embed_dim": embed_dim, "n_tokens": n_tokens, "scale": 1.0}
+
+    def load_image_encoder(self, scfg, sd: Dict[str, torch.Tensor]):
+        """The IP-Adapter's image encoder from a config (ip_adapter.image_encoder_config) and a state dict under the transformers keys."""
+        if getattr(self, "_image_encoder", None):
+            raise ValueError("load_image_encoder: an image encoder is already loaded (one per pipeline; unload_image_encoder first)")
+        self.engine.image_encoder_load(scfg, sd)
+        self._image_encoder = scfg
+
+    def unload_image_encoder(self):
+        if getattr(self, "_image_encoder", None):
+            self.engine.image_encoder_unload()
+        self._image_encoder = None
+
+    def set_ip_adapter_scale(self, scale: float = 1.0):
+        if getattr(self, "_ip_adapter", None) is None:
+            raise ValueError("set_ip_adapter_scale: no IP-Adapter loaded (load_ip_adapter first)")
+        if isinstance(scale, (list, tuple, dict)):
+            raise ValueError("set_ip_adapter_scale: a list-valued scale (per adapter or per layer) is not supported; pass one number")
+        if not math.isfinite(float(scale)):
+            raise ValueError(f"set_ip_adapter_scale: scale {scale}")
+        self._ip_adapter["scale"] = float(scale)
+
+    def unload_ip_adapter(self):
+        if getattr(self, "_ip_adapter", None) is not None:
+            self.engine.ip_adapter_unload()
+        self._ip_adapter = None
+
+    def _apply_ip_adapter(self, B: int, prompt_batch: int, images_per_prompt: int, ip_adapter_image, ip_adapter_image_embeds):
+        """The call's image prompt into the engine (after the LoRA scale: the image products are built from the merged to_q / to_out);
+        with neither argument a loaded adapter is left idle and the call runs the plain UNet."""
+        st = getattr(self, "_ip_adapter", None)
+        if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+            raise ValueError("ip_adapter_image and ip_adapter_image_embeds were both given; pass one of them")
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            if st is not None:
+                self.engine.ip_adapter_clear()
+            return
+        which = "ip_adapter_image" if ip_adapter_image is not None else "ip_adapter_image_embeds"
+        if st is None:
+            raise ValueError(f"{which} was given but no IP-Adapter is loaded (load_ip_adapter first)")
+        from . import ip_adapter as ipa
+        if ip_adapter_image is not None:
+            enc = getattr(self, "_image_encoder", None)
+            if not enc:
+                raise ValueError("ip_adapter_image was given but no image encoder is loaded (load_ip_adapter with an image_encoder_folder, or "
+                                 "load_image_encoder; or pass ip_adapter_image_embeds)")
+            if enc.projection_dim != st["embed_dim"]:
+                raise ValueError(f"ip_adapter_image: the image encoder projects to {enc.projection_dim}, the adapter takes {st['embed_dim']}")
+            if st["scale"] == 0.0:
+                self.engine.ip_adapter_clear()
+                return
+            ip_adapter_image_embeds = self.engine.image_embeds(ipa.prepare_ip_adapter_image(ip_adapter_image))
+        emb = ipa.cfg_image_embeds(ip_adapter_image_embeds, B, prompt_batch, images_per_prompt, st["embed_dim"])
+        if st["scale"] == 0.0:
+            self.engine.ip_adapter_clear()                     # scale 0: exactly the plain UNet, nothing projected
+            return
+        self.engine.ip_adapter_set(emb, st["scale"])
+
     def save_pretrained(self, save_directory: str):
         """`pipeline.save_pretrained(dir)` (finetune_sd_token.py:164-187 writes its result this way): the diffusers layout
         `from_pretrained` reads.  This pipeline is an inference engine -- UNet / VAE / scheduler are exactly what was loaded, so
@@ -1072,7 +1266,7 @@ class StableDiffusionPipeline:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
-                 cross_attention_kwargs: Optional[dict] = None):
+                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None):
         self._refuse_inpainting_unet()
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
@@ -1081,8 +1275,9 @@ class StableDiffusionPipeline:
         Lh, Lw = height // self.vae_scale_factor, width // self.vae_scale_factor
         self._refuse_rectangular_hook(Lh, Lw)
         L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
-        prompt_embeds = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)[0]
+        prompt_embeds, pb, ipp = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)
         B = prompt_embeds.shape[0] // 2
+        self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
         self._begin_recording(prompt_embeds, B, L)
         self._denoise(lat, num_inference_steps, guidance_scale)
@@ -1140,7 +1335,7 @@ class StableDiffusionPipeline:
     def img2img(self, prompt=None, image: torch.Tensor = None, strength: float = 0.8, num_inference_steps: int = 50,
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
-                cross_attention_kwargs: Optional[dict] = None):
+                cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None):
         """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
@@ -1160,6 +1355,7 @@ class StableDiffusionPipeline:
         if prompt_embeds is None:
             prompts = [prompt] * B if isinstance(prompt, str) else list(prompt)
             prompt_embeds = self.encode_prompt(prompts)
+        self._apply_ip_adapter(B, B, 1, ip_adapter_image, ip_adapter_image_embeds)
         shape = (B, self.cfg.unet.out_channels, Lh, Lw)
         if generator is not None and generator.device.type != "cpu":
             raise ValueError("use a CPU torch.Generator")

@@ -192,6 +192,47 @@ int agd_adapter_clear(agd_ctx* ctx);                 /* the schedule and the per
  * (maps with no legal statistics tile, or "gn_fused_stats" off: the norm runs its own statistics pass) */
 int agd_adapter_add_counts(agd_ctx* ctx, long long* counts);
 
+/* ---- IP-Adapter (image prompts; diffusers >= 0.24 load_ip_adapter / ip_adapter_image, the SD-1.x "ip-adapter_sd15" family): an image
+ * projection turns CLIP image embeddings into n_tokens extra context tokens, and every UNet attn2 adds a second cross-attention over them:
+ *   out = to_out(attn(q, K_text, V_text) + scale * attn(q, to_k_ip(tokens), to_v_ip(tokens))).
+ * Loaded AFTER agd_finalize, like a LoRA; one adapter at a time.  The ControlNet's attn2 layers take no image branch.
+ * agd_ip_adapter_begin(embed_dim, n_tokens), then agd_ip_adapter_tensor per tensor (fp32, host or device): "image_proj.proj.weight"
+ * [n_tokens * cross_attention_dim, embed_dim], "image_proj.proj.bias", "image_proj.norm.weight", "image_proj.norm.bias", and per UNet
+ * transformer block "<block prefix>transformer_blocks.0.attn2.to_k_ip.weight" / "...to_v_ip.weight" [C, cross_attention_dim] (the block
+ * prefix with or without "unet."); agd_ip_adapter_commit names whatever is missing or misshapen.  agd_ip_adapter_unload frees everything. */
+int agd_ip_adapter_begin(agd_ctx* ctx, int embed_dim, int n_tokens);
+int agd_ip_adapter_tensor(agd_ctx* ctx, const char* name, const void* ptr, int dtype, int ndim, const long long* shape);
+int agd_ip_adapter_commit(agd_ctx* ctx);
+int agd_ip_adapter_unload(agd_ctx* ctx);
+/* once per call, AFTER agd_lora_set_scale: image_embeds fp32 [batch2][embed_dim] (rows [0,B) the unconditional half -- the caller passes
+ * zeros there, which the projection turns into non-zero tokens), a finite scale.  Runs the image projection and builds, per attn2 layer, the
+ * pre-multiplied per-image matrices from the CURRENT to_q / to_out; a later agd_lora_set_scale makes them stale and the next forward refuses
+ * until agd_ip_adapter_set runs again.  With tokens set and scale != 0, agd_denoise* and agd_unet_forward(_hw) on batch2 rows run the image
+ * branch in every UNet transformer block; agd_unet_forward_ts*, agd_denoise_panorama and any call with a ControlNet, GLIGEN or T2I-Adapter
+ * schedule, an inpainting state or an InstructPix2Pix state are refused.  Scale 0 or nothing set: exactly the plain UNet, launch for launch.
+ * agd_attn_processor / agd_cross_attn stay text-only; DAAM and the hook.py recorder see the text branch only. */
+int agd_ip_adapter_set(agd_ctx* ctx, const float* image_embeds, int batch2, float scale, void* stream);
+int agd_ip_adapter_clear(agd_ctx* ctx);              /* the per-call state and the counts; the weights stay loaded */
+int agd_ip_adapter_tokens(agd_ctx* ctx, float* out); /* the projected tokens fp32 [batch2][n_tokens][cross_attention_dim] (host or device; syncs) */
+/* seam for tests: x + scale * to_out_weight . attn_ip(norm2(x)) of one block on x fp32 [batch2][h*w][C] (device), any map shape */
+int agd_ip_adapter_block(agd_ctx* ctx, const char* block_name, const float* x, int batch2, int h, int w, float* out, void* stream);
+/* seam for tests: the score / add launches of the block walk since the last agd_ip_adapter_clear (or load) */
+int agd_ip_adapter_counts(agd_ctx* ctx, long long* counts);
+
+/* ---- the IP-Adapter's image encoder (a transformers CLIPVisionModelWithProjection: image_embeds = visual_projection(post_layernorm(CLS));
+ * the published SD-1.5 adapters use OpenCLIP ViT-H/14: hidden 1280, 32 layers, 16 heads of 80, MLP 5120, gelu, patch 14, 224 px,
+ * projection 1024).  It runs the safety checker's vision path (CLIPImageProcessor front end, patch embedding, encoder, pooled head) under
+ * its own weights, loaded AFTER agd_finalize: agd_image_encoder_begin(vcfg) with n_special = n_concepts = 0 and head dim 64 or 80, then
+ * agd_image_encoder_tensor per tensor (fp32; names "image_encoder." + the transformers key: "image_encoder.vision_model.embeddings.…",
+ * "image_encoder.visual_projection.weight"), then agd_image_encoder_commit (checks every shape, fuses q/k/v).  One encoder per context;
+ * agd_image_encoder_unload frees it, and is also how a load that failed part way (a refused tensor or commit) is cleared before it is
+ * tried again.  agd_image_embeds: uint8 NHWC [batch,h,w,3] (device) -> fp32 [batch][projection_dim] (device). */
+int agd_image_encoder_begin(agd_ctx* ctx, const agd_vision_config* vcfg);
+int agd_image_encoder_tensor(agd_ctx* ctx, const char* name, const void* ptr, int dtype, int ndim, const long long* shape);
+int agd_image_encoder_commit(agd_ctx* ctx);
+int agd_image_encoder_unload(agd_ctx* ctx);
+int agd_image_embeds(agd_ctx* ctx, const unsigned char* images, int batch, int h, int w, float* out, void* stream);
+
 /* ---- GLIGEN (diffusers StableDiffusionGLIGENPipeline, a UNet of attention_type "gated"): a PositionNet turns per-object phrase
  * embeddings and boxes into grounding tokens, and a GatedSelfAttentionDense ("fuser") in every transformer block, after attn1's residual
  * add, attends over the block's rows plus those tokens:  x += tanh(alpha_attn) attn(norm1([x; o]))[:N];  x += tanh(alpha_dense) ff(norm2(x)).
