@@ -117,6 +117,14 @@ enum : int {
 
 struct ProfEv { int cls; double flops, bytes; hipEvent_t a, b; };   // algorithmic flop / HBM bytes of the launch
 
+// What ONE model evaluation runs beside the UNet (resolve_cond() -> CallCond::at(i) -> unet_walk).  Default: the plain UNet.
+struct EvalCond {
+  float cn_scale = 0.f;    // != 0: the ControlNet runs after the mid block, its residuals times cn_scale land on the skips and the mid output
+  bool grounded = false;   // the GLIGEN fusers run in the UNet's transformer blocks
+  float ad_scale = 0.f;    // != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs
+  bool ipa = false;        // the IP-Adapter's image branch runs beside every UNet attn2
+};
+
 struct agd_ctx {
   int device = 0; agd_config cfg{}; std::string err;
   std::unordered_map<std::string, WMat> W;
@@ -207,27 +215,28 @@ struct agd_ctx {
   float lora_scale = 0.f; bool lora_dirty = false;
   bool ctx_stale = false;                             // the raw matrices changed after agd_set_context: the projected context must be rebuilt
   // GLIGEN (agd_gligen_configure): one Fuser per UNet transformer block (gl_idx: block prefix -> index), the PositionNet output of the call
-  // (gl_objb [gl_B2][max_objs][cross_attention_dim] bf16), one flag per model evaluation; gl_active: the forward being walked runs the fusers
+  // (gl_objb [gl_B2][max_objs][cross_attention_dim] bf16), one flag per model evaluation
   agd_gligen_config glc{}; bool gl_on = false;
   std::vector<Fuser> gl_f; std::unordered_map<std::string, int> gl_idx;
-  DBuf gl_objb; int gl_B2 = 0; std::vector<int> gl_sched; bool gl_active = false;
+  DBuf gl_objb; int gl_B2 = 0; std::vector<int> gl_sched;
   // T2I-Adapter (agd_adapter_configure): weights "adapter.*"; the per-call UNSCALED features fp32 NHWC [ad_B][Lh >> i][Lw >> i][channels[i]]
-  // (agd_adapter_set_cond_hw), one scale per model evaluation; ad_cur: the scale of the forward being walked (0: the plain UNet);
+  // (agd_adapter_set_cond_hw), one scale per model evaluation;
   // ad_adds: adds launched with / without GroupNorm partial sums
   agd_adapter_config adc{}; bool ad_on = false;
   DBuf ad_featb[AGD_MAX_LEVELS]; int ad_B = 0, ad_Lh = 0, ad_Lw = 0;
-  std::vector<float> ad_sched; float ad_cur = 0.f; long long ad_adds[2] = {0, 0};
+  std::vector<float> ad_sched; long long ad_adds[2] = {0, 0};
   // IP-Adapter (agd_ip_adapter_begin .. commit, after agd_finalize): the image projection and, per UNet attn2 layer (ipa_idx: block prefix ->
   // index), to_k_ip / to_v_ip; ipa_t: what agd_ip_adapter_tensor has received so far (name -> shape).  Per call (agd_ip_adapter_set): the
   // projected tokens fp32 [ipa_B2][ipa_nt][cross_attention_dim], every layer's pre-multiplied matrices and the scale; ipa_stale: a LoRA scale
-  // change rewrote to_q / to_out after they were built; ipa_active: the forward being walked runs the two stages; ipa_counts: score / add launches
+  // change rewrote to_q / to_out after they were built; ipa_counts: score / add launches
   bool ipa_loading = false, ipa_on = false; int ipa_E = 0, ipa_nt = 0;
   DBuf ipa_projw, ipa_projb, ipa_ng, ipa_nb;
   std::unordered_map<std::string, std::vector<long long>> ipa_t;
   std::vector<IpaLayer> ipa_l; std::unordered_map<std::string, int> ipa_idx;
   DBuf ipa_embb, ipa_tokb, ipa_kipb, ipa_vipb, ipa_wqbb;
-  int ipa_B2 = 0; float ipa_scale = 0.f; bool ipa_stale = false, ipa_active = false; long long ipa_counts[2] = {0, 0};
+  int ipa_B2 = 0; float ipa_scale = 0.f; bool ipa_stale = false; long long ipa_counts[2] = {0, 0};
   // profiling
+  EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   long long launches[AGD_N_CLASSES] = {0};
 };
@@ -239,7 +248,7 @@ static void ipa_release(agd_ctx* c) {
   c->ipa_l.clear(); c->ipa_idx.clear(); c->ipa_t.clear();
   for (DBuf* b : {&c->ipa_projw, &c->ipa_projb, &c->ipa_ng, &c->ipa_nb, &c->ipa_embb, &c->ipa_tokb, &c->ipa_kipb, &c->ipa_vipb, &c->ipa_wqbb}) b->release();
   c->ipa_loading = c->ipa_on = false; c->ipa_E = c->ipa_nt = 0;
-  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->ipa_active = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
+  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->cur.ipa = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
 }
 static inline int rec_images(const agd_ctx* c) { return c->rec_call > 0 ? c->rec_call : c->rec_B; }   // images a recording forward must have
 #define API_CK(c, expr) do { if ((expr) != 0) return fail_ctx(c); } while (0)
@@ -722,7 +731,7 @@ struct TBlock {
 // proj_in, norm1 and the self-attention run once on B' rows; the result is duplicated right before the first
 // cross-attention and the block returns 2B' rows.  Bit-identical to running both halves (every op here is
 // row- or image-local), at half the cost for the most expensive attention call of the forward.
-// GLIGEN (c->gl_active, a UNet block with a fuser): the fuser runs between attn1's residual add and attn2.  The CFG halves diverge there
+// GLIGEN (c->cur.grounded, a UNet block with a fuser): the fuser runs between attn1's residual add and attn2.  The CFG halves diverge there
 // (the unconditional half sees null objects only), so the shared prefix is duplicated BEFORE the fuser (DUP_COPY) and attn1.to_out stays a
 // GEMM of its own.  norm2's statistics for whatever attn2 form follows come from the fuser's last GEMM (the gated ff.net.2 is a produce()
 // launch).  Evaluations without the flag take the same plan as a model without fusers.
@@ -773,8 +782,8 @@ static TBlockPlan tblock_plan(const TBlock& s, int dup) {
   p.attn2 = premul ? ATTN2_PREMUL : chain ? ATTN2_CHAIN : ATTN2_KERNELS;
   p.chain_rows32 = tb(TBF_ATTN2_ROWS32);
   // --- between them: the duplication of the CFG-shared prefix, the fuser, and where attn1.to_out runs ---
-  if (c->gl_active) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) p.fuser = &c->gl_f[itf->second]; }
-  if (c->ipa_active) { auto iti = c->ipa_idx.find(pre); if (iti != c->ipa_idx.end()) p.ipa = &c->ipa_l[iti->second]; }
+  if (c->cur.grounded) { auto itf = c->gl_idx.find(pre); if (itf != c->gl_idx.end()) p.fuser = &c->gl_f[itf->second]; }
+  if (c->cur.ipa) { auto iti = c->ipa_idx.find(pre); if (iti != c->ipa_idx.end()) p.ipa = &c->ipa_l[iti->second]; }
   const bool lazy = dup && tb(TBF_LAZY_DUP) && chain && C == 320 && (p.ff == FF_FUSED_PROJ || p.ff == FF_FUSED_PREMUL) && !p.fuser && !p.ipa;
   p.dup = !dup ? DUP_NONE : lazy ? DUP_LAZY : DUP_COPY;
   p.attn1_in_chain = chain && tb(TBF_ATTN1_OUT) && p.dup != DUP_COPY && has(t + "attn1.to_out.frag") && !p.fuser && !p.ipa;
@@ -783,7 +792,7 @@ static TBlockPlan tblock_plan(const TBlock& s, int dup) {
   return p;
 }
 
-// IP-Adapter (c->ipa_active, a UNet block): the image branch reads attn2's INPUT rows, so -- as with the fuser -- that input must exist in
+// IP-Adapter (c->cur.ipa, a UNet block): the image branch reads attn2's INPUT rows, so -- as with the fuser -- that input must exist in
 // memory with all B rows: attn1.to_out stays a GEMM of its own and a CFG-shared prefix is duplicated by copies.  Whatever attn2 form the plan
 // picked then runs unchanged and in place, and the add lands on its output.  norm3's row statistics must describe h AFTER the add, so attn2's
 // last launch leaves none (stats_attn2 off) and tb_ip_adapter_add takes them from the rows (stats_ipa: one slot, launch_rowstat_bf16).
@@ -1066,7 +1075,7 @@ static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float*
 // every res sample in order (conv_in, each resnet / transformer output, each downsampler: the UNet's skips); h = the mid block's output.
 // conv_in_res: added in conv_in's epilogue (the ControlNet's conditioning embedding).  shared: rows [0,B2/2) and [B2/2,B2) of xin (and of
 // conv_in_res) are identical -- everything ahead of the first attn2 runs on B2/2 rows.
-// T2I-Adapter (the UNet's walk with ad_cur != 0): after the last layer of level i and before on_sample sees it, h becomes h + ad_cur * feature i
+// T2I-Adapter (the UNet's walk with c->cur.ad_scale != 0): after the last layer of level i and before on_sample sees it, h becomes h + ad_scale * feature i
 // in a fresh activation (adapter_add) -- the sum is the level's last skip and the input of the downsampler / the mid block.
 static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act& out);
 static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int Lh, int Lw, bool shared,
@@ -1074,7 +1083,7 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
   const agd_config& g = c->cfg;
   const int nl = g.n_levels, G = g.norm_num_groups;
   const int Bh = shared ? B2 / 2 : B2;
-  const bool inject = c->ad_cur != 0.f && u == "unet.";
+  const bool inject = c->cur.ad_scale != 0.f && u == "unet.";
   h = alloc_act(c, B2, Lh, Lw, g.block_out_channels[0], true); if (!h.p) return -1;
   { GETW(w, u + "conv_in.weight"); GETV(b, u + "conv_in.bias"); GemmOpt o; o.bias = b; o.out_act = &h; o.residual = conv_in_res;
     CK(run_conv(c, st, xin, 64, nullptr, 0, Bh, Lh, Lw, *w, 3, h.p, o, c->zero_page)); }
@@ -1127,7 +1136,7 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
   return 0;
 }
 
-// h + ad_cur * feature `level` into a fresh activation, with the GroupNorm partial sums of the sum on 64-row tiles where the consumer takes
+// h + c->cur.ad_scale * feature `level` into a fresh activation, with the GroupNorm partial sums of the sum on 64-row tiles where the consumer takes
 // them (norm.hip gn_part_ok: HW % bm == 0, C % 8 == 0, the 65536 index bound) and cpart_bm = 0 -- the norm's own statistics pass -- elsewhere
 static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act& out) {
   const int HW = h.H * h.W;
@@ -1139,7 +1148,7 @@ static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act&
   out.cpart_bm = bm;
   const double rows = (double)h.B * HW;
   ProfScope ps(c, st, PC_ELEM, 0, rows * h.C * (2.0 + 4.0 + 2.0) + (bm ? rows / bm * h.C * 8.0 : 0.0));
-  CK(launch_adapter_add(h.p, c->ad_featb[level].as<float>(), out.p, bm ? out.cpart : nullptr, bm, h.B, HW, h.C, c->ad_B, c->ad_cur, st));
+  CK(launch_adapter_add(h.p, c->ad_featb[level].as<float>(), out.p, bm ? out.cpart : nullptr, bm, h.B, HW, h.C, c->ad_B, c->cur.ad_scale, st));
   c->ad_adds[bm ? 0 : 1]++;
   return 0;
 }
@@ -1219,17 +1228,12 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
 // tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
 // cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
 // tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
-// cn_scale != 0: the ControlNet runs after the mid block and its scaled residuals are added to the skips and the mid output
-// grounded: the GLIGEN fusers run in the UNet's transformer blocks (agd_gligen_set_schedule)
-// ad_scale != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs (agd_adapter_set_schedule)
-// ipa: the IP-Adapter's image branch runs beside every UNet attn2 (agd_ip_adapter_set with a non-zero scale)
+// ec: what this evaluation runs beside the UNet -- one element of the CallCond that resolve_cond() built for the call before its first launch
+// (nothing is refused here any more); it becomes c->cur, where tblock_plan (fusers, image branch) and down_mid_walk / adapter_add (features) read it
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
-                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, float cn_scale = 0.f, bool grounded = false,
-                     float ad_scale = 0.f, bool ipa = false) {
+                     const float* tproj_row = nullptr, bool cfg_shared = false, int tproj_ld = 0, const EvalCond& ec = EvalCond()) {
   const agd_config& g = c->cfg;
-  c->gl_active = grounded;
-  c->ad_cur = ad_scale;
-  c->ipa_active = ipa;
+  c->cur = ec;
   if (c->ctx_stale) FAIL("the context is stale: a LoRA scale change rewrote the weights it was projected with (call agd_set_context)");
   const int nl = g.n_levels, G = g.norm_num_groups;
   const std::string u = "unet.";
@@ -1241,9 +1245,9 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
   const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share;
   Act h;
   CK(down_mid_walk(c, st, u, xin, B2, Lh, Lw, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h));
-  if (cn_scale != 0.f) {
+  if (ec.cn_scale != 0.f) {
     if (c->tproj_cur_ld != 0) FAIL("controlnet: per-image timesteps are not supported");
-    CK(controlnet_walk(c, st, xin, B2, Lh, Lw, t, cn_scale, cfg_shared, &skips, &h, nullptr, 0));
+    CK(controlnet_walk(c, st, xin, B2, Lh, Lw, t, ec.cn_scale, cfg_shared, &skips, &h, nullptr, 0));
   }
   for (int i = 0; i < nl; ++i) {
     const int lvl = nl - 1 - i, co = g.block_out_channels[lvl];
@@ -2074,84 +2078,122 @@ static int ensure_lat(agd_ctx* c, int B2, int Lh, int Lw) {
 }
 
 static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timesteps, int n, const float** out);
-// the ControlNet schedule of a call of n model evaluations on B2 rows at latent size Lh x Lw: nullptr = none set (the UNet alone); else its
-// length must be n, and a conditioning embedding for exactly these rows must exist when any scale is non-zero (checked before anything runs)
-static int cn_schedule_for(agd_ctx* c, int n, int B2, int Lh, int Lw, const float** out) {
-  *out = nullptr;
-  if (c->cn_sched.empty()) return 0;
-  if ((int)c->cn_sched.size() != n) FAIL("controlnet: the schedule has %zu scales, this call runs %d model evaluations (agd_controlnet_set_schedule)", c->cn_sched.size(), n);
-  bool any = false; for (float v : c->cn_sched) any = any || v != 0.f;
-  if (any && (c->cn_emb_B2 != B2 || c->cn_emb_Lh != Lh || c->cn_emb_Lw != Lw))
-    FAIL("controlnet: no conditioning image set for %d rows at latent sides %d x %d (agd_controlnet_set_cond has %d rows at %d x %d)", B2, Lh, Lw, c->cn_emb_B2,
-         c->cn_emb_Lh, c->cn_emb_Lw);
-  *out = c->cn_sched.data();
+// ---- the conditioning of a call ------------------------------------------------------------------------------------------------------
+// What a whole call runs beside the UNet, resolved ONCE by resolve_cond() before the call's first launch: the per-evaluation ControlNet
+// scales, GLIGEN flags, T2I-Adapter scales and inpainting-blend (sa, sb) pairs -- each nullptr when none -- and the IP-Adapter's image branch.
+struct CallCond {
+  const float* cn = nullptr; const int* gl = nullptr; const float* ad = nullptr; const float* blend = nullptr; bool ipa = false;
+  EvalCond at(int i) const { EvalCond e; e.cn_scale = cn ? cn[i] : 0.f; e.grounded = gl && gl[i]; e.ad_scale = ad ? ad[i] : 0.f; e.ipa = ipa; return e; }
+};
+enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA };   // who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama
+enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, N_COND_STATES };                              // the states a call can meet, in the order of a row's cells
+// One row per refusing party: a state (self) that, when set, refuses to run beside others in the callers that consult it, or an entry point
+// that runs the UNet alone (self < 0: it refuses whenever it is the caller).  with[s]: nullptr = allowed beside state s, else the refusal.
+// Rows are looked at top to bottom, the first set cell wins.  Whatever is not here is allowed: ControlNet + GLIGEN, GLIGEN + either
+// inpainting, agd_unet_forward_hw beside an inpainting / InstructPix2Pix state (it does not read them), an idle IP-Adapter beside anything.
+struct ConflictRow { int self; unsigned callers; const char* with[N_COND_STATES]; };
+static const ConflictRow kConflicts[] = {
+  { ST_INP, 1u << CALL_EVAL_LOOP, {   // inpaint
+    "inpaint: a ControlNet schedule is set; ControlNet inpainting is not implemented", nullptr, nullptr, nullptr, nullptr, nullptr } },
+  { ST_I2P, 1u << CALL_IP2P_LOOP, {   // ip2p
+    "ip2p: a ControlNet schedule is set; ControlNet with InstructPix2Pix is not implemented (clear it first)",
+    "ip2p: a GLIGEN schedule is set; GLIGEN with InstructPix2Pix is not implemented (clear it first)",
+    "ip2p: an inpainting state is set; inpainting with InstructPix2Pix is not implemented (agd_inpaint_clear first)",
+    nullptr,
+    "ip2p: a T2I-Adapter schedule is set; the T2I-Adapter with InstructPix2Pix is not implemented (clear it first)",
+    "ip2p: an IP-Adapter image is set; ip2p runs without it (agd_ip_adapter_clear first)" } },
+  { ST_AD, 1u << CALL_UNET_FORWARD | 1u << CALL_EVAL_LOOP, {   // adapter
+    "adapter: a ControlNet schedule is set; the T2I-Adapter with a ControlNet is not implemented (clear one of them)",
+    "adapter: a GLIGEN schedule is set; the T2I-Adapter with GLIGEN is not implemented (clear one of them)",
+    "adapter: an inpainting state is set; the T2I-Adapter with inpainting is not implemented (agd_inpaint_clear first)",
+    "adapter: an InstructPix2Pix state is set; the T2I-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)",
+    nullptr, nullptr } },
+  { ST_IPA, 1u << CALL_UNET_FORWARD | 1u << CALL_EVAL_LOOP, {   // ip_adapter
+    "ip_adapter: a ControlNet schedule is set; the IP-Adapter with a ControlNet is not implemented (clear one of them)",
+    "ip_adapter: a GLIGEN schedule is set; the IP-Adapter with GLIGEN is not implemented (clear one of them)",
+    "ip_adapter: an inpainting state is set; the IP-Adapter with inpainting is not implemented (agd_inpaint_clear first)",
+    "ip_adapter: an InstructPix2Pix state is set; the IP-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)",
+    "ip_adapter: a T2I-Adapter schedule is set; the IP-Adapter with a T2I-Adapter is not implemented (clear one of them)",
+    nullptr } },
+  { -1, 1u << CALL_UNET_FORWARD_TS, {   // unet_forward_ts (it reads neither an inpainting nor an InstructPix2Pix state)
+    "unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)",
+    "unet_forward_ts: a GLIGEN schedule is set; per-image timesteps run the UNet alone (clear it first)",
+    nullptr, nullptr,
+    "unet_forward_ts: a T2I-Adapter schedule is set; per-image timesteps run the UNet alone (clear it first)",
+    "unet_forward_ts: an IP-Adapter image is set; unet_forward_ts runs without it (agd_ip_adapter_clear first)" } },
+  { -1, 1u << CALL_PANORAMA, {   // denoise_panorama
+    "denoise_panorama: a ControlNet schedule is set; ControlNet on a panorama is not implemented (clear it first)",
+    "denoise_panorama: a GLIGEN schedule is set; GLIGEN on a panorama is not implemented (clear it first)",
+    "denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)",
+    "denoise_panorama: an InstructPix2Pix state is set; InstructPix2Pix on a panorama is not implemented (agd_ip2p_clear first)",
+    "denoise_panorama: a T2I-Adapter schedule is set; the T2I-Adapter on a panorama is not implemented (clear it first)",
+    "denoise_panorama: an IP-Adapter image is set; denoise_panorama runs without it (agd_ip_adapter_clear first)" } },
+};
+// an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
+static int ip2p_check_unet(agd_ctx* c, const char* what) {
+  const agd_config& g = c->cfg;
+  if (g.in_channels != g.out_channels + g.vae_latent_channels || g.in_channels > 64)
+    FAIL("%s: the UNet takes %d input channels, InstructPix2Pix needs %d latent + %d image-latent channels", what, g.in_channels, g.out_channels, g.vae_latent_channels);
   return 0;
 }
-// the GLIGEN schedule of a call of n model evaluations on B2 rows: nullptr = none set (no fuser runs); else its length must be n, and the
-// grounding objects must be set for exactly these rows when any flag is on (checked before anything runs)
-static int gl_schedule_for(agd_ctx* c, int n, int B2, const int** out) {
-  *out = nullptr;
-  if (c->gl_sched.empty()) return 0;
-  if ((int)c->gl_sched.size() != n) FAIL("gligen: the schedule has %zu flags, this call runs %d model evaluations (agd_gligen_set_schedule)", c->gl_sched.size(), n);
-  bool any = false; for (int v : c->gl_sched) any = any || v != 0;
-  if (any && c->gl_B2 != B2) FAIL("gligen: the grounding objects are set for %d rows, this call runs %d (agd_gligen_set)", c->gl_B2, B2);
-  *out = c->gl_sched.data();
-  return 0;
-}
-// the T2I-Adapter schedule of a call of n model evaluations on `rows` images (a fused loop: its batch; agd_unet_forward: its rows) at latent
-// size Lh x Lw: nullptr = none set (the plain UNet); else its length must be n, nothing else that changes the walk may be set, and features
-// for these sizes must exist when any scale is non-zero -- for ad_B images with rows a multiple of ad_B (row image b reads feature image b % ad_B)
-static int adapter_for(agd_ctx* c, int n, int rows, int Lh, int Lw, const float** out) {
-  *out = nullptr;
-  if (c->ad_sched.empty()) return 0;
-  if ((int)c->ad_sched.size() != n) FAIL("adapter: the schedule has %zu scales, this call runs %d model evaluations (agd_adapter_set_schedule)", c->ad_sched.size(), n);
-  if (!c->cn_sched.empty()) FAIL("adapter: a ControlNet schedule is set; the T2I-Adapter with a ControlNet is not implemented (clear one of them)");
-  if (!c->gl_sched.empty()) FAIL("adapter: a GLIGEN schedule is set; the T2I-Adapter with GLIGEN is not implemented (clear one of them)");
-  if (c->ip_mode != 0) FAIL("adapter: an inpainting state is set; the T2I-Adapter with inpainting is not implemented (agd_inpaint_clear first)");
-  if (c->i2_on) FAIL("adapter: an InstructPix2Pix state is set; the T2I-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)");
-  bool any = false; for (float v : c->ad_sched) any = any || v != 0.f;
-  if (any && (c->ad_B < 1 || rows % c->ad_B || c->ad_Lh != Lh || c->ad_Lw != Lw))
-    FAIL("adapter: the features are set for %d images at latent sides %d x %d, this call runs %d rows at %d x %d (agd_adapter_set_cond_hw)", c->ad_B, c->ad_Lh, c->ad_Lw,
-         rows, Lh, Lw);
-  *out = c->ad_sched.data();
-  return 0;
-}
-// The IP-Adapter state of a call on B2 rows: *on = the image branch runs.  Nothing set, or scale 0: the plain UNet, whatever else is set.
-// Otherwise nothing else that changes the walk may be set, the products must be current and built for exactly these rows.
-static int ipa_for(agd_ctx* c, int B2, bool* on) {
-  *on = false;
-  if (c->ipa_B2 < 1 || c->ipa_scale == 0.f) return 0;
-  if (!c->cn_sched.empty()) FAIL("ip_adapter: a ControlNet schedule is set; the IP-Adapter with a ControlNet is not implemented (clear one of them)");
-  if (!c->gl_sched.empty()) FAIL("ip_adapter: a GLIGEN schedule is set; the IP-Adapter with GLIGEN is not implemented (clear one of them)");
-  if (!c->ad_sched.empty()) FAIL("ip_adapter: a T2I-Adapter schedule is set; the IP-Adapter with a T2I-Adapter is not implemented (clear one of them)");
-  if (c->ip_mode != 0) FAIL("ip_adapter: an inpainting state is set; the IP-Adapter with inpainting is not implemented (agd_inpaint_clear first)");
-  if (c->i2_on) FAIL("ip_adapter: an InstructPix2Pix state is set; the IP-Adapter with InstructPix2Pix is not implemented (agd_ip2p_clear first)");
-  if (c->ipa_stale) FAIL("ip_adapter: a LoRA scale change rewrote to_q / to_out after the image products were built (call agd_ip_adapter_set again)");
-  if (c->ipa_B2 != B2) FAIL("ip_adapter: the image tokens are set for %d rows, this call runs %d (agd_ip_adapter_set)", c->ipa_B2, B2);
-  *on = true;
-  return 0;
-}
-// an entry point that runs the UNet alone
-static int ipa_refuse(agd_ctx* c, const char* what) {
-  if (c->ipa_B2 > 0 && c->ipa_scale != 0.f) FAIL("%s: an IP-Adapter image is set; %s runs without it (agd_ip_adapter_clear first)", what, what);
-  return 0;
-}
-// the inpaint state of a fused loop of n model evaluations on `batch` images at latent size Lh x Lw: *blend = the (sa, sb) schedule of the
-// 4-channel blend, nullptr otherwise.  Without a state the UNet must take exactly the latent channels.
-static int inpaint_for(agd_ctx* c, int n, int batch, int Lh, int Lw, const float** blend) {
-  *blend = nullptr;
-  if (c->ip_mode == 0) {
-    if (c->cfg.in_channels != c->cfg.out_channels)
-      FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first, an InstructPix2Pix UNet agd_ip2p_set_hw",
-           c->cfg.in_channels, c->cfg.out_channels);
+// The conditioning of the call `who` makes: n model evaluations on `rows` images at latent size Lh x Lw (agd_unet_forward_hw: its UNet rows;
+// a loop: its batch, the UNet then runs 2 rows of them under CFG).  Everything that can refuse does so here, before the first launch, in this
+// order: (a) which states are set, (b) the conflict table, (c) whether each state that runs fits this call.  *out: what the call then runs.
+static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw, CallCond* out) {
+  *out = CallCond();
+  const int B2 = who == CALL_UNET_FORWARD ? rows : 2 * rows;
+  // (a) a schedule counts once it is non-empty, all zeros too; the IP-Adapter only with rows and a non-zero scale (idle otherwise)
+  bool set[N_COND_STATES];
+  set[ST_CN] = !c->cn_sched.empty(); set[ST_GL] = !c->gl_sched.empty(); set[ST_INP] = c->ip_mode != 0; set[ST_I2P] = c->i2_on;
+  set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f;
+  for (const ConflictRow& r : kConflicts) {                          // (b) rows top to bottom, the first set cell wins
+    if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
+    for (int s = 0; s < N_COND_STATES; ++s) if (set[s] && r.with[s]) FAIL("%s", r.with[s]);
+  }
+  // (c) the entry points that run the UNet alone have refused every state they read; the latents must be all the UNet takes
+  if (who == CALL_PANORAMA && c->cfg.in_channels != c->cfg.out_channels)
+    FAIL("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels);
+  if (who == CALL_UNET_FORWARD_TS || who == CALL_PANORAMA) return 0;
+  if (who == CALL_IP2P_LOOP) {
+    CK(ip2p_check_unet(c, "ip2p"));
+    if (c->i2_B != rows || c->i2_Lh != Lh || c->i2_Lw != Lw)
+      FAIL("ip2p: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->i2_B, c->i2_Lh, c->i2_Lw, rows, Lh, Lw);
     return 0;
   }
-  if (c->ip_B != batch || c->ip_Lh != Lh || c->ip_Lw != Lw)
-    FAIL("inpaint: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->ip_B, c->ip_Lh, c->ip_Lw, batch, Lh, Lw);
-  if (!c->cn_sched.empty()) FAIL("inpaint: a ControlNet schedule is set; ControlNet inpainting is not implemented");
-  if (c->ip_mode == 2) {
-    if ((int)c->ip_sched.size() != 2 * n) FAIL("inpaint: the blend schedule has %zu entries, this call runs %d model evaluations (agd_inpaint_set_schedule)", c->ip_sched.size() / 2, n);
-    *blend = c->ip_sched.data();
+  // a schedule's length is the call's evaluations; what it reads must exist for exactly these rows and sizes once any entry is non-zero
+  auto any = [](const auto& v) { for (auto x : v) if (x != 0) return true; return false; };
+  if (set[ST_CN]) {
+    if ((int)c->cn_sched.size() != n) FAIL("controlnet: the schedule has %zu scales, this call runs %d model evaluations (agd_controlnet_set_schedule)", c->cn_sched.size(), n);
+    if (any(c->cn_sched) && (c->cn_emb_B2 != B2 || c->cn_emb_Lh != Lh || c->cn_emb_Lw != Lw))
+      FAIL("controlnet: no conditioning image set for %d rows at latent sides %d x %d (agd_controlnet_set_cond has %d rows at %d x %d)", B2, Lh, Lw, c->cn_emb_B2, c->cn_emb_Lh, c->cn_emb_Lw);
+    out->cn = c->cn_sched.data();
+  }
+  if (set[ST_GL]) {
+    if ((int)c->gl_sched.size() != n) FAIL("gligen: the schedule has %zu flags, this call runs %d model evaluations (agd_gligen_set_schedule)", c->gl_sched.size(), n);
+    if (any(c->gl_sched) && c->gl_B2 != B2) FAIL("gligen: the grounding objects are set for %d rows, this call runs %d (agd_gligen_set)", c->gl_B2, B2);
+    out->gl = c->gl_sched.data();
+  }
+  if (who == CALL_EVAL_LOOP && !set[ST_INP] && c->cfg.in_channels != c->cfg.out_channels)
+    FAIL("denoise: the UNet takes %d input channels, the latents have %d: an inpainting UNet needs agd_inpaint_set first, an InstructPix2Pix UNet agd_ip2p_set_hw",
+         c->cfg.in_channels, c->cfg.out_channels);
+  if (who == CALL_EVAL_LOOP && set[ST_INP]) {
+    if (c->ip_B != rows || c->ip_Lh != Lh || c->ip_Lw != Lw)
+      FAIL("inpaint: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->ip_B, c->ip_Lh, c->ip_Lw, rows, Lh, Lw);
+    if (c->ip_mode == 2) {
+      if ((int)c->ip_sched.size() != 2 * n) FAIL("inpaint: the blend schedule has %zu entries, this call runs %d model evaluations (agd_inpaint_set_schedule)", c->ip_sched.size() / 2, n);
+      out->blend = c->ip_sched.data();
+    }
+  }
+  if (set[ST_AD]) {                                                // features for ad_B images serve rows a multiple of it (row image b reads feature image b % ad_B)
+    if ((int)c->ad_sched.size() != n) FAIL("adapter: the schedule has %zu scales, this call runs %d model evaluations (agd_adapter_set_schedule)", c->ad_sched.size(), n);
+    if (any(c->ad_sched) && (c->ad_B < 1 || rows % c->ad_B || c->ad_Lh != Lh || c->ad_Lw != Lw))
+      FAIL("adapter: the features are set for %d images at latent sides %d x %d, this call runs %d rows at %d x %d (agd_adapter_set_cond_hw)", c->ad_B, c->ad_Lh, c->ad_Lw, rows, Lh, Lw);
+    out->ad = c->ad_sched.data();
+  }
+  if (set[ST_IPA]) {
+    if (c->ipa_stale) FAIL("ip_adapter: a LoRA scale change rewrote to_q / to_out after the image products were built (call agd_ip_adapter_set again)");
+    if (c->ipa_B2 != B2) FAIL("ip_adapter: the image tokens are set for %d rows, this call runs %d (agd_ip_adapter_set)", c->ipa_B2, B2);
+    out->ipa = true;
   }
   return 0;
 }
@@ -2182,16 +2224,9 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
-  const float* cs = nullptr;
-  API_CK(c, cn_schedule_for(c, 1, batch2, Lh, Lw, &cs));                     // a one-element ControlNet schedule: one injected forward
-  const int* gs = nullptr;
-  API_CK(c, gl_schedule_for(c, 1, batch2, &gs));                             // a one-element GLIGEN schedule: one grounded forward
-  const float* as = nullptr;
-  API_CK(c, adapter_for(c, 1, batch2, Lh, Lw, &as));                         // a one-element T2I-Adapter schedule: one forward with the features added
-  bool ipa = false;
-  API_CK(c, ipa_for(c, batch2, &ipa));                                       // the IP-Adapter's image branch (agd_ip_adapter_set)
+  CallCond cc; API_CK(c, resolve_cond(c, CALL_UNET_FORWARD, 1, batch2, Lh, Lw, &cc));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cs ? cs[0] : 0.f, gs && gs[0], as ? as[0] : 0.f, ipa));
+  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cc.at(0)));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
 }
@@ -2205,10 +2240,7 @@ AGD_API int agd_unet_forward_ts_hw(agd_ctx* c, const float* sample, int batch2, 
   API_CK(c, need_final(c));
   API_CK(c, check_latent_hw(c, "unet_forward_ts", Lh, Lw));
   if (!timesteps || batch2 < 1) { agd_set_error("unet_forward_ts: bad arguments"); return fail_ctx(c); }
-  if (!c->cn_sched.empty()) { agd_set_error("unet_forward_ts: a ControlNet schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
-  if (!c->gl_sched.empty()) { agd_set_error("unet_forward_ts: a GLIGEN schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
-  if (!c->ad_sched.empty()) { agd_set_error("unet_forward_ts: a T2I-Adapter schedule is set; per-image timesteps run the UNet alone (clear it first)"); return fail_ctx(c); }
-  API_CK(c, ipa_refuse(c, "unet_forward_ts"));
+  CallCond cc; API_CK(c, resolve_cond(c, CALL_UNET_FORWARD_TS, 1, batch2, Lh, Lw, &cc));
   hipStream_t st = S(stream);
   API_CK(c, ensure_lat(c, batch2, Lh, Lw));
   const int Cl = c->cfg.in_channels;
@@ -2267,25 +2299,6 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
   return 0;
 }
 
-// an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
-static int ip2p_check_unet(agd_ctx* c, const char* what) {
-  const agd_config& g = c->cfg;
-  if (g.in_channels != g.out_channels + g.vae_latent_channels || g.in_channels > 64)
-    FAIL("%s: the UNet takes %d input channels, InstructPix2Pix needs %d latent + %d image-latent channels", what, g.in_channels, g.out_channels, g.vae_latent_channels);
-  return 0;
-}
-// The InstructPix2Pix state of a fused loop of n model evaluations on `batch` images at Lh x Lw; every refusal names its cause
-static int ip2p_for(agd_ctx* c, int batch, int Lh, int Lw) {
-  CK(ip2p_check_unet(c, "ip2p"));
-  if (c->i2_B != batch || c->i2_Lh != Lh || c->i2_Lw != Lw)
-    FAIL("ip2p: the state holds %d images at latent sides %d x %d, this call runs %d at %d x %d", c->i2_B, c->i2_Lh, c->i2_Lw, batch, Lh, Lw);
-  if (!c->cn_sched.empty()) FAIL("ip2p: a ControlNet schedule is set; ControlNet with InstructPix2Pix is not implemented (clear it first)");
-  if (!c->gl_sched.empty()) FAIL("ip2p: a GLIGEN schedule is set; GLIGEN with InstructPix2Pix is not implemented (clear it first)");
-  if (c->ip_mode != 0) FAIL("ip2p: an inpainting state is set; inpainting with InstructPix2Pix is not implemented (agd_inpaint_clear first)");
-  if (!c->ad_sched.empty()) FAIL("ip2p: a T2I-Adapter schedule is set; the T2I-Adapter with InstructPix2Pix is not implemented (clear it first)");
-  CK(ipa_refuse(c, "ip2p"));
-  return 0;
-}
 // The uncond walk of an InstructPix2Pix evaluation runs `rows` images against the first `rows` context rows -- the [uncond x B] half of the
 // [uncond x B | cond x B] agd_set_context projected -- and records nothing.  The engine is put back as it was when the walk ends, on an error too.
 struct Ip2pUncond {
@@ -2300,7 +2313,7 @@ struct Ip2pUncond {
 template <class Step>
 static int run_ip2p_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, int Lh, int Lw, int n, const float* timesteps, Step&& step) {
   const int B2 = 2 * batch, HW = Lh * Lw, oc = c->cfg.out_channels;
-  CK(ip2p_for(c, batch, Lh, Lw));
+  CallCond cc; CK(resolve_cond(c, CALL_IP2P_LOOP, n, batch, Lh, Lw, &cc));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
   CK(ensure_lat(c, 3 * batch, Lh, Lw));
   const float* tp_all = nullptr;
@@ -2322,7 +2335,7 @@ static int run_ip2p_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
 }
 
 // The CFG evaluation loop of every fused denoise call: n model evaluations on `batch` images at Lh x Lw, `latents` updated in place.  Per
-// evaluation i: the UNet input from the latents, the walk under that evaluation's time embedding, ControlNet scale and GLIGEN flag, then
+// evaluation i: the UNet input from the latents, the walk under that evaluation's time embedding and conditioning (cc.at(i)), then
 // step(i, eps) -- the scheduler's kernel, eps [uncond | cond] -> latents -- then the inpainting blend when a blend schedule is set.  With an
 // InstructPix2Pix state the three-branch loop above runs instead.  Every refusal comes before the first launch.
 template <class Step>
@@ -2331,23 +2344,14 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   const int B2 = 2 * batch, HW = Lh * Lw;
   CK(ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
-  const float* cs = nullptr;                                       // the ControlNet's per-evaluation scales (none: the UNet alone)
-  CK(cn_schedule_for(c, n, B2, Lh, Lw, &cs));
-  const int* gs = nullptr;                                         // the GLIGEN per-evaluation flags (none: no fuser runs)
-  CK(gl_schedule_for(c, n, B2, &gs));
-  const float* ib = nullptr;                                       // the inpainting blend's (sa, sb) per evaluation (none: no blend)
-  CK(inpaint_for(c, n, batch, Lh, Lw, &ib));
-  const float* as = nullptr;                                       // the T2I-Adapter's per-evaluation scales (none: no feature is added)
-  CK(adapter_for(c, n, batch, Lh, Lw, &as));
-  bool ipa = false;                                                // the IP-Adapter's image branch in every evaluation (none: the plain UNet)
-  CK(ipa_for(c, B2, &ipa));
+  CallCond cc; CK(resolve_cond(c, CALL_EVAL_LOOP, n, batch, Lh, Lw, &cc));
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
-    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cs ? cs[i] : 0.f, gs && gs[i], as ? as[i] : 0.f, ipa));
+    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cc.at(i)));
     CK(step(i, c->eps_nhwc));
-    if (ib) CK(inpaint_blend(c, st, latents, batch, HW, ib + 2 * i));
+    if (cc.blend) CK(inpaint_blend(c, st, latents, batch, HW, cc.blend + 2 * i));
   }
   return 0;
 }
@@ -2429,13 +2433,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
   int nbh = 0, nbw = 0;
   API_CK(c, check_panorama(c, "denoise_panorama", Lh, Lw, window, stride, &nbh, &nbw));
   if (batch < 1 || n_steps < 1 || !canvas || !timesteps || !alpha_t || !alpha_prev) { agd_set_error("denoise_panorama: batch %d, steps %d or a null argument", batch, n_steps); return fail_ctx(c); }
-  if (!c->cn_sched.empty()) { agd_set_error("denoise_panorama: a ControlNet schedule is set; ControlNet on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
-  if (!c->gl_sched.empty()) { agd_set_error("denoise_panorama: a GLIGEN schedule is set; GLIGEN on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
-  if (c->ip_mode != 0) { agd_set_error("denoise_panorama: an inpainting state is set; inpainting on a panorama is not implemented (agd_inpaint_clear first)"); return fail_ctx(c); }
-  if (c->i2_on) { agd_set_error("denoise_panorama: an InstructPix2Pix state is set; InstructPix2Pix on a panorama is not implemented (agd_ip2p_clear first)"); return fail_ctx(c); }
-  if (!c->ad_sched.empty()) { agd_set_error("denoise_panorama: a T2I-Adapter schedule is set; the T2I-Adapter on a panorama is not implemented (clear it first)"); return fail_ctx(c); }
-  API_CK(c, ipa_refuse(c, "denoise_panorama"));
-  if (c->cfg.in_channels != c->cfg.out_channels) { agd_set_error("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels); return fail_ctx(c); }
+  CallCond cc; API_CK(c, resolve_cond(c, CALL_PANORAMA, n_steps, batch, window, window, &cc));
   if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
   const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
   const int Cl = c->cfg.out_channels, HW = window * window;
@@ -3831,15 +3829,18 @@ AGD_API int agd_controlnet_set_cond(agd_ctx* c, const float* cond, int batch, in
   return agd_controlnet_set_cond_hw(c, cond, batch, side, side, repeat, stream);
 }
 
-AGD_API int agd_controlnet_set_schedule(agd_ctx* c, const float* scales, int n) {
-  if (!c) { agd_set_error("null ctx"); return -1; }
-  if (n < 0 || (n > 0 && !scales)) { agd_set_error("controlnet_set_schedule: %d scales", n); return fail_ctx(c); }
-  if (n > 0 && !c->cn_on) { agd_set_error("controlnet_set_schedule: no ControlNet loaded"); return fail_ctx(c); }
-  for (int i = 0; i < n; ++i) if (!std::isfinite(scales[i])) { agd_set_error("controlnet_set_schedule: scale %d is %g", i, scales[i]); return fail_ctx(c); }
-  c->cn_sched.assign(scales, scales + n);
+// agd_controlnet_set_schedule / agd_adapter_set_schedule: n finite scales, one per model evaluation (n = 0 clears) for a loaded model
+static int set_scale_schedule(agd_ctx* c, const char* what, const char* model, bool loaded, const float* scales, int n, std::vector<float>* sched) {
+  if (n < 0 || (n > 0 && !scales)) { agd_set_error("%s: %d scales", what, n); return fail_ctx(c); }
+  if (n > 0 && !loaded) { agd_set_error("%s: no %s loaded", what, model); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i) if (!std::isfinite(scales[i])) { agd_set_error("%s: scale %d is %g", what, i, scales[i]); return fail_ctx(c); }
+  sched->assign(scales, scales + n);
   return 0;
 }
-
+AGD_API int agd_controlnet_set_schedule(agd_ctx* c, const float* scales, int n) {
+  if (!c) { agd_set_error("null ctx"); return -1; }
+  return set_scale_schedule(c, "controlnet_set_schedule", "ControlNet", c->cn_on, scales, n, &c->cn_sched);
+}
 
 AGD_API int agd_controlnet_residuals_hw(agd_ctx* c, const float* sample, int batch2, int Lh, int Lw, float timestep, float scale, int nhwc,
                                         float* out, long long* n_out, void* stream) {
@@ -3966,16 +3967,12 @@ AGD_API int agd_adapter_features(agd_ctx* c, float* out) {
 
 AGD_API int agd_adapter_set_schedule(agd_ctx* c, const float* scales, int n) {
   if (!c) { agd_set_error("null ctx"); return -1; }
-  if (n < 0 || (n > 0 && !scales)) { agd_set_error("adapter_set_schedule: %d scales", n); return fail_ctx(c); }
-  if (n > 0 && !c->ad_on) { agd_set_error("adapter_set_schedule: no T2I-Adapter loaded"); return fail_ctx(c); }
-  for (int i = 0; i < n; ++i) if (!std::isfinite(scales[i])) { agd_set_error("adapter_set_schedule: scale %d is %g", i, scales[i]); return fail_ctx(c); }
-  c->ad_sched.assign(scales, scales + n);
-  return 0;
+  return set_scale_schedule(c, "adapter_set_schedule", "T2I-Adapter", c->ad_on, scales, n, &c->ad_sched);
 }
 
 AGD_API int agd_adapter_clear(agd_ctx* c) {
   if (!c) { agd_set_error("null ctx"); return -1; }
-  c->ad_sched.clear(); c->ad_B = 0; c->ad_Lh = c->ad_Lw = 0; c->ad_cur = 0.f;
+  c->ad_sched.clear(); c->ad_B = 0; c->ad_Lh = c->ad_Lw = 0; c->cur.ad_scale = 0.f;
   return 0;
 }
 
@@ -4296,7 +4293,7 @@ AGD_API int agd_gligen_set_schedule(agd_ctx* c, const int* flags, int n) {
 
 AGD_API int agd_gligen_clear(agd_ctx* c) {
   if (!c) { agd_set_error("null ctx"); return -1; }
-  c->gl_sched.clear(); c->gl_B2 = 0; c->gl_active = false;
+  c->gl_sched.clear(); c->gl_B2 = 0; c->cur.grounded = false;
   return 0;
 }
 
@@ -4310,14 +4307,19 @@ AGD_API int agd_gligen_objs(agd_ctx* c, float* out) {
   return 0;
 }
 
+// a UNet transformer block as callers name it ("down_blocks.0.attentions.0", with or without "unet." and the trailing dot) -> its weight prefix
+static std::string unet_block_prefix(const char* block_name) {
+  std::string pre(block_name);
+  if (pre.compare(0, 5, "unet.") != 0) pre = "unet." + pre;
+  if (pre.back() != '.') pre += ".";
+  return pre;
+}
 AGD_API int agd_gligen_fuser(agd_ctx* c, const char* block_name, const float* x, int batch2, int h, int w, float* out, void* stream) {
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   if (!c->gl_on) { agd_set_error("gligen_fuser: no GLIGEN UNet loaded"); return fail_ctx(c); }
   if (!block_name || !x || !out || batch2 < 1 || h < 1 || w < 1) { agd_set_error("gligen_fuser: bad arguments"); return fail_ctx(c); }
-  std::string pre(block_name);
-  if (pre.compare(0, 5, "unet.") != 0) pre = "unet." + pre;
-  if (pre.back() != '.') pre += ".";
+  const std::string pre = unet_block_prefix(block_name);
   auto it = c->gl_idx.find(pre);
   if (it == c->gl_idx.end()) { agd_set_error("gligen_fuser: no fuser in block '%s'", block_name); return fail_ctx(c); }
   const Fuser& f = c->gl_f[it->second];
@@ -4464,7 +4466,7 @@ AGD_API int agd_ip_adapter_set(agd_ctx* c, const float* image_embeds, int batch2
 
 AGD_API int agd_ip_adapter_clear(agd_ctx* c) {
   if (!c) { agd_set_error("null ctx"); return -1; }
-  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->ipa_active = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
+  c->ipa_B2 = 0; c->ipa_scale = 0.f; c->ipa_stale = c->cur.ipa = false; c->ipa_counts[0] = c->ipa_counts[1] = 0;
   return 0;
 }
 
@@ -4484,9 +4486,7 @@ AGD_API int agd_ip_adapter_block(agd_ctx* c, const char* block_name, const float
   if (!c->ipa_on || c->ipa_B2 < 1) { agd_set_error("ip_adapter_block: no image tokens set (agd_ip_adapter_set)"); return fail_ctx(c); }
   if (!block_name || !x || !out || batch2 < 1 || h < 1 || w < 1) { agd_set_error("ip_adapter_block: bad arguments"); return fail_ctx(c); }
   if (c->ipa_stale) { agd_set_error("ip_adapter_block: a LoRA scale change rewrote to_q / to_out after the image products were built (call agd_ip_adapter_set again)"); return fail_ctx(c); }
-  std::string pre(block_name);
-  if (pre.compare(0, 5, "unet.") != 0) pre = "unet." + pre;
-  if (pre.back() != '.') pre += ".";
+  const std::string pre = unet_block_prefix(block_name);
   auto it = c->ipa_idx.find(pre);
   if (it == c->ipa_idx.end()) { agd_set_error("ip_adapter_block: no attn2 layer in block '%s'", block_name); return fail_ctx(c); }
   const IpaLayer& l = c->ipa_l[it->second];
