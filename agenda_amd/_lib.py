@@ -195,6 +195,10 @@ _SIGS = {
     "agd_op_window_mean": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
     "agd_denoise_panorama": (C.c_int, [_P, _P] + [C.c_int] * 7 + [C.POINTER(C.c_float)] * 3 + [C.c_float, _P]),
     "agd_daam_global_panorama": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "agd_freeu_set": (C.c_int, [_P] + [C.c_float] * 4),
+    "agd_freeu_clear": (C.c_int, [_P]),
+    "agd_freeu_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "agd_op_freeu": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_float, _P]),
     "agd_profile_begin": (C.c_int, [_P]),
     "agd_profile_end": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "agd_profile_end_ex": (C.c_int, [_P, C.c_double, C.c_double] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_longlong)]),

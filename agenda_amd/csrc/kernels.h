@@ -260,6 +260,13 @@ int launch_adapter_avgpool(const bf16_t* x, bf16_t* y, int B, int H, int W, int 
 int launch_adapter_relu(bf16_t* x, long long n, hipStream_t st);
 int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, int bm, int B2, int HW, int C, int Bf, float s, hipStream_t st);
 
+// FreeU (freeu.hip): one launch re-weights one up-block resnet's inputs into fresh activations -- hidden_out = hidden with its first Ch / 2
+// channels times b, skip_out = skip with the four lowest frequencies of every map times s (diffusers fourier_filter, threshold 1, as a rank-4
+// projection in fp32), bf16 NHWC [B2][H W][C].  hidden_out / skip_out == nullptr: that tensor is left alone (b == 1 / s == 1).  *_part != nullptr:
+// the GroupNorm partial sums [B2 HW / 64][C] float2 of the bf16-rounded outputs (colstat_out layout; HW % 64 == 0), reduced in a fixed order
+int launch_freeu(const bf16_t* hidden, bf16_t* hidden_out, float* hidden_part, int Ch, const bf16_t* skip, bf16_t* skip_out, float* skip_part, int Cs,
+                 int B2, int H, int W, float b, float s, hipStream_t st);
+
 // IP-Adapter (ipadapter.hip): the once-per-call pieces (fp32 rows against bf16 matrices: y = x W^T + bias, an in-place fp32 LayerNorm, the
 // pre-multiplied per-image matrices of one attn2 layer) and the two per-forward stages.  col = (head, token); colsP = heads * nt padded to 16.
 #define IPA_MAX_COLS 80

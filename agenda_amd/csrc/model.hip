@@ -235,6 +235,9 @@ struct agd_ctx {
   std::vector<IpaLayer> ipa_l; std::unordered_map<std::string, int> ipa_idx;
   DBuf ipa_embb, ipa_tokb, ipa_kipb, ipa_vipb, ipa_wqbb;
   int ipa_B2 = 0; float ipa_scale = 0.f; bool ipa_stale = false; long long ipa_counts[2] = {0, 0};
+  // FreeU (agd_freeu_set / agd_freeu_clear): persistent; unet_walk re-weights the resnet inputs of up blocks 0 and 1 (freeu_apply).
+  // fu_counts: launches that left GroupNorm partial sums / that left none
+  bool fu_on = false; float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f}; long long fu_counts[2] = {0, 0};
   // profiling
   EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
@@ -1224,6 +1227,31 @@ static int controlnet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2
   return 0;
 }
 
+// FreeU on the inputs of one resnet of up block `blk` (0 or 1): ho = h with its first C / 2 channels times b, so = sk with its lowest four
+// frequencies times s, both in FRESH activations written by one launch (freeu.hip) -- the old Acts may still be a ControlNet's or a recorder's
+// operand, and their partial sums / normed copies describe the un-weighted tensors.  b == 1 / s == 1 leaves that tensor (and its Act) alone;
+// both 1 launches nothing.  The outputs carry the GroupNorm partial sums of their bf16-rounded values on 64-row tiles where the concat norm
+// takes them (as adapter_add), cpart_bm = 0 -- the norm's own statistics pass -- elsewhere.
+static int freeu_apply(agd_ctx* c, hipStream_t st, int blk, const Act& h, const Act& sk, Act& ho, Act& so) {
+  const float b = c->fu_b[blk], s = c->fu_s[blk];
+  ho = h; so = sk;
+  if (b == 1.f && s == 1.f) return 0;
+  if (h.B != sk.B || h.H != sk.H || h.W != sk.W) FAIL("freeu: up block %d joins %d x %d x %d with a skip of %d x %d x %d", blk, h.B, h.H, h.W, sk.B, sk.H, sk.W);
+  const int HW = h.H * h.W;
+  if (b != 1.f) { ho = alloc_act(c, h.B, h.H, h.W, h.C, true); if (!ho.p) return -1; }
+  if (s != 1.f) { so = alloc_act(c, sk.B, sk.H, sk.W, sk.C, true); if (!so.p) return -1; }
+  const bool stats = (b == 1.f || ho.cpart) && (s == 1.f || so.cpart) && HW % 64 == 0 &&
+                     (long long)(std::max(h.C, sk.C) / c->cfg.norm_num_groups) * (HW / 64) < 65536;
+  if (b != 1.f) ho.cpart_bm = stats ? 64 : 0;
+  if (s != 1.f) so.cpart_bm = stats ? 64 : 0;
+  const double rows = (double)h.B * HW, ch = (b != 1.f ? h.C : 0) + (s != 1.f ? 1.5 * sk.C : 0);          // (the filter reads its map twice)
+  ProfScope ps(c, st, PC_ELEM, 0, rows * ch * 4.0 + (stats ? rows / 64 * ch * 8.0 : 0.0));
+  CK(launch_freeu(h.p, b != 1.f ? ho.p : nullptr, stats ? ho.cpart : nullptr, h.C, sk.p, s != 1.f ? so.p : nullptr, stats ? so.cpart : nullptr, sk.C,
+                  h.B, h.H, h.W, b, s, st));
+  c->fu_counts[stats ? 0 : 1]++;
+  return 0;
+}
+
 // x: [B2][Lh*Lw][64] bf16 (latent channels zero-padded) -> eps [B2][Lh*Lw][out_channels] fp32 NHWC
 // tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
 // cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
@@ -1256,7 +1284,9 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
       NextGn ngu;
       if (g.down_cross[lvl]) { const std::string nk = u + "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".norm.";
         auto ig = c->V.find(nk + "weight"), ib = c->V.find(nk + "bias"); if (ig != c->V.end() && ib != c->V.end()) { ngu.gamma = ig->second; ngu.beta = ib->second; ngu.eps = 1e-6f; ngu.silu = 0; } }
-      Act r; CK(resnet(c, st, u + "up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", h, &sk, co, 1e-5f, true, G, r, &ngu));
+      Act hf = h, skf = sk;
+      if (c->fu_on && i < 2) CK(freeu_apply(c, st, i, h, sk, hf, skf));       // (off: the plain walk, launch for launch)
+      Act r; CK(resnet(c, st, u + "up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", hf, &skf, co, 1e-5f, true, G, r, &ngu));
       h = r;
       if (g.down_cross[lvl]) {
         Act a; CK(transformer(c, st, u + "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".", h, g.num_heads[lvl], G, a));
@@ -3979,6 +4009,57 @@ AGD_API int agd_adapter_clear(agd_ctx* c) {
 AGD_API int agd_adapter_add_counts(agd_ctx* c, long long* counts) {
   if (!c || !counts) { agd_set_error("adapter_add_counts: null argument"); return fail_ctx(c); }
   counts[0] = c->ad_adds[0]; counts[1] = c->ad_adds[1];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// FreeU (diffusers >= 0.22 enable_freeu / disable_freeu [upstream-knowledge]): persistent state that every later unet_walk reads (freeu_apply)
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_freeu_set(agd_ctx* c, float s1, float s2, float b1, float b2) {
+  API_CK(c, need_final(c));
+  const float v[4] = {s1, s2, b1, b2}; const char* nm[4] = {"s1", "s2", "b1", "b2"};
+  for (int i = 0; i < 4; ++i) if (!std::isfinite(v[i])) { agd_set_error("freeu_set: %s = %g (a finite number)", nm[i], (double)v[i]); return fail_ctx(c); }
+  if (c->cfg.n_levels < 2) { agd_set_error("freeu_set: the UNet has %d level(s); FreeU re-weights up blocks 0 and 1", c->cfg.n_levels); return fail_ctx(c); }
+  c->fu_s[0] = s1; c->fu_s[1] = s2; c->fu_b[0] = b1; c->fu_b[1] = b2;
+  c->fu_on = !(s1 == 1.f && s2 == 1.f && b1 == 1.f && b2 == 1.f);
+  return 0;
+}
+
+AGD_API int agd_freeu_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("freeu_clear: null context"); return -1; }
+  c->fu_on = false; c->fu_s[0] = c->fu_s[1] = c->fu_b[0] = c->fu_b[1] = 1.f;
+  return 0;
+}
+
+AGD_API int agd_freeu_counts(agd_ctx* c, long long* counts) {
+  if (!c || !counts) { agd_set_error("freeu_counts: null argument"); return fail_ctx(c); }
+  counts[0] = c->fu_counts[0]; counts[1] = c->fu_counts[1];
+  return 0;
+}
+
+// The production kernel on fp32 NCHW device tensors (the test seam): inputs rounded to bf16 NHWC, one launch_freeu as the UNet walk issues it
+// (with the partial sums where H W % 64 == 0), outputs widened back.  b == 1 / s == 1: that output is the bf16-rounded input.
+AGD_API int agd_op_freeu(const float* hidden_nchw, const float* skip_nchw, float* hidden_out, float* skip_out, int B, int Ch, int Cs, int H, int W,
+                         float b, float s, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!hidden_nchw || !skip_nchw || !hidden_out || !skip_out) { agd_set_error("op_freeu: null argument"); return -1; }
+  if (B < 1 || H < 1 || W < 1 || Ch < 8 || Ch % 8 || Cs < 8 || Cs % 8 || (long long)H * W >= (1ll << 24) || (long long)B * H * W * std::max(Ch, Cs) >= (1ll << 31)) {
+    agd_set_error("op_freeu: %d maps of %d x %d, %d backbone / %d skip channels (multiples of 8)", B, H, W, Ch, Cs); return -1; }
+  if (!std::isfinite(b) || !std::isfinite(s)) { agd_set_error("op_freeu: b = %g, s = %g (finite numbers)", (double)b, (double)s); return -1; }
+  const int HW = H * W; const size_t nh = (size_t)B * HW * Ch, ns = (size_t)B * HW * Cs;
+  bf16_t* hb = tmp.get<bf16_t>(nh); bf16_t* sb = tmp.get<bf16_t>(ns); bf16_t* ho = tmp.get<bf16_t>(nh); bf16_t* so = tmp.get<bf16_t>(ns);
+  float* hf = tmp.get<float>(nh); float* sf = tmp.get<float>(ns);
+  float* hp = nullptr; float* sp = nullptr;
+  if (HW % 64 == 0) { hp = tmp.get<float>(nh / 64 * 2); sp = tmp.get<float>(ns / 64 * 2); if (!hp || !sp) return -1; }
+  if (!hb || !sb || !ho || !so || !hf || !sf) return -1;
+  CK(to_nhwc_bf16(hidden_nchw, hb, B, Ch, HW, Ch, st));
+  CK(to_nhwc_bf16(skip_nchw, sb, B, Cs, HW, Cs, st));
+  if (b != 1.f || s != 1.f) CK(launch_freeu(hb, b != 1.f ? ho : nullptr, hp, Ch, sb, s != 1.f ? so : nullptr, sp, Cs, B, H, W, b, s, st));
+  CK(launch_bf16_to_f32(b != 1.f ? ho : hb, hf, (long long)nh, st));
+  CK(launch_bf16_to_f32(s != 1.f ? so : sb, sf, (long long)ns, st));
+  CK(launch_nchw_from_nhwc_f32(hf, Ch, hidden_out, B, Ch, HW, st));
+  CK(launch_nchw_from_nhwc_f32(sf, Cs, skip_out, B, Cs, HW, st));
+  hipStreamSynchronize(st);
   return 0;
 }
 

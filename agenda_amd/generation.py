@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -310,7 +311,12 @@ def parse_args(argv=None):
                         "and at least the checkpoint's size (default: that size x 4 times it); DDIM only")
     p.add_argument("--view-batch-size", type=int, default=None, help="panorama: views per UNet call (default: all views of a step at once)")
     p.add_argument("--gligen-beta", type=float, default=0.3, help="GLIGEN: gligen_scheduled_sampling_beta (the grounded share of the evaluations)")
+    p.add_argument("--freeu", type=float, default=None, nargs=4, metavar=("S1", "S2", "B1", "B2"),
+                   help="FreeU (enable_freeu) on every UNet evaluation, with any pipeline: the skip filters' scales and the backbone scales of "
+                        "up blocks 0 and 1; suggested 0.9 0.2 1.2 1.4 (SD-1.4), 0.9 0.2 1.5 1.6 (SD-1.5), 0.9 0.2 1.4 1.6 (SD-2.1)")
     args = p.parse_args(argv)
+    if args.freeu is not None and not all(math.isfinite(v) for v in args.freeu):
+        p.error(f"--freeu {' '.join(str(v) for v in args.freeu)}: four finite numbers")
     if args.lora_path is None and (args.lora_weight_name is not None or args.lora_scale != 1.0):
         p.error("--lora-weight-name / --lora-scale need --lora-path")
     if (args.init_image is None) != (args.mask_image is None):
@@ -543,6 +549,8 @@ def main(argv=None):
     if args.lora_path:
         pipe.load_lora_weights(args.lora_path, weight_name=args.lora_weight_name)
         pipe.fuse_lora(lora_scale=args.lora_scale)
+    if args.freeu is not None:
+        pipe.enable_freeu(*args.freeu)
     ipa_files = None
     if args.ip_adapter_path:
         pipe.load_ip_adapter(args.ip_adapter_path, image_encoder_folder=args.image_encoder_path or "image_encoder")

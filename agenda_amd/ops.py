@@ -218,3 +218,18 @@ def window_mean(views, batch, Lh, Lw, stride=8):
     _lib.check(lib.agd_op_window_mean(_lib.ptr(views), _lib.ptr(out), batch, Cc, Lh, Lw, window, stride, _lib.current_stream_ptr()), None,
                "agd_op_window_mean")
     return out
+
+
+def freeu(hidden, skip, b, s):
+    """FreeU on one resnet's inputs, the production kernel: hidden [B, Ch, H, W] with its first Ch // 2 channels times b, skip [B, Cs, H, W]
+    with the four lowest frequencies of every map times s (diffusers fourier_filter, threshold 1).  Inputs are rounded to bf16; the outputs
+    are the bf16 results as fp32 (b == 1 / s == 1: the rounded input itself)."""
+    lib = _lib.load()
+    hidden, skip = _f32c(hidden), _f32c(skip)
+    B, Ch, H, W = hidden.shape
+    if skip.ndim != 4 or skip.shape[0] != B or tuple(skip.shape[2:]) != (H, W):
+        raise ValueError(f"freeu: hidden {tuple(hidden.shape)} and skip {tuple(skip.shape)} must share batch and map size")
+    ho, so = torch.empty_like(hidden), torch.empty_like(skip)
+    _lib.check(lib.agd_op_freeu(_lib.ptr(hidden), _lib.ptr(skip), _lib.ptr(ho), _lib.ptr(so), B, Ch, skip.shape[1], H, W, float(b), float(s),
+                                _lib.current_stream_ptr()), None, "agd_op_freeu")
+    return ho, so

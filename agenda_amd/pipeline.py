@@ -385,6 +385,19 @@ class Engine:
         self._ck(self.lib.agd_ip_adapter_counts(self.ctx, n), "agd_ip_adapter_counts")
         return int(n[0]), int(n[1])
 
+    def freeu_set(self, s1: float, s2: float, b1: float, b2: float):
+        """`agd_freeu_set`: FreeU on every later UNet evaluation of this engine, until freeu_clear (all four 1: the plain UNet)."""
+        self._ck(self.lib.agd_freeu_set(self.ctx, float(s1), float(s2), float(b1), float(b2)), "agd_freeu_set")
+
+    def freeu_clear(self):
+        self._ck(self.lib.agd_freeu_clear(self.ctx), "agd_freeu_clear")
+
+    def freeu_counts(self):
+        """`agd_freeu_counts`: (FreeU launches that left GroupNorm partial sums, launches that left none) since the engine was created."""
+        n = (C.c_longlong * 2)()
+        self._ck(self.lib.agd_freeu_counts(self.ctx, n), "agd_freeu_counts")
+        return int(n[0]), int(n[1])
+
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
         self._glcfg = _lib.AgdGligenConfig()
         self._glcfg.struct_size = C.sizeof(_lib.AgdGligenConfig)
@@ -738,6 +751,7 @@ class UNetHandle:
         names = cross_attn_layer_names(pipe.cfg.unet, include_mid=True)
         self._attn2 = {n: AttnHandle(self, n, 0, True) for n in names}
         self._attn1 = {n.replace("attn2", "attn1"): AttnHandle(self, n.replace("attn2", "attn1"), 0, False) for n in names}
+        self.freeu = None                 # enable_freeu: (s1, s2, b1, b2)
         self._procs = {}
         for n in names:
             self._procs[n + ".processor"] = self._default
@@ -783,6 +797,15 @@ class UNetHandle:
             raise TypeError(f"unsupported unet() arguments: {sorted(unused)}")
         out = self._forward(sample, timestep, encoder_hidden_states)
         return UNetOutput(sample=out) if return_dict else (out,)
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' `unet.enable_freeu`: FreeU on every later evaluation of this UNet (the engine holds the state) until disable_freeu."""
+        self._pipe.engine.freeu_set(s1, s2, b1, b2)
+        self.freeu = (float(s1), float(s2), float(b1), float(b2))
+
+    def disable_freeu(self):
+        self._pipe.engine.freeu_clear()
+        self.freeu = None
 
     def _forward(self, sample, timestep, encoder_hidden_states=None):
         if encoder_hidden_states is not None:
@@ -1191,6 +1214,16 @@ class StableDiffusionPipeline:
         if "cuda" not in str(device):
             raise _lib.AgendaHipError("agenda_amd runs on the GPU only")
         return self
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al. 2023; diffusers >= 0.22 `pipe.enable_freeu`): in up blocks 0 / 1 the first half of the backbone's channels times
+        b1 / b2 and the skip's lowest frequencies times s1 / s2, at every UNet evaluation of every later call, until disable_freeu.
+        Suggested: SD-1.4 (0.9, 0.2, 1.2, 1.4), SD-1.5 (0.9, 0.2, 1.5, 1.6), SD-2.1 (0.9, 0.2, 1.4, 1.6).  Not saved by save_pretrained."""
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        """The plain UNet again, launch for launch: results are bit-identical to a pipeline that never enabled FreeU."""
+        self.unet.disable_freeu()
 
     def set_progress_bar_config(self, **kw):
         self._progress = kw

@@ -505,6 +505,28 @@ int agd_denoise_panorama(agd_ctx* ctx, float* canvas, int batch, int Lh, int Lw,
                          const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
 int agd_daam_global_panorama(agd_ctx* ctx, int img, int rows, float* out, void* stream);
 
+/* ---- FreeU (Si et al. 2023; diffusers >= 0.22 enable_freeu(s1, s2, b1, b2) / disable_freeu [upstream-knowledge]; csrc/freeu.hip): a
+ * training-free re-weighting of the UNet decoder.  In up block i in {0, 1}, for every resnet of the block and immediately before its concat,
+ *   hidden[:, : C / 2] *= b_i           (the first half of the backbone's channels)
+ *   skip = fourier_filter(skip, 1, s_i) (the centred 2 x 2 block of the shifted 2-D spectrum times s_i: the frequencies {-1, 0} x {-1, 0})
+ * with (b, s) = (b1, s1) in block 0 and (b2, s2) in block 1; the upsamplers, the transformers and every other block are untouched, and with a
+ * ControlNet the filtered skip is the one with the residual added.  The filter runs as a rank-4 projection (seven real sums per image and
+ * channel, no transform), any map size; both tensors of a resnet are written by ONE launch into fresh activations.
+ * agd_freeu_set: persistent context state after agd_finalize, read by every later UNet evaluation (agd_unet_forward*, agd_denoise*,
+ *   the InstructPix2Pix loop, agd_denoise_panorama) beside any conditioning state; needs finite values and at least two UNet levels.  A b of
+ *   exactly 1 skips that block's scale, an s of exactly 1 its filter; all four 1 is agd_freeu_clear.  Suggested: SD-1.4 (0.9, 0.2, 1.2, 1.4),
+ *   SD-1.5 (0.9, 0.2, 1.5, 1.6), SD-2.1 (0.9, 0.2, 1.4, 1.6).
+ * agd_freeu_clear: the plain UNet again, launch for launch (bit-identical results).
+ * agd_freeu_counts (seam for tests): the FreeU launches since agd_create -- counts[0] those that left GroupNorm partial sums for the concat
+ *   norm, counts[1] those that left none (maps whose pixel count is no multiple of 64, or "gn_fused_stats" off).
+ * agd_op_freeu (seam for tests): the production kernel on fp32 NCHW device tensors hidden [B][Ch][H][W] / skip [B][Cs][H][W], rounded to
+ *   bf16 on the way in; the outputs are the bf16 results widened (b == 1 / s == 1: the rounded input itself).  Ch, Cs multiples of 8. */
+int agd_freeu_set(agd_ctx* ctx, float s1, float s2, float b1, float b2);
+int agd_freeu_clear(agd_ctx* ctx);
+int agd_freeu_counts(agd_ctx* ctx, long long* counts);
+int agd_op_freeu(const float* hidden_nchw, const float* skip_nchw, float* hidden_out, float* skip_out, int B, int Ch, int Cs, int H, int W,
+                 float b, float s, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
