@@ -199,6 +199,10 @@ _SIGS = {
     "agd_freeu_clear": (C.c_int, [_P]),
     "agd_freeu_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
     "agd_op_freeu": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_float, _P]),
+    "agd_guidance_rescale_set": (C.c_int, [_P, C.c_float]),
+    "agd_guidance_rescale_clear": (C.c_int, [_P]),
+    "agd_guidance_rescale_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "agd_op_guidance_rescale": (C.c_int, [_P, _P] + [C.c_int] * 4 + [C.c_float, C.c_float, _P, _P]),
     "agd_profile_begin": (C.c_int, [_P]),
     "agd_profile_end": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "agd_profile_end_ex": (C.c_int, [_P, C.c_double, C.c_double] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_longlong)]),

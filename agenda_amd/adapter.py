@@ -176,7 +176,7 @@ class StableDiffusionAdapterPipeline(StableDiffusionPipeline):
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None, generator=None,
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  num_images_per_prompt: int = 1, adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0,
-                 cross_attention_kwargs: Optional[dict] = None):
+                 cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0):
         if isinstance(adapter_conditioning_scale, (list, tuple)):
             raise NotImplementedError("a list-valued adapter_conditioning_scale (MultiAdapter) is not implemented")
         if image is None:
@@ -197,7 +197,7 @@ class StableDiffusionAdapterPipeline(StableDiffusionPipeline):
             return super().__call__(prompt, height=height, width=width, num_inference_steps=num_inference_steps,
                                     guidance_scale=guidance_scale, negative_prompt=negative_prompt, generator=generator, latents=latents,
                                     prompt_embeds=prompt_embeds, output_type=output_type, num_images_per_prompt=num_images_per_prompt,
-                                    cross_attention_kwargs=cross_attention_kwargs)
+                                    cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale)
         finally:
             self._ad_pending = None
             self.engine.adapter_set_schedule([])

@@ -54,11 +54,14 @@ class SchedulerConfig:
     skip_prk_steps: bool = True       # PNDM only: SD checkpoints set it (pure PLMS); False (Runge-Kutta warm-up) is refused, not ignored
     # DPMSolverMultistepScheduler only (any other value of the solver keys is refused, not ignored)
     use_karras_sigmas: bool = False
-    timestep_spacing: str = "linspace"   # DDIM / PNDM always run "leading"
+    timestep_spacing: str = "linspace"   # DPM's own spacing; DDIM's is ddim_timestep_spacing below, PNDM always runs "leading"
     algorithm_type: str = "dpmsolver++"
     solver_order: int = 2
     solver_type: str = "midpoint"
     lower_order_final: bool = True
+    # DDIMScheduler only (img2img's DDIM table follows them; PNDM and DPM-Solver++ refuse anything but these defaults, by name)
+    ddim_timestep_spacing: str = "leading"   # "leading" | "trailing" | "linspace"
+    rescale_betas_zero_snr: bool = False     # Lin et al. 2023: the last timestep carries pure noise (alphas_cumprod[-1] == 0)
 
 
 @dataclass

@@ -172,7 +172,8 @@ class StableDiffusionControlNetPipeline(StableDiffusionPipeline):
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None, generator=None,
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  num_images_per_prompt: int = 1, controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
-                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, cross_attention_kwargs: Optional[dict] = None):
+                 control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, cross_attention_kwargs: Optional[dict] = None,
+                 guidance_rescale: float = 0.0):
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not implemented")
         if isinstance(controlnet_conditioning_scale, (list, tuple)) or isinstance(control_guidance_start, (list, tuple)) \
@@ -195,7 +196,7 @@ class StableDiffusionControlNetPipeline(StableDiffusionPipeline):
             return super().__call__(prompt, height=height, width=width, num_inference_steps=num_inference_steps,
                                     guidance_scale=guidance_scale, negative_prompt=negative_prompt, generator=generator, latents=latents,
                                     prompt_embeds=prompt_embeds, output_type=output_type, num_images_per_prompt=num_images_per_prompt,
-                                    cross_attention_kwargs=cross_attention_kwargs)
+                                    cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale)
         finally:
             self._cn_pending = None
             self.engine.controlnet_set_schedule([])

@@ -213,12 +213,18 @@ int launch_prep_latents(const float* lat_nchw, bf16_t* out_nhwc, int B, int C, i
 int launch_timestep_embed(float t, float* out, int dim, hipStream_t st);
 int launch_small_linear(const float* x, const bf16_t* W, const float* bias, float* out, int M, int N, int K, int silu_in,
                         int silu_out, hipStream_t st);
+// the three CFG step kernels: factor == nullptr is the plain combine; else [B] device floats (launch_guidance_factor) that multiply the
+// combined prediction of each image before the step uses it (guidance_rescale)
 int launch_cfg_ddim(const float* eps_nhwc, int ldc, float* lat_nchw, int B, int C, int HW, float guidance,
-                    float a_t, float a_p, int vpred, hipStream_t st);
+                    float a_t, float a_p, int vpred, const float* factor, hipStream_t st);
 int launch_cfg_plms(const float* eps_nhwc, int ldc, float* lat, const float* src, const float* h1, const float* h2, const float* h3,
-                    float* store, int B, int C, int HW, float guidance, const float* w4, float a, float b, hipStream_t st);
+                    float* store, int B, int C, int HW, float guidance, const float* w4, float a, float b, const float* factor, hipStream_t st);
 int launch_cfg_dpm(const float* eps_nhwc, int ldc, float* lat, const float* prev, float* store, int B, int C, int HW, float guidance,
-                   const float* coef5 /* cx, ce, a, b0, b1 */, hipStream_t st);
+                   const float* coef5 /* cx, ce, a, b0, b1 */, const float* factor, hipStream_t st);
+// guidance_rescale (guidance.hip): factor[b] = 1 + phi (std(eps_c[b]) / std(m[b]) - 1), m = eps_u + g (eps_c - eps_u), std over the C HW values
+// of image b (channels c < C of each ldc-wide row), eps in the step kernels' layout.  One workgroup per image, mean-shifted fp32 sums in a
+// fixed order: bit-identical between runs and for an image alone or in a batch.  std(m[b]) == 0 gives 1.  C * HW >= 2.
+int launch_guidance_factor(const float* eps_nhwc, int ldc, int B, int C, int HW, float guidance, float phi, float* factor, hipStream_t st);
 int launch_ln_fold_weight(const bf16_t* W, const float* gamma, const float* beta, const float* bias, int N, int K, int geglu_bn, bf16_t* Wf,
                           float* colsum, float* bias_f, hipStream_t st);
 int launch_image_u8(const float* x_nhwc, int ldc, unsigned char* out, long long npix, int C, hipStream_t st);

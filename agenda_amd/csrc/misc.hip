@@ -170,8 +170,11 @@ int launch_small_linear(const float* x, const bf16_t* W, const float* bias, floa
 
 // CFG combine + DDIM step (eta=0), in place on fp32 NCHW latents.
 // eps NHWC fp32 [2B][HW][ldc]: rows [0,B) unconditional, [B,2B) conditional.
+// RESC (all three step kernels): guidance_rescale -- the combined prediction times factor[image] (guidance.hip) before anything else uses
+// it.  The <false> instantiations are the plain kernels, statement for statement.
+template <bool RESC>
 __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int ldc, float* __restrict__ lat, int B, int C, int HW,
-                                float guidance, float sa_t, float s1a_t, float sa_p, float s1a_p, int vpred) {
+                                float guidance, float sa_t, float s1a_t, float sa_p, float s1a_p, int vpred, const float* __restrict__ factor) {
   const long long total = (long long)B * C * HW;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int p = (int)(i % HW);
@@ -179,7 +182,8 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int ldc, float* _
     const int b = (int)(i / ((long long)HW * C));
     const float eu = eps[((long long)b * HW + p) * ldc + c];
     const float ec = eps[((long long)(b + B) * HW + p) * ldc + c];
-    const float mo = eu + guidance * (ec - eu);
+    float mo = eu + guidance * (ec - eu);
+    if (RESC) mo *= factor[b];
     const float x = lat[i];
     float x0, e;
     if (!vpred) { x0 = (x - s1a_t * mo) / sa_t; e = mo; }
@@ -188,20 +192,22 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int ldc, float* _
   }
 }
 int launch_cfg_ddim(const float* eps, int ldc, float* lat, int B, int C, int HW, float guidance, float a_t, float a_p,
-                    int vpred, hipStream_t st) {
-  hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, st, eps, ldc, lat, B, C, HW, guidance,
-                     sqrtf(a_t), sqrtf(1.f - a_t), sqrtf(a_p), sqrtf(1.f - a_p), vpred);
+                    int vpred, const float* factor, hipStream_t st) {
+  hipLaunchKernelGGL(factor ? cfg_ddim_kernel<true> : cfg_ddim_kernel<false>, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, st, eps, ldc, lat, B, C, HW,
+                     guidance, sqrtf(a_t), sqrtf(1.f - a_t), sqrtf(a_p), sqrtf(1.f - a_p), vpred, factor);
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }
 
 // CFG combine + one linear-multistep (PNDM / PLMS) update on fp32 NCHW latents:
 //   e0 = eps_u + g (eps_c - eps_u);  e = w0 e0 + w1 h1 + w2 h2 + w3 h3;  lat = a * src + b * e;  store (if given) = e0
+// (with guidance_rescale e0 is the rescaled one, in the history too: upstream rescales before scheduler.step)
 // h1..h3: CFG-combined eps of earlier model evaluations (NCHW); src: the sample the step starts from (lat itself, or the
 // sample saved at the first evaluation for PLMS's second call).
+template <bool RESC>
 __global__ void cfg_plms_kernel(const float* __restrict__ eps, int ldc, float* __restrict__ lat, const float* __restrict__ src,
                                 const float* __restrict__ h1, const float* __restrict__ h2, const float* __restrict__ h3,
                                 float* __restrict__ store, int B, int C, int HW, float guidance, float w0, float w1, float w2, float w3,
-                                float a, float b) {
+                                float a, float b, const float* __restrict__ factor) {
   const long long total = (long long)B * C * HW;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int p = (int)(i % HW);
@@ -209,7 +215,8 @@ __global__ void cfg_plms_kernel(const float* __restrict__ eps, int ldc, float* _
     const int bb = (int)(i / ((long long)HW * C));
     const float eu = eps[((long long)bb * HW + p) * ldc + c];
     const float ec = eps[((long long)(bb + B) * HW + p) * ldc + c];
-    const float e0 = eu + guidance * (ec - eu);
+    float e0 = eu + guidance * (ec - eu);
+    if (RESC) e0 *= factor[bb];
     float e = w0 * e0;
     if (h1) e += w1 * h1[i];
     if (h2) e += w2 * h2[i];
@@ -220,9 +227,9 @@ __global__ void cfg_plms_kernel(const float* __restrict__ eps, int ldc, float* _
   }
 }
 int launch_cfg_plms(const float* eps, int ldc, float* lat, const float* src, const float* h1, const float* h2, const float* h3, float* store,
-                    int B, int C, int HW, float guidance, const float* w, float a, float b, hipStream_t st) {
-  hipLaunchKernelGGL(cfg_plms_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, st, eps, ldc, lat, src, h1, h2, h3, store, B, C, HW,
-                     guidance, w[0], w[1], w[2], w[3], a, b);
+                    int B, int C, int HW, float guidance, const float* w, float a, float b, const float* factor, hipStream_t st) {
+  hipLaunchKernelGGL(factor ? cfg_plms_kernel<true> : cfg_plms_kernel<false>, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, st, eps, ldc, lat, src, h1, h2, h3,
+                     store, B, C, HW, guidance, w[0], w[1], w[2], w[3], a, b, factor);
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }
 
@@ -231,16 +238,19 @@ int launch_cfg_plms(const float* eps, int ldc, float* lat, const float* src, con
 // The latent has 4 channels.  One thread per pixel of one image: its eps row (ldc floats, ldc % 4 == 0) is read as one float4 per
 // CFG half, the four channel planes are read / written with lane-contiguous 4-B accesses.  prev (x0 of the previous evaluation;
 // nullptr on the first) and store are the two ping-pong history slots of agd_denoise_dpm, never the same buffer.
+template <bool RESC>
 __global__ void cfg_dpm_kernel(const float* __restrict__ eps, int ldc, float* __restrict__ lat, const float* __restrict__ prev,
-                               float* __restrict__ store, int B, int HW, float guidance, float cx, float ce, float a, float b0, float b1) {
+                               float* __restrict__ store, int B, int HW, float guidance, float cx, float ce, float a, float b0, float b1,
+                               const float* __restrict__ factor) {
   const long long total = (long long)B * HW;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int b = (int)(i / HW);
     const int p = (int)(i - (long long)b * HW);
     const float4 eu = *reinterpret_cast<const float4*>(eps + i * ldc);
     const float4 ec = *reinterpret_cast<const float4*>(eps + ((long long)B * HW + i) * ldc);
-    const float m[4] = {eu.x + guidance * (ec.x - eu.x), eu.y + guidance * (ec.y - eu.y),
-                        eu.z + guidance * (ec.z - eu.z), eu.w + guidance * (ec.w - eu.w)};
+    float m[4] = {eu.x + guidance * (ec.x - eu.x), eu.y + guidance * (ec.y - eu.y),
+                  eu.z + guidance * (ec.z - eu.z), eu.w + guidance * (ec.w - eu.w)};
+    if (RESC) { const float f = factor[b]; m[0] *= f; m[1] *= f; m[2] *= f; m[3] *= f; }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const long long o = ((long long)b * 4 + c) * HW + p;
@@ -254,11 +264,11 @@ __global__ void cfg_dpm_kernel(const float* __restrict__ eps, int ldc, float* __
   }
 }
 int launch_cfg_dpm(const float* eps, int ldc, float* lat, const float* prev, float* store, int B, int C, int HW, float guidance,
-                   const float* coef5, hipStream_t st) {
+                   const float* coef5, const float* factor, hipStream_t st) {
   if (C != 4 || ldc < 4 || (ldc & 3) || ((uintptr_t)eps & 15)) { agd_set_error("cfg_dpm: needs 4 latent channels and 16-B aligned eps rows (C=%d ldc=%d)", C, ldc); return -1; }
   if (prev && prev == store) { agd_set_error("cfg_dpm: history read and write slots alias"); return -1; }
-  hipLaunchKernelGGL(cfg_dpm_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, st, eps, ldc, lat, prev, store, B, HW, guidance,
-                     coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]);
+  hipLaunchKernelGGL(factor ? cfg_dpm_kernel<true> : cfg_dpm_kernel<false>, dim3(grid_for((long long)B * HW)), dim3(256), 0, st, eps, ldc, lat, prev, store, B, HW,
+                     guidance, coef5[0], coef5[1], coef5[2], coef5[3], coef5[4], factor);
   HIP_CHECK_RET(hipGetLastError()); return 0;
 }
 

@@ -238,6 +238,9 @@ struct agd_ctx {
   // FreeU (agd_freeu_set / agd_freeu_clear): persistent; unet_walk re-weights the resnet inputs of up blocks 0 and 1 (freeu_apply).
   // fu_counts: launches that left GroupNorm partial sums / that left none
   bool fu_on = false; float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f}; long long fu_counts[2] = {0, 0};
+  // guidance_rescale (agd_guidance_rescale_set / _clear): phi > 0 = set; the step lambdas of the two-branch loops read it (guidance_factor).
+  // gr_factb: the [batch] factors of the evaluation in flight; gr_count: factor launches since create
+  float gr_phi = 0.f; DBuf gr_factb; long long gr_count = 0;
   // profiling
   EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
@@ -1483,7 +1486,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release(); c->i2_latb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->cn_embb.release(); c->lora_descb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->cn_embb.release(); c->lora_descb.release();
   for (auto& f : c->gl_f) f.gkvb.release();
   c->gl_objb.release();
   for (auto& b : c->ad_featb) b.release();
@@ -2299,7 +2302,7 @@ AGD_API int agd_cfg_ddim_step_hw(agd_ctx* c, const float* eps, float* latents, i
   // out[b][p][c] = eps[b][c][p]  == nchw_from_nhwc with (C,HW) swapped
   API_CK(c, launch_nchw_from_nhwc_f32(eps, HW, tmp, 2 * batch, HW, C, st));
   ProfScope ps(c, st, PC_ELEM, 0);
-  API_CK(c, launch_cfg_ddim(tmp, C, latents, batch, C, HW, guidance, alpha_t, alpha_prev, c->cfg.prediction_type, st));
+  API_CK(c, launch_cfg_ddim(tmp, C, latents, batch, C, HW, guidance, alpha_t, alpha_prev, c->cfg.prediction_type, nullptr, st));
   return 0;
 }
 AGD_API int agd_cfg_ddim_step(agd_ctx* c, const float* eps, float* latents, int batch, int L, float guidance, float alpha_t,
@@ -2329,6 +2332,27 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
   return 0;
 }
 
+// guidance_rescale inside a step lambda (under the step's ProfScope): state clear -> *f = nullptr and no launch (the plain step, launch for
+// launch); set -> one launch that reduces this evaluation's eps to a factor per image (guidance.hip), which the step kernel multiplies in.
+static int guidance_factor(agd_ctx* c, hipStream_t st, const float* eps, int batch, int Cl, int HW, float guidance, const float** f) {
+  *f = nullptr;
+  if (!(c->gr_phi > 0.f)) return 0;
+  CK(c->gr_factb.ensure((size_t)batch * sizeof(float)));
+  CK(launch_guidance_factor(eps, c->cfg.out_channels, batch, Cl, HW, guidance, c->gr_phi, c->gr_factb.as<float>(), st));
+  c->gr_count++;
+  *f = c->gr_factb.as<float>();
+  return 0;
+}
+// a loop that cannot rescale refuses a set state before its first launch
+static int refuse_guidance_rescale(agd_ctx* c, const char* loop) {
+  if (c->gr_phi > 0.f) FAIL("%s: guidance rescale (phi = %g) is set; this loop does not apply it (agd_guidance_rescale_clear)", loop, (double)c->gr_phi);
+  return 0;
+}
+static int check_guidance_rescale(agd_ctx* c, const char* what, int Cl, int HW) {
+  if (c->gr_phi > 0.f && (long long)Cl * HW < 2) FAIL("%s: guidance rescale needs at least 2 values per image (C * HW = %lld)", what, (long long)Cl * HW);
+  return 0;
+}
+
 // The uncond walk of an InstructPix2Pix evaluation runs `rows` images against the first `rows` context rows -- the [uncond x B] half of the
 // [uncond x B | cond x B] agd_set_context projected -- and records nothing.  The engine is put back as it was when the walk ends, on an error too.
 struct Ip2pUncond {
@@ -2343,6 +2367,7 @@ struct Ip2pUncond {
 template <class Step>
 static int run_ip2p_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, int Lh, int Lw, int n, const float* timesteps, Step&& step) {
   const int B2 = 2 * batch, HW = Lh * Lw, oc = c->cfg.out_channels;
+  CK(refuse_guidance_rescale(c, "the InstructPix2Pix denoise loop"));
   CallCond cc; CK(resolve_cond(c, CALL_IP2P_LOOP, n, batch, Lh, Lw, &cc));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
   CK(ensure_lat(c, 3 * batch, Lh, Lw));
@@ -2392,9 +2417,11 @@ AGD_API int agd_denoise_hw(agd_ctx* c, float* latents, int batch, int Lh, int Lw
   API_CK(c, check_latent_hw(c, "denoise", Lh, Lw));
   hipStream_t st = S(stream);
   const int Cl = c->cfg.out_channels, HW = Lh * Lw;                          // Cl: the latent channels (a 9-channel UNet's input has more)
+  API_CK(c, check_guidance_rescale(c, "denoise", Cl, HW));
   API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_steps, timesteps, [&](int s, const float* eps) {
     ProfScope ps(c, st, PC_ELEM, 0);
-    return launch_cfg_ddim(eps, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st);
+    const float* f; CK(guidance_factor(c, st, eps, batch, Cl, HW, guidance, &f));
+    return launch_cfg_ddim(eps, c->cfg.out_channels, latents, batch, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, f, st);
   }));
   return 0;
 }
@@ -2463,6 +2490,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
   int nbh = 0, nbw = 0;
   API_CK(c, check_panorama(c, "denoise_panorama", Lh, Lw, window, stride, &nbh, &nbw));
   if (batch < 1 || n_steps < 1 || !canvas || !timesteps || !alpha_t || !alpha_prev) { agd_set_error("denoise_panorama: batch %d, steps %d or a null argument", batch, n_steps); return fail_ctx(c); }
+  API_CK(c, refuse_guidance_rescale(c, "denoise_panorama"));
   CallCond cc; API_CK(c, resolve_cond(c, CALL_PANORAMA, n_steps, batch, window, window, &cc));
   if (c->rec_mode == 2) { agd_set_error("denoise_panorama: the hook.py recorder is installed; a panorama records through the DAAM recorder only"); return fail_ctx(c); }
   const int V = nbh * nbw, n = (view_batch < 1 || view_batch > V) ? V : view_batch;
@@ -2494,7 +2522,7 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
       API_CK(c, prep_unet_input(c, st, vb, batch * m, HW));
       API_CK(c, unet_walk(c, st, c->lat_bf16, 2 * batch * m, window, window, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true));
       { ProfScope ps(c, st, PC_ELEM, 0);
-        API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, vb, batch * m, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, st)); }
+        API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, vb, batch * m, Cl, HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, nullptr, st)); }
     }
     ProfScope ps(c, st, PC_ELEM, 0, 4.0 * batch * (double)img * V + 4.0 * batch * (double)Cl * Lh * Lw);
     API_CK(c, launch_window_mean(views, canvas, batch, Cl, Lh, Lw, window, stride, 1, batch, st));
@@ -2519,6 +2547,7 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
   if (n_evals < 2) { agd_set_error("denoise_plms: needs >= 2 model evaluations (got %d)", n_evals); return fail_ctx(c); }
   const int Cl = c->cfg.out_channels, HW = Lh * Lw;
   const size_t n1 = (size_t)batch * Cl * HW;
+  API_CK(c, check_guidance_rescale(c, "denoise_plms", Cl, HW));
   API_CK(c, c->plmsb.ensure(n1 * 5 * sizeof(float)));            // 4 history slots + the kept sample
   float* hist[4]; for (int k = 0; k < 4; ++k) hist[k] = c->plmsb.as<float>() + n1 * k;
   float* kept = c->plmsb.as<float>() + n1 * 4;                    // the blend rewrites `latents` only: the kept sample stays unblended
@@ -2538,8 +2567,9 @@ AGD_API int agd_denoise_plms_hw(agd_ctx* c, float* latents, int batch, int Lh, i
       else if (n_hist >= 3) { w[0] = 55.f / 24.f; w[1] = -59.f / 24.f; w[2] = 37.f / 24.f; w[3] = -9.f / 24.f; }
     }
     ProfScope ps(c, st, PC_ELEM, 0);
+    const float* f; CK(guidance_factor(c, st, eps, batch, Cl, HW, guidance, &f));
     CK(launch_cfg_plms(eps, c->cfg.out_channels, latents, src, h[0], h[1], h[2], store, batch, Cl, HW, guidance, w, sample_coeff[i],
-                       eps_coeff[i], st));
+                       eps_coeff[i], f, st));
     if (store) { ++head; if (n_hist < 3) ++n_hist; }
     return 0;
   }));
@@ -2564,13 +2594,15 @@ AGD_API int agd_denoise_dpm_hw(agd_ctx* c, float* latents, int batch, int Lh, in
   if (n_evals < 1 || !timesteps || !coeffs) { agd_set_error("denoise_dpm: needs >= 1 model evaluation and host timesteps / coeffs (got %d)", n_evals); return fail_ctx(c); }
   const int Cl = c->cfg.out_channels, HW = Lh * Lw;
   const size_t n1 = (size_t)batch * Cl * HW;
+  API_CK(c, check_guidance_rescale(c, "denoise_dpm", Cl, HW));
   API_CK(c, c->dpmb.ensure(n1 * 2 * sizeof(float)));
   float* slot[2] = {c->dpmb.as<float>(), c->dpmb.as<float>() + n1};
   API_CK(c, run_eval_loop(c, st, latents, batch, Lh, Lw, n_evals, timesteps, [&](int i, const float* eps) {
     const float* prev = i > 0 ? slot[(i - 1) & 1] : nullptr;
     float* store = i + 1 < n_evals ? slot[i & 1] : nullptr;     // the last x0 has no reader
     ProfScope ps(c, st, PC_ELEM, 0);
-    return launch_cfg_dpm(eps, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, st);
+    const float* f; CK(guidance_factor(c, st, eps, batch, Cl, HW, guidance, &f));
+    return launch_cfg_dpm(eps, c->cfg.out_channels, latents, prev, store, batch, Cl, HW, guidance, coeffs + (size_t)5 * i, f, st);
   }));
   return 0;
 }
@@ -4059,6 +4091,37 @@ AGD_API int agd_op_freeu(const float* hidden_nchw, const float* skip_nchw, float
   CK(launch_bf16_to_f32(s != 1.f ? so : sb, sf, (long long)ns, st));
   CK(launch_nchw_from_nhwc_f32(hf, Ch, hidden_out, B, Ch, HW, st));
   CK(launch_nchw_from_nhwc_f32(sf, Cs, skip_out, B, Cs, HW, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// guidance_rescale (diffusers 0.21.2 StableDiffusionPipeline.__call__(guidance_rescale=phi) -> rescale_noise_cfg [upstream-knowledge]): state
+// that the step lambdas of agd_denoise_hw / agd_denoise_plms_hw / agd_denoise_dpm_hw read (guidance_factor)
+// ---------------------------------------------------------------------------------------
+AGD_API int agd_guidance_rescale_set(agd_ctx* c, float phi) {
+  API_CK(c, need_final(c));
+  if (!std::isfinite(phi) || phi < 0.f || phi > 1.f) { agd_set_error("guidance_rescale_set: guidance rescale phi = %g (a number in [0, 1])", (double)phi); return fail_ctx(c); }
+  c->gr_phi = phi;
+  return 0;
+}
+
+AGD_API int agd_guidance_rescale_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("guidance_rescale_clear: null context"); return -1; }
+  c->gr_phi = 0.f;
+  return 0;
+}
+
+AGD_API int agd_guidance_rescale_counts(agd_ctx* c, long long* launches) {
+  if (!c || !launches) { agd_set_error("guidance_rescale_counts: null argument"); return fail_ctx(c); }
+  *launches = c->gr_count;
+  return 0;
+}
+
+// The production kernel alone (the test seam): eps [2 B][HW][ldc] fp32 on the device, as the step kernels read it -> factor [B] on the device
+AGD_API int agd_op_guidance_rescale(agd_ctx* c, const float* eps, int ldc, int B, int C, int HW, float guidance, float phi, float* factor, void* stream) {
+  hipStream_t st = S(stream);                                       // (c may be null: it only keeps the error text)
+  API_CK(c, launch_guidance_factor(eps, ldc, B, C, HW, guidance, phi, factor, st));
   hipStreamSynchronize(st);
   return 0;
 }

@@ -314,7 +314,24 @@ def parse_args(argv=None):
     p.add_argument("--freeu", type=float, default=None, nargs=4, metavar=("S1", "S2", "B1", "B2"),
                    help="FreeU (enable_freeu) on every UNet evaluation, with any pipeline: the skip filters' scales and the backbone scales of "
                         "up blocks 0 and 1; suggested 0.9 0.2 1.2 1.4 (SD-1.4), 0.9 0.2 1.5 1.6 (SD-1.5), 0.9 0.2 1.4 1.6 (SD-2.1)")
+    p.add_argument("--guidance-rescale", type=float, default=0.0, metavar="PHI",
+                   help="guidance_rescale (Lin et al. 2023): after the CFG combine, rescale the prediction to the text branch's per-image "
+                        "standard deviation, blended by PHI in [0, 1] (0: off; 0.7 is the paper's value); not with --panorama / --instruct-image")
+    p.add_argument("--timestep-spacing", type=str, default=None, choices=["leading", "trailing", "linspace"],
+                   help="the scheduler's timestep grid (default: the checkpoint's; DDIM and img2img take all three, DPM-Solver++ its own "
+                        "three, PNDM runs 'leading' only)")
+    p.add_argument("--rescale-betas-zero-snr", action="store_true",
+                   help="DDIM: the zero-terminal-SNR beta table (the last timestep is pure noise); needs a v-prediction checkpoint and a grid "
+                        "that starts there (--timestep-spacing trailing)")
     args = p.parse_args(argv)
+    if not (math.isfinite(args.guidance_rescale) and 0.0 <= args.guidance_rescale <= 1.0):
+        p.error(f"--guidance-rescale {args.guidance_rescale}: a number in [0, 1]")
+    if args.guidance_rescale and (args.panorama or args.instruct_image):
+        p.error("--guidance-rescale with --panorama or --instruct-image is not implemented")
+    if args.scheduler == "PNDMScheduler" and args.timestep_spacing not in (None, "leading"):
+        p.error(f"--timestep-spacing {args.timestep_spacing}: PNDMScheduler runs 'leading' only")
+    if args.rescale_betas_zero_snr and args.scheduler in ("PNDMScheduler", "DPMSolverMultistepScheduler"):
+        p.error(f"--rescale-betas-zero-snr is DDIMScheduler's ({args.scheduler} has no such option)")
     if args.freeu is not None and not all(math.isfinite(v) for v in args.freeu):
         p.error(f"--freeu {' '.join(str(v) for v in args.freeu)}: four finite numbers")
     if args.lora_path is None and (args.lora_weight_name is not None or args.lora_scale != 1.0):
@@ -391,6 +408,22 @@ def parse_args(argv=None):
         except ValueError as e:
             p.error(f"--panorama: {e}")
     return args
+
+
+def apply_schedule_flags(pipe, timestep_spacing: Optional[str], rescale_betas_zero_snr: bool) -> None:
+    """--timestep-spacing / --rescale-betas-zero-snr on a built pipeline: the scheduler config takes them and the pipeline's scheduler is
+    built again from it (every rank does the same).  DPM-Solver++ takes the spacing as its own; PNDM and DPM-Solver++ refuse what they
+    do not implement, by name (ValueError)."""
+    from .scheduler import DPMSolverMultistepScheduler
+    sc = pipe.cfg.sched
+    if timestep_spacing is not None:
+        if isinstance(pipe.scheduler, DPMSolverMultistepScheduler):
+            sc.timestep_spacing = timestep_spacing
+        else:
+            sc.ddim_timestep_spacing = timestep_spacing
+    if rescale_betas_zero_snr:
+        sc.rescale_betas_zero_snr = True
+    pipe.scheduler = type(pipe.scheduler).from_config(sc)
 
 
 def panorama_window(args) -> int:
@@ -560,6 +593,8 @@ def main(argv=None):
         from .scheduler import DPMSolverMultistepScheduler
         pipe.cfg.sched.use_karras_sigmas = True
         pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.cfg.sched)
+    if args.timestep_spacing is not None or args.rescale_betas_zero_snr:
+        apply_schedule_flags(pipe, args.timestep_spacing, args.rescale_betas_zero_snr)
     embeds = torch.load(args.learnable_tokens_embedding_path) if args.learnable_tokens_embedding_path else {}
     if embeds:
         new_tokens, words, prompt = select_learned_tokens(args.prompt, args.initialize_token, list(embeds.keys()),
@@ -597,6 +632,8 @@ def main(argv=None):
             if i2_files:                                                             # (parse_args refused --height / --width: both are None)
                 control = ip2p_inputs_for(i2_files, chunk, args.image_guidance_scale)
                 height, width = control.pop("height"), control.pop("width")          # the image's size is the call's
+            if args.guidance_rescale:
+                control = dict(control or {}, guidance_rescale=args.guidance_rescale)
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
                                        height=height, width=width)
         if not gather:

@@ -275,7 +275,7 @@ class StableDiffusionGLIGENPipeline(StableDiffusionPipeline):
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, gligen_scheduled_sampling_beta: float = 0.3,
                  gligen_phrases=None, gligen_boxes=None, gligen_inpaint_image=None, negative_prompt=None, num_images_per_prompt: int = 1,
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
-                 output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None):
+                 output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0):
         if gligen_inpaint_image is not None:
             raise ValueError("gligen_inpaint_image (GLIGEN inpainting) is not implemented")
         if eta != 0.0:
@@ -293,7 +293,7 @@ class StableDiffusionGLIGENPipeline(StableDiffusionPipeline):
             return super().__call__(prompt, height=height, width=width, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                     negative_prompt=negative_prompt, generator=generator, latents=latents, prompt_embeds=prompt_embeds,
                                     output_type=output_type, num_images_per_prompt=num_images_per_prompt,
-                                    cross_attention_kwargs=cross_attention_kwargs)
+                                    cross_attention_kwargs=cross_attention_kwargs, guidance_rescale=guidance_rescale)
         finally:
             self._gl_pending = None
             self.engine.gligen_clear()

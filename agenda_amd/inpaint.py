@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .config import SDConfig, inpaint_flavour, inpaint_variant
-from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size
+from .pipeline import PipelineOutput, StableDiffusionPipeline, check_guidance_rescale, check_image_size
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 
 
@@ -192,11 +192,13 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
                  negative_prompt=None, num_images_per_prompt: int = 1, generator: Optional[torch.Generator] = None,
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  noise_enc_image: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                 noise_enc_masked: Optional[torch.Tensor] = None, cross_attention_kwargs: Optional[dict] = None):
+                 noise_enc_masked: Optional[torch.Tensor] = None, cross_attention_kwargs: Optional[dict] = None,
+                 guidance_rescale: float = 0.0):
         """image / mask_image as `prepare_mask_and_image` takes them.  Noise draws come from a CPU generator in diffusers' order, or are
         passed explicitly (noise_enc_image [N,4,L,L], noise (or latents) [B,4,L,L], noise_enc_masked [N,4,L,L]; N distinct images)."""
         if image is None or mask_image is None:
             raise ValueError("StableDiffusionInpaintPipeline needs image= and mask_image=")
+        check_guidance_rescale(guidance_rescale)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
         check_image_size(height, width)
@@ -249,10 +251,11 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
                 eng.inpaint_set(mask_lat, image_lat, nz)
                 eng.inpaint_set_schedule(blend_schedule(self.scheduler, evaluation_timesteps(self.scheduler, num_inference_steps, strength)))
             self._begin_recording(prompt_embeds, B, L)
-            if strength < 1.0:
-                eng.denoise(lat, ts[t0:], a_t[t0:], a_p[t0:], guidance_scale)
-            else:
-                self._denoise(lat, num_inference_steps, guidance_scale)
+            with self._guidance_rescaled(guidance_rescale):
+                if strength < 1.0:
+                    eng.denoise(lat, ts[t0:], a_t[t0:], a_p[t0:], guidance_scale)
+                else:
+                    self._denoise(lat, num_inference_steps, guidance_scale)
         finally:
             eng.inpaint_clear()
         self._inpaint_inputs = {"mask": mask_lat, "image_latents": image_lat, "masked_image_latents": masked_lat, "noise": nz}

@@ -113,11 +113,14 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionPipeline):
                  image_guidance_scale: float = 1.5, negative_prompt=None, num_images_per_prompt: int = 1,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
-                 height: Optional[int] = None, width: Optional[int] = None):
+                 height: Optional[int] = None, width: Optional[int] = None, guidance_rescale: float = 0.0):
         """image as `prepare_image` takes it; height and width are the image's (given ones must equal them: nothing is resized).
         prompt_embeds is [2B,T,D] = [uncond | cond]."""
         if image is None:
             raise ValueError("StableDiffusionInstructPix2PixPipeline needs image=")
+        if guidance_rescale:
+            raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale is not implemented for the InstructPix2Pix pipeline "
+                             "(its three-branch loop has no text-branch spread to rescale to); leave it 0")
         check_unet(self.cfg)
         check_guidance(guidance_scale, image_guidance_scale)
         img = prepare_image(image)

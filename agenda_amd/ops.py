@@ -233,3 +233,18 @@ def freeu(hidden, skip, b, s):
     _lib.check(lib.agd_op_freeu(_lib.ptr(hidden), _lib.ptr(skip), _lib.ptr(ho), _lib.ptr(so), B, Ch, skip.shape[1], H, W, float(b), float(s),
                                 _lib.current_stream_ptr()), None, "agd_op_freeu")
     return ho, so
+
+
+def guidance_rescale(eps, channels, guidance, phi):
+    """The guidance_rescale factor of every image, the production kernel: eps [2B, HW, ldc] fp32 as the step kernels read it (rows [0, B)
+    unconditional, [B, 2B) conditional; only channels < `channels` of each ldc-wide row count) -> [B] fp32,
+    f_b = 1 + phi (std(eps_c[b]) / std(m[b]) - 1) with m = eps_u + guidance (eps_c - eps_u) and the unbiased std over all of an image."""
+    lib = _lib.load()
+    eps = _f32c(eps)
+    if eps.ndim != 3 or eps.shape[0] % 2 or eps.shape[0] < 2:
+        raise ValueError(f"guidance_rescale: eps {tuple(eps.shape)} must be [2B, HW, ldc]")
+    B2, HW, ldc = eps.shape
+    out = torch.empty(B2 // 2, dtype=torch.float32, device=eps.device)
+    _lib.check(lib.agd_op_guidance_rescale(None, _lib.ptr(eps), ldc, B2 // 2, int(channels), HW, float(guidance), float(phi), _lib.ptr(out),
+                                           _lib.current_stream_ptr()), None, "agd_op_guidance_rescale")
+    return out

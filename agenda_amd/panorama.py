@@ -74,7 +74,11 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, view_batch_size: Optional[int] = None,
                  circular_padding: bool = False, negative_prompt=None, num_images_per_prompt: int = 1,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
-                 prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None):
+                 prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
+                 guidance_rescale: float = 0.0):
+        if guidance_rescale:
+            raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale is not implemented for the panorama pipeline "
+                             "(its views are stepped one by one); leave it 0")
         f, win = self.vae_scale_factor, self.window
         height = height or f * win
         width = width or 4 * height

@@ -15,6 +15,7 @@ Differences that are deliberate:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import math
@@ -54,6 +55,13 @@ def _hw(L) -> Tuple[int, int]:
         h, w = L
         return int(h), int(w)
     return int(L), int(L)
+
+
+def check_guidance_rescale(guidance_rescale: float) -> None:
+    """`guidance_rescale` is Lin et al.'s phi: a finite number in [0, 1].  Refused here, before a call does any device work."""
+    phi = float(guidance_rescale)
+    if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale takes a number in [0, 1]")
 
 
 def check_image_size(height: int, width: int, multiple: int = 64) -> None:
@@ -397,6 +405,20 @@ class Engine:
         n = (C.c_longlong * 2)()
         self._ck(self.lib.agd_freeu_counts(self.ctx, n), "agd_freeu_counts")
         return int(n[0]), int(n[1])
+
+    def guidance_rescale_set(self, phi: float):
+        """`agd_guidance_rescale_set`: every later evaluation of the DDIM / PLMS / DPM loops rescales its CFG-combined prediction to the text
+        branch's per-image standard deviation, blended by phi in [0, 1], until guidance_rescale_clear (0: clear)."""
+        self._ck(self.lib.agd_guidance_rescale_set(self.ctx, float(phi)), "agd_guidance_rescale_set")
+
+    def guidance_rescale_clear(self):
+        self._ck(self.lib.agd_guidance_rescale_clear(self.ctx), "agd_guidance_rescale_clear")
+
+    def guidance_rescale_counts(self) -> int:
+        """`agd_guidance_rescale_counts`: factor launches (one per rescaled evaluation) since the engine was created."""
+        n = C.c_longlong(0)
+        self._ck(self.lib.agd_guidance_rescale_counts(self.ctx, C.byref(n)), "agd_guidance_rescale_counts")
+        return int(n.value)
 
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
         self._glcfg = _lib.AgdGligenConfig()
@@ -1299,8 +1321,10 @@ class StableDiffusionPipeline:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
-                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                 guidance_rescale: float = 0.0):
         self._refuse_inpainting_unet()
+        check_guidance_rescale(guidance_rescale)
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
@@ -1313,7 +1337,8 @@ class StableDiffusionPipeline:
         self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
         self._begin_recording(prompt_embeds, B, L)
-        self._denoise(lat, num_inference_steps, guidance_scale)
+        with self._guidance_rescaled(guidance_rescale):
+            self._denoise(lat, num_inference_steps, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
         return self._finish(lat, B, output_type)
@@ -1332,6 +1357,19 @@ class StableDiffusionPipeline:
         if u.in_channels != u.out_channels:
             raise ValueError(f"this UNet takes {u.in_channels} input channels (an inpainting checkpoint): txt2img and img2img need "
                              f"{u.out_channels}; use StableDiffusionInpaintPipeline")
+
+    @contextlib.contextmanager
+    def _guidance_rescaled(self, guidance_rescale: float):
+        """diffusers' `guidance_rescale` (Lin et al. 2023, section 3.4) around one call's denoise loop: the engine state is set for the loop
+        and cleared when it ends, on an error too, so the next call without the argument is the plain one.  0 sets nothing."""
+        if not guidance_rescale:
+            yield
+            return
+        self.engine.guidance_rescale_set(guidance_rescale)
+        try:
+            yield
+        finally:
+            self.engine.guidance_rescale_clear()
 
     def _denoise(self, lat, num_inference_steps, guidance_scale):
         """`for t in scheduler.timesteps: unet -> CFG -> scheduler.step`, fused on the device, under the pipeline's scheduler."""
@@ -1368,13 +1406,15 @@ class StableDiffusionPipeline:
     def img2img(self, prompt=None, image: torch.Tensor = None, strength: float = 0.8, num_inference_steps: int = 50,
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
-                cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+                cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                guidance_rescale: float = 0.0):
         """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
         # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
         # PLMS and DPM-Solver++ img2img are not implemented)
         self._refuse_inpainting_unet()
+        check_guidance_rescale(guidance_rescale)
         self._apply_lora_scale(cross_attention_kwargs)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
@@ -1404,7 +1444,8 @@ class StableDiffusionPipeline:
         a = float(sched.alphas_cumprod[int(ts[0])])
         lat = (a ** 0.5 * x0 + (1 - a) ** 0.5 * noise.to(mean.device)).contiguous()
         self._begin_recording(prompt_embeds, B, L)
-        self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
+        with self._guidance_rescaled(guidance_rescale):
+            self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
         return self._finish(lat, B, output_type)

@@ -13,15 +13,50 @@ import numpy as np
 from .config import SchedulerConfig
 
 
+def rescale_zero_terminal_snr(betas):
+    """diffusers' `rescale_zero_terminal_snr` (Lin et al. 2023, algorithm 1) in the same torch float32 operations [upstream-knowledge:
+    diffusers 0.21.2 scheduling_ddim.py], so the table is bit-identical: sqrt(alphas_cumprod) is shifted so that its last entry is 0 and
+    scaled so that its first is unchanged, then turned back into betas."""
+    import torch
+    alphas = 1.0 - betas
+    alphas_cumprod = torch.cumprod(alphas, dim=0)
+    alphas_bar_sqrt = alphas_cumprod.sqrt()
+    alphas_bar_sqrt_0 = alphas_bar_sqrt[0].clone()
+    alphas_bar_sqrt_T = alphas_bar_sqrt[-1].clone()
+    alphas_bar_sqrt -= alphas_bar_sqrt_T
+    alphas_bar_sqrt *= alphas_bar_sqrt_0 / (alphas_bar_sqrt_0 - alphas_bar_sqrt_T)
+    alphas_bar = alphas_bar_sqrt ** 2
+    alphas = alphas_bar[1:] / alphas_bar[:-1]
+    alphas = torch.cat([alphas_bar[0:1], alphas])
+    return 1 - alphas
+
+
 class DDIMScheduler:
+    """diffusers `DDIMScheduler` (eta 0) [upstream-knowledge: diffusers 0.21.2 set_timesteps / step].  Timestep grids (T training
+    timesteps, n steps):
+        "leading"  (SD's own): arange(0, n) * (T // n), reversed, + steps_offset;
+        "trailing": round(arange(T, 0, -T / n)) - 1          (the first evaluation is at T - 1);
+        "linspace": linspace(0, T - 1, n).round(), reversed  (end points T - 1 and 0).
+    For every spacing prev_t = t - T // n, and prev_t < 0 takes final_alpha_cumprod.  `rescale_betas_zero_snr`: the zero-terminal-SNR
+    beta table (alphas_cumprod[-1] == 0); a grid that visits such a timestep needs v-prediction -- epsilon prediction divides by
+    sqrt(alpha) -- and step_coeffs refuses it otherwise."""
+
+    _SPACINGS = ("leading", "trailing", "linspace")
+
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
-                 set_alpha_to_one=False, prediction_type="epsilon"):
+                 set_alpha_to_one=False, prediction_type="epsilon", timestep_spacing="leading", rescale_betas_zero_snr=False):
+        if timestep_spacing not in self._SPACINGS:
+            raise ValueError(f"DDIMScheduler: timestep_spacing {timestep_spacing!r} is not one of {self._SPACINGS}")
         self.num_train_timesteps = num_train_timesteps
         self.steps_offset = steps_offset
         self.prediction_type = prediction_type
+        self.timestep_spacing = timestep_spacing
+        self.rescale_betas_zero_snr = bool(rescale_betas_zero_snr)
         # the same torch float32 ops diffusers uses (scaled_linear betas -> cumprod), so the table is bit-identical
         import torch
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        if self.rescale_betas_zero_snr:
+            betas = rescale_zero_terminal_snr(betas)
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0).numpy()
         self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
@@ -31,13 +66,20 @@ class DDIMScheduler:
     @classmethod
     def from_config(cls, sc):
         return cls(sc.num_train_timesteps, sc.beta_start, sc.beta_end, sc.steps_offset, sc.set_alpha_to_one,
-                   sc.prediction_type)
+                   sc.prediction_type, timestep_spacing=getattr(sc, "ddim_timestep_spacing", "leading"),
+                   rescale_betas_zero_snr=getattr(sc, "rescale_betas_zero_snr", False))
 
     def set_timesteps(self, num_inference_steps: int):
         if num_inference_steps > self.num_train_timesteps:
             raise ValueError("num_inference_steps exceeds num_train_timesteps")
-        ratio = self.num_train_timesteps // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
+        T = self.num_train_timesteps
+        if self.timestep_spacing == "trailing":
+            ts = np.round(np.arange(T, 0, -T / num_inference_steps)).astype(np.int64) - 1
+        elif self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        else:
+            ratio = T // num_inference_steps
+            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
         self.num_inference_steps = num_inference_steps
         self.timesteps = ts
         return ts
@@ -48,6 +90,10 @@ class DDIMScheduler:
         a_t = np.array([self.alphas_cumprod[t] for t in self.timesteps], dtype=np.float32)
         a_p = np.array([self.alphas_cumprod[t - ratio] if t - ratio >= 0 else self.final_alpha_cumprod
                         for t in self.timesteps], dtype=np.float32)
+        if self.prediction_type == "epsilon" and (a_t == 0).any():
+            t0 = int(self.timesteps[int(np.argmax(a_t == 0))])
+            raise ValueError(f"DDIMScheduler: timestep {t0} has alphas_cumprod == 0 (rescale_betas_zero_snr) and epsilon prediction divides "
+                             "by its square root there; a zero-terminal-SNR schedule needs prediction_type='v_prediction'")
         return a_t, a_p
 
 
@@ -57,7 +103,12 @@ class PNDMScheduler:
     `num_inference_steps` = n means n + 1 model evaluations: the second timestep is evaluated twice."""
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1, set_alpha_to_one=False,
-                 prediction_type="epsilon", skip_prk_steps=True):
+                 prediction_type="epsilon", skip_prk_steps=True, timestep_spacing="leading", rescale_betas_zero_snr=False):
+        if timestep_spacing != "leading":
+            raise ValueError(f"PNDMScheduler: only timestep_spacing='leading' is implemented (got {timestep_spacing!r}); "
+                             "'trailing' and 'linspace' are DDIMScheduler's")
+        if rescale_betas_zero_snr:
+            raise ValueError("PNDMScheduler: rescale_betas_zero_snr is not implemented (diffusers 0.21.2 has it on DDIMScheduler only)")
         if prediction_type != "epsilon":
             raise ValueError("PNDMScheduler: only epsilon prediction is implemented (what SD-1.x checkpoints use)")
         if not skip_prk_steps:
@@ -76,7 +127,8 @@ class PNDMScheduler:
     @classmethod
     def from_config(cls, sc):
         return cls(sc.num_train_timesteps, sc.beta_start, sc.beta_end, sc.steps_offset, sc.set_alpha_to_one, sc.prediction_type,
-                   getattr(sc, "skip_prk_steps", True))
+                   getattr(sc, "skip_prk_steps", True), timestep_spacing=getattr(sc, "ddim_timestep_spacing", "leading"),
+                   rescale_betas_zero_snr=getattr(sc, "rescale_betas_zero_snr", False))
 
     def set_timesteps(self, num_inference_steps: int):
         if num_inference_steps < 2 or num_inference_steps > self.num_train_timesteps:
@@ -142,8 +194,11 @@ class DPMSolverMultistepScheduler:
     _SPACINGS = ("linspace", "leading", "trailing")
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1, prediction_type="epsilon",
-                 use_karras_sigmas=False, timestep_spacing="linspace", **options):
+                 use_karras_sigmas=False, timestep_spacing="linspace", rescale_betas_zero_snr=False, **options):
         self.check_options(options)
+        if rescale_betas_zero_snr:
+            raise ValueError("DPMSolverMultistepScheduler: rescale_betas_zero_snr is not implemented (diffusers 0.21.2 has no such "
+                             "option there; it is DDIMScheduler's)")
         if prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"DPMSolverMultistepScheduler: prediction_type {prediction_type!r} is not implemented")
         if timestep_spacing not in self._SPACINGS:
@@ -176,7 +231,8 @@ class DPMSolverMultistepScheduler:
     @classmethod
     def from_config(cls, sc):
         return cls(sc.num_train_timesteps, sc.beta_start, sc.beta_end, sc.steps_offset, sc.prediction_type,
-                   use_karras_sigmas=sc.use_karras_sigmas, timestep_spacing=sc.timestep_spacing, algorithm_type=sc.algorithm_type,
+                   use_karras_sigmas=sc.use_karras_sigmas, timestep_spacing=sc.timestep_spacing,
+                   rescale_betas_zero_snr=getattr(sc, "rescale_betas_zero_snr", False), algorithm_type=sc.algorithm_type,
                    solver_order=sc.solver_order, solver_type=sc.solver_type, lower_order_final=sc.lower_order_final)
 
     def _grid(self, n):
@@ -261,6 +317,12 @@ def scheduler_config_from_json(sj: dict, sched_name: str) -> SchedulerConfig:
         DPMSolverMultistepScheduler.check_options(opts)
         sc.use_karras_sigmas = bool(sj.get("use_karras_sigmas", False)) if own else False
         sc.timestep_spacing = sj.get("timestep_spacing", "linspace")
+    if sched_name == "DDIMScheduler" and sj.get("_class_name") == sched_name:
+        # a DDIM checkpoint's own spacing and beta rescale are honoured (they used to be run as "leading" / unrescaled, silently)
+        sc.ddim_timestep_spacing = sj.get("timestep_spacing", "leading")
+        sc.rescale_betas_zero_snr = bool(sj.get("rescale_betas_zero_snr", False))
+        if sc.ddim_timestep_spacing not in DDIMScheduler._SPACINGS:
+            raise ValueError(f"DDIMScheduler: timestep_spacing {sc.ddim_timestep_spacing!r} is not one of {DDIMScheduler._SPACINGS}")
     return sc
 
 
@@ -269,6 +331,11 @@ def scheduler_config_to_json(sched_name: str, sc: SchedulerConfig) -> dict:
     sj = {"_class_name": sched_name, "num_train_timesteps": sc.num_train_timesteps, "beta_start": sc.beta_start, "beta_end": sc.beta_end,
           "beta_schedule": "scaled_linear", "steps_offset": sc.steps_offset, "set_alpha_to_one": sc.set_alpha_to_one,
           "prediction_type": sc.prediction_type}
+    if sched_name == "DDIMScheduler":                  # written only off their defaults: every JSON written before them is unchanged
+        if sc.ddim_timestep_spacing != "leading":
+            sj["timestep_spacing"] = sc.ddim_timestep_spacing
+        if sc.rescale_betas_zero_snr:
+            sj["rescale_betas_zero_snr"] = True
     if sched_name == "PNDMScheduler":
         sj["skip_prk_steps"] = bool(sc.skip_prk_steps)
     if sched_name == "DPMSolverMultistepScheduler":

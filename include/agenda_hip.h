@@ -527,6 +527,25 @@ int agd_freeu_counts(agd_ctx* ctx, long long* counts);
 int agd_op_freeu(const float* hidden_nchw, const float* skip_nchw, float* hidden_out, float* skip_out, int B, int Ch, int Cs, int H, int W,
                  float b, float s, void* stream);
 
+/* ---- guidance_rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed"; diffusers 0.21.2
+ * StableDiffusionPipeline.__call__(guidance_rescale=phi) -> rescale_noise_cfg [upstream-knowledge]; csrc/guidance.hip).  After the CFG combine
+ *   m = eps_u + g (eps_c - eps_u),   f_b = 1 + phi (std(eps_c[b]) / std(m[b]) - 1),   m' = f_b m
+ * with std over the (C, H, W) values of image b jointly, unbiased; m' is what the scheduler step sees (PLMS keeps m' in its history).  One
+ * extra launch per model evaluation -- one workgroup per image, mean-shifted fp32 sums in a fixed order, so f_b is bit-identical between runs
+ * and between an image alone and the same image in a batch -- and one multiply inside the step kernel.  std(m[b]) == 0 gives f_b = 1 (upstream
+ * divides by zero there).
+ * agd_guidance_rescale_set: context state after agd_finalize, read by agd_denoise* (DDIM), agd_denoise_plms* and agd_denoise_dpm* at every
+ *   evaluation, until cleared; phi must be a finite number in [0, 1]; 0 is agd_guidance_rescale_clear.  The InstructPix2Pix loop and
+ *   agd_denoise_panorama refuse a set state before their first launch; agd_cfg_ddim_step* never rescales.
+ * agd_guidance_rescale_clear: the plain loops again, launch for launch (bit-identical results).
+ * agd_guidance_rescale_counts (seam for tests): the factor launches since agd_create.
+ * agd_op_guidance_rescale (seam for tests): the factor kernel alone on device memory -- eps fp32 [2 B][HW][ldc], rows [0, B) unconditional and
+ *   [B, 2 B) conditional, channels c < C of every ldc-wide row -> factor [B].  C * HW >= 2.  ctx may be NULL (it only keeps the error text). */
+int agd_guidance_rescale_set(agd_ctx* ctx, float phi);
+int agd_guidance_rescale_clear(agd_ctx* ctx);
+int agd_guidance_rescale_counts(agd_ctx* ctx, long long* launches);
+int agd_op_guidance_rescale(agd_ctx* ctx, const float* eps, int ldc, int B, int C, int HW, float guidance, float phi, float* factor, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
