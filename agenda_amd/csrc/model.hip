@@ -3256,6 +3256,45 @@ AGD_API int agd_op_attention_headsum(const float* q, const float* k, const float
   return 0;
 }
 
+// train.hip's attention backward in isolation: q [B][N][H*D], kv [B][T][2*H*D] (K columns then V columns), d_o [B][N][H*D] (gradient of the
+// per-head attention output, BEFORE to_out; may be NULL), d_map [B - b0][T][N] (gradient of the head-mean map of batch rows >= b0; may be
+// NULL) -> dq [B][N][H*D], dkv [B][T][2*H*D].  Operands rounded to bf16, fp32 arithmetic, bf16 results returned as fp32.
+AGD_API int agd_op_attention_backward(const float* q, const float* kv, const float* d_o, const float* d_map, int b0, int B, int H, int D, int N,
+                                      int T, float scale, float* dq, float* dkv, void* stream) {
+  // every refusal comes before any allocation or launch (the shapes first: an empty tensor arrives as a null pointer)
+  if (D != 32 && D != 40 && D != 64 && D != 80 && D != 128 && D != 160) { agd_set_error("attention_backward: unsupported head dim D=%d", D); return -1; }
+  if (T < 1 || T > 96) { agd_set_error("attention_backward: T=%d keys unsupported (1..96)", T); return -1; }
+  if (B < 1 || H < 1 || N < 1) { agd_set_error("attention_backward: bad shape B=%d H=%d N=%d", B, H, N); return -1; }
+  if (b0 < 0 || b0 > B) { agd_set_error("attention_backward: b0=%d outside [0, %d]", b0, B); return -1; }
+  if (!q || !kv || !dq || !dkv) { agd_set_error("attention_backward: q, kv, dq and dkv are required"); return -1; }
+  if (!d_o && !d_map) { agd_set_error("attention_backward: d_o and d_map are both null (no gradient to propagate)"); return -1; }
+  hipStream_t st = S(stream); Tmp tmp;
+  const int C = H * D;
+  const long long nq = (long long)B * N * C, nkv = (long long)B * T * 2 * C;
+  bf16_t* qb = tmp.get<bf16_t>((size_t)nq); bf16_t* kvb = tmp.get<bf16_t>((size_t)nkv);
+  bf16_t* dob = d_o ? tmp.get<bf16_t>((size_t)nq) : nullptr;
+  bf16_t* dqb = tmp.get<bf16_t>((size_t)nq); bf16_t* dkvb = tmp.get<bf16_t>((size_t)nkv);
+  float* part = tmp.get<float>((size_t)attention_backward_ws_floats(B, H, D, N, T));
+  if (!qb || !kvb || (d_o && !dob) || !dqb || !dkvb || !part) return -1;
+  CK(launch_f32_to_bf16(q, qb, nq, st));
+  CK(launch_f32_to_bf16(kv, kvb, nkv, st));
+  if (d_o) CK(launch_f32_to_bf16(d_o, dob, nq, st));
+  CK(launch_attention_backward(qb, kvb, dob, d_map, b0, B, H, D, N, T, scale, dqb, dkvb, part, st));
+  CK(launch_bf16_to_f32(dqb, dq, nq, st));
+  CK(launch_bf16_to_f32(dkvb, dkv, nkv, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
+// hook.py:55 in isolation: heads [Bp][H][T][N] fp32 -> map [Bp][T][N] = the mean over the heads, summed in head order
+AGD_API int agd_op_hook_headmean(const float* heads, int Bp, int H, int T, int N, float* map, void* stream) {
+  if (!heads || !map || Bp < 1 || H < 1 || T < 1 || N < 1) { agd_set_error("hook_headmean: bad argument Bp=%d H=%d T=%d N=%d", Bp, H, T, N); return -1; }
+  hipStream_t st = S(stream);
+  CK(launch_hook_headmean(heads, Bp, H, T, N, map, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
 AGD_API int agd_op_bicubic_clamp_mean(const float* maps, int n_maps, int T, int side, int S_, float* out, void* stream) {
   hipStream_t st = S(stream);
   // n_maps accumulators of [T][side][side]: treat as one layer with n_maps "heads"

@@ -142,6 +142,46 @@ def attention_headsum(q, k, v, heads, scale=None):
     return o, probs
 
 
+def attention_backward(q, kv, heads, d_o=None, d_map=None, b0=0, scale=None):
+    """The attention backward of the training seam (train.hip) in isolation: q [B,N,H*D], kv [B,T,2*H*D] (K columns then V columns),
+    d_o [B,N,H*D] = gradient of the per-head attention output (before to_out), d_map [B-b0,T,N] = gradient of the head-mean map of
+    batch rows >= b0 -> (dq [B,N,H*D], dkv [B,T,2*H*D]), the gradient of sum(O * d_o) + sum(map[b0:] * d_map).  Operands are rounded
+    to bf16; the outputs are the bf16 results as fp32.  The library refuses unsupported head dims / key counts / b0 and two absent gradients."""
+    lib = _lib.load()
+    q, kv = _f32c(q), _f32c(kv)
+    if q.ndim != 3 or kv.ndim != 3 or kv.shape[0] != q.shape[0] or q.shape[2] % heads or kv.shape[2] != 2 * q.shape[2]:
+        raise ValueError(f"attention_backward: q {tuple(q.shape)} / kv {tuple(kv.shape)} must be [B, N, H*D] / [B, T, 2*H*D] with H = {heads}")
+    B, N, Cc = q.shape
+    T = kv.shape[1]
+    D = Cc // heads
+    scale = D ** -0.5 if scale is None else scale
+    do = _f32c(d_o) if d_o is not None else None
+    dm = _f32c(d_map) if d_map is not None else None
+    if do is not None and do.shape != q.shape:
+        raise ValueError(f"attention_backward: d_o {tuple(do.shape)} must match q {tuple(q.shape)}")
+    if dm is not None and 0 <= b0 <= B:
+        if tuple(dm.shape) != (B - b0, T, N):
+            raise ValueError(f"attention_backward: d_map {tuple(dm.shape)} must be {(B - b0, T, N)}")
+        if dm.numel() == 0:                  # b0 == B: given but empty -- still a valid pointer, the kernel's `b >= b0` keeps every row out
+            dm = torch.zeros(1, device=q.device, dtype=torch.float32)
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    _lib.check(lib.agd_op_attention_backward(_lib.ptr(q), _lib.ptr(kv), _lib.ptr(do), _lib.ptr(dm), int(b0), B, heads, D, N, T, float(scale),
+                                             _lib.ptr(dq), _lib.ptr(dkv), _lib.current_stream_ptr()), None, "agd_op_attention_backward")
+    return dq, dkv
+
+
+def hook_headmean(heads):
+    """hook.py:55 `maps.mean(dim=1)`, the production kernel: heads [Bp, H, T, N] -> [Bp, T, N], the heads summed in order times 1/H."""
+    lib = _lib.load()
+    heads = _f32c(heads)
+    if heads.ndim != 4:
+        raise ValueError(f"hook_headmean: heads {tuple(heads.shape)} must be [Bp, H, T, N]")
+    Bp, H, T, N = heads.shape
+    out = torch.empty(Bp, T, N, device=heads.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_hook_headmean(_lib.ptr(heads), Bp, H, T, N, _lib.ptr(out), _lib.current_stream_ptr()), None, "agd_op_hook_headmean")
+    return out
+
+
 def bicubic_clamp_mean(maps, out_side):
     """maps [n_maps, T, side, side] -> mean_n clamp(bicubic(maps[n]), 0) : [T, S, S]"""
     lib = _lib.load()

@@ -455,6 +455,15 @@ int agd_op_attention(const float* q, const float* k, const float* v, float* o, i
 /* same, the probabilities summed over the heads (the recording form of the daam layers at latent resolution): probs_sum_out [B,Nk,Nq] */
 int agd_op_attention_headsum(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                              float scale, float* probs_sum_out, void* stream);
+/* The attention backward of the training seam in isolation (what agd_attn_processor_backward runs between its GEMMs): recompute
+ * P = softmax(scale q k^T) per head, then the gradient of  sum(O . d_o) + sum(mean_heads(P)[b0:] . d_map)  w.r.t. q and kv.
+ * q / d_o / dq [B,N,H*D], kv / dkv [B,T,2*H*D] (K columns, then V columns), d_map [B-b0,T,N]; d_o is the gradient of the per-head
+ * attention output (before to_out).  d_o or d_map may be NULL, not both.  D in {32,40,64,80,128,160}, 1 <= T <= 96, 0 <= b0 <= B.
+ * Operands are rounded to bf16, the arithmetic is fp32, dq / dkv are the bf16 results as fp32.  Syncs. */
+int agd_op_attention_backward(const float* q, const float* kv, const float* d_o, const float* d_map, int b0, int B, int H, int D,
+                              int N, int T, float scale, float* dq, float* dkv, void* stream);
+/* hook.py:55 `maps.mean(dim=1)` in isolation: heads [Bp,H,T,N] fp32 -> map [Bp,T,N] = (heads summed in order h = 0, 1, ...) * (1/H).  Syncs. */
+int agd_op_hook_headmean(const float* heads, int Bp, int H, int T, int N, float* map, void* stream);
 int agd_op_bicubic_clamp_mean(const float* maps, int n_maps, int T, int side, int S, float* out, void* stream);
 
 /* ---- export path on device, bit-exact with the reference's host code:

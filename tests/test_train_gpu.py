@@ -17,31 +17,95 @@ def _rel(got, want):
 def test_attention_regulariser_loss_and_gradient_match_autograd():
     """agd_op_attn_reg_loss vs torch autograd through the oracle's line-by-line restatement of finetune_sd_token.py:1046-1066:
     both loss terms per map and d loss / d map (min/max paths, coinciding token rows, samples without an object)."""
-    from agenda_amd import ops
-    from oracle import sd_oracle as O
     g = torch.Generator().manual_seed(11)
     for (B, T, side, n_obj_emb, idx) in [(3, 77, 16, 1, [[5, 9, 12], [-1, 3, 7], [2, -1, -1]]),
                                          (2, 20, 8, 0, [[4, 6, 8], [1, 2, -1]]),
                                          (2, 77, 64, 2, [[3, 8, 11], [6, 9, 15]])]:
         maps = [torch.rand(B, T, side, side, generator=g).softmax(1) for _ in range(2)]
-        idx_t = torch.tensor(idx)
-        leaf = [m.clone().requires_grad_(True) for m in maps]
-        attn, bg, fg = O.attention_regulariser(leaf, idx_t, n_obj_emb, 0.5)
-        attn.backward()
-        has = idx_t[:, 0] > 0
-        cnt = int(has.sum())
-        obj = [int(r[0]) + n_obj_emb if r[0] > 0 else -1 for r in idx_t]
-        fgi = [int(r[0]) if r[0] > 0 else -1 for r in idx_t]
-        bgi = [int(r[r > -1][-1]) if r[0] > 0 else -1 for r in idx_t]
-        tot_bg = tot_fg = 0.0
-        for m, lf in zip(maps, leaf):
-            loss, dmap = ops.attn_reg_loss(m.cuda(), obj, fgi, bgi, 0.5 / cnt)
-            tot_bg += float(loss[:, 0].sum()); tot_fg += float(loss[:, 1].sum())
-            want = lf.grad * len(maps)                              # the oracle divided by len(maps) (:1069)
-            assert _rel(dmap, want) < 2e-3, (B, T, side, _rel(dmap, want))
-            assert float(dmap.cpu()[~has].abs().max() if (~has).any() else 0.0) == 0.0
-        assert tot_bg == pytest.approx(float(bg.detach()), rel=1e-4) and tot_fg == pytest.approx(float(fg.detach()), rel=1e-4)
-        assert (tot_bg + tot_fg) / len(maps) == pytest.approx(float(attn.detach()), rel=1e-4)
+        _regulariser_check(maps, idx, n_obj_emb)
+
+
+def _token_rows(idx_t, n_obj_emb):
+    """finetune_sd_token.py:1048-1060: the object / foreground / background map row of every sample, -1 = the sample has no object"""
+    obj = [int(r[0]) + n_obj_emb if r[0] > 0 else -1 for r in idx_t]
+    fgi = [int(r[0]) if r[0] > 0 else -1 for r in idx_t]
+    bgi = [int(r[r > -1][-1]) if r[0] > 0 else -1 for r in idx_t]
+    return obj, fgi, bgi
+
+
+def _regulariser_check(maps, idx, n_obj_emb):
+    """Both loss terms (1e-4 relative) and d loss / d map (2e-3 of its maximum) of `ops.attn_reg_loss` on every map of `maps`
+    [B, T, h, w] against autograd through `O.attention_regulariser`; returns (bg, fg) of the reference and the kernel's sums."""
+    from agenda_amd import ops
+    from oracle import sd_oracle as O
+    idx_t = torch.tensor(idx)
+    shape = tuple(maps[0].shape)
+    leaf = [m.clone().requires_grad_(True) for m in maps]
+    attn, bg, fg = O.attention_regulariser(leaf, idx_t, n_obj_emb, 0.5)
+    attn.backward()
+    has = idx_t[:, 0] > 0
+    cnt = int(has.sum())
+    obj, fgi, bgi = _token_rows(idx_t, n_obj_emb)
+    tot_bg = tot_fg = 0.0
+    for m, lf in zip(maps, leaf):
+        loss, dmap = ops.attn_reg_loss(m.cuda(), obj, fgi, bgi, 0.5 / cnt)
+        tot_bg += float(loss[:, 0].sum()); tot_fg += float(loss[:, 1].sum())
+        want = lf.grad * len(maps)                              # the oracle divided by len(maps) (:1069)
+        assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+        print(f"attn_reg_loss {shape} n_obj_emb={n_obj_emb}: d_map rel {_rel(dmap, want):.6f}")
+        assert _rel(dmap, want) < 2e-3, (shape, _rel(dmap, want))
+        assert float(dmap.cpu()[~has].abs().max() if (~has).any() else 0.0) == 0.0
+    assert tot_bg == pytest.approx(float(bg.detach()), rel=1e-4) and tot_fg == pytest.approx(float(fg.detach()), rel=1e-4)
+    assert (tot_bg + tot_fg) / len(maps) == pytest.approx(float(attn.detach()), rel=1e-4)
+    return float(bg.detach()), float(fg.detach()), tot_bg, tot_fg
+
+
+@pytest.mark.parametrize("h,w", [(3, 3), (12, 12), (20, 13)])
+def test_attention_regulariser_ragged_map_sizes(h, w):
+    """P = 9 (fewer pixels than a wave), 144 (no multiple of 64) and 260 (just over one 256-thread pass): the strided loops' tails."""
+    g = torch.Generator().manual_seed(100 * h + w)
+    maps = [torch.rand(3, 77, h, w, generator=g).softmax(1) for _ in range(2)]
+    _regulariser_check(maps, [[5, 9, 12], [-1, 3, 7], [2, -1, -1]], 1)
+
+
+def _quantised_maps(B, T, h, w, seed, n=2):
+    """Softmax maps of a broad range rounded to multiples of 1/256 and capped at 6/256: seven levels, so every row has many pixels
+    at its minimum and several at its maximum."""
+    g = torch.Generator().manual_seed(seed)
+    return [(torch.round((3.0 * torch.randn(B, T, h, w, generator=g)).softmax(1) * 256.0).clamp(max=6.0) / 256.0) for _ in range(n)]
+
+
+@pytest.mark.parametrize("h,w", [(16, 16), (20, 13)])
+def test_attention_regulariser_spreads_min_max_gradient_over_ties(h, w):
+    """Rows whose minimum and maximum are each shared by at least three pixels: torch's x.min() / x.max() backward splits the
+    gradient evenly between the tied elements, and so must the kernel (`nmin` / `nmax` in add_minmax_grad)."""
+    idx, n_obj_emb = [[5, 9, 12], [-1, 3, 7], [2, 6, -1]], 1
+    maps = _quantised_maps(3, 20, h, w, seed=7 + h)
+    idx_t = torch.tensor(idx)
+    for m in maps:
+        for b, rows in enumerate(zip(*_token_rows(idx_t, n_obj_emb))):
+            for r in rows:
+                if r < 0:
+                    continue
+                x = m[b, r].flatten()
+                assert float(x.max()) > float(x.min()), (b, r, "constant row: NaN in the reference too")
+                assert int((x == x.min()).sum()) >= 3 and int((x == x.max()).sum()) >= 3, (b, r)
+    _regulariser_check(maps, idx, n_obj_emb)
+
+
+def test_attention_regulariser_with_all_three_rows_coinciding():
+    """n_object_embedding = 0 and a single new token: object, foreground and background are the same map row.  The foreground term
+    and its gradient are exactly zero; the background term's three contributions accumulate on that one row."""
+    g = torch.Generator().manual_seed(31)
+    maps = [torch.rand(2, 20, 12, 12, generator=g).softmax(1) for _ in range(2)]
+    idx = [[4, -1, -1], [7, -1, -1]]
+    assert _token_rows(torch.tensor(idx), 0) == ([4, 7], [4, 7], [4, 7])
+    from oracle import sd_oracle as O
+    leaf = [m.clone().requires_grad_(True) for m in maps]
+    fg_only = torch.autograd.grad(O.attention_regulariser(leaf, torch.tensor(idx), 0, 0.5)[2], leaf)
+    assert all(float(d.abs().max()) == 0.0 for d in fg_only)          # so the gradient compared below is the background term's alone
+    bg, fg, got_bg, got_fg = _regulariser_check(maps, idx, 0)
+    assert fg == 0.0 and got_fg == 0.0 and bg > 0.0
 
 
 @pytest.fixture(scope="module")
@@ -102,6 +166,27 @@ def seam_backward_check(pipe, cfg, u, name, heads, side, is_train, B2=4, tol=0.0
 def test_seam_call_backward_matches_torch_autograd(tiny, is_train):
     pipe, cfg, u = tiny
     seam_backward_check(pipe, cfg, u, "up_blocks.2.attentions.1.transformer_blocks.0.attn2", 2, 16, is_train)
+
+
+@pytest.fixture(scope="module")
+def tiny40():
+    from agenda_amd import StableDiffusionPipeline, config, synthetic
+    cfg = config.tiny40()
+    u, v = synthetic.make_unet_weights(cfg, 11, bias_std=0.05), synthetic.make_vae_weights(cfg, 12)
+    pipe = StableDiffusionPipeline(cfg, u, v, workspace_bytes=1 << 30)
+    yield pipe, cfg, u
+    pipe.engine.close()
+
+
+@pytest.mark.parametrize("is_train", [True, False])
+@pytest.mark.parametrize("name,side", [("down_blocks.0.attentions.0.transformer_blocks.0.attn2", 16),      # C = 320: D = 40, N = 256
+                                       ("mid_block.attentions.0.transformer_blocks.0.attn2", 8)])         # C = 640: D = 80, N = 64
+def test_seam_call_backward_at_sd_head_dims(tiny40, name, side, is_train):
+    """The same check at the head dims SD-1.x runs (8 heads of 40 / 80): the entry point hands the kernel the right D, strides and b0
+    for other layers.  The kernel's own precision is tests/test_train_ops_gpu.py's."""
+    pipe, cfg, u = tiny40
+    assert u[name.rsplit("attn2", 1)[0] + "attn2.to_q.weight"].shape[0] // 8 == (40 if side == 16 else 80)
+    seam_backward_check(pipe, cfg, u, name, 8, side, is_train)
 
 
 def test_train_mode_fused_walk_keeps_the_sixteen_maps(tiny):
