@@ -219,12 +219,15 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
 #pragma unroll
       for (int j = 0; j < 16; ++j) oacc[qb][i][j] = 0.f;
   float m_run[QB], l_run[QB];
+  // AMASK: has this query met a key the mask left standing?  Until it has, its reference maximum is still to be fixed (a -inf mask can remove
+  // whole leading tiles), whichever tile that happens in -- the plain and causal forms fix it in tile 0, whose first key every query sees
+  [[maybe_unused]] bool seen[QB];
   // non-RECORD: -m_run replicated over a 16-register tuple = the C operand of the first QK^T MFMA, so the
   // accumulator comes out as (logit - m) and exp2 applies to it directly.  Rewritten only on a (rare) rescale.
   f32x16 negm[CNEG ? QB : 1];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
-    m_run[qb] = RECORD ? -INFINITY : 0.f; l_run[qb] = 0.f;
+    m_run[qb] = RECORD ? -INFINITY : 0.f; l_run[qb] = 0.f; seen[qb] = false;
     if constexpr (CNEG) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) negm[qb][j] = 0.f;
@@ -317,17 +320,22 @@ __global__ __launch_bounds__(256, ATTN_LB((AMASK ? 1 : (QB == 1 && D <= 64 && !R
       } else {
         // sacc already holds (logit - m_run) in log2 units.  Deferred rescale: only when some score of this
         // tile exceeds the reference by 2^DEFER_THR (or on the first tile, which fixes the reference).
-        if (t == 0 || !__all(mx <= DEFER_THR)) {
+        bool fresh = (t == 0);                              // this tile fixes the reference: take its maximum as it is, above or below 0
+        if constexpr (AMASK) fresh = !seen[qb];
+        if ((AMASK ? __any(fresh) : (t == 0)) || !__all(mx <= DEFER_THR)) {
           const float mxf = xhalf_max(mx);
-          float delta = (t == 0) ? mxf : fmaxf(mxf, 0.f);
-          if (!(delta > -INFINITY)) delta = 0.f;
+          float delta = fresh ? mxf : fmaxf(mxf, 0.f);
+          if (!(delta > -INFINITY)) delta = 0.f;            // every key of the tile masked away: nothing to refer to yet
+          else if constexpr (AMASK) seen[qb] = true;
           if constexpr (QPAD) {                             // the reference lives in a bf16 Q slot: round it
             const float mb = (float)(__bf16)(m_run[qb] + delta);
             delta = mb - m_run[qb];
             constexpr int pc = D - 16 * (KSTEPS - 1);       // pad column within the last k-step
             if (hh == pc / 8) qf[qb][KSTEPS - 1][pc % 8] = (__bf16)(-mb);
           }
-          const float alpha = __builtin_amdgcn_exp2f(-delta);
+          // delta < 0 only where the reference is being fixed, and then l_run and oacc are still 0: keep the factor finite (a first tile
+          // more than 2^128 below 0 gave alpha = inf and 0 * inf = NaN); everywhere else the clamp changes nothing
+          const float alpha = __builtin_amdgcn_exp2f(fminf(-delta, 0.f));
           m_run[qb] += delta;
           l_run[qb] *= alpha;
 #pragma unroll

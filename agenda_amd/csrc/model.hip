@@ -3233,6 +3233,81 @@ AGD_API int agd_op_attention(const float* q, const float* k, const float* v, flo
   return 0;
 }
 
+// Every instantiation of attention.hip's attn_kernel through one context-free entry (tests/test_attention_ops_gpu.py).  q [B][Nq][H*D],
+// k / v [B][Nk][H*D], mask [B][Nk] (additive, or NULL), k2 / v2 [B][Nk2][H*D] (the second K/V source, or both NULL): packed fp32, rounded to
+// bf16 here.  layout: how the bf16 operands lie in memory when the kernel reads them --
+//   0  packed: q, k, v (and k2, v2) each [.][H*D], pitch C
+//   1  q | k | v are the column blocks of ONE [B][N][3C] buffer (pitch 3C, batch stride N * 3C; needs Nq == Nk) -- UNet / CLIP self-attention
+//   2  k | v are the column blocks of ONE [B][Nk][2C] buffer (pitch 2C) -- cross-attention; q packed
+//   (layouts 1 and 2 keep the second source as the k2 | v2 column blocks of one [B][Nk2][2C] buffer, as GLIGEN's fuser does)
+// record: 0 = none; 1 = every head's probabilities, probs_out [B][H][Nk][Nq]; 2 = their sum over the heads, probs_out [B][Nk][Nq].  probs_out
+// is zeroed here; batch rows >= rec_b0 and token rows < rec_T are then recorded, every other row stays zero.
+// Every refusal of this entry comes before any allocation or launch; the launcher's own (mask + causal, a second source with a mask, causal
+// order or recording, Nk2 outside 1..64, head-summed recording with a mask) come back as errors before its launch.  Syncs.
+AGD_API int agd_op_attention_ex(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk, float scale,
+                                int causal, const float* mask, const float* k2, const float* v2, int Nk2, int layout, float* probs_out,
+                                int record, int rec_b0, int rec_T, void* stream) {
+  if (D != 32 && D != 40 && D != 64 && D != 80 && D != 128 && D != 160) { agd_set_error("attention_ex: unsupported head dim D=%d", D); return -1; }
+  if (B < 1 || H < 1 || Nq < 1 || Nk < 1) { agd_set_error("attention_ex: bad shape B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk); return -1; }
+  if (!q || !k || !v || !o) { agd_set_error("attention_ex: q, k, v and o are required"); return -1; }
+  if (layout < 0 || layout > 2) { agd_set_error("attention_ex: layout=%d (0 packed, 1 fused q|k|v rows, 2 fused k|v rows)", layout); return -1; }
+  if (layout == 1 && Nq != Nk) { agd_set_error("attention_ex: layout=1 (fused q|k|v rows) needs Nq == Nk (got Nq=%d Nk=%d)", Nq, Nk); return -1; }
+  if (record < 0 || record > 2 || (record != 0) != (probs_out != nullptr)) { agd_set_error("attention_ex: record=%d needs probs_out, and probs_out needs record 1 or 2", record); return -1; }
+  if (record && Nk > 96) { agd_set_error("attention_ex: recording needs Nk <= 96 (got Nk=%d)", Nk); return -1; }
+  if (record && (rec_b0 < 0 || rec_b0 > B)) { agd_set_error("attention_ex: rec_b0=%d outside [0, %d]", rec_b0, B); return -1; }
+  if (record && (rec_T < 1 || rec_T > Nk)) { agd_set_error("attention_ex: rec_T=%d outside [1, %d]", rec_T, Nk); return -1; }
+  if ((k2 != nullptr) != (v2 != nullptr)) { agd_set_error("attention_ex: k2 and v2 come together"); return -1; }
+  if (!k2 && Nk2 != 0) { agd_set_error("attention_ex: Nk2=%d without a second source", Nk2); return -1; }
+  hipStream_t st = S(stream); Tmp tmp;
+  const int C = H * D;
+  const long long nq = (long long)B * Nq * C, nk = (long long)B * Nk * C, nk2 = k2 ? (long long)B * (Nk2 > 0 ? Nk2 : 0) * C : 0;
+  bf16_t* qb = tmp.get<bf16_t>((size_t)nq); bf16_t* kb = tmp.get<bf16_t>((size_t)nk); bf16_t* vb = tmp.get<bf16_t>((size_t)nk);
+  bf16_t* ob = tmp.get<bf16_t>((size_t)nq);
+  bf16_t* k2b = k2 ? tmp.get<bf16_t>((size_t)nk2 + 8) : nullptr; bf16_t* v2b = k2 ? tmp.get<bf16_t>((size_t)nk2 + 8) : nullptr;
+  bf16_t* fused = layout ? tmp.get<bf16_t>((size_t)(layout == 1 ? 3 : 2) * nk) : nullptr;
+  bf16_t* fused2 = (layout && k2) ? tmp.get<bf16_t>((size_t)2 * nk2 + 8) : nullptr;
+  if (!qb || !kb || !vb || !ob || (k2 && (!k2b || !v2b)) || (layout && !fused) || (layout && k2 && !fused2)) return -1;
+  CK(launch_f32_to_bf16(q, qb, nq, st));
+  CK(launch_f32_to_bf16(k, kb, nk, st));
+  CK(launch_f32_to_bf16(v, vb, nk, st));
+  if (nk2 > 0) { CK(launch_f32_to_bf16(k2, k2b, nk2, st)); CK(launch_f32_to_bf16(v2, v2b, nk2, st)); }
+  // column block `col` of a [rows][wide * C] buffer <- packed [rows][C]
+  auto place = [&](bf16_t* dst, int wide, int col, const bf16_t* src, long long rows) {
+    if (rows < 1) return 0;
+    if (hipMemcpy2DAsync(dst + (size_t)col * C, (size_t)wide * C * 2, src, (size_t)C * 2, (size_t)C * 2, (size_t)rows, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      agd_set_error("attention_ex: layout copy failed"); return -1; }
+    return 0;
+  };
+  AttnP a{}; a.q = qb; a.k = kb; a.v = vb; a.o = ob; a.ldq = a.ldk = a.ldv = a.ldo = C;
+  a.sq = (long long)Nq * C; a.so = a.sq; a.sk = (long long)Nk * C; a.sv = a.sk;
+  if (layout == 1) {
+    CK(place(fused, 3, 0, qb, (long long)B * Nq)); CK(place(fused, 3, 1, kb, (long long)B * Nk)); CK(place(fused, 3, 2, vb, (long long)B * Nk));
+    a.q = fused; a.k = fused + C; a.v = fused + 2 * C; a.ldq = a.ldk = a.ldv = 3 * C; a.sq = a.sk = a.sv = (long long)Nk * 3 * C;
+  } else if (layout == 2) {
+    CK(place(fused, 2, 0, kb, (long long)B * Nk)); CK(place(fused, 2, 1, vb, (long long)B * Nk));
+    a.k = fused; a.v = fused + C; a.ldk = a.ldv = 2 * C; a.sk = a.sv = (long long)Nk * 2 * C;
+  }
+  a.B = B; a.H = H; a.D = D; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.causal = causal ? 1 : 0; a.mask = mask;
+  if (k2) {
+    a.k2 = k2b; a.v2 = v2b; a.ldk2 = a.ldv2 = C; a.sk2 = a.sv2 = (long long)Nk2 * C; a.Nk2 = Nk2;
+    if (layout) {
+      CK(place(fused2, 2, 0, k2b, (long long)B * Nk2)); CK(place(fused2, 2, 1, v2b, (long long)B * Nk2));
+      a.k2 = fused2; a.v2 = fused2 + C; a.ldk2 = a.ldv2 = 2 * C; a.sk2 = a.sv2 = (long long)Nk2 * 2 * C;
+    }
+  }
+  if (record) {
+    const long long rows = (record == 1 ? (long long)B * H : (long long)B) * Nk * Nq;
+    if (hipMemsetAsync(probs_out, 0, (size_t)rows * 4, st) != hipSuccess) { agd_set_error("memset probs"); return -1; }
+    a.record_mode = record == 1 ? 1 : 3; a.rec_hpb = record == 1 ? 0 : H; a.rec_b0 = rec_b0; a.rec_T = rec_T;
+    a.rec_head_stride = (long long)Nk * Nq; a.rec_img_stride = record == 1 ? a.rec_head_stride * H : a.rec_head_stride;
+    a.rec = probs_out + (long long)rec_b0 * a.rec_img_stride;      // the kernel indexes the recording rows from rec_b0
+  }
+  CK(launch_attention(a, st));
+  CK(launch_bf16_to_f32(ob, o, nq, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
 // as agd_op_attention with the probabilities summed over the heads: probs_sum_out [B][Nk][Nq] (attention.hip RECORD 2)
 AGD_API int agd_op_attention_headsum(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                                      float scale, float* probs_sum_out, void* stream) {

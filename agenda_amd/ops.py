@@ -111,8 +111,22 @@ def xattn_premul(x, gamma, beta, wq, kv, wo, bo, heads=8, eps=1e-5, return_probs
     return (y, pr) if return_probs else y
 
 
-def attention(q, k, v, heads, scale=None, return_probs=False):
-    """q [B,Nq,H*D], k/v [B,Nk,H*D] -> o [B,Nq,H*D] (+ probs [B,H,Nk,Nq] token-major if asked, Nk<=96)."""
+def _given(t):
+    """a tensor to hand over even when it is empty (an empty tensor has a null data pointer): the library refuses the shape, by name"""
+    t = _f32c(t)
+    return t if t.numel() else torch.zeros(1, device=t.device, dtype=torch.float32)
+
+
+def attention(q, k, v, heads, scale=None, return_probs=False, *, causal=False, mask=None, k2=None, v2=None, layout=0, head_sum=False,
+              rec_b0=0, rec_T=None):
+    """q [B,Nq,H*D], k/v [B,Nk,H*D] -> o [B,Nq,H*D] (+ probs [B,H,Nk,Nq] token-major if asked, Nk<=96).
+
+    The keyword arguments reach the other forms of the kernel (`agd_op_attention_ex`); without them the call is what it always was.
+    causal: key j is seen by queries i >= j.  mask: additive [B,Nk], broadcast over heads and queries.  k2 / v2 [B,Nk2,H*D]: a second
+    K/V source of 1..64 keys attended after the Nk keys.  layout: 0 packed operands, 1 q|k|v as column blocks of one [B,N,3C] buffer
+    (Nq == Nk), 2 k|v as column blocks of one [B,Nk,2C] buffer -- built by the library from the same packed tensors.  With return_probs:
+    head_sum gives the probabilities summed over the heads, [B,Nk,Nq]; only batch rows >= rec_b0 and token rows < rec_T (default Nk)
+    are recorded, the rest of probs stays zero."""
     lib = _lib.load()
     q, k, v = _f32c(q), _f32c(k), _f32c(v)
     B, Nq, Cc = q.shape
@@ -120,6 +134,25 @@ def attention(q, k, v, heads, scale=None, return_probs=False):
     D = Cc // heads
     scale = D ** -0.5 if scale is None else scale
     o = torch.empty_like(q)
+    if causal or mask is not None or k2 is not None or v2 is not None or layout != 0 or head_sum or rec_b0 != 0 or rec_T is not None:
+        if k.shape != (B, Nk, Cc) or v.shape != k.shape:
+            raise ValueError(f"attention: k {tuple(k.shape)} / v {tuple(v.shape)} must both be [B, Nk, H*D] = [{B}, Nk, {Cc}]")
+        if mask is not None and tuple(mask.shape) != (B, Nk):
+            raise ValueError(f"attention: mask {tuple(mask.shape)} must be {(B, Nk)}")
+        if (k2 is None) != (v2 is None) or (k2 is not None and (k2.shape != v2.shape or k2.ndim != 3 or k2.shape[0] != B or k2.shape[2] != Cc)):
+            raise ValueError("attention: k2 and v2 come together, both [B, Nk2, H*D]")
+        if head_sum and not return_probs:
+            raise ValueError("attention: head_sum is a form of return_probs")
+        Nk2 = 0 if k2 is None else k2.shape[1]
+        probs = None
+        if return_probs:       # an empty key axis would make this a null pointer: keep one element, the library refuses Nk < 1 by name
+            probs = torch.empty((B, max(Nk, 1), max(Nq, 1)) if head_sum else (B, heads, max(Nk, 1), max(Nq, 1)), device=q.device, dtype=torch.float32)
+        _lib.check(lib.agd_op_attention_ex(_lib.ptr(_given(q)), _lib.ptr(_given(k)), _lib.ptr(_given(v)), _lib.ptr(_given(o)), B, heads, D, Nq, Nk, float(scale),
+                                           int(bool(causal)), _lib.ptr(None if mask is None else _given(mask)),
+                                           _lib.ptr(None if k2 is None else _given(k2)), _lib.ptr(None if v2 is None else _given(v2)), Nk2, int(layout),
+                                           _lib.ptr(probs), (2 if head_sum else 1) if return_probs else 0, int(rec_b0),
+                                           Nk if rec_T is None else int(rec_T), _lib.current_stream_ptr()), None, "agd_op_attention_ex")
+        return (o, probs) if return_probs else o
     probs = torch.empty(B, heads, Nk, Nq, device=q.device, dtype=torch.float32) if return_probs else None
     _lib.check(lib.agd_op_attention(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), B, heads, D, Nq, Nk, float(scale),
                                     _lib.ptr(probs), _lib.current_stream_ptr()), None, "agd_op_attention")

@@ -452,6 +452,19 @@ int agd_op_layernorm(const float* x, const float* gamma, const float* beta, floa
 /* q [B,Nq,H*D], k/v [B,Nk,H*D] fp32 -> o [B,Nq,H*D]; probs_out (may be NULL): [B,H,Nk,Nq] fp32, needs Nk<=96 */
 int agd_op_attention(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                      float scale, float* probs_out, void* stream);
+/* agd_op_attention reaching EVERY form of the attention kernel (causal order, an additive mask, a second K/V source, the fused operand
+ * layouts of the production callers, partial recording), for per-kernel tests.  All operands packed fp32, rounded to bf16 by the entry:
+ * q / o [B,Nq,H*D], k / v [B,Nk,H*D]; mask (may be NULL) [B,Nk] additive, broadcast over heads and queries; k2 / v2 (both or neither)
+ * [B,Nk2,H*D], 1 <= Nk2 <= 64, attended after the Nk keys.  layout: the memory layout the entry builds for the kernel -- 0 packed rows of
+ * pitch C; 1 q | k | v as the column blocks of one [B,N,3C] buffer (Nq == Nk); 2 k | v as the column blocks of one [B,Nk,2C] buffer (with
+ * 1 and 2, k2 | v2 likewise share one [B,Nk2,2C] buffer).  The values, and so the result, do not depend on the layout.
+ * record: 0 none (probs_out NULL); 1 probs_out [B,H,Nk,Nq] = every head's probabilities; 2 probs_out [B,Nk,Nq] = their sum over the
+ * heads.  probs_out is zeroed first; only batch rows >= rec_b0 (0 .. B) and token rows < rec_T (1 .. Nk) are recorded.  Recording needs
+ * Nk <= 96.  D in {32,40,64,80,128,160}.  Refused with a message, before anything is launched: the above, mask + causal, a second source
+ * together with a mask, causal order or recording, and head-summed recording with a mask.  Syncs. */
+int agd_op_attention_ex(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk, float scale,
+                        int causal, const float* mask, const float* k2, const float* v2, int Nk2, int layout, float* probs_out,
+                        int record, int rec_b0, int rec_T, void* stream);
 /* same, the probabilities summed over the heads (the recording form of the daam layers at latent resolution): probs_sum_out [B,Nk,Nq] */
 int agd_op_attention_headsum(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                              float scale, float* probs_sum_out, void* stream);

@@ -394,6 +394,18 @@ def _attn_ref(q, k, v, heads):
     return O.batch_to_head_dim(torch.bmm(p, vh), heads), p
 
 
+def _attn_slabs(name, got, q, k, v, heads, fold):
+    """The per-slab measure of tests/test_attention_ops_gpu.py on top of `rel_err`: every (batch row, head) slab of the output against
+    the fp64 reference, max and RMS, within twice the error of the declared-roundings model (tests/_attn_model.py)."""
+    from _attn_model import MODEL_FACTOR, attention_fp64, attention_model, model_bounds, slab_errors
+    want, _ = attention_fp64(q, k, v, heads)
+    e_model, e_rms = model_bounds(attention_model(q, k, v, heads, fold=fold), want, heads)
+    mx, rms = slab_errors(got.cpu(), want, heads)
+    report(f"attention_slabs[{name}]", kernel_max=float(mx.max()), model_max=e_model, kernel_rms=float(rms.max()), model_rms=e_rms)
+    assert float(mx.max()) <= MODEL_FACTOR * e_model, (name, float(mx.max()), e_model)
+    assert float(rms.max()) <= MODEL_FACTOR * e_rms, (name, float(rms.max()), e_rms)
+
+
 @pytest.mark.parametrize("B,H,D,Nq,Nk", [
     (2, 8, 40, 256, 256), (1, 8, 80, 64, 64), (1, 8, 160, 64, 64), (2, 2, 64, 128, 128),
     (1, 2, 32, 256, 256), (1, 4, 40, 144, 144),   # ragged query/key tails (768-px mid block)
@@ -406,6 +418,7 @@ def test_self_attention(ops, B, H, D, Nq, Nk):
     want, _ = _attn_ref(q, k, v, H)
     got = ops.attention(q.cuda(), k.cuda(), v.cuda(), H)
     assert rel_err(got, want) < REL
+    _attn_slabs(f"self {B}x{H}x{D}x{Nq}x{Nk}", got, q, k, v, H, fold=True)
 
 
 def test_self_attention_online_softmax_rescale(ops):
@@ -432,6 +445,7 @@ def test_cross_attention_with_probs(ops, B, H, D, Nq, Nk):
     want_p = p.reshape(B, H, Nq, Nk).permute(0, 1, 3, 2)  # token-major [B,H,Nk,Nq]
     assert float((probs.cpu() - want_p).abs().max()) < 2e-3
     assert float((probs.cpu().sum(2) - 1).abs().max()) < 1e-3   # rows of P sum to 1
+    _attn_slabs(f"cross+probs {B}x{H}x{D}x{Nq}x{Nk}", got, q, k, v, H, fold=False)
 
 
 @pytest.mark.parametrize("B,H,D,Nq,Nk", [(2, 8, 40, 256, 77), (2, 8, 80, 200, 77), (2, 8, 160, 16, 77), (4, 5, 64, 130, 77), (1, 2, 32, 64, 20)])
@@ -450,6 +464,7 @@ def test_cross_attention_head_summed_probs(ops, B, H, D, Nq, Nk):
     got1, probs = ops.attention(q.cuda(), k.cuda(), v.cuda(), H, return_probs=True)
     assert torch.equal(got, got1)                                  # same arithmetic per head
     assert float((psum - probs.sum(1)).abs().max()) < 1e-5
+    _attn_slabs(f"cross+headsum {B}x{H}x{D}x{Nq}x{Nk}", got, q, k, v, H, fold=False)
 
 
 def test_bicubic_clamp_mean_matches_torch(ops):
