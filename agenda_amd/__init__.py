@@ -4,6 +4,7 @@ HIP kernels behind a C ABI (include/agenda_hip.h), with the Python call surfaces
 scripts use (StableDiffusionPipeline, daam.trace, the attention-processor hooker)."""
 from . import config, synthetic, ip_adapter  # noqa: F401
 from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine  # noqa: F401
+from .pipeline import StableDiffusionPipeline as StableDiffusionPAGPipeline  # noqa: F401  (diffusers' name: the same class, pag_applied_layers=)
 from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indices  # noqa: F401
 from .hook import UNetCrossAttentionHooker  # noqa: F401
 from .scheduler import DDIMScheduler  # noqa: F401
@@ -14,7 +15,7 @@ from .ip2p import StableDiffusionInstructPix2PixPipeline  # noqa: F401
 from .gligen import StableDiffusionGLIGENPipeline  # noqa: F401
 from .panorama import StableDiffusionPanoramaPipeline, get_views  # noqa: F401
 
-__all__ = ["StableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
+__all__ = ["StableDiffusionPipeline", "StableDiffusionPAGPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
            "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic", "ip_adapter",
            "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
            "StableDiffusionInpaintPipeline",

@@ -480,6 +480,41 @@ def cross_attn_layer_names(cfg: UNetConfig, include_mid: bool = True) -> List[st
     return names
 
 
+def self_attn_layer_names(cfg) -> List[str]:
+    """Module paths of every `attn1` of the UNet's transformer blocks: `cross_attn_layer_names`' spelling and order with attn1 in place of
+    attn2.  cfg: a UNetConfig or an SDConfig."""
+    ucfg = getattr(cfg, "unet", cfg)
+    return [n[:-len("attn2")] + "attn1" for n in cross_attn_layer_names(ucfg)]
+
+
+def resolve_pag_layers(cfg, layers) -> List[str]:
+    """diffusers' `pag_applied_layers` [upstream-knowledge: diffusers 0.30 PAGMixin]: every string is `re.search`ed against the module names
+    of the UNet's self-attention layers; the result is the matched names in `self_attn_layer_names`' order, each once.  A string that
+    matches no layer is a ValueError naming it."""
+    import re
+    if isinstance(layers, str):
+        layers = [layers]
+    names = self_attn_layer_names(cfg)
+    hit = set()
+    for pat in layers:
+        if not isinstance(pat, str):
+            raise ValueError(f"pag_applied_layers takes strings, got {pat!r}")
+        found = [n for n in names if re.search(pat, n) is not None]
+        if not found:
+            raise ValueError(f"Cannot find PAG layer to set attention processor for: {pat}")
+        hit.update(found)
+    return [n for n in names if n in hit]
+
+
+def pag_schedule(timesteps, pag_scale: float, pag_adaptive_scale: float = 0.0) -> List[float]:
+    """The PAG scale of every model evaluation [upstream-knowledge: diffusers 0.30 PAGMixin._get_pag_scale]:
+    p_i = max(0, pag_scale - pag_adaptive_scale (1000 - t_i)); constant pag_scale when the adaptive scale is 0."""
+    p, a = float(pag_scale), float(pag_adaptive_scale)
+    if not a:
+        return [p] * len(timesteps)
+    return [max(0.0, p - a * (1000.0 - float(t))) for t in timesteps]
+
+
 # ==========================================================================================
 # ControlNet (diffusers ControlNetModel) [upstream-knowledge: diffusers 0.21.2]
 # ==========================================================================================

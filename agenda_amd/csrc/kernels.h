@@ -266,6 +266,13 @@ int launch_adapter_avgpool(const bf16_t* x, bf16_t* y, int B, int H, int W, int 
 int launch_adapter_relu(bf16_t* x, long long n, hipStream_t st);
 int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, int bm, int B2, int HW, int C, int Bf, float s, hipStream_t st);
 
+// Perturbed-Attention Guidance (pag.hip): the "attention" of a perturbed self-attention layer -- att[m][0:C] = qkv[m][2C:3C], bf16 rows of the
+// fused q|k|v layout (leading dimension 3 C) -> rows of C, 16-byte loads and stores (C % 8 == 0, else refused), bit-exact -- and the in-place
+// fold of eps fp32 [3][n] (uncond | cond | perturbed): d = p (e_c - e_p) with the product rounded on its own, e_u += d, e_c += d, for the
+// two-way step kernels; e_p == e_c leaves both rows untouched
+int launch_pag_v_rows(const bf16_t* qkv, bf16_t* att, int M, int C, hipStream_t st);
+int launch_pag_fold(float* eps, long long n, float p, hipStream_t st);
+
 // FreeU (freeu.hip): one launch re-weights one up-block resnet's inputs into fresh activations -- hidden_out = hidden with its first Ch / 2
 // channels times b, skip_out = skip with the four lowest frequencies of every map times s (diffusers fourier_filter, threshold 1, as a rank-4
 // projection in fp32), bf16 NHWC [B2][H W][C].  hidden_out / skip_out == nullptr: that tensor is left alone (b == 1 / s == 1).  *_part != nullptr:

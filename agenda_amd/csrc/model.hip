@@ -12,6 +12,7 @@
 #include <functional>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 // ---------------------------------------------------------------------------------------
@@ -123,6 +124,7 @@ struct EvalCond {
   bool grounded = false;   // the GLIGEN fusers run in the UNet's transformer blocks
   float ad_scale = 0.f;    // != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs
   bool ipa = false;        // the IP-Adapter's image branch runs beside every UNet attn2
+  bool pag = false;        // the perturbed branch of Perturbed-Attention Guidance: the applied self-attention layers pass their value rows through
 };
 
 struct agd_ctx {
@@ -241,6 +243,9 @@ struct agd_ctx {
   // guidance_rescale (agd_guidance_rescale_set / _clear): phi > 0 = set; the step lambdas of the two-branch loops read it (guidance_factor).
   // gr_factb: the [batch] factors of the evaluation in flight; gr_count: factor launches since create
   float gr_phi = 0.f; DBuf gr_factb; long long gr_count = 0;
+  // Perturbed-Attention Guidance (agd_pag_set / agd_pag_clear): one scale per model evaluation (non-empty = set) and the applied self-attention
+  // layers as transformer prefixes ("unet.mid_block.attentions.0."); pag_counts: perturbed walks / perturbed self-attention layers launched
+  std::vector<float> pag_sched; std::unordered_set<std::string> pag_layers; long long pag_counts[2] = {0, 0};
   // profiling
   EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
@@ -854,7 +859,12 @@ static int tb_self_attention(TBlock& s, const TBlockPlan& p) {
   AttnP a{}; a.q = s.qkv; a.k = s.qkv + C; a.v = s.qkv + 2 * C; a.o = s.att;
   a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.sq = a.sk = a.sv = (long long)HW * 3 * C; a.so = (long long)HW * C;
   a.B = s.Bs; a.H = s.heads; a.D = D; a.Nq = HW; a.Nk = HW; a.scale = 1.0f / sqrtf((float)D);
-  CK(run_attention(c, s.st, PC_ATTN_SELF, a));
+  if (c->cur.pag && c->pag_layers.count(s.pre)) {          // the perturbed branch: the attention map is the identity, the output is the value rows
+    const double M = (double)s.Bs * HW;
+    ProfScope ps(c, s.st, PC_ELEM, 0, 4.0 * M * C);
+    CK(launch_pag_v_rows(s.qkv, s.att, s.Bs * HW, C, s.st));
+    c->pag_counts[1]++;
+  } else CK(run_attention(c, s.st, PC_ATTN_SELF, a));
   if (p.attn1_in_chain) return 0;
   GETW(wo, t + "attn1.to_out.0.weight"); GETV(bo, t + "attn1.to_out.0.bias");
   GemmOpt oo; oo.bias = bo; oo.residual = s.h;
@@ -2116,10 +2126,11 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
 // scales, GLIGEN flags, T2I-Adapter scales and inpainting-blend (sa, sb) pairs -- each nullptr when none -- and the IP-Adapter's image branch.
 struct CallCond {
   const float* cn = nullptr; const int* gl = nullptr; const float* ad = nullptr; const float* blend = nullptr; bool ipa = false;
+  const float* pag = nullptr;                                      // the PAG scales: the loop runs a third walk where pag[i] > 0 (at(i) stays the main walk's)
   EvalCond at(int i) const { EvalCond e; e.cn_scale = cn ? cn[i] : 0.f; e.grounded = gl && gl[i]; e.ad_scale = ad ? ad[i] : 0.f; e.ipa = ipa; return e; }
 };
 enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA };   // who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama
-enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, N_COND_STATES };                              // the states a call can meet, in the order of a row's cells
+enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, N_COND_STATES };                              // the states a call can meet, in the order of a row's cells
 // One row per refusing party: a state (self) that, when set, refuses to run beside others in the callers that consult it, or an entry point
 // that runs the UNet alone (self < 0: it refuses whenever it is the caller).  with[s]: nullptr = allowed beside state s, else the refusal.
 // Rows are looked at top to bottom, the first set cell wins.  Whatever is not here is allowed: ControlNet + GLIGEN, GLIGEN + either
@@ -2162,6 +2173,23 @@ static const ConflictRow kConflicts[] = {
     "denoise_panorama: a T2I-Adapter schedule is set; the T2I-Adapter on a panorama is not implemented (clear it first)",
     "denoise_panorama: an IP-Adapter image is set; denoise_panorama runs without it (agd_ip_adapter_clear first)" } },
 };
+// Perturbed-Attention Guidance's row and column of the table, consulted after it (so whatever kConflicts refuses keeps its message).  They
+// stand apart because tests/test_conditioning_gpu.py counts kConflicts' cells against a recording made before PAG existed, in which every
+// cell above is refused somewhere; the rows above leave their ST_PAG cell empty (nullptr).
+static const ConflictRow kPagConflicts[] = {
+  { ST_PAG, 1u << CALL_UNET_FORWARD | 1u << CALL_EVAL_LOOP | 1u << CALL_IP2P_LOOP, {   // pag
+    "pag: a ControlNet schedule is set; Perturbed-Attention Guidance with a ControlNet is not implemented (clear one of them)",
+    "pag: a GLIGEN schedule is set; Perturbed-Attention Guidance with GLIGEN is not implemented (clear one of them)",
+    "pag: an inpainting state is set; Perturbed-Attention Guidance with inpainting is not implemented (agd_inpaint_clear or agd_pag_clear first)",
+    "pag: an InstructPix2Pix state is set; Perturbed-Attention Guidance with InstructPix2Pix is not implemented (agd_ip2p_clear or agd_pag_clear first)",
+    "pag: a T2I-Adapter schedule is set; Perturbed-Attention Guidance with a T2I-Adapter is not implemented (clear one of them)",
+    "pag: an IP-Adapter image is set; Perturbed-Attention Guidance with an IP-Adapter is not implemented (agd_ip_adapter_clear or agd_pag_clear first)",
+    nullptr } },
+  { -1, 1u << CALL_UNET_FORWARD_TS, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    "unet_forward_ts: a Perturbed-Attention Guidance schedule is set; per-image timesteps run the UNet alone (agd_pag_clear first)" } },
+  { -1, 1u << CALL_PANORAMA, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    "denoise_panorama: a Perturbed-Attention Guidance schedule is set; Perturbed-Attention Guidance on a panorama is not implemented (agd_pag_clear first)" } },
+};
 // an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
 static int ip2p_check_unet(agd_ctx* c, const char* what) {
   const agd_config& g = c->cfg;
@@ -2178,10 +2206,14 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   // (a) a schedule counts once it is non-empty, all zeros too; the IP-Adapter only with rows and a non-zero scale (idle otherwise)
   bool set[N_COND_STATES];
   set[ST_CN] = !c->cn_sched.empty(); set[ST_GL] = !c->gl_sched.empty(); set[ST_INP] = c->ip_mode != 0; set[ST_I2P] = c->i2_on;
-  set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f;
-  for (const ConflictRow& r : kConflicts) {                          // (b) rows top to bottom, the first set cell wins
-    if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
-    for (int s = 0; s < N_COND_STATES; ++s) if (set[s] && r.with[s]) FAIL("%s", r.with[s]);
+  set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f; set[ST_PAG] = !c->pag_sched.empty();
+  for (const ConflictRow* t : {kConflicts, kPagConflicts}) {          // (b) rows top to bottom, the first set cell wins
+    const size_t rows = t == kConflicts ? sizeof(kConflicts) / sizeof(kConflicts[0]) : sizeof(kPagConflicts) / sizeof(kPagConflicts[0]);
+    for (size_t k = 0; k < rows; ++k) {
+      const ConflictRow& r = t[k];
+      if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
+      for (int s = 0; s < N_COND_STATES; ++s) if (set[s] && r.with[s]) FAIL("%s", r.with[s]);
+    }
   }
   // (c) the entry points that run the UNet alone have refused every state they read; the latents must be all the UNet takes
   if (who == CALL_PANORAMA && c->cfg.in_channels != c->cfg.out_channels)
@@ -2228,8 +2260,40 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
     if (c->ipa_B2 != B2) FAIL("ip_adapter: the image tokens are set for %d rows, this call runs %d (agd_ip_adapter_set)", c->ipa_B2, B2);
     out->ipa = true;
   }
+  if (set[ST_PAG]) {
+    if ((int)c->pag_sched.size() != n) FAIL("pag: the schedule has %zu scales, this call runs %d model evaluations (agd_pag_set)", c->pag_sched.size(), n);
+    out->pag = c->pag_sched.data();
+  }
   return 0;
 }
+// The perturbed walk of a Perturbed-Attention Guidance evaluation runs `rows` images against context rows [row0, row0 + rows) of what
+// agd_set_context projected -- in a loop the [cond x B] half of [uncond x B | cond x B] (PanoCtx::point's arithmetic), in agd_unet_forward_hw
+// all of it -- and records nothing.  The engine is put back as it was when the walk ends, on an error too.
+struct PagWalk {
+  struct Saved { bf16_t* kv; bf16_t* kpp; bf16_t* vpp; float* kcs; float* kbs; };
+  agd_ctx* c; int B2, mode; std::vector<Saved> saved;
+  PagWalk(agd_ctx* c_, int row0, int rows) : c(c_), B2(c_->ctx_B2), mode(c_->rec_mode) {
+    const size_t off = (size_t)row0;
+    if (off) {
+      saved.reserve(c->xl.size());
+      for (auto& xl : c->xl) {
+        saved.push_back({xl.kv, xl.pm_kpp, xl.pm_vpp, xl.pm_kcs, xl.pm_kbs});
+        xl.kv += off * c->ctx_T * 2 * xl.C;
+        if (!xl.pm_ready) continue;
+        const size_t HT = (size_t)xl.heads * XATTN_TP;
+        xl.pm_kpp += off * HT * xl.C; xl.pm_vpp += off * HT * xl.C; xl.pm_kcs += off * HT; xl.pm_kbs += off * HT;
+      }
+    }
+    c->ctx_B2 = rows; c->rec_mode = 0; c->pag_counts[0]++;
+  }
+  ~PagWalk() {
+    for (size_t k = 0; k < saved.size(); ++k) {
+      XLayer& xl = c->xl[k]; const Saved& v = saved[k];
+      xl.kv = v.kv; xl.pm_kpp = v.kpp; xl.pm_vpp = v.vpp; xl.pm_kcs = v.kcs; xl.pm_kbs = v.kbs;
+    }
+    c->ctx_B2 = B2; c->rec_mode = mode; c->cur.pag = false;
+  }
+};
 // the UNet input of one CFG evaluation: the latents (txt2img) or latents | mask | masked-image latents (9-channel inpainting), both CFG halves
 static int prep_unet_input(agd_ctx* c, hipStream_t st, const float* latents, int batch, int HW) {
   ProfScope ps(c, st, PC_ELEM, 0);
@@ -2259,7 +2323,14 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   const int Cl = c->cfg.in_channels;
   CallCond cc; API_CK(c, resolve_cond(c, CALL_UNET_FORWARD, 1, batch2, Lh, Lw, &cc));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
-  API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, cc.at(0)));
+  EvalCond ec = cc.at(0);
+  if (cc.pag && cc.pag[0] > 0.f) {                                  // every row is the perturbed branch, against the caller's context as it is; nothing is recorded
+    ec.pag = true;
+    PagWalk pw(c, 0, c->ctx_B2);
+    API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec));
+  } else {
+    API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec));
+  }
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, batch2, c->cfg.out_channels, Lh * Lw, st)); }
   return 0;
 }
@@ -2400,11 +2471,27 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   CK(ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
   CallCond cc; CK(resolve_cond(c, CALL_EVAL_LOOP, n, batch, Lh, Lw, &cc));
+  if (cc.pag) {                                                    // Perturbed-Attention Guidance: a third, B-row walk where its scale is > 0
+    CK(refuse_guidance_rescale(c, "the Perturbed-Attention Guidance denoise loop"));
+    CK(ensure_lat(c, 3 * batch, Lh, Lw));
+  }
   const float* tp_all = nullptr;                                   // all timesteps are known up front: embed them now
   CK(embed_all_timesteps(c, st, timesteps, n, &tp_all));
+  const long long ne = (long long)batch * HW * c->cfg.out_channels;   // one branch of eps
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
     CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cc.at(i)));
+    if (cc.pag && cc.pag[i] > 0.f) {
+      // e_p: the conditional rows again (a copy of their input, the conditional half of the context) with the applied layers perturbed,
+      // into eps rows [2 B, 3 B); then d = p (e_c - e_p) lands on both rows the step kernel reads
+      bf16_t* xin_p = c->lat_bf16 + (size_t)B2 * HW * 64;
+      { ProfScope ps(c, st, PC_ELEM, 0);
+        if (hipMemcpyAsync(xin_p, c->lat_bf16 + (size_t)batch * HW * 64, (size_t)batch * HW * 64 * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("pag: input copy failed"); }
+      { EvalCond ep = cc.at(i); ep.pag = true;
+        PagWalk pw(c, batch, batch);
+        CK(unet_walk(c, st, xin_p, batch, Lh, Lw, timesteps[i], c->eps_nhwc + 2 * ne, tp_all + (size_t)i * c->tproj_total, false, 0, ep)); }
+      { ProfScope ps(c, st, PC_ELEM, 0); CK(launch_pag_fold(c->eps_nhwc, ne, cc.pag[i], st)); }
+    }
     CK(step(i, c->eps_nhwc));
     if (cc.blend) CK(inpaint_blend(c, st, latents, batch, HW, cc.blend + 2 * i));
   }
@@ -4229,6 +4316,58 @@ AGD_API int agd_guidance_rescale_clear(agd_ctx* c) {
 AGD_API int agd_guidance_rescale_counts(agd_ctx* c, long long* launches) {
   if (!c || !launches) { agd_set_error("guidance_rescale_counts: null argument"); return fail_ctx(c); }
   *launches = c->gr_count;
+  return 0;
+}
+
+// ---- Perturbed-Attention Guidance (pag.hip) -------------------------------------------------------------------------------------------
+// scales: one per model evaluation of the next call(s); layers: attn1 module names in config.py's spelling (self_attn_layer_names)
+AGD_API int agd_pag_set(agd_ctx* c, const float* scales, int n, const char* const* layers, int n_layers) {
+  API_CK(c, need_final(c));
+  if (!scales || n < 1 || n_layers < 0 || (n_layers > 0 && !layers)) { agd_set_error("pag_set: %d scales, %d layers or a null argument", n, n_layers); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(scales[i]) || scales[i] < 0.f) { agd_set_error("pag_set: scale %d is %g (every scale a finite number >= 0)", i, (double)scales[i]); return fail_ctx(c); }
+  std::unordered_set<std::string> pres;
+  static const char kTail[] = "transformer_blocks.0.attn1";
+  for (int k = 0; k < n_layers; ++k) {
+    const std::string name = layers[k] ? layers[k] : "";
+    const size_t tl = sizeof(kTail) - 1;
+    bool ok = name.size() > tl && name.compare(name.size() - tl, tl, kTail) == 0;
+    std::string pre;
+    if (ok) {
+      pre = "unet." + name.substr(0, name.size() - tl);                      // "unet.mid_block.attentions.0."
+      auto it = c->xl_idx.find(pre + "transformer_blocks.0.attn2");
+      ok = it != c->xl_idx.end() && !c->xl[it->second].cn;
+    }
+    if (!ok) { agd_set_error("pag_set: '%s' is not a self-attention layer of this UNet (e.g. mid_block.attentions.0.transformer_blocks.0.attn1)", name.c_str()); return fail_ctx(c); }
+    pres.insert(pre);
+  }
+  c->pag_sched.assign(scales, scales + n); c->pag_layers.swap(pres);
+  return 0;
+}
+
+AGD_API int agd_pag_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("pag_clear: null context"); return -1; }
+  c->pag_sched.clear(); c->pag_layers.clear();
+  return 0;
+}
+
+AGD_API int agd_pag_counts(agd_ctx* c, long long* walks, long long* layers) {
+  if (!c || !walks || !layers) { agd_set_error("pag_counts: null argument"); return fail_ctx(c); }
+  *walks = c->pag_counts[0]; *layers = c->pag_counts[1];
+  return 0;
+}
+
+// The production kernels alone (the test seams), on device memory
+AGD_API int agd_op_pag_v_rows(agd_ctx* c, const void* qkv, void* att, int M, int C, void* stream) {
+  hipStream_t st = S(stream);                                       // (c may be null: it only keeps the error text)
+  API_CK(c, launch_pag_v_rows((const bf16_t*)qkv, (bf16_t*)att, M, C, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+AGD_API int agd_op_pag_fold(agd_ctx* c, float* eps, long long n, float p, void* stream) {
+  hipStream_t st = S(stream);
+  API_CK(c, launch_pag_fold(eps, n, p, st));
+  hipStreamSynchronize(st);
   return 0;
 }
 

@@ -317,6 +317,13 @@ def parse_args(argv=None):
     p.add_argument("--guidance-rescale", type=float, default=0.0, metavar="PHI",
                    help="guidance_rescale (Lin et al. 2023): after the CFG combine, rescale the prediction to the text branch's per-image "
                         "standard deviation, blended by PHI in [0, 1] (0: off; 0.7 is the paper's value); not with --panorama / --instruct-image")
+    p.add_argument("--pag-scale", type=float, default=0.0, metavar="P",
+                   help="Perturbed-Attention Guidance (Ahn et al. 2024): every evaluation runs a third UNet branch whose applied self-attention "
+                        "maps are the identity, and sampling is pushed away from it by P (0: off; 3 is the paper's value); plain txt2img only")
+    p.add_argument("--pag-adaptive-scale", type=float, default=0.0, metavar="A",
+                   help="PAG: the scale of the evaluation at timestep t is max(0, P - A (1000 - t)) (0: constant P); needs --pag-scale")
+    p.add_argument("--pag-applied-layers", type=str, default=None, nargs="+", metavar="L",
+                   help="PAG: regular expressions searched in the UNet's self-attention module names (default: mid); needs --pag-scale")
     p.add_argument("--timestep-spacing", type=str, default=None, choices=["leading", "trailing", "linspace"],
                    help="the scheduler's timestep grid (default: the checkpoint's; DDIM and img2img take all three, DPM-Solver++ its own "
                         "three, PNDM runs 'leading' only)")
@@ -328,6 +335,14 @@ def parse_args(argv=None):
         p.error(f"--guidance-rescale {args.guidance_rescale}: a number in [0, 1]")
     if args.guidance_rescale and (args.panorama or args.instruct_image):
         p.error("--guidance-rescale with --panorama or --instruct-image is not implemented")
+    if not (math.isfinite(args.pag_scale) and args.pag_scale >= 0.0 and math.isfinite(args.pag_adaptive_scale) and args.pag_adaptive_scale >= 0.0):
+        p.error(f"--pag-scale {args.pag_scale} / --pag-adaptive-scale {args.pag_adaptive_scale}: finite numbers >= 0")
+    if not args.pag_scale and (args.pag_adaptive_scale or args.pag_applied_layers is not None):
+        p.error("--pag-adaptive-scale and --pag-applied-layers need --pag-scale P with P > 0")
+    if args.pag_scale and (args.controlnet_model_path or args.adapter_model_path or args.ip_adapter_path or args.init_image or args.instruct_image
+                           or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama or args.guidance_rescale):
+        p.error("--pag-scale with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
+                "--gligen-phrases / --gligen-layouts, --panorama or --guidance-rescale is not implemented")
     if args.scheduler == "PNDMScheduler" and args.timestep_spacing not in (None, "leading"):
         p.error(f"--timestep-spacing {args.timestep_spacing}: PNDMScheduler runs 'leading' only")
     if args.rescale_betas_zero_snr and args.scheduler in ("PNDMScheduler", "DPMSolverMultistepScheduler"):
@@ -584,6 +599,8 @@ def main(argv=None):
         pipe.fuse_lora(lora_scale=args.lora_scale)
     if args.freeu is not None:
         pipe.enable_freeu(*args.freeu)
+    if args.pag_applied_layers is not None:
+        pipe.set_pag_applied_layers(args.pag_applied_layers)
     ipa_files = None
     if args.ip_adapter_path:
         pipe.load_ip_adapter(args.ip_adapter_path, image_encoder_folder=args.image_encoder_path or "image_encoder")
@@ -634,6 +651,8 @@ def main(argv=None):
                 height, width = control.pop("height"), control.pop("width")          # the image's size is the call's
             if args.guidance_rescale:
                 control = dict(control or {}, guidance_rescale=args.guidance_rescale)
+            if args.pag_scale:
+                control = dict(control or {}, pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale)
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
                                        height=height, width=width)
         if not gather:

@@ -321,3 +321,28 @@ def guidance_rescale(eps, channels, guidance, phi):
     _lib.check(lib.agd_op_guidance_rescale(None, _lib.ptr(eps), ldc, B2 // 2, int(channels), HW, float(guidance), float(phi), _lib.ptr(out),
                                            _lib.current_stream_ptr()), None, "agd_op_guidance_rescale")
     return out
+
+
+def pag_v_rows(qkv):
+    """The "attention" of a perturbed self-attention layer, the production kernel: qkv bf16 [M, 3C] (the fused q | k | v rows) -> bf16 [M, C],
+    the value third of every row, bit for bit.  C % 8 != 0 is refused."""
+    lib = _lib.load()
+    assert qkv.is_cuda and qkv.dtype == torch.bfloat16, "ops run on the GPU only (no CPU fallback); pag_v_rows takes bf16 rows"
+    qkv = qkv.detach().contiguous()
+    if qkv.ndim != 2 or qkv.shape[1] % 3:
+        raise ValueError(f"pag_v_rows: qkv {tuple(qkv.shape)} must be [M, 3C]")
+    M, C = qkv.shape[0], qkv.shape[1] // 3
+    out = torch.empty(M, C, dtype=torch.bfloat16, device=qkv.device)
+    _lib.check(lib.agd_op_pag_v_rows(None, _lib.ptr(qkv), _lib.ptr(out), M, C, _lib.current_stream_ptr()), None, "agd_op_pag_v_rows")
+    return out
+
+
+def pag_fold(eps, p):
+    """The Perturbed-Attention Guidance fold, the production kernel: eps fp32 [3, n] (uncond | cond | perturbed) -> a folded copy whose rows
+    0 and 1 are e_u + d and e_c + d with d = p (e_c - e_p); row 2 is unchanged."""
+    lib = _lib.load()
+    eps = _f32c(eps).clone()
+    if eps.ndim != 2 or eps.shape[0] != 3:
+        raise ValueError(f"pag_fold: eps {tuple(eps.shape)} must be [3, n]")
+    _lib.check(lib.agd_op_pag_fold(None, _lib.ptr(eps), eps.shape[1], float(p), _lib.current_stream_ptr()), None, "agd_op_pag_fold")
+    return eps

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from .pipeline import PipelineOutput, StableDiffusionPipeline
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_pag
 from .scheduler import DDIMScheduler
 
 STRIDE = 8            # latent pixels between views (diffusers get_views default)
@@ -75,7 +75,8 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
                  circular_padding: bool = False, negative_prompt=None, num_images_per_prompt: int = 1,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
-                 guidance_rescale: float = 0.0):
+                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+        refuse_pag("StableDiffusionPanoramaPipeline", pag_scale, pag_adaptive_scale)
         if guidance_rescale:
             raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale is not implemented for the panorama pipeline "
                              "(its views are stepped one by one); leave it 0")

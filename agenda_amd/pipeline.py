@@ -64,6 +64,28 @@ def check_guidance_rescale(guidance_rescale: float) -> None:
         raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale takes a number in [0, 1]")
 
 
+def check_pag(pag_scale: float, pag_adaptive_scale: float = 0.0, guidance_rescale: float = 0.0) -> None:
+    """`pag_scale` / `pag_adaptive_scale`: finite numbers >= 0, the adaptive scale only beside a pag_scale > 0, and no guidance rescale with
+    them (diffusers rescales against the text branch, which the fold has overwritten).  Refused here, before a call does any device work."""
+    p, a = float(pag_scale), float(pag_adaptive_scale)
+    if not (math.isfinite(p) and p >= 0.0):
+        raise ValueError(f"pag_scale={pag_scale!r}: Perturbed-Attention Guidance takes a finite scale >= 0")
+    if not (math.isfinite(a) and a >= 0.0):
+        raise ValueError(f"pag_adaptive_scale={pag_adaptive_scale!r}: Perturbed-Attention Guidance takes a finite adaptive scale >= 0")
+    if a > 0.0 and not p > 0.0:
+        raise ValueError(f"pag_adaptive_scale={pag_adaptive_scale!r} needs pag_scale > 0 (got pag_scale={pag_scale!r})")
+    if p > 0.0 and guidance_rescale:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} with pag_scale={pag_scale!r}: guidance rescale beside Perturbed-Attention "
+                         "Guidance is not implemented (the text branch it rescales to is folded away); leave one of them 0")
+
+
+def refuse_pag(pipeline: str, pag_scale: float, pag_adaptive_scale: float = 0.0) -> None:
+    """The pipelines that run beside something the perturbed branch does not carry refuse a non-zero scale by name."""
+    if pag_scale or pag_adaptive_scale:
+        raise ValueError(f"pag_scale={pag_scale!r}, pag_adaptive_scale={pag_adaptive_scale!r}: Perturbed-Attention Guidance is not implemented "
+                         f"for {pipeline} (StableDiffusionPipeline's txt2img and img2img run it); leave both 0")
+
+
 def check_image_size(height: int, width: int, multiple: int = 64) -> None:
     """The pipelines' size rule: each side a positive multiple of 64, applied per axis (height and width may differ)."""
     if not all(isinstance(v, int) and v > 0 and v % multiple == 0 for v in (height, width)):
@@ -419,6 +441,23 @@ class Engine:
         n = C.c_longlong(0)
         self._ck(self.lib.agd_guidance_rescale_counts(self.ctx, C.byref(n)), "agd_guidance_rescale_counts")
         return int(n.value)
+
+    def pag_set(self, scales, layers):
+        """`agd_pag_set`: Perturbed-Attention Guidance for the calls to come, until pag_clear -- one scale >= 0 per model evaluation, and
+        the applied self-attention layers as attn1 module names (`config.self_attn_layer_names`; [] perturbs nothing)."""
+        sc = _floats(scales)
+        names = [str(n).encode() for n in layers]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        self._ck(self.lib.agd_pag_set(self.ctx, sc, len(scales), arr, len(names)), "agd_pag_set")
+
+    def pag_clear(self):
+        self._ck(self.lib.agd_pag_clear(self.ctx), "agd_pag_clear")
+
+    def pag_counts(self) -> Tuple[int, int]:
+        """`agd_pag_counts`: (perturbed walks run, perturbed self-attention layers launched) since the engine was created."""
+        w, l = C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.lib.agd_pag_counts(self.ctx, C.byref(w), C.byref(l)), "agd_pag_counts")
+        return int(w.value), int(l.value)
 
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
         self._glcfg = _lib.AgdGligenConfig()
@@ -858,8 +897,9 @@ class StableDiffusionPipeline:
     def __init__(self, cfg: SDConfig, unet_sd: Dict[str, torch.Tensor], vae_sd: Dict[str, torch.Tensor],
                  tokenizer=None, text_encoder=None, device: Union[int, str] = 0, workspace_bytes: int = 0,
                  text_sd: Optional[Dict[str, torch.Tensor]] = None, scheduler: str = "DDIMScheduler",
-                 safety_sd: Optional[Dict[str, torch.Tensor]] = None):
+                 safety_sd: Optional[Dict[str, torch.Tensor]] = None, pag_applied_layers: Union[str, Sequence[str]] = ("mid",)):
         self.cfg = cfg
+        self.set_pag_applied_layers(pag_applied_layers)     # (refuses a string that matches no layer before anything is loaded)
         dev = int(str(device).split(":")[-1]) if not isinstance(device, int) and ":" in str(device) else (device if isinstance(device, int) else 0)
         self.engine = Engine(cfg, dev, workspace_bytes)
         if not self._gligen:      # a GLIGEN (gated) UNet under the plain pipeline: diffusers never runs its fusers, so they are not loaded
@@ -914,12 +954,13 @@ class StableDiffusionPipeline:
     # ---- construction -------------------------------------------------------------------
     @classmethod
     def from_synthetic(cls, cfg: Union[str, SDConfig] = "sd15", seed: int = 1234, device=0, workspace_bytes: int = 0,
-                       weights_device: str = "cpu", keep_weights: bool = False, scheduler: str = "DDIMScheduler", **kw):
+                       weights_device: str = "cpu", keep_weights: bool = False, scheduler: str = "DDIMScheduler",
+                       pag_applied_layers: Union[str, Sequence[str]] = ("mid",), **kw):
         from . import synthetic
         cfg = CONFIGS[cfg]() if isinstance(cfg, str) else cfg
         usd = synthetic.make_unet_weights(cfg, seed, device=weights_device, **kw)
         vsd = synthetic.make_vae_weights(cfg, seed + 1, device=weights_device, **kw)
-        pipe = cls(cfg, usd, vsd, device=device, workspace_bytes=workspace_bytes, scheduler=scheduler)
+        pipe = cls(cfg, usd, vsd, device=device, workspace_bytes=workspace_bytes, scheduler=scheduler, pag_applied_layers=pag_applied_layers)
         if keep_weights:
             pipe.synthetic_weights = (usd, vsd)
         return pipe
@@ -1247,6 +1288,16 @@ class StableDiffusionPipeline:
         """The plain UNet again, launch for launch: results are bit-identical to a pipeline that never enabled FreeU."""
         self.unet.disable_freeu()
 
+    def set_pag_applied_layers(self, layers: Union[str, Sequence[str]]):
+        """diffusers' `pag_applied_layers` (the constructor / from_pretrained keyword of StableDiffusionPAGPipeline, default ["mid"]): every
+        string is `re.search`ed against the UNet's self-attention module names (`config.self_attn_layer_names`); the layers they match are
+        the ones the perturbed branch of a call with pag_scale > 0 runs with an identity attention map.  A string that matches none is a
+        ValueError naming it."""
+        from .config import resolve_pag_layers
+        pats = [layers] if isinstance(layers, str) else list(layers)
+        self._pag_layers = resolve_pag_layers(self.cfg, pats)
+        self.pag_applied_layers = pats
+
     def set_progress_bar_config(self, **kw):
         self._progress = kw
 
@@ -1322,9 +1373,10 @@ class StableDiffusionPipeline:
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
                  cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                 guidance_rescale: float = 0.0):
+                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
+        check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
@@ -1337,7 +1389,7 @@ class StableDiffusionPipeline:
         self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
         self._begin_recording(prompt_embeds, B, L)
-        with self._guidance_rescaled(guidance_rescale):
+        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, self.scheduler, num_inference_steps):
             self._denoise(lat, num_inference_steps, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
@@ -1370,6 +1422,23 @@ class StableDiffusionPipeline:
             yield
         finally:
             self.engine.guidance_rescale_clear()
+
+    @contextlib.contextmanager
+    def _pag(self, pag_scale: float, pag_adaptive_scale: float, scheduler, num_inference_steps: int, strength: float = 1.0):
+        """Perturbed-Attention Guidance (Ahn et al. 2024; diffusers >= 0.30 StableDiffusionPAGPipeline) around one call's denoise loop: the
+        scale of every model evaluation (`config.pag_schedule` over `inpaint.evaluation_timesteps`) and the applied layers are set for the
+        loop and cleared when it ends, on an error too, so the next call without the argument is the plain one.  0 sets nothing."""
+        if not pag_scale:
+            yield
+            return
+        from .config import pag_schedule
+        from .inpaint import evaluation_timesteps
+        sched = pag_schedule(evaluation_timesteps(scheduler, num_inference_steps, strength), pag_scale, pag_adaptive_scale)
+        self.engine.pag_set(sched, self._pag_layers)
+        try:
+            yield
+        finally:
+            self.engine.pag_clear()
 
     def _denoise(self, lat, num_inference_steps, guidance_scale):
         """`for t in scheduler.timesteps: unet -> CFG -> scheduler.step`, fused on the device, under the pipeline's scheduler."""
@@ -1407,7 +1476,7 @@ class StableDiffusionPipeline:
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                guidance_rescale: float = 0.0):
+                guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
         """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
@@ -1415,6 +1484,7 @@ class StableDiffusionPipeline:
         # PLMS and DPM-Solver++ img2img are not implemented)
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
+        check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
         self._apply_lora_scale(cross_attention_kwargs)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
@@ -1444,7 +1514,7 @@ class StableDiffusionPipeline:
         a = float(sched.alphas_cumprod[int(ts[0])])
         lat = (a ** 0.5 * x0 + (1 - a) ** 0.5 * noise.to(mean.device)).contiguous()
         self._begin_recording(prompt_embeds, B, L)
-        with self._guidance_rescaled(guidance_rescale):
+        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, sched, num_inference_steps, strength):
             self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)

@@ -568,6 +568,31 @@ int agd_guidance_rescale_clear(agd_ctx* ctx);
 int agd_guidance_rescale_counts(agd_ctx* ctx, long long* launches);
 int agd_op_guidance_rescale(agd_ctx* ctx, const float* eps, int ldc, int B, int C, int HW, float guidance, float phi, float* factor, void* stream);
 
+/* ---- Perturbed-Attention Guidance (Ahn et al. 2024, "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance"; diffusers >= 0.30
+ * StableDiffusionPAGPipeline [upstream-knowledge]; csrc/pag.hip).  Where its scale p_i is > 0, model evaluation i runs a third UNet branch on
+ * the conditional rows (same latents, timestep and text context) in which every applied self-attention layer computes to_out(to_v(norm1(h)))
+ * -- the attention map replaced by the identity -- and the step sees
+ *   eps = e_u + s (e_c - e_u) + p_i (e_c - e_p).
+ * The branch is one extra B-row walk; it records nothing (the DAAM / hook.py recorders see the main walk's conditional half as without PAG)
+ * and takes its K/V from the conditional half of what agd_set_context projected.  q and k of a perturbed layer are still computed and ignored.
+ * agd_pag_set: context state after agd_finalize, until cleared.  scales: one finite p_i >= 0 per model evaluation of the calls to come
+ *   (agd_denoise*, agd_denoise_plms*, agd_denoise_dpm* check n against their evaluations; an evaluation with p_i == 0 is the plain one, launch
+ *   for launch).  layers: n_layers attn1 module names ("mid_block.attentions.0.transformer_blocks.0.attn1"); a name that is no self-attention
+ *   layer of this UNet is refused by name; n_layers == 0 perturbs nothing (the third walk still runs).  With the state set,
+ *   agd_unet_forward_hw under a schedule of length 1 with p_0 > 0 runs ALL its rows as the perturbed branch against the context as it is,
+ *   recording nothing.  Refused by name before the first launch: a ControlNet, GLIGEN or T2I-Adapter schedule, an active IP-Adapter, either
+ *   inpainting state, an InstructPix2Pix state, agd_denoise_panorama, agd_unet_forward_ts*, and a set guidance rescale.
+ * agd_pag_clear: the plain loops again, launch for launch (bit-identical results).
+ * agd_pag_counts (seam for tests): perturbed walks run, and perturbed self-attention layers launched, since agd_create.
+ * agd_op_pag_v_rows (seam for tests): att[m][0:C] = qkv[m][2C:3C] on device bf16 memory, rows of 3 C -> rows of C; C % 8 != 0 is refused.
+ * agd_op_pag_fold (seam for tests): eps fp32 [3][n] on the device (uncond | cond | perturbed), in place: d = p (e_c - e_p) with the product
+ *   rounded on its own, e_u += d, e_c += d.  For both seams ctx may be NULL (it only keeps the error text). */
+int agd_pag_set(agd_ctx* ctx, const float* scales, int n, const char* const* layers, int n_layers);
+int agd_pag_clear(agd_ctx* ctx);
+int agd_pag_counts(agd_ctx* ctx, long long* walks, long long* layers);
+int agd_op_pag_v_rows(agd_ctx* ctx, const void* qkv, void* att, int M, int C, void* stream);
+int agd_op_pag_fold(agd_ctx* ctx, float* eps, long long n, float p, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
