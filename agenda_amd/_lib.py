@@ -180,8 +180,11 @@ _SIGS = {
     "agd_op_conv2d_ex": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 10 + [_P]),
     "agd_op_linear": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "agd_op_groupnorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "agd_op_groupnorm_ex": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [C.c_float, C.c_int, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), _P]),
+    "agd_op_gn_fold": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.c_float] + [_P] * 4 + [C.c_int, C.c_int] + [_P] * 5 + [_P]),
     "agd_op_conv_groupnorm": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, _P]),
     "agd_op_layernorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "agd_op_layernorm_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), _P]),
     "agd_op_ff_fused": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_float, _P]),
     "agd_op_attn_chain": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, _P]),
     "agd_op_xattn_premul": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, _P]),

@@ -192,14 +192,18 @@ struct GroupNormP {
   // per-channel partial sums emitted by the igemm launches that produced x0 / x1 ([HW*B / bm tiles][Cs] float2, bm rows per
   // tile): when given for every source, the statistics pass over the activation is skipped (one kernel instead of two)
   const float* part0; const float* part1; int bm0, bm1;
+  int* path;                                         // tests (may be null): *path = 1 when the partial-sum kernel ran, 2 for the two-kernel path, 0 when refused
 };
+int groupnorm_check(int B, int C0, int C1, int HW, int groups);   // 0, or -1 with the error set: the shapes every GroupNorm form supports
+int layernorm_check(int rows, int C);
 int launch_groupnorm(const GroupNormP& p, hipStream_t st);
 // GroupNorm (no activation) folded into the 1x1 projection that follows it: per image, Wb = W . diag(rstd_g gamma) (bf16) and
 // rowadd = bias + W beta - Wb mu (fp32), statistics from the producer's per-(tile, channel) partial sums [HW / bm tiles][C] float2
 int launch_gn_fold_weight(const float* part, int bm, int B, int HW, int C, int groups, float eps, const float* gamma, const float* beta,
                           const bf16_t* W, const float* bias, int N, bf16_t* Wb, float* rowadd, hipStream_t st, int frag_ni = 0);   // frag_ni > 0: Wb in MFMA fragment order (tblock.hip)
 long long groupnorm_ws_floats(int B, int C, int HW, int groups);   // workspace floats a launch_groupnorm call needs
-int launch_layernorm(const bf16_t* x, bf16_t* y, const float* g, const float* b, int rows, int C, float eps, hipStream_t st);
+int launch_layernorm(const bf16_t* x, bf16_t* y, const float* g, const float* b, int rows, int C, float eps, hipStream_t st,
+                     int* inst = nullptr);   // tests: *inst = 100 * LPR + MAXV of the layernorm_kernel<LPR, MAXV> that ran
 
 // ---------------------------------------------------------------------------------------
 // Misc elementwise / layout kernels

@@ -415,6 +415,7 @@ static int run_gn(agd_ctx* c, hipStream_t st, const bf16_t* x0, int C0, const bf
     g.part0 = a0->cpart; g.bm0 = a0->cpart_bm;
     if (x1) { g.part1 = a1->cpart; g.bm1 = a1->cpart_bm; }
   }
+  if (groupnorm_check(B, C0, C1, HW, groups)) return -1;                 // before the workspace geometry divides by C / 8
   const long long wsf = groupnorm_ws_floats(B, C0 + C1, HW, groups);
   const size_t mk = c->arena.mark();
   g.ws = (float*)c->arena.alloc((size_t)wsf * 4);
@@ -3141,17 +3142,71 @@ AGD_API int agd_op_linear(const float* x, const float* w, const float* bias, con
   return 0;
 }
 
-AGD_API int agd_op_groupnorm(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int HW, int groups,
-                                float eps, int silu, void* stream) {
+// GroupNorm(+SiLU) reaching every form of launch_groupnorm: one source or the channel concat x0 | x1 (x1 null with C1 = 0), and optional
+// host-supplied partial-sum tables in the layout igemm's colstat_out leaves ([(b * HW / bm + tile) * Cs + ch] * 2 floats: sum and sum of
+// squares of the source's bf16 values over the tile's bm pixels).  *path (may be null): 1 the partial-sum kernel ran, 2 the two-kernel path.
+AGD_API int agd_op_groupnorm_ex(const float* x0, const float* x1, const float* gamma, const float* beta, float* y, int B, int C0, int C1, int HW,
+                                int groups, float eps, int silu, const float* part0, int bm0, const float* part1, int bm1, int* path, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;
-  bf16_t* xb = tmp.get<bf16_t>((size_t)B * HW * C); bf16_t* yb = tmp.get<bf16_t>((size_t)B * HW * C);
-  float* ws = tmp.get<float>((size_t)groupnorm_ws_floats(B, C, HW, groups)); float* yf = tmp.get<float>((size_t)B * HW * C);
-  if (!xb || !yb || !ws || !yf) return -1;
-  CK(to_nhwc_bf16(x, xb, B, C, HW, C, st));
-  GroupNormP g{}; g.x0 = xb; g.C0 = C; g.y = yb; g.gamma = gamma; g.beta = beta; g.B = B; g.HW = HW; g.groups = groups; g.eps = eps; g.silu = silu; g.ws = ws;
+  if (path) *path = 0;
+  if (groupnorm_check(B, C0, C1, HW, groups)) return -1;
+  if (!x0 || !gamma || !beta || !y || (C1 > 0) != (x1 != nullptr)) { agd_set_error("op_groupnorm: null operand, or x1 and C1 = %d disagree", C1); return -1; }
+  const int C = C0 + C1;
+  const long long wsf = groupnorm_ws_floats(B, C, HW, groups);
+  if (wsf < 0) return -1;
+  bf16_t* xb0 = tmp.get<bf16_t>((size_t)B * HW * C0); bf16_t* xb1 = C1 ? tmp.get<bf16_t>((size_t)B * HW * C1) : nullptr;
+  bf16_t* yb = tmp.get<bf16_t>((size_t)B * HW * C);
+  float* ws = tmp.get<float>((size_t)wsf); float* yf = tmp.get<float>((size_t)B * HW * C);
+  if (!xb0 || (C1 && !xb1) || !yb || !ws || !yf) return -1;
+  CK(to_nhwc_bf16(x0, xb0, B, C0, HW, C0, st));
+  if (C1) CK(to_nhwc_bf16(x1, xb1, B, C1, HW, C1, st));
+  GroupNormP g{}; g.x0 = xb0; g.x1 = xb1; g.C0 = C0; g.C1 = C1; g.y = yb; g.gamma = gamma; g.beta = beta; g.B = B; g.HW = HW; g.groups = groups; g.eps = eps; g.silu = silu; g.ws = ws;
+  g.part0 = part0; g.bm0 = bm0; g.part1 = part1; g.bm1 = bm1; g.path = path;
   CK(launch_groupnorm(g, st));
   CK(launch_bf16_to_f32(yb, yf, (long long)B * HW * C, st));
   CK(launch_nchw_from_nhwc_f32(yf, C, y, B, C, HW, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+AGD_API int agd_op_groupnorm(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int HW, int groups,
+                                float eps, int silu, void* stream) {
+  return agd_op_groupnorm_ex(x, nullptr, gamma, beta, y, B, C, 0, HW, groups, eps, silu, nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+// GroupNorm folded into the projection behind it (launch_gn_fold_weight), piece by piece: the statistics come from the partial-sum table
+// `part` (layout as in agd_op_groupnorm_ex, bm pixels per tile).  wb [B][N][C] and rowadd [B][N]: the row-major fold; with frag_ni > 0 also
+// wb_frag = the kernel's fragment-ordered Wb and wb_frag_ref = launch_frag_order_w (NI = frag_ni, KC = C) of each image's row-major Wb, both
+// [B][N * C] in storage order; y (may be null, then x may be) [B * HW][N]: the raw activation x (NCHW, rounded to bf16) through the per-image
+// matrices plus rowadd, as the transformer's proj_in runs it.  Everything fp32 (bf16 values widened exactly).
+AGD_API int agd_op_gn_fold(const float* x, const float* part, int bm, int B, int C, int HW, int groups, float eps, const float* gamma, const float* beta,
+                           const float* w, const float* bias, int N, int frag_ni, float* wb, float* rowadd, float* wb_frag, float* wb_frag_ref,
+                           float* y, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (groupnorm_check(B, C, 0, HW, groups)) return -1;
+  if (N < 1 || N > 65536 || !part || !gamma || !beta || !w || !wb || !rowadd || (frag_ni > 0 && (!wb_frag || !wb_frag_ref)) || (y && !x)) { agd_set_error("op_gn_fold: bad arguments (N %d)", N); return -1; }
+  if (y && (C % 64 || HW % 64)) { agd_set_error("op_gn_fold: the projection needs C %% 64 == 0 and HW %% 64 == 0 (C %d HW %d)", C, HW); return -1; }
+  const size_t nw = (size_t)B * N * C;
+  bf16_t* w16 = tmp.get<bf16_t>((size_t)N * C); bf16_t* wbb = tmp.get<bf16_t>(nw); float* radd = tmp.get<float>((size_t)B * N);
+  if (!w16 || !wbb || !radd) return -1;
+  CK(launch_convert_weight(w, w16, N, C, 1, C, 0, st));
+  CK(launch_gn_fold_weight(part, bm, B, HW, C, groups, eps, gamma, beta, w16, bias, N, wbb, radd, st, 0));
+  CK(launch_bf16_to_f32(wbb, wb, (long long)nw, st));
+  if (hipMemcpyAsync(rowadd, radd, (size_t)B * N * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("op_gn_fold: rowadd copy"); return -1; }
+  if (frag_ni > 0) {
+    bf16_t* wf = tmp.get<bf16_t>(nw); bf16_t* wr = tmp.get<bf16_t>(nw); float* radd2 = tmp.get<float>((size_t)B * N);
+    if (!wf || !wr || !radd2) return -1;
+    CK(launch_gn_fold_weight(part, bm, B, HW, C, groups, eps, gamma, beta, w16, bias, N, wf, radd2, st, frag_ni));
+    for (int b = 0; b < B; ++b) CK(launch_frag_order_w(wbb + (size_t)b * N * C, wr + (size_t)b * N * C, N, C, frag_ni, C, st));
+    CK(launch_bf16_to_f32(wf, wb_frag, (long long)nw, st));
+    CK(launch_bf16_to_f32(wr, wb_frag_ref, (long long)nw, st));
+  }
+  if (y) {
+    bf16_t* xb = tmp.get<bf16_t>((size_t)B * HW * C); if (!xb) return -1;
+    CK(to_nhwc_bf16(x, xb, B, C, HW, C, st));
+    WMat wi; wi.w = wbb; wi.N = N; wi.Cin = C; wi.Cpad = C; wi.taps = 1;
+    GemmOpt o; o.rowadd = radd; o.rowadd_ld = N; o.w_per_image = 1; o.out_f32 = 1;
+    CK(run_conv(nullptr, st, xb, C, nullptr, 0, B, 1, HW, wi, 1, y, o, op_zero_page()));
+  }
   hipStreamSynchronize(st);
   return 0;
 }
@@ -3162,6 +3217,8 @@ AGD_API int agd_op_groupnorm(const float* x, const float* gamma, const float* be
 AGD_API int agd_op_conv_groupnorm(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, float* y, int B,
                                   int Cin, int H, int W, int Cout, int groups, float eps, int silu, int fused, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;
+  if (Cin < 1 || H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) { agd_set_error("op_conv_groupnorm: bad shape Cin=%d H=%d W=%d", Cin, H, W); return -1; }
+  if (groupnorm_check(B, Cout, 0, H * W, groups)) return -1;
   const int Cpad = (Cin + 63) / 64 * 64, HW = H * W;
   bf16_t* xb = tmp.get<bf16_t>((size_t)B * HW * Cpad); bf16_t* wb = tmp.get<bf16_t>((size_t)Cout * 9 * Cpad);
   bf16_t* hb = tmp.get<bf16_t>((size_t)B * HW * Cout); bf16_t* yb = tmp.get<bf16_t>((size_t)B * HW * Cout);
@@ -3193,15 +3250,21 @@ AGD_API int agd_op_conv_groupnorm(const float* x, const float* w, const float* b
   return 0;
 }
 
-AGD_API int agd_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, void* stream) {
+// *inst (may be null): which layernorm_kernel<LPR, MAXV> ran, as 100 * LPR + MAXV (6404, 1605 or 1610)
+AGD_API int agd_op_layernorm_ex(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, int* inst, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;
+  if (inst) *inst = 0;
+  if (layernorm_check(rows, C)) return -1;
   bf16_t* xb = tmp.get<bf16_t>((size_t)rows * C); bf16_t* yb = tmp.get<bf16_t>((size_t)rows * C);
   if (!xb || !yb) return -1;
   CK(launch_f32_to_bf16(x, xb, (long long)rows * C, st));
-  CK(launch_layernorm(xb, yb, gamma, beta, rows, C, eps, st));
+  CK(launch_layernorm(xb, yb, gamma, beta, rows, C, eps, st, inst));
   CK(launch_bf16_to_f32(yb, y, (long long)rows * C, st));
   hipStreamSynchronize(st);
   return 0;
+}
+AGD_API int agd_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, void* stream) {
+  return agd_op_layernorm_ex(x, gamma, beta, y, rows, C, eps, nullptr, stream);
 }
 
 // y = x + ff.net.2(GEGLU(ff.net.0(LayerNorm(x)))) through the fused row-panel kernel (tblock.hip); w1 [8C][C] (values then gates),
@@ -3693,6 +3756,7 @@ AGD_API int agd_bench_groupnorm_ex(int B, int HW, int C0, int C1, int fused_stat
   Tmp tmp;
   const int C = C0 + C1;
   if (B < 1 || HW < 1 || C0 < 8 || C1 < 0 || iters < 1 || !ms_out) { agd_set_error("bench_groupnorm: bad arguments"); return -1; }
+  if (groupnorm_check(B, C0, C1, HW, 32)) return -1;
   bf16_t* x0 = tmp.get<bf16_t>((size_t)B * HW * C0); bf16_t* x1 = C1 ? tmp.get<bf16_t>((size_t)B * HW * C1) : nullptr;
   bf16_t* y = tmp.get<bf16_t>((size_t)B * HW * C);
   float* ws = tmp.get<float>((size_t)groupnorm_ws_floats(B, C, HW, 32)); float* g = tmp.get<float>(2 * C);

@@ -11,6 +11,15 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // Thread t owns channel vector (t % nvec) and pixel-row (t / nvec) of its block's pixel chunk, so no
 // index division happens inside the streaming loops.
 struct GnGeom { int nvec, PR, ppb, nchunk; };
+// what every GroupNorm form supports; checked before any geometry is derived from the arguments (gn_geom divides by C / 8, the launcher by groups)
+int groupnorm_check(int B, int C0, int C1, int HW, int groups) {
+  const long long C = (long long)C0 + C1;
+  if (B < 1 || HW < 1 || C0 < 8 || C1 < 0 || C > 4096 || C % 8 || C0 % 8 || groups < 1 || groups > 64 || C % groups) {
+    agd_set_error("groupnorm: unsupported B=%d HW=%d C0=%d C1=%d groups=%d (C0 + C1 in 8 .. 4096, C0 and C1 multiples of 8, 1 <= groups <= 64 dividing C0 + C1)", B, HW, C0, C1, groups);
+    return -1;
+  }
+  return 0;
+}
 static GnGeom gn_geom(int B, int C, int HW) {
   GnGeom g; g.nvec = C / 8; g.PR = 512 / g.nvec;
   constexpr int nblk = 256;   // one 512-thread block per CU measured best (kbench gn: 0.96 -> 0.88 ms per forward vs 512; 128 / 64: +10 / +21 %)
@@ -254,12 +263,11 @@ static bool gn_part_ok(const GroupNormP& p) {
 }
 
 int launch_groupnorm(const GroupNormP& p, hipStream_t st) {
+  if (p.path) *p.path = 0;
+  if (groupnorm_check(p.B, p.C0, p.C1, p.HW, p.groups)) return -1;
   const int C = p.C0 + p.C1;
-  const int nvec = C / 8;
-  if (C % 8 || p.C0 % 8 || nvec > 512 || C % p.groups || p.groups > 64) {
-    agd_set_error("groupnorm: unsupported C0=%d C1=%d groups=%d", p.C0, p.C1, p.groups); return -1;
-  }
   if (gn_part_ok(p)) {
+    if (p.path) *p.path = 1;
     const int nvs = C / GN_SLICES / 8, PR = 512 / nvs;
     // pixel chunks per channel slice: ~128 for the 64x64 maps (UNet batch 8), ~64 below (tools/kb_gn.py: 256 -> 128: 16.9 -> 15.4 us at 64x64
     // C = 320, 64: 10.6 -> 9.4 at 32x32 C = 640, 8.4 -> 6.9 at 16x16 C = 1280; 32 and 512 are 20-50 % slower): every block pays the
@@ -273,6 +281,7 @@ int launch_groupnorm(const GroupNormP& p, hipStream_t st) {
     HIP_CHECK_RET(hipGetLastError());
     return 0;
   }
+  if (p.path) *p.path = 2;
   const GnGeom g = gn_geom(p.B, C, p.HW);
   float* part = p.ws;
   const int lds = 2 * g.PR * C * 4;
@@ -283,8 +292,9 @@ int launch_groupnorm(const GroupNormP& p, hipStream_t st) {
   return 0;
 }
 
-// required workspace floats for a groupnorm call (host helper)
+// required workspace floats for a groupnorm call (host helper); -1 (and the error set) for a problem launch_groupnorm refuses
 long long groupnorm_ws_floats(int B, int C, int HW, int groups) {
+  if (groupnorm_check(B, C, 0, HW, groups)) return -1;
   const GnGeom g = gn_geom(B, C, HW);
   return (long long)B * g.nchunk * groups * 2 + 2LL * B * C;
 }
@@ -344,13 +354,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
   }
 }
 
-int launch_layernorm(const bf16_t* x, bf16_t* y, const float* g, const float* b, int rows, int C, float eps, hipStream_t st) {
-  if (C % 8 || C > 2048) { agd_set_error("layernorm: unsupported C=%d", C); return -1; }
+int layernorm_check(int rows, int C) {
+  if (rows < 1 || C < 8 || C % 8 || C > 2048) { agd_set_error("layernorm: unsupported rows=%d C=%d", rows, C); return -1; }
+  return 0;
+}
+int launch_layernorm(const bf16_t* x, bf16_t* y, const float* g, const float* b, int rows, int C, float eps, hipStream_t st, int* inst) {
+  if (inst) *inst = 0;
+  if (layernorm_check(rows, C)) return -1;
   // few rows (16x16 / 8x8 feature maps): one wave per row so the grid still covers the 256 CUs
   const bool few = rows < 16 * 512;
   if (few || C > 1280) hipLaunchKernelGGL((layernorm_kernel<64, 4>), dim3((rows + 3) / 4), dim3(256), 0, st, x, y, g, b, rows, C, eps);
   else if (C <= 640) hipLaunchKernelGGL((layernorm_kernel<16, 5>), dim3((rows + 15) / 16), dim3(256), 0, st, x, y, g, b, rows, C, eps);
   else hipLaunchKernelGGL((layernorm_kernel<16, 10>), dim3((rows + 15) / 16), dim3(256), 0, st, x, y, g, b, rows, C, eps);
+  if (inst) *inst = (few || C > 1280) ? 6404 : C <= 640 ? 1605 : 1610;
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

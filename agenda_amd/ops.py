@@ -3,6 +3,8 @@ torch.nn.functional calls that diffusers makes on the reference path so each HIP
 parity-tested in isolation through the C ABI (`agd_op_*` in include/agenda_hip.h)."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -47,23 +49,79 @@ def linear(x, w, bias=None, residual=None, geglu=False, p8=0, wreg=False, kgroup
     return y.reshape(*x.shape[:-1], Nout)
 
 
-def group_norm(x, groups, gamma, beta, eps=1e-5, silu=False):
+GN_PATH_PARTIAL, GN_PATH_TWO_KERNEL = 1, 2      # what return_path reports: the partial-sum kernel, or statistics kernel + apply kernel
+
+
+def group_norm(x, groups, gamma, beta, eps=1e-5, silu=False, *, x1=None, part=None, bm=None, part1=None, bm1=None, return_path=False):
+    """GroupNorm(+SiLU) of x [B, C0, ...], or of the channel concat x | x1.  part / bm (and part1 / bm1 for x1): partial-sum tables made by
+    the caller, [B, HW / bm, Cs, 2] fp32 = (sum, sum of squares) of the source's bf16 values per tile of bm pixels -- what the producing GEMM
+    leaves in production; given for every source and on a supported shape, the one-kernel form runs.  return_path: also which form ran."""
     lib = _lib.load()
     x = _f32c(x)
-    B, Cc = x.shape[:2]
+    B, C0 = x.shape[:2]
     HW = x[0, 0].numel()
-    y = torch.empty_like(x)
-    _lib.check(lib.agd_op_groupnorm(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), B, Cc, HW,
-                                    groups, float(eps), int(silu), _lib.current_stream_ptr()), None, "agd_op_groupnorm")
-    return y
+    C1 = 0
+    if x1 is not None:
+        x1 = _f32c(x1)
+        assert x1.shape[0] == B and x1.shape[2:] == x.shape[2:], "x1 must share x's batch and map"
+        C1 = x1.shape[1]
+    if part is None and part1 is None and x1 is None and not return_path:
+        y = torch.empty_like(x)
+        _lib.check(lib.agd_op_groupnorm(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), B, C0, HW,
+                                        groups, float(eps), int(silu), _lib.current_stream_ptr()), None, "agd_op_groupnorm")
+        return y
+    for t, b_, cs in ((part, bm, C0), (part1, bm1, C1)):
+        if t is not None:
+            assert b_ and b_ > 0 and t.dtype == torch.float32 and t.numel() == B * (HW // b_) * cs * 2, "partial-sum table [B, HW // bm, Cs, 2] fp32"
+    part = _f32c(part) if part is not None else None
+    part1 = _f32c(part1) if part1 is not None else None
+    y = torch.empty(B, C0 + C1, *x.shape[2:], device=x.device, dtype=torch.float32)
+    path = ctypes.c_int(0)
+    _lib.check(lib.agd_op_groupnorm_ex(_lib.ptr(x), _lib.ptr(x1), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), B, C0, C1, HW,
+                                       groups, float(eps), int(silu), _lib.ptr(part), int(bm or 0), _lib.ptr(part1), int(bm1 or 0),
+                                       ctypes.byref(path), _lib.current_stream_ptr()), None, "agd_op_groupnorm_ex")
+    return (y, path.value) if return_path else y
 
 
-def layer_norm(x, gamma, beta, eps=1e-5):
+def gn_fold(part, bm, groups, gamma, beta, w, bias=None, eps=1e-6, x=None, frag_ni=0, hw=None):
+    """The GroupNorm folded into the projection behind it, piece by piece (agd_op_gn_fold): part [B, HW / bm, C, 2] fp32 partial sums, w [N, C].
+    -> dict: wb [B, N, C], rowadd [B, N]; with frag_ni > 0 wb_frag and wb_frag_ref [B, N * C] (the kernel's fragment order, and the library's
+    re-layout of the row-major wb); with x [B, C, ...]: y [B, HW, N] = the raw x through the per-image matrices plus rowadd.
+    hw: the pixel count where it is not (tiles x bm) -- a shape the entry refuses."""
+    lib = _lib.load()
+    part, w = _f32c(part), _f32c(w)
+    B, nt, Cc = part.shape[:3]
+    HW = nt * bm if hw is None else hw
+    N = w.shape[0]
+    assert w.shape[1] == Cc and part.shape[3] == 2
+    b = _f32c(bias) if bias is not None else None
+    dev = part.device
+    out = {"wb": torch.empty(B, N, Cc, device=dev), "rowadd": torch.empty(B, N, device=dev)}
+    if frag_ni > 0:
+        out["wb_frag"] = torch.empty(B, N * Cc, device=dev)
+        out["wb_frag_ref"] = torch.empty(B, N * Cc, device=dev)
+    if x is not None:
+        x = _f32c(x)
+        assert x.shape[0] == B and x.shape[1] == Cc and x[0, 0].numel() == HW
+        out["y"] = torch.empty(B, HW, N, device=dev)
+    _lib.check(lib.agd_op_gn_fold(_lib.ptr(x), _lib.ptr(part), int(bm), B, Cc, HW, groups, float(eps), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)),
+                                  _lib.ptr(w), _lib.ptr(b), N, int(frag_ni), _lib.ptr(out["wb"]), _lib.ptr(out["rowadd"]), _lib.ptr(out.get("wb_frag")),
+                                  _lib.ptr(out.get("wb_frag_ref")), _lib.ptr(out.get("y")), _lib.current_stream_ptr()), None, "agd_op_gn_fold")
+    return out
+
+
+def layer_norm(x, gamma, beta, eps=1e-5, return_path=False):
+    """return_path: also which layernorm_kernel<LPR, MAXV> ran, as (LPR, MAXV)"""
     lib = _lib.load()
     x = _f32c(x)
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     y = torch.empty_like(x)
+    if return_path:
+        inst = ctypes.c_int(0)
+        _lib.check(lib.agd_op_layernorm_ex(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), rows, Cc,
+                                           float(eps), ctypes.byref(inst), _lib.current_stream_ptr()), None, "agd_op_layernorm_ex")
+        return y, divmod(inst.value, 100)
     _lib.check(lib.agd_op_layernorm(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), rows, Cc,
                                     float(eps), _lib.current_stream_ptr()), None, "agd_op_layernorm")
     return y

@@ -443,12 +443,35 @@ int agd_op_xattn_premul(const float* x, const float* gamma, const float* beta, c
                         const float* bo, float* y, float* probs, int B, int HW, int T, int C, int heads, float eps, void* stream);
 int agd_op_groupnorm(const float* x_nchw, const float* gamma, const float* beta, float* y_nchw, int B, int C, int HW,
                      int groups, float eps, int silu, void* stream);
+/* agd_op_groupnorm reaching EVERY form of the GroupNorm launcher, for per-kernel tests: one source, or the channel concat x0 | x1 (both NCHW
+ * fp32, rounded to bf16 by the entry; x1 NULL with C1 = 0), and optional partial-sum tables made by the caller in the layout the producing
+ * GEMM's epilogue leaves: part[((b * (HW / bm) + tile) * Cs + ch) * 2 + {0, 1}] = sum / sum of squares of source channel ch's bf16 values
+ * over the bm pixels of tile `tile` of image b (Cs = C0 for part0 / bm0, C1 for part1 / bm1; device fp32; NULL / 0: none).  With tables for
+ * every source and a shape the one-kernel form supports, the statistics pass is skipped; otherwise the two-kernel form runs.  *path (may be
+ * NULL): 1 = the partial-sum kernel ran, 2 = the two-kernel path.  Refused (-1, nothing computed or allocated), like every GroupNorm entry:
+ * C0 + C1 < 8 or > 4096, C0 + C1 or C0 not a multiple of 8, groups < 1 or > 64 or not dividing C0 + C1. */
+int agd_op_groupnorm_ex(const float* x0_nchw, const float* x1_nchw, const float* gamma, const float* beta, float* y_nchw, int B, int C0,
+                        int C1, int HW, int groups, float eps, int silu, const float* part0, int bm0, const float* part1, int bm1,
+                        int* path, void* stream);
+/* The GroupNorm folded into the projection behind it (Transformer2DModel norm -> proj_in), piece by piece: per image,
+ * wb [B][N][C] = bf16(W gamma rstd) and rowadd [B][N] = bias + W beta - wb mu, statistics from `part` (layout above, bm pixels per tile).
+ * frag_ni > 0: also wb_frag = the kernel's MFMA-fragment-ordered matrices and wb_frag_ref = the library's fragment re-layout of each
+ * image's row-major wb, both [B][N * C] in storage order (N % (16 frag_ni) == 0).  y (may be NULL) [B * HW][N]: the RAW activation x (NCHW,
+ * rounded to bf16) times image i's matrix plus image i's row, as the transformer's proj_in runs (C % 64 == 0, HW % 64 == 0).  All fp32
+ * (bf16 values widened exactly); w [N][C], bias (may be NULL) [N].  C <= 1024, HW % bm == 0. */
+int agd_op_gn_fold(const float* x_nchw, const float* part, int bm, int B, int C, int HW, int groups, float eps, const float* gamma,
+                   const float* beta, const float* w, const float* bias, int N, int frag_ni, float* wb, float* rowadd, float* wb_frag,
+                   float* wb_frag_ref, float* y, void* stream);
 /* conv3x3(+bias) -> GroupNorm(+SiLU), chained as the graph walk chains them; fused != 0: the conv launch emits the per-channel
  * partial sums and the GroupNorm skips its statistics pass (the production path), fused == 0: the two-kernel GroupNorm. */
 int agd_op_conv_groupnorm(const float* x_nchw, const float* w, const float* bias, const float* gamma, const float* beta, float* y_nchw,
                           int B, int Cin, int H, int W, int Cout, int groups, float eps, int silu, int fused, void* stream);
 int agd_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps,
                      void* stream);
+/* the same; *inst (may be NULL) = which instantiation of the LayerNorm kernel ran, as 100 * lanes per row + vectors per lane (6404, 1605, 1610).
+ * Both refuse rows < 1, C < 8, C % 8 != 0 and C > 2048. */
+int agd_op_layernorm_ex(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, int* inst,
+                        void* stream);
 /* q [B,Nq,H*D], k/v [B,Nk,H*D] fp32 -> o [B,Nq,H*D]; probs_out (may be NULL): [B,H,Nk,Nq] fp32, needs Nk<=96 */
 int agd_op_attention(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                      float scale, float* probs_out, void* stream);

@@ -333,6 +333,18 @@ def test_xattn_premul_matches_torch(ops, B, HW, T, C):
     assert torch.equal(got, got2) and torch.equal(pr, pr2)                               # run-to-run identical (no atomics)
 
 
+def _gn_slabs(name, got, x, groups, ga, be, eps, silu):
+    """The per-slab measure of tests/test_norm_ops_gpu.py on top of `rel_err`: every (image, group) slab of the output against the fp64
+    reference, max and RMS, within twice the error of the declared-roundings model (tests/_norm_model.py)."""
+    from _norm_model import MODEL_FACTOR, gn_slabs, groupnorm_fp64, groupnorm_model, model_bounds, slab_errors
+    want, model = (gn_slabs(f(x, None, groups, ga, be, eps, silu), groups) for f in (groupnorm_fp64, groupnorm_model))
+    e_model, e_rms = model_bounds(model, want)
+    mx, rms = slab_errors(gn_slabs(got, groups), want, model)
+    report(f"groupnorm_slabs[{name}]", kernel_max=float(mx.max()), model_max=e_model, kernel_rms=float(rms.max()), model_rms=e_rms)
+    assert float(mx.max()) <= MODEL_FACTOR * e_model, (name, float(mx.max()), e_model)
+    assert float(rms.max()) <= MODEL_FACTOR * e_rms, (name, float(rms.max()), e_rms)
+
+
 @pytest.mark.parametrize("B,C,H,groups,silu,eps", [
     (2, 320, 16, 32, True, 1e-5), (1, 1920, 8, 32, True, 1e-5), (2, 2560, 4, 32, False, 1e-6),
     (1, 128, 64, 32, True, 1e-6), (2, 64, 8, 32, False, 1e-5), (1, 960, 16, 32, True, 1e-5),
@@ -347,6 +359,7 @@ def test_groupnorm(ops, B, C, H, groups, silu, eps):
         want = F.silu(want)
     got = ops.group_norm(x.cuda(), groups, ga.cuda(), be.cuda(), eps, silu)
     assert rel_err(got, want) < REL
+    _gn_slabs(f"{B}x{C}x{H}x{H} G={groups} silu={silu}", got, x, groups, ga, be, eps, silu)
 
 
 @pytest.mark.parametrize("B,Cin,H,Cout", [(2, 64, 16, 320), (8, 320, 32, 320), (2, 128, 16, 640), (1, 64, 8, 1280), (3, 64, 16, 128)])
@@ -366,6 +379,13 @@ def test_groupnorm_statistics_from_the_conv_epilogue(ops, B, Cin, H, Cout):
     fused = ops.conv_groupnorm(x.cuda(), w.cuda(), b.cuda(), ga.cuda(), be.cuda(), fused=True)
     sep = ops.conv_groupnorm(x.cuda(), w.cuda(), b.cuda(), ga.cuda(), be.cuda(), fused=False)
     assert rel_err(fused, want) < REL and rel_err(sep, want) < REL
+    # every (image, group) slab on its own.  The reference normalises torch's conv output, the kernels their own: an element of it that rounds
+    # the other way moves by a bf16 ulp of the INPUT, which no model of the GroupNorm alone covers -- so the bound per slab is REL itself
+    from _norm_model import gn_slabs, slab_errors
+    for nm, t in (("fused", fused), ("separate", sep)):
+        mx, rms = slab_errors(gn_slabs(t, 32), gn_slabs(want, 32))
+        report(f"groupnorm_slabs[conv {B}x{Cin}x{H}->{Cout} {nm}]", kernel_max=float(mx.max()), kernel_rms=float(rms.max()))
+        assert float(mx.max()) < REL and float(rms.max()) < REL, (nm, float(mx.max()), float(rms.max()))
     d = (fused - sep).abs().cpu()
     assert float(d.max()) <= float(want.abs().max()) * 2.0 ** -7                      # at most a bf16 ulp of the largest value
     assert float((d > 0).float().mean()) < 0.02                                       # ... and only on isolated elements
@@ -384,6 +404,13 @@ def test_layernorm(ops, rows, C):
     want = F.layer_norm(x, (C,), ga, be, 1e-5)
     got = ops.layer_norm(x.cuda(), ga.cuda(), be.cuda())
     assert rel_err(got, want) < REL
+    # every row on its own, within twice the error of the declared-roundings model (tests/_norm_model.py)
+    from _norm_model import MODEL_FACTOR, layernorm_fp64, layernorm_model, ln_slabs, model_bounds, slab_errors
+    w64, model = layernorm_fp64(x, ga, be, 1e-5), layernorm_model(x, ga, be, 1e-5)
+    e_model, e_rms = model_bounds(model, w64)
+    mx, rms = slab_errors(ln_slabs(got), w64, model)
+    report(f"layernorm_slabs[{rows}x{C}]", kernel_max=float(mx.max()), model_max=e_model, kernel_rms=float(rms.max()), model_rms=e_rms)
+    assert float(mx.max()) <= MODEL_FACTOR * e_model and float(rms.max()) <= MODEL_FACTOR * e_rms, (float(mx.max()), e_model, float(rms.max()), e_rms)
 
 
 def _attn_ref(q, k, v, heads):
