@@ -3,7 +3,7 @@ Stable-Diffusion UNet denoise loop + DAAM cross-attention heat maps + VAE decode
 HIP kernels behind a C ABI (include/agenda_hip.h), with the Python call surfaces the reference
 scripts use (StableDiffusionPipeline, daam.trace, the attention-processor hooker)."""
 from . import config, synthetic, ip_adapter  # noqa: F401
-from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine  # noqa: F401
+from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine, DeepCacheSDHelper  # noqa: F401
 from .pipeline import StableDiffusionPipeline as StableDiffusionPAGPipeline  # noqa: F401  (diffusers' name: the same class, pag_applied_layers=)
 from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indices  # noqa: F401
 from .hook import UNetCrossAttentionHooker  # noqa: F401
@@ -20,4 +20,4 @@ __all__ = ["StableDiffusionPipeline", "StableDiffusionPAGPipeline", "PipelineOut
            "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
            "StableDiffusionInpaintPipeline",
            "StableDiffusionInstructPix2PixPipeline",
-           "StableDiffusionGLIGENPipeline", "StableDiffusionPanoramaPipeline", "get_views"]
+           "StableDiffusionGLIGENPipeline", "StableDiffusionPanoramaPipeline", "get_views", "DeepCacheSDHelper"]

@@ -214,6 +214,11 @@ _SIGS = {
     "agd_pag_counts": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "agd_op_pag_v_rows": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "agd_op_pag_fold": (C.c_int, [_P, _P, C.c_longlong, C.c_float, _P]),
+    "agd_deepcache_set": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "agd_deepcache_clear": (C.c_int, [_P]),
+    "agd_deepcache_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "agd_deepcache_forward_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P]),
+    "agd_op_deepcache_capture": (C.c_int, [_P, _P, _P, C.c_longlong, _P, _P, C.c_longlong, _P]),
     "agd_profile_begin": (C.c_int, [_P]),
     "agd_profile_end": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "agd_profile_end_ex": (C.c_int, [_P, C.c_double, C.c_double] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_longlong)]),

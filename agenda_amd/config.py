@@ -515,6 +515,17 @@ def pag_schedule(timesteps, pag_scale: float, pag_adaptive_scale: float = 0.0) -
     return [max(0.0, p - a * (1000.0 - float(t))) for t in timesteps]
 
 
+def deepcache_schedule(n_evaluations: int, cache_interval: int) -> List[int]:
+    """DeepCache's uniform schedule [upstream-knowledge: DeepCacheSDHelper, skip_mode "uniform"; parity-unpinned]: one flag per model
+    evaluation of a call, counted from 0 whatever the scheduler (PNDM's extra evaluation and img2img's tail of the grid included) --
+    1 = the full UNet, 0 = the shallow walk on the cached features; evaluation i is full iff i % cache_interval == 0."""
+    if isinstance(n_evaluations, bool) or not isinstance(n_evaluations, int) or n_evaluations < 1:
+        raise ValueError(f"n_evaluations={n_evaluations!r}: a call runs at least one model evaluation")
+    if isinstance(cache_interval, bool) or not isinstance(cache_interval, int) or cache_interval < 1:
+        raise ValueError(f"cache_interval={cache_interval!r}: DeepCache takes an integer interval >= 1")
+    return [1 if i % cache_interval == 0 else 0 for i in range(n_evaluations)]
+
+
 # ==========================================================================================
 # ControlNet (diffusers ControlNetModel) [upstream-knowledge: diffusers 0.21.2]
 # ==========================================================================================

@@ -277,6 +277,11 @@ int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, 
 int launch_pag_v_rows(const bf16_t* qkv, bf16_t* att, int M, int C, hipStream_t st);
 int launch_pag_fold(float* eps, long long n, float p, hipStream_t st);
 
+// DeepCache (deepcache.hip): the capture of a full evaluation -- two byte regions (the cached activation, its GroupNorm partial sums) copied
+// bit for bit in one launch, 16-byte loads and stores with the tail bytes handled (every region 16-byte aligned, else refused; a region of 0
+// bytes is skipped)
+int launch_deepcache_capture(const void* src0, void* dst0, long long bytes0, const void* src1, void* dst1, long long bytes1, hipStream_t st);
+
 // FreeU (freeu.hip): one launch re-weights one up-block resnet's inputs into fresh activations -- hidden_out = hidden with its first Ch / 2
 // channels times b, skip_out = skip with the four lowest frequencies of every map times s (diffusers fourier_filter, threshold 1, as a rank-4
 // projection in fp32), bf16 NHWC [B2][H W][C].  hidden_out / skip_out == nullptr: that tensor is left alone (b == 1 / s == 1).  *_part != nullptr:

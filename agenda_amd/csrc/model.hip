@@ -125,7 +125,10 @@ struct EvalCond {
   float ad_scale = 0.f;    // != 0: the T2I-Adapter's features times ad_scale are added to the down blocks' outputs
   bool ipa = false;        // the IP-Adapter's image branch runs beside every UNet attn2
   bool pag = false;        // the perturbed branch of Perturbed-Attention Guidance: the applied self-attention layers pass their value rows through
+  int dc = 0;              // DeepCache: 0 = the plain walk, DC_CAPTURE = the plain walk + the capture of U_{b+1}'s hidden-state input, DC_SHALLOW = the shallow walk on the cached one
+  int dc_branch = 0;       // b of the above
 };
+enum : int { DC_CAPTURE = 1, DC_SHALLOW = 2 };
 
 struct agd_ctx {
   int device = 0; agd_config cfg{}; std::string err;
@@ -246,6 +249,13 @@ struct agd_ctx {
   // Perturbed-Attention Guidance (agd_pag_set / agd_pag_clear): one scale per model evaluation (non-empty = set) and the applied self-attention
   // layers as transformer prefixes ("unet.mid_block.attentions.0."); pag_counts: perturbed walks / perturbed self-attention layers launched
   std::vector<float> pag_sched; std::unordered_set<std::string> pag_layers; long long pag_counts[2] = {0, 0};
+  // DeepCache (agd_deepcache_set / agd_deepcache_clear): one flag per model evaluation (1 = full, 0 = shallow; non-empty = set) and the branch b.
+  // dc_buf: the persistent slot outside the arena (unet_walk releases the arena at its start) -- the hidden state that entered U_{b+1} at the
+  // last capture, bf16 [rows][Lh][Lw][C], and behind it (256-byte aligned) its GroupNorm partial sums; dc_act describes it (cpart_bm == 0: no
+  // sums were left, the consumer runs its own statistics pass).  dc_valid: the slot holds a capture of (dc_rows, dc_Lh, dc_Lw, dc_b).
+  // dc_counts: full evaluations that captured / shallow evaluations
+  std::vector<int> dc_sched; int dc_branch = 0; long long dc_counts[2] = {0, 0};
+  DBuf dc_buf; Act dc_act; bool dc_valid = false; int dc_rows = 0, dc_Lh = 0, dc_Lw = 0, dc_b = 0;
   // profiling
   EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
   bool prof_on = false; std::vector<ProfEv> prof; std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
@@ -290,12 +300,14 @@ template <typename T> static T* dmalloc(agd_ctx* c, size_t n) {
   return (T*)p;
 }
 
+// the smallest row tile a producer leaves GroupNorm partial sums on: every partial-sum table (an activation's below, DeepCache's slot) is sized for it
+static const int kMinStatTile = 64;
 // stats: the activation will be written by an igemm launch and read by a GroupNorm -> room for the producer's partial sums
 static Act alloc_act(agd_ctx* c, int B, int H, int W, int C, bool stats = false) {
   Act a; a.B = B; a.H = H; a.W = W; a.C = C;
   a.p = (bf16_t*)c->arena.alloc((size_t)a.n() * 2);
-  if (a.p && stats && c->opt_gn_fused && ((long long)H * W) % 64 == 0) {
-    a.cpart = (float*)c->arena.alloc((size_t)((long long)B * H * W / 64) * C * 2 * sizeof(float));     // worst case: 64-row tiles
+  if (a.p && stats && c->opt_gn_fused && ((long long)H * W) % kMinStatTile == 0) {
+    a.cpart = (float*)c->arena.alloc((size_t)((long long)B * H * W / kMinStatTile) * C * 2 * sizeof(float));     // worst case: 64-row tiles
     if (!a.cpart) a.p = nullptr;
   }
   return a;
@@ -1096,7 +1108,7 @@ static int time_embed(agd_ctx* c, hipStream_t st, const float* ts, int n, float*
 // in a fresh activation (adapter_add) -- the sum is the level's last skip and the input of the downsampler / the mid block.
 static int adapter_add(agd_ctx* c, hipStream_t st, int level, const Act& h, Act& out);
 static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const bf16_t* xin, int B2, int Lh, int Lw, bool shared,
-                         const bf16_t* conv_in_res, const std::function<int(const Act&)>& on_sample, Act& h) {
+                         const bf16_t* conv_in_res, const std::function<int(const Act&)>& on_sample, Act& h, int stop_layer = -1) {
   const agd_config& g = c->cfg;
   const int nl = g.n_levels, G = g.norm_num_groups;
   const int Bh = shared ? B2 / 2 : B2;
@@ -1134,6 +1146,7 @@ static int down_mid_walk(agd_ctx* c, hipStream_t st, const std::string& u, const
       }
       if (add_here) { Act s; CK(adapter_add(c, st, i, h, s)); h = s; }
       CK(on_sample(h));
+      if (i == 0 && j == stop_layer) return 0;                             // DeepCache's shallow walk: s_0 .. s_{b+1} exist, nothing deeper runs
     }
     if (i != nl - 1) {
       const std::string k = u + "down_blocks." + std::to_string(i) + ".downsamplers.0.conv.";
@@ -1266,10 +1279,44 @@ static int freeu_apply(agd_ctx* c, hipStream_t st, int blk, const Act& h, const 
   return 0;
 }
 
+// DeepCache: the bytes the slot needs for a capture of `rows` rows at Lh x Lw -- the widest tensor that can enter the last up block (its own
+// channels, or the previous block's through the upsampler) and the partial sums of kMinStatTile-row tiles, alloc_act's own worst case: a
+// table that fits the activation it came from fits here, so a capture cannot run out of room in the middle of an evaluation
+static size_t deepcache_slot_bytes(const agd_ctx* c, int rows, int Lh, int Lw, size_t* part_off) {
+  const agd_config& g = c->cfg;
+  const int C = std::max(g.block_out_channels[0], g.block_out_channels[g.n_levels > 1 ? 1 : 0]);
+  const size_t act = ((size_t)rows * Lh * Lw * C * 2 + 255) & ~(size_t)255;
+  if (part_off) *part_off = act;
+  return act + ((size_t)rows * Lh * Lw / kMinStatTile + 1) * C * 2 * sizeof(float);
+}
+static void deepcache_invalidate(agd_ctx* c) { c->dc_valid = false; }
+// h (the hidden state about to enter U_{b+1}) and its partial sums into the slot, one launch; dc_act then describes the copy.  The slot was
+// sized before the call's first launch (deepcache_reserve); a tensor that does not fit is refused, never written.
+static int deepcache_capture(agd_ctx* c, hipStream_t st, const Act& h, int branch) {
+  size_t part_off = 0;
+  const size_t need = deepcache_slot_bytes(c, h.B, h.H, h.W, &part_off);
+  const long long nb = h.n() * 2;
+  const long long pb = h.cpart_bm > 0 ? (long long)((long long)h.B * h.H * h.W / h.cpart_bm) * h.C * 2 * (long long)sizeof(float) : 0;
+  if (!c->dc_buf.p || c->dc_buf.cap < need || (size_t)nb > part_off || (size_t)pb > need - part_off || (pb > 0 && !h.cpart))
+    FAIL("deepcache: the slot holds %zu bytes, the capture of %d x %d x %d x %d needs %lld + %lld", c->dc_buf.cap, h.B, h.H, h.W, h.C, nb, pb);
+  c->dc_valid = false;
+  char* base = c->dc_buf.as<char>();
+  { ProfScope ps(c, st, PC_ELEM, 0, 2.0 * (double)(nb + pb));
+    CK(launch_deepcache_capture(h.p, base, nb, h.cpart, base + part_off, pb, st)); }
+  Act a; a.p = (bf16_t*)base; a.B = h.B; a.H = h.H; a.W = h.W; a.C = h.C; a.cpart_bm = h.cpart_bm; a.cpart = pb > 0 ? (float*)(base + part_off) : nullptr;
+  c->dc_act = a; c->dc_valid = true; c->dc_rows = h.B; c->dc_Lh = h.H; c->dc_Lw = h.W; c->dc_b = branch;
+  c->dc_counts[0]++;
+  return 0;
+}
+static int deepcache_reserve(agd_ctx* c, int rows, int Lh, int Lw) { return c->dc_buf.ensure(deepcache_slot_bytes(c, rows, Lh, Lw, nullptr)); }
+
 // x: [B2][Lh*Lw][64] bf16 (latent channels zero-padded) -> eps [B2][Lh*Lw][out_channels] fp32 NHWC
 // tproj_row: this timestep's time_emb_proj outputs when the caller computed them up front (agd_denoise), else nullptr
 // cfg_shared: rows [0,B2/2) and [B2/2,B2) of xin are identical (agd_denoise): share everything ahead of the first attn2
 // tproj_ld: 0 = tproj_row serves every image; tproj_total = tproj_row holds one row per image (per-sample timesteps, training)
+// DeepCache (ec.dc): DC_SHALLOW runs conv_in and layers 0 .. b of down block 0, then enters the last up block at layer lpb - b - 1 with h taken
+// from the context's slot (dc_act) -- the same up loop entered later, so the CFG-shared prefix, the recorders and FreeU ride along; DC_CAPTURE is
+// the plain walk, launch for launch, plus one capture launch in front of that layer (before FreeU touches h).
 // ec: what this evaluation runs beside the UNet -- one element of the CallCond that resolve_cond() built for the call before its first launch
 // (nothing is refused here any more); it becomes c->cur, where tblock_plan (fusers, image branch) and down_mid_walk / adapter_add (features) read it
 static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int Lh, int Lw, float t, float* eps_out,
@@ -1286,14 +1333,25 @@ static int unet_walk(agd_ctx* c, hipStream_t st, const bf16_t* xin, int B2, int 
   std::vector<Act> skips;
   const bool shared = cfg_shared && (B2 % 2) == 0 && g.down_cross[0] && c->opt_cfg_share;
   Act h;
-  CK(down_mid_walk(c, st, u, xin, B2, Lh, Lw, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h));
+  const int lpb = g.layers_per_block;
+  const bool shallow = ec.dc == DC_SHALLOW;
+  const int dc_j = ec.dc ? lpb - ec.dc_branch - 1 : -1;              // the last up block's layer U_{b+1}
+  if (ec.dc && (ec.dc_branch < 0 || ec.dc_branch > lpb - 1)) FAIL("deepcache: branch %d (this UNet has branches 0 .. %d)", ec.dc_branch, lpb - 1);
+  if (shallow) {
+    if (!c->dc_valid || c->dc_rows != B2 || c->dc_Lh != Lh || c->dc_Lw != Lw || c->dc_b != ec.dc_branch)
+      FAIL("deepcache: a shallow evaluation of %d rows at %d x %d, branch %d, without a valid cache (a full evaluation that captures comes first)", B2, Lh, Lw, ec.dc_branch);
+    c->dc_counts[1]++;
+  }
+  CK(down_mid_walk(c, st, u, xin, B2, Lh, Lw, shared, nullptr, [&](const Act& a) { skips.push_back(a); return 0; }, h, shallow ? ec.dc_branch : -1));
+  if (shallow) h = c->dc_act;
   if (ec.cn_scale != 0.f) {
     if (c->tproj_cur_ld != 0) FAIL("controlnet: per-image timesteps are not supported");
     CK(controlnet_walk(c, st, xin, B2, Lh, Lw, t, ec.cn_scale, cfg_shared, &skips, &h, nullptr, 0));
   }
-  for (int i = 0; i < nl; ++i) {
+  for (int i = shallow ? nl - 1 : 0; i < nl; ++i) {
     const int lvl = nl - 1 - i, co = g.block_out_channels[lvl];
-    for (int j = 0; j < g.layers_per_block + 1; ++j) {
+    for (int j = shallow ? dc_j : 0; j < g.layers_per_block + 1; ++j) {
+      if (ec.dc == DC_CAPTURE && i == nl - 1 && j == dc_j) CK(deepcache_capture(c, st, h, ec.dc_branch));
       Act sk = skips.back(); skips.pop_back();
       NextGn ngu;
       if (g.down_cross[lvl]) { const std::string nk = u + "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j) + ".norm.";
@@ -1497,7 +1555,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release(); c->i2_latb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->cn_embb.release(); c->lora_descb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->dc_buf.release(); c->cn_embb.release(); c->lora_descb.release();
   for (auto& f : c->gl_f) f.gkvb.release();
   c->gl_objb.release();
   for (auto& b : c->ad_featb) b.release();
@@ -2080,6 +2138,7 @@ AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int to
   API_CK(c, c->ctxb.ensure((size_t)batch2 * tokens * Dc * 2)); c->ctx_bf16 = c->ctxb.as<bf16_t>();
   for (auto& xl : c->xl) { API_CK(c, xl.kvb.ensure((size_t)batch2 * tokens * 2 * xl.C * 2)); xl.kv = xl.kvb.as<bf16_t>(); }
   c->ctx_B2 = batch2; c->ctx_T = tokens;
+  deepcache_invalidate(c);                              // (a captured hidden state belongs to the context it was computed under)
   API_CK(c, launch_f32_to_bf16(ctx_emb, c->ctx_bf16, (long long)batch2 * tokens * Dc, st));
   API_CK(c, project_context(c, st, batch2, tokens));
   return 0;
@@ -2128,10 +2187,17 @@ static int embed_all_timesteps(agd_ctx* c, hipStream_t st, const float* timestep
 struct CallCond {
   const float* cn = nullptr; const int* gl = nullptr; const float* ad = nullptr; const float* blend = nullptr; bool ipa = false;
   const float* pag = nullptr;                                      // the PAG scales: the loop runs a third walk where pag[i] > 0 (at(i) stays the main walk's)
-  EvalCond at(int i) const { EvalCond e; e.cn_scale = cn ? cn[i] : 0.f; e.grounded = gl && gl[i]; e.ad_scale = ad ? ad[i] : 0.f; e.ipa = ipa; return e; }
+  // DeepCache's flags (1 = full, 0 = shallow) of the call's dc_n evaluations at branch dc_b: a full evaluation captures iff the next one is shallow
+  const int* dc = nullptr; int dc_n = 0, dc_b = 0;
+  EvalCond at(int i) const {
+    EvalCond e; e.cn_scale = cn ? cn[i] : 0.f; e.grounded = gl && gl[i]; e.ad_scale = ad ? ad[i] : 0.f; e.ipa = ipa;
+    if (dc) { e.dc = !dc[i] ? DC_SHALLOW : (i + 1 < dc_n && !dc[i + 1]) ? DC_CAPTURE : 0; e.dc_branch = dc_b; }
+    return e;
+  }
 };
-enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA };   // who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama
-enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, N_COND_STATES };                              // the states a call can meet, in the order of a row's cells
+// who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama, agd_deepcache_forward_hw
+enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA, CALL_DC_FORWARD };
+enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, ST_DC, N_COND_STATES };                       // the states a call can meet, in the order of a row's cells
 // One row per refusing party: a state (self) that, when set, refuses to run beside others in the callers that consult it, or an entry point
 // that runs the UNet alone (self < 0: it refuses whenever it is the caller).  with[s]: nullptr = allowed beside state s, else the refusal.
 // Rows are looked at top to bottom, the first set cell wins.  Whatever is not here is allowed: ControlNet + GLIGEN, GLIGEN + either
@@ -2191,6 +2257,31 @@ static const ConflictRow kPagConflicts[] = {
   { -1, 1u << CALL_PANORAMA, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
     "denoise_panorama: a Perturbed-Attention Guidance schedule is set; Perturbed-Attention Guidance on a panorama is not implemented (agd_pag_clear first)" } },
 };
+// DeepCache's rows, consulted last, in a table of their own for the same reason (the tables above leave their ST_DC cell empty).  The shallow
+// walk runs the plain UNet alone: nothing that injects into, or runs beside, the layers it skips.  agd_unet_forward_hw does not read the state.
+static const ConflictRow kDcConflicts[] = {
+  { ST_DC, 1u << CALL_EVAL_LOOP | 1u << CALL_IP2P_LOOP, {   // deepcache
+    "deepcache: a ControlNet schedule is set; DeepCache with a ControlNet is not implemented (clear one of them)",
+    "deepcache: a GLIGEN schedule is set; DeepCache with GLIGEN is not implemented (clear one of them)",
+    "deepcache: an inpainting state is set; DeepCache with inpainting is not implemented (agd_inpaint_clear or agd_deepcache_clear first)",
+    "deepcache: an InstructPix2Pix state is set; DeepCache with InstructPix2Pix is not implemented (agd_ip2p_clear or agd_deepcache_clear first)",
+    "deepcache: a T2I-Adapter schedule is set; DeepCache with a T2I-Adapter is not implemented (clear one of them)",
+    "deepcache: an IP-Adapter image is set; DeepCache with an IP-Adapter is not implemented (agd_ip_adapter_clear or agd_deepcache_clear first)",
+    "deepcache: a Perturbed-Attention Guidance schedule is set; DeepCache with Perturbed-Attention Guidance is not implemented (agd_pag_clear or agd_deepcache_clear first)",
+    nullptr } },
+  { -1, 1u << CALL_DC_FORWARD, {   // deepcache_forward (it reads neither an inpainting nor an InstructPix2Pix state, nor a DeepCache schedule)
+    "deepcache_forward: a ControlNet schedule is set; DeepCache with a ControlNet is not implemented (clear it first)",
+    "deepcache_forward: a GLIGEN schedule is set; DeepCache with GLIGEN is not implemented (clear it first)",
+    nullptr, nullptr,
+    "deepcache_forward: a T2I-Adapter schedule is set; DeepCache with a T2I-Adapter is not implemented (clear it first)",
+    "deepcache_forward: an IP-Adapter image is set; DeepCache with an IP-Adapter is not implemented (agd_ip_adapter_clear first)",
+    "deepcache_forward: a Perturbed-Attention Guidance schedule is set; DeepCache with Perturbed-Attention Guidance is not implemented (agd_pag_clear first)",
+    nullptr } },
+  { -1, 1u << CALL_UNET_FORWARD_TS, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    "unet_forward_ts: a DeepCache schedule is set; per-image timesteps run the UNet alone (agd_deepcache_clear first)" } },
+  { -1, 1u << CALL_PANORAMA, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    "denoise_panorama: a DeepCache schedule is set; DeepCache on a panorama is not implemented (agd_deepcache_clear first)" } },
+};
 // an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
 static int ip2p_check_unet(agd_ctx* c, const char* what) {
   const agd_config& g = c->cfg;
@@ -2203,13 +2294,15 @@ static int ip2p_check_unet(agd_ctx* c, const char* what) {
 // order: (a) which states are set, (b) the conflict table, (c) whether each state that runs fits this call.  *out: what the call then runs.
 static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw, CallCond* out) {
   *out = CallCond();
-  const int B2 = who == CALL_UNET_FORWARD ? rows : 2 * rows;
+  const int B2 = who == CALL_UNET_FORWARD || who == CALL_DC_FORWARD ? rows : 2 * rows;
   // (a) a schedule counts once it is non-empty, all zeros too; the IP-Adapter only with rows and a non-zero scale (idle otherwise)
   bool set[N_COND_STATES];
   set[ST_CN] = !c->cn_sched.empty(); set[ST_GL] = !c->gl_sched.empty(); set[ST_INP] = c->ip_mode != 0; set[ST_I2P] = c->i2_on;
   set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f; set[ST_PAG] = !c->pag_sched.empty();
-  for (const ConflictRow* t : {kConflicts, kPagConflicts}) {          // (b) rows top to bottom, the first set cell wins
-    const size_t rows = t == kConflicts ? sizeof(kConflicts) / sizeof(kConflicts[0]) : sizeof(kPagConflicts) / sizeof(kPagConflicts[0]);
+  set[ST_DC] = !c->dc_sched.empty();
+  for (const ConflictRow* t : {kConflicts, kPagConflicts, kDcConflicts}) {          // (b) rows top to bottom, the first set cell wins
+    const size_t rows = t == kConflicts ? sizeof(kConflicts) / sizeof(kConflicts[0]) : t == kPagConflicts ? sizeof(kPagConflicts) / sizeof(kPagConflicts[0])
+                                        : sizeof(kDcConflicts) / sizeof(kDcConflicts[0]);
     for (size_t k = 0; k < rows; ++k) {
       const ConflictRow& r = t[k];
       if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
@@ -2264,6 +2357,14 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   if (set[ST_PAG]) {
     if ((int)c->pag_sched.size() != n) FAIL("pag: the schedule has %zu scales, this call runs %d model evaluations (agd_pag_set)", c->pag_sched.size(), n);
     out->pag = c->pag_sched.data();
+  }
+  if (set[ST_DC] && who == CALL_EVAL_LOOP) {
+    if ((int)c->dc_sched.size() != n) FAIL("deepcache: the schedule has %zu flags, this call runs %d model evaluations (agd_deepcache_set)", c->dc_sched.size(), n);
+    if (c->dc_branch > c->cfg.layers_per_block - 1) FAIL("deepcache: branch %d (this UNet has branches 0 .. %d)", c->dc_branch, c->cfg.layers_per_block - 1);
+    if (!std::all_of(c->dc_sched.begin(), c->dc_sched.end(), [](int f) { return f != 0; })) {   // (all full: the plain call, nothing reserved)
+      CK(deepcache_reserve(c, B2, Lh, Lw));
+      out->dc = c->dc_sched.data(); out->dc_n = n; out->dc_b = c->dc_branch;
+    }
   }
   return 0;
 }
@@ -2472,6 +2573,7 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   CK(ensure_lat(c, B2, Lh, Lw));
   if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
   CallCond cc; CK(resolve_cond(c, CALL_EVAL_LOOP, n, batch, Lh, Lw, &cc));
+  struct DcLoop { agd_ctx* c; DcLoop(agd_ctx* c_) : c(c_) { deepcache_invalidate(c); } ~DcLoop() { deepcache_invalidate(c); } } dc_loop(c);   // a cache never outlives, or enters, a loop
   if (cc.pag) {                                                    // Perturbed-Attention Guidance: a third, B-row walk where its scale is > 0
     CK(refuse_guidance_rescale(c, "the Perturbed-Attention Guidance denoise loop"));
     CK(ensure_lat(c, 3 * batch, Lh, Lw));
@@ -4319,12 +4421,14 @@ AGD_API int agd_freeu_set(agd_ctx* c, float s1, float s2, float b1, float b2) {
   if (c->cfg.n_levels < 2) { agd_set_error("freeu_set: the UNet has %d level(s); FreeU re-weights up blocks 0 and 1", c->cfg.n_levels); return fail_ctx(c); }
   c->fu_s[0] = s1; c->fu_s[1] = s2; c->fu_b[0] = b1; c->fu_b[1] = b2;
   c->fu_on = !(s1 == 1.f && s2 == 1.f && b1 == 1.f && b2 == 1.f);
+  deepcache_invalidate(c);
   return 0;
 }
 
 AGD_API int agd_freeu_clear(agd_ctx* c) {
   if (!c) { agd_set_error("freeu_clear: null context"); return -1; }
   c->fu_on = false; c->fu_s[0] = c->fu_s[1] = c->fu_b[0] = c->fu_b[1] = 1.f;
+  deepcache_invalidate(c);
   return 0;
 }
 
@@ -4431,6 +4535,68 @@ AGD_API int agd_op_pag_v_rows(agd_ctx* c, const void* qkv, void* att, int M, int
 AGD_API int agd_op_pag_fold(agd_ctx* c, float* eps, long long n, float p, void* stream) {
   hipStream_t st = S(stream);
   API_CK(c, launch_pag_fold(eps, n, p, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
+// ---- DeepCache (deepcache.hip; the upstream DeepCacheSDHelper's uniform schedule [upstream-knowledge]) ---------------------------------
+// One flag per model evaluation of the next fused loop (1 = the full walk, 0 = the shallow walk at `branch`), counted from evaluation 0 of the
+// call whatever its scheduler.  flags[0] must be full; every flag 1 is the plain call.
+AGD_API int agd_deepcache_set(agd_ctx* c, const int* full_flags, int n, int branch) {
+  API_CK(c, need_final(c));
+  if (!full_flags || n < 1) { agd_set_error("deepcache_set: %d flags or a null argument", n); return fail_ctx(c); }
+  const int lpb = c->cfg.layers_per_block;
+  if (branch < 0 || branch > lpb - 1) { agd_set_error("deepcache_set: branch %d (this UNet has branches 0 .. %d: the layers of its first down block)", branch, lpb - 1); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i)
+    if (full_flags[i] != 0 && full_flags[i] != 1) { agd_set_error("deepcache_set: flag %d is %d (1 = full, 0 = shallow)", i, full_flags[i]); return fail_ctx(c); }
+  if (full_flags[0] != 1) { agd_set_error("deepcache_set: flag 0 is shallow; the first evaluation of a call has no cache to read and must be full"); return fail_ctx(c); }
+  c->dc_sched.assign(full_flags, full_flags + n); c->dc_branch = branch;
+  deepcache_invalidate(c);
+  return 0;
+}
+
+AGD_API int agd_deepcache_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("deepcache_clear: null context"); return -1; }
+  c->dc_sched.clear(); c->dc_branch = 0;
+  deepcache_invalidate(c);
+  return 0;
+}
+
+AGD_API int agd_deepcache_counts(agd_ctx* c, long long* out) {
+  if (!c || !out) { agd_set_error("deepcache_counts: null argument"); return fail_ctx(c); }
+  out[0] = c->dc_counts[0]; out[1] = c->dc_counts[1];
+  return 0;
+}
+
+// One evaluation of a DeepCache pair outside a loop (the test and tool seam; agd_unet_forward_hw's arguments).  shallow == 0: the plain forward
+// plus the capture for `branch`; shallow == 1: the shallow walk on what the last such call captured for the same (rows, Lh, Lw, branch) --
+// refused on the host when there is none, or when agd_set_context, a LoRA scale change, agd_freeu_set / _clear or agd_deepcache_clear came between.
+AGD_API int agd_deepcache_forward_hw(agd_ctx* c, const float* sample, int rows, int Lh, int Lw, float timestep, int branch, int shallow, float* out, void* stream) {
+  API_CK(c, need_final(c));
+  API_CK(c, check_latent_hw(c, "deepcache_forward", Lh, Lw));
+  if (!sample || !out || rows < 1 || (shallow != 0 && shallow != 1)) { agd_set_error("deepcache_forward: %d rows, shallow %d or a null argument", rows, shallow); return fail_ctx(c); }
+  const int lpb = c->cfg.layers_per_block;
+  if (branch < 0 || branch > lpb - 1) { agd_set_error("deepcache_forward: branch %d (this UNet has branches 0 .. %d: the layers of its first down block)", branch, lpb - 1); return fail_ctx(c); }
+  CallCond cc; API_CK(c, resolve_cond(c, CALL_DC_FORWARD, 1, rows, Lh, Lw, &cc));
+  if (shallow && (!c->dc_valid || c->dc_rows != rows || c->dc_Lh != Lh || c->dc_Lw != Lw || c->dc_b != branch)) {
+    agd_set_error("deepcache_forward: a shallow evaluation of %d rows at %d x %d, branch %d, without a valid cache (%s)", rows, Lh, Lw, branch,
+                  c->dc_valid ? "the captured one has another shape or branch" : "none was captured since the last invalidating call");
+    return fail_ctx(c);
+  }
+  hipStream_t st = S(stream);
+  API_CK(c, ensure_lat(c, rows, Lh, Lw));
+  if (!shallow) API_CK(c, deepcache_reserve(c, rows, Lh, Lw));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, rows, c->cfg.in_channels, Lh * Lw, 64, 1, 1.0f, st)); }
+  EvalCond ec = cc.at(0); ec.dc = shallow ? DC_SHALLOW : DC_CAPTURE; ec.dc_branch = branch;
+  API_CK(c, unet_walk(c, st, c->lat_bf16, rows, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec));
+  { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_nchw_from_nhwc_f32(c->eps_nhwc, c->cfg.out_channels, out, rows, c->cfg.out_channels, Lh * Lw, st)); }
+  return 0;
+}
+
+// The capture kernel alone (the test seam): two device regions of bytes0 / bytes1 bytes, copied as the walk's capture launch copies them
+AGD_API int agd_op_deepcache_capture(agd_ctx* c, const void* src0, void* dst0, long long bytes0, const void* src1, void* dst1, long long bytes1, void* stream) {
+  hipStream_t st = S(stream);
+  API_CK(c, launch_deepcache_capture(src0, dst0, bytes0, src1, dst1, bytes1, st));
   hipStreamSynchronize(st);
   return 0;
 }
@@ -4654,6 +4820,7 @@ static int lora_apply(agd_ctx* c, float s, hipStream_t st) {
   CK(lora_rederive(c));
   if (hipDeviceSynchronize() != hipSuccess) FAIL("lora: merge failed");
   c->lora_scale = s; c->lora_dirty = false; c->ctx_stale = true;
+  deepcache_invalidate(c);
   if (c->ipa_B2 > 0) c->ipa_stale = true;               // K'' / V'' of the image tokens were built from the old to_q / to_out
   return 0;
 }

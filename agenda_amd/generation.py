@@ -324,6 +324,11 @@ def parse_args(argv=None):
                    help="PAG: the scale of the evaluation at timestep t is max(0, P - A (1000 - t)) (0: constant P); needs --pag-scale")
     p.add_argument("--pag-applied-layers", type=str, default=None, nargs="+", metavar="L",
                    help="PAG: regular expressions searched in the UNet's self-attention module names (default: mid); needs --pag-scale")
+    p.add_argument("--deepcache-interval", type=int, default=None, metavar="N",
+                   help="DeepCache (Ma et al. 2024; enable_deepcache): only every N-th model evaluation runs the whole UNet, the others its "
+                        "shallowest layers on the cached deep features (1: off; 2 - 3 suggested at 50 steps); plain txt2img only")
+    p.add_argument("--deepcache-branch", type=int, default=None, metavar="B",
+                   help="DeepCache: the layers 0 .. B of the first down block run on a shallow evaluation (default 0); needs --deepcache-interval")
     p.add_argument("--timestep-spacing", type=str, default=None, choices=["leading", "trailing", "linspace"],
                    help="the scheduler's timestep grid (default: the checkpoint's; DDIM and img2img take all three, DPM-Solver++ its own "
                         "three, PNDM runs 'leading' only)")
@@ -343,6 +348,17 @@ def parse_args(argv=None):
                            or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama or args.guidance_rescale):
         p.error("--pag-scale with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
                 "--gligen-phrases / --gligen-layouts, --panorama or --guidance-rescale is not implemented")
+    if args.deepcache_branch is not None and args.deepcache_interval is None:
+        p.error("--deepcache-branch needs --deepcache-interval N")
+    if args.deepcache_interval is not None and args.deepcache_interval < 1:
+        p.error(f"--deepcache-interval {args.deepcache_interval}: an integer >= 1")
+    if args.deepcache_branch is not None and args.deepcache_branch < 0:
+        p.error(f"--deepcache-branch {args.deepcache_branch}: an integer >= 0")
+    if (args.deepcache_interval or 1) > 1 and (
+            args.controlnet_model_path or args.adapter_model_path or args.ip_adapter_path or args.init_image or args.instruct_image
+            or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama or args.pag_scale):
+        p.error("--deepcache-interval with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
+                "--gligen-phrases / --gligen-layouts, --panorama or --pag-scale is not implemented")
     if args.scheduler == "PNDMScheduler" and args.timestep_spacing not in (None, "leading"):
         p.error(f"--timestep-spacing {args.timestep_spacing}: PNDMScheduler runs 'leading' only")
     if args.rescale_betas_zero_snr and args.scheduler in ("PNDMScheduler", "DPMSolverMultistepScheduler"):
@@ -601,6 +617,8 @@ def main(argv=None):
         pipe.enable_freeu(*args.freeu)
     if args.pag_applied_layers is not None:
         pipe.set_pag_applied_layers(args.pag_applied_layers)
+    if args.deepcache_interval is not None:
+        pipe.enable_deepcache(cache_interval=args.deepcache_interval, cache_branch_id=args.deepcache_branch or 0)
     ipa_files = None
     if args.ip_adapter_path:
         pipe.load_ip_adapter(args.ip_adapter_path, image_encoder_folder=args.image_encoder_path or "image_encoder")

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .config import SDConfig, cross_attn_layer_names
-from .pipeline import StableDiffusionPipeline, refuse_pag
+from .pipeline import StableDiffusionPipeline, refuse_deepcache, refuse_pag
 
 MAX_OBJS = 30                 # [upstream-knowledge] StableDiffusionGLIGENPipeline.__call__: max_objs = 30
 FOURIER_FREQS = 8             # [upstream-knowledge] PositionNet(fourier_freqs=8)
@@ -277,6 +277,7 @@ class StableDiffusionGLIGENPipeline(StableDiffusionPipeline):
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                  output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
         refuse_pag("StableDiffusionGLIGENPipeline", pag_scale, pag_adaptive_scale)
+        refuse_deepcache("StableDiffusionGLIGENPipeline", getattr(self, "_deepcache", None))
         if gligen_inpaint_image is not None:
             raise ValueError("gligen_inpaint_image (GLIGEN inpainting) is not implemented")
         if eta != 0.0:

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .config import SDConfig, ip2p_variant
-from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_pag
 
 
 def check_unet(cfg: SDConfig) -> None:
@@ -117,6 +117,7 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionPipeline):
         """image as `prepare_image` takes it; height and width are the image's (given ones must equal them: nothing is resized).
         prompt_embeds is [2B,T,D] = [uncond | cond]."""
         refuse_pag("StableDiffusionInstructPix2PixPipeline", pag_scale, pag_adaptive_scale)
+        refuse_deepcache("StableDiffusionInstructPix2PixPipeline", getattr(self, "_deepcache", None))
         if image is None:
             raise ValueError("StableDiffusionInstructPix2PixPipeline needs image=")
         if guidance_rescale:

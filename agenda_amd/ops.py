@@ -404,3 +404,26 @@ def pag_fold(eps, p):
         raise ValueError(f"pag_fold: eps {tuple(eps.shape)} must be [3, n]")
     _lib.check(lib.agd_op_pag_fold(None, _lib.ptr(eps), eps.shape[1], float(p), _lib.current_stream_ptr()), None, "agd_op_pag_fold")
     return eps
+
+
+def deepcache_capture(act, part=None):
+    """DeepCache's capture launch, the production kernel: two device byte regions (the cached activation and its GroupNorm partial sums, any
+    dtype, any byte count; `part` None or empty = the cpart_bm == 0 case, one region) -> bit-for-bit copies (act_copy, part_copy) made by ONE
+    launch.  The copies are allocated with 64 guard bytes behind each, returned as well so a test can see they were left alone."""
+    lib = _lib.load()
+    assert act.is_cuda and (part is None or part.is_cuda), "ops run on the GPU only (no CPU fallback)"
+    regions, outs = [], []
+    for t in (act, part):
+        if t is None or t.numel() == 0:
+            regions.append((None, None, 0))
+            outs.append(None)
+            continue
+        src = t.detach().contiguous().view(torch.uint8).reshape(-1)
+        nb = src.numel()
+        dst = torch.full(((nb + 15) // 16 * 16 + 64,), 0xA5, dtype=torch.uint8, device=src.device)
+        regions.append((src, dst, nb))
+        outs.append((dst[:nb].view(t.dtype).reshape(t.shape), dst[nb:]))
+    (s0, d0, n0), (s1, d1, n1) = regions
+    _lib.check(lib.agd_op_deepcache_capture(None, _lib.ptr(s0), _lib.ptr(d0), n0, _lib.ptr(s1), _lib.ptr(d1), n1, _lib.current_stream_ptr()),
+               None, "agd_op_deepcache_capture")
+    return outs[0], outs[1]

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_pag
 from .scheduler import DDIMScheduler
 
 STRIDE = 8            # latent pixels between views (diffusers get_views default)
@@ -77,6 +77,7 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
                  guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
         refuse_pag("StableDiffusionPanoramaPipeline", pag_scale, pag_adaptive_scale)
+        refuse_deepcache("StableDiffusionPanoramaPipeline", getattr(self, "_deepcache", None))
         if guidance_rescale:
             raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale is not implemented for the panorama pipeline "
                              "(its views are stepped one by one); leave it 0")

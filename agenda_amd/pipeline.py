@@ -86,6 +86,60 @@ def refuse_pag(pipeline: str, pag_scale: float, pag_adaptive_scale: float = 0.0)
                          f"for {pipeline} (StableDiffusionPipeline's txt2img and img2img run it); leave both 0")
 
 
+def check_deepcache(cache_interval, cache_branch_id, layers_per_block: int, skip_mode: str = "uniform") -> None:
+    """`enable_deepcache`'s arguments: an integer interval >= 1, a branch among the layers of the first down block, the uniform schedule."""
+    for name, v in (("cache_interval", cache_interval), ("cache_branch_id", cache_branch_id)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name}={v!r}: DeepCache takes an integer")
+    if cache_interval < 1:
+        raise ValueError(f"cache_interval={cache_interval!r}: DeepCache takes an interval >= 1 (1 = every evaluation is full)")
+    if not 0 <= cache_branch_id <= layers_per_block - 1:
+        raise ValueError(f"cache_branch_id={cache_branch_id!r}: this UNet has branches 0 .. {layers_per_block - 1} (the layers of its first "
+                         "down block); deeper branches are not implemented")
+    if skip_mode != "uniform":
+        raise ValueError(f"skip_mode={skip_mode!r}: only the 'uniform' DeepCache schedule is implemented")
+
+
+def refuse_deepcache(pipeline: str, deepcache, what: str = "") -> None:
+    """The pipelines (and call arguments) that run beside something the shallow walk does not carry refuse an enabled DeepCache by name.
+    `deepcache`: the pipeline's state, None or (cache_interval, cache_branch_id); interval 1 sets nothing and is never refused."""
+    if deepcache is not None and deepcache[0] > 1:
+        raise ValueError(f"DeepCache (cache_interval={deepcache[0]}, cache_branch_id={deepcache[1]}) is enabled: it is not implemented for "
+                         f"{pipeline}{' with ' + what if what else ''} (StableDiffusionPipeline's txt2img and img2img run it); "
+                         "call disable_deepcache() first")
+
+
+def refuse_deepcache_beside(deepcache, pag_scale: float, ip_adapter, ip_adapter_image, ip_adapter_image_embeds) -> None:
+    """What a txt2img / img2img call can carry that the shallow walk does not, decided from the call's arguments alone, before any device
+    work: a non-zero pag_scale, and an image prompt for a loaded IP-Adapter whose scale is not 0 (`ip_adapter`: the pipeline's adapter
+    state, None = none loaded -- the call then fails on that by itself; scale 0 or no image leaves the adapter idle, which is allowed)."""
+    if pag_scale:
+        refuse_deepcache("StableDiffusionPipeline", deepcache, f"pag_scale={pag_scale!r}")
+    if (ip_adapter_image is not None or ip_adapter_image_embeds is not None) and ip_adapter is not None and ip_adapter["scale"] != 0.0:
+        refuse_deepcache("StableDiffusionPipeline", deepcache, f"an active IP-Adapter (scale {ip_adapter['scale']!r})")
+
+
+class DeepCacheSDHelper:
+    """The upstream `DeepCache.DeepCacheSDHelper` [upstream-knowledge], parity-unpinned: `set_params`, `enable`, `disable` forwarded to the
+    pipeline's enable_deepcache / disable_deepcache, so a script written for the upstream helper runs unchanged."""
+
+    def __init__(self, pipe=None):
+        self.pipe = pipe
+        self.params = dict(cache_interval=1, cache_branch_id=0, skip_mode="uniform")
+
+    def set_params(self, cache_interval: int = 1, cache_branch_id: int = 0, skip_mode: str = "uniform"):
+        check_deepcache(cache_interval, cache_branch_id, self.pipe.cfg.unet.layers_per_block, skip_mode)
+        self.params = dict(cache_interval=cache_interval, cache_branch_id=cache_branch_id, skip_mode=skip_mode)
+
+    def enable(self, pipe=None):
+        if pipe is not None:
+            self.pipe = pipe
+        self.pipe.enable_deepcache(**self.params)
+
+    def disable(self):
+        self.pipe.disable_deepcache()
+
+
 def check_image_size(height: int, width: int, multiple: int = 64) -> None:
     """The pipelines' size rule: each side a positive multiple of 64, applied per axis (height and width may differ)."""
     if not all(isinstance(v, int) and v > 0 and v % multiple == 0 for v in (height, width)):
@@ -458,6 +512,32 @@ class Engine:
         w, l = C.c_longlong(0), C.c_longlong(0)
         self._ck(self.lib.agd_pag_counts(self.ctx, C.byref(w), C.byref(l)), "agd_pag_counts")
         return int(w.value), int(l.value)
+
+    def deepcache_set(self, full_flags, branch: int = 0):
+        """`agd_deepcache_set`: DeepCache for the calls to come, until deepcache_clear -- one flag per model evaluation (1 = the full walk,
+        0 = the shallow walk at `branch` on the features the last full one cached; `config.deepcache_schedule`)."""
+        flags = [int(f) for f in full_flags]
+        arr = (C.c_int * max(len(flags), 1))(*flags)
+        self._ck(self.lib.agd_deepcache_set(self.ctx, arr, len(flags), int(branch)), "agd_deepcache_set")
+
+    def deepcache_clear(self):
+        self._ck(self.lib.agd_deepcache_clear(self.ctx), "agd_deepcache_clear")
+
+    def deepcache_counts(self) -> Tuple[int, int]:
+        """`agd_deepcache_counts`: (full evaluations that captured, shallow evaluations) since the engine was created."""
+        n = (C.c_longlong * 2)()
+        self._ck(self.lib.agd_deepcache_counts(self.ctx, n), "agd_deepcache_counts")
+        return int(n[0]), int(n[1])
+
+    def deepcache_forward(self, sample: torch.Tensor, timestep: float, branch: int = 0, shallow: bool = False) -> torch.Tensor:
+        """`agd_deepcache_forward_hw`: one evaluation of a DeepCache pair -- shallow=False is unet_forward plus the capture for `branch`,
+        shallow=True the shallow walk on that capture (refused on the host when there is no valid one)."""
+        sample = sample.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        b2, _, Lh, Lw = sample.shape
+        out = torch.empty(b2, self.cfg.unet.out_channels, Lh, Lw, device=sample.device, dtype=torch.float32)
+        self._ck(self.lib.agd_deepcache_forward_hw(self.ctx, _lib.ptr(sample), b2, Lh, Lw, float(timestep), int(branch), int(bool(shallow)),
+                                                   _lib.ptr(out), self._stream()), "agd_deepcache_forward_hw")
+        return out
 
     def gligen_configure(self, positive_len: int, max_objs: int = 30, fourier_freqs: int = 8):
         self._glcfg = _lib.AgdGligenConfig()
@@ -899,6 +979,7 @@ class StableDiffusionPipeline:
                  text_sd: Optional[Dict[str, torch.Tensor]] = None, scheduler: str = "DDIMScheduler",
                  safety_sd: Optional[Dict[str, torch.Tensor]] = None, pag_applied_layers: Union[str, Sequence[str]] = ("mid",)):
         self.cfg = cfg
+        self._deepcache = None                              # enable_deepcache: (cache_interval, cache_branch_id)
         self.set_pag_applied_layers(pag_applied_layers)     # (refuses a string that matches no layer before anything is loaded)
         dev = int(str(device).split(":")[-1]) if not isinstance(device, int) and ":" in str(device) else (device if isinstance(device, int) else 0)
         self.engine = Engine(cfg, dev, workspace_bytes)
@@ -1288,6 +1369,20 @@ class StableDiffusionPipeline:
         """The plain UNet again, launch for launch: results are bit-identical to a pipeline that never enabled FreeU."""
         self.unet.disable_freeu()
 
+    def enable_deepcache(self, cache_interval: int = 3, cache_branch_id: int = 0, skip_mode: str = "uniform"):
+        """DeepCache (Ma, Fang, Wang, CVPR 2024; the upstream DeepCacheSDHelper [upstream-knowledge], parity-unpinned): of every later
+        call's model evaluations only each `cache_interval`-th runs the whole UNet; the ones between run conv_in, layers 0 .. cache_branch_id
+        of the first down block, the up layers that consume their skips and conv_out, on the deep features the last full evaluation
+        cached on the device.  Evaluations count from 0 per call.  The state persists like FreeU's until disable_deepcache; `to()` and LoRA
+        scale changes leave it alone and save_pretrained does not write it.  cache_interval=1 sets nothing: the plain call, bit for bit.
+        The recorders see the attn2 layers that run, so the deep layers' maps accumulate on full evaluations only."""
+        check_deepcache(cache_interval, cache_branch_id, self.cfg.unet.layers_per_block, skip_mode)
+        self._deepcache = (cache_interval, cache_branch_id)
+
+    def disable_deepcache(self):
+        """The plain loops again, launch for launch: results are bit-identical to a pipeline that never enabled DeepCache."""
+        self._deepcache = None
+
     def set_pag_applied_layers(self, layers: Union[str, Sequence[str]]):
         """diffusers' `pag_applied_layers` (the constructor / from_pretrained keyword of StableDiffusionPAGPipeline, default ["mid"]): every
         string is `re.search`ed against the UNet's self-attention module names (`config.self_attn_layer_names`); the layers they match are
@@ -1377,6 +1472,7 @@ class StableDiffusionPipeline:
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
         check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        refuse_deepcache_beside(getattr(self, "_deepcache", None), pag_scale, getattr(self, "_ip_adapter", None), ip_adapter_image, ip_adapter_image_embeds)
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
         height, width = height or side, width or side
@@ -1389,7 +1485,8 @@ class StableDiffusionPipeline:
         self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
         self._begin_recording(prompt_embeds, B, L)
-        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, self.scheduler, num_inference_steps):
+        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, self.scheduler, num_inference_steps), \
+                self._deepcached(self.scheduler, num_inference_steps):
             self._denoise(lat, num_inference_steps, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
@@ -1440,6 +1537,23 @@ class StableDiffusionPipeline:
         finally:
             self.engine.pag_clear()
 
+    @contextlib.contextmanager
+    def _deepcached(self, scheduler, num_inference_steps: int, strength: float = 1.0):
+        """DeepCache around one call's denoise loop: the full / shallow flag of every model evaluation (`config.deepcache_schedule` over the
+        length of `inpaint.evaluation_timesteps`) is set for the loop and cleared when it ends, on an error too.  Disabled, or interval 1,
+        sets nothing."""
+        if self._deepcache is None or self._deepcache[0] == 1:
+            yield
+            return
+        from .config import deepcache_schedule
+        from .inpaint import evaluation_timesteps
+        interval, branch = self._deepcache
+        self.engine.deepcache_set(deepcache_schedule(len(evaluation_timesteps(scheduler, num_inference_steps, strength)), interval), branch)
+        try:
+            yield
+        finally:
+            self.engine.deepcache_clear()
+
     def _denoise(self, lat, num_inference_steps, guidance_scale):
         """`for t in scheduler.timesteps: unet -> CFG -> scheduler.step`, fused on the device, under the pipeline's scheduler."""
         ts = self.scheduler.set_timesteps(num_inference_steps)
@@ -1485,6 +1599,7 @@ class StableDiffusionPipeline:
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
         check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        refuse_deepcache_beside(getattr(self, "_deepcache", None), pag_scale, getattr(self, "_ip_adapter", None), ip_adapter_image, ip_adapter_image_embeds)
         self._apply_lora_scale(cross_attention_kwargs)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
         if image.dtype == torch.uint8:
@@ -1514,7 +1629,8 @@ class StableDiffusionPipeline:
         a = float(sched.alphas_cumprod[int(ts[0])])
         lat = (a ** 0.5 * x0 + (1 - a) ** 0.5 * noise.to(mean.device)).contiguous()
         self._begin_recording(prompt_embeds, B, L)
-        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, sched, num_inference_steps, strength):
+        with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, sched, num_inference_steps, strength), \
+                self._deepcached(sched, num_inference_steps, strength):
             self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)

@@ -616,6 +616,36 @@ int agd_pag_counts(agd_ctx* ctx, long long* walks, long long* layers);
 int agd_op_pag_v_rows(agd_ctx* ctx, const void* qkv, void* att, int M, int C, void* stream);
 int agd_op_pag_fold(agd_ctx* ctx, float* eps, long long n, float p, void* stream);
 
+/* ---- DeepCache (Ma, Fang, Wang 2024, "DeepCache: Accelerating Diffusion Models for Free"; the upstream DeepCacheSDHelper's uniform schedule
+ * [upstream-knowledge]; csrc/deepcache.hip).  Number the UNet's skip tensors in the order the down path makes them: s_0 = conv_in's output,
+ * s_1 .. s_lpb the outputs of the layers of down block 0 (lpb = layers_per_block), then the downsampler's, and so on; U_k is the up layer that
+ * consumes s_k, so U_lpb .. U_0 are layers 0 .. lpb of the last up block.  A SHALLOW evaluation at branch b runs the time embedding, conv_in
+ * and layers 0 .. b of down block 0, then U_{b+1} .. U_0 and conv_norm_out / conv_out; the hidden-state input of U_{b+1} is the one that entered
+ * that layer at the most recent FULL evaluation, kept with its GroupNorm partial sums in a slot of the context outside the activation arena.
+ * A full evaluation is the plain walk, launch for launch, plus -- when the next evaluation is shallow -- one copy launch into the slot.
+ * The recorders (DAAM, hook.py) see exactly the attn2 layers that run; FreeU acts inside the shallow walk where it touches the last up block.
+ * agd_deepcache_set: context state after agd_finalize, until cleared.  full_flags: one flag per model evaluation of the calls to come (1 = full,
+ *   0 = shallow), counted from evaluation 0 of the call (agd_denoise*, agd_denoise_plms* with its extra evaluation, agd_denoise_dpm* check n
+ *   against their evaluations); full_flags[0] must be 1; all ones is the plain call, bit for bit, and captures nothing.  branch: 0 ..
+ *   layers_per_block - 1, anything else is refused by name.  Refused by name before the first launch: a ControlNet, GLIGEN or T2I-Adapter
+ *   schedule, an active IP-Adapter, either inpainting state, an InstructPix2Pix state, a Perturbed-Attention Guidance schedule,
+ *   agd_denoise_panorama and agd_unet_forward_ts*.  agd_unet_forward_hw does not read the state.
+ * agd_deepcache_clear: the plain loops again, launch for launch.
+ * agd_deepcache_counts (seam for tests): out[0] = full evaluations that captured, out[1] = shallow evaluations, since agd_create.
+ * agd_deepcache_forward_hw (seam for tests and tools; agd_unet_forward_hw's arguments): shallow == 0 is the plain forward plus a capture for
+ *   `branch`, shallow == 1 the shallow walk on that capture.  A capture is valid for one (rows, Lh, Lw, branch); a fused loop invalidates it at
+ *   its start and its end, and so do agd_set_context, a LoRA scale change, agd_freeu_set / agd_freeu_clear, agd_deepcache_set and
+ *   agd_deepcache_clear.  shallow == 1 without a valid capture is refused on the host; nothing is launched.  It does not read the schedule.
+ *   A loop that is refused (a conflicting state, a wrong schedule length) fails before it invalidates anything: it leaves the schedule, the
+ *   counters and a capture made through this seam as they were.
+ * agd_op_deepcache_capture (seam for tests): the capture launch alone on two device regions of bytes0 / bytes1 bytes (either may be 0), each
+ *   16-byte aligned, copied bit for bit.  ctx may be NULL (it only keeps the error text). */
+int agd_deepcache_set(agd_ctx* ctx, const int* full_flags, int n, int branch);
+int agd_deepcache_clear(agd_ctx* ctx);
+int agd_deepcache_counts(agd_ctx* ctx, long long* out);
+int agd_deepcache_forward_hw(agd_ctx* ctx, const float* sample, int rows, int Lh, int Lw, float timestep, int branch, int shallow, float* out, void* stream);
+int agd_op_deepcache_capture(agd_ctx* ctx, const void* src0, void* dst0, long long bytes0, const void* src1, void* dst1, long long bytes1, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
