@@ -190,6 +190,7 @@ _SIGS = {
     "agd_op_xattn_premul": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, _P]),
     "agd_op_attention": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_op_attention_ex": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "agd_op_attention_long": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_int, _P, C.c_int, C.c_int, _P]),
     "agd_op_attention_headsum": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_op_attention_backward": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, _P, _P, _P]),
     "agd_op_hook_headmean": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .config import ControlNetConfig, SDConfig, controlnet_config_from_json, controlnet_keep_schedule
-from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag
 from .scheduler import DPMSolverMultistepScheduler, PNDMScheduler
 
 _WEIGHTS = "diffusion_pytorch_model.safetensors"
@@ -173,9 +173,11 @@ class StableDiffusionControlNetPipeline(StableDiffusionPipeline):
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  num_images_per_prompt: int = 1, controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, cross_attention_kwargs: Optional[dict] = None,
-                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 max_embeddings_multiples: Optional[int] = None):
         refuse_pag("StableDiffusionControlNetPipeline", pag_scale, pag_adaptive_scale)
         refuse_deepcache("StableDiffusionControlNetPipeline", getattr(self, "_deepcache", None))
+        refuse_long_prompt("StableDiffusionControlNetPipeline", max_embeddings_multiples, prompt_embeds)
         if guess_mode:
             raise NotImplementedError("ControlNet guess_mode is not implemented")
         if isinstance(controlnet_conditioning_scale, (list, tuple)) or isinstance(control_guidance_start, (list, tuple)) \

@@ -93,6 +93,10 @@ struct AttnP {
   const bf16_t* k2; const bf16_t* v2; int ldk2, ldv2; long long sk2, sv2; int Nk2;
 };
 int launch_attention(const AttnP& p, hipStream_t st);
+// record_mode 1 at 97 .. ATTN_LONG_MAX_KEYS keys (attention_long.hip): two passes over 64-key tiles, the recorded probabilities final.
+// No mask, causal order, second source or head-group sums; non-recording calls of that many keys stay with launch_attention.
+constexpr int ATTN_LONG_MAX_KEYS = 320;
+int launch_attention_long(const AttnP& p, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // Fused row-panel kernels of the transformer blocks at C = 320 (tblock.hip)

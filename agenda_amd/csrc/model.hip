@@ -577,7 +577,17 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
   a.record_mode = 0; a.mask = mask;
   const int side = qh;                                 // (hook.py mode: square maps only)
   bool hook_call = false;
+  // a context beyond 96 tokens: DAAM records through attention_long.hip (per-head rows, final probabilities over several key tiles);
+  // whatever does not record runs the flash kernel, which walks key tiles already
+  const bool long_ctx = T > 96;
+  if (long_ctx && record && c->rec_mode == 2) FAIL("the hook.py recorder takes contexts of at most 96 tokens (this one has %d)", T);
   if (record && daam_records(c, xl, B2, qh, qw)) {
+    if (long_ctx) {
+      if (mask) FAIL("attention_mask together with daam recording is not supported beyond 96 tokens (this context has %d)", T);
+      if (xl.acc_heads < xl.heads || c->rec_T > T)
+        FAIL("%s: the daam accumulators hold %d of %d head rows and %d token rows, this context has %d tokens: reset after agd_set_context (agd_record_reset)",
+             xl.name.c_str(), xl.acc_heads, xl.heads, c->rec_T, T);
+    }
     a.rec_b0 = B2 / 2; a.rec_T = c->rec_T;
     a.rec_head_stride = (long long)c->rec_T * N; a.rec_img_stride = a.rec_head_stride * xl.acc_heads;
     a.rec = xl.acc + (size_t)c->rec_base * a.rec_img_stride;
@@ -600,7 +610,12 @@ static int cross_attention(agd_ctx* c, hipStream_t st, XLayer& xl, const bf16_t*
       hook_call = true;
     }
   }
-  CK(run_attention(c, st, PC_ATTN_CROSS, a));
+  if (long_ctx && a.record_mode != 0) {
+    const double fl = 6.0 * a.B * a.H * (double)a.Nq * a.Nk * a.D;      // Q K^T twice (attention_long.hip's two passes), P V once
+    const double by = 2.0 * a.B * a.H * (double)a.D * (2.0 * a.Nq + 3.0 * a.Nk) + 8.0 * (a.B - a.rec_b0) * a.H * (double)a.rec_T * a.Nq;
+    ProfScope ps(c, st, PC_ATTN_CROSS, fl, by);
+    CK(launch_attention_long(a, st));
+  } else CK(run_attention(c, st, PC_ATTN_CROSS, a));
   if (hook_call) {
     ProfScope ps(c, st, PC_HEAT, 0);
     CK(launch_hook_headmean(c->hook_headsb.as<float>(), c->hook_Bp, xl.heads, T, N, c->hook_scratch, st));
@@ -2132,7 +2147,7 @@ AGD_API int agd_set_context(agd_ctx* c, const float* ctx_emb, int batch2, int to
   API_CK(c, need_final(c));
   hipStream_t st = S(stream);
   const int Dc = c->cfg.cross_attention_dim;
-  if (tokens > 96) { agd_set_error("set_context: tokens %d > 96 unsupported", tokens); return fail_ctx(c); }
+  if (tokens > AGD_MAX_CONTEXT_TOKENS) { agd_set_error("set_context: tokens %d > %d unsupported", tokens, AGD_MAX_CONTEXT_TOKENS); return fail_ctx(c); }
   if (batch2 < 1 || tokens < 1) { agd_set_error("set_context: batch2 %d tokens %d", batch2, tokens); return fail_ctx(c); }
   // buffers only ever grow (capacity-tracked); a shorter/smaller context reuses the same blocks
   API_CK(c, c->ctxb.ensure((size_t)batch2 * tokens * Dc * 2)); c->ctx_bf16 = c->ctxb.as<bf16_t>();
@@ -2309,7 +2324,21 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
       for (int s = 0; s < N_COND_STATES; ++s) if (set[s] && r.with[s]) FAIL("%s", r.with[s]);
     }
   }
-  // (c) the entry points that run the UNet alone have refused every state they read; the latents must be all the UNet takes
+  // (c) a context beyond 96 tokens runs the plain UNet in the fused loops, agd_unet_forward_hw and agd_deepcache_forward_hw, recorded by DAAM alone
+  if (c->ctx_T > 96) {
+    const int T = c->ctx_T;
+    if (c->rec_mode == 2) FAIL("long context: the hook.py recorder takes contexts of at most 96 tokens (this one has %d)", T);
+    if (who == CALL_UNET_FORWARD_TS) FAIL("unet_forward_ts: a context of %d tokens is not supported (at most 96)", T);
+    if (who == CALL_PANORAMA) FAIL("denoise_panorama: a context of %d tokens is not supported (at most 96)", T);
+    static const struct { int st; const char* what; } kLong[] = {
+      {ST_CN, "a ControlNet schedule"}, {ST_GL, "a GLIGEN schedule"}, {ST_INP, "an inpainting state"}, {ST_I2P, "an InstructPix2Pix state"},
+      {ST_AD, "a T2I-Adapter schedule"}, {ST_IPA, "an IP-Adapter image"} };
+    for (const auto& k : kLong) {
+      if (!set[k.st] || (k.st == ST_INP && who != CALL_EVAL_LOOP) || (k.st == ST_I2P && who != CALL_IP2P_LOOP)) continue;   // (only where the caller reads the state)
+      FAIL("long context: %s is set; a context of %d tokens (over 96) runs the plain UNet only (clear it first)", k.what, T);
+    }
+  }
+  // the entry points that run the UNet alone have refused every state they read; the latents must be all the UNet takes
   if (who == CALL_PANORAMA && c->cfg.in_channels != c->cfg.out_channels)
     FAIL("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels);
   if (who == CALL_UNET_FORWARD_TS || who == CALL_PANORAMA) return 0;
@@ -2876,6 +2905,7 @@ AGD_API int agd_hook_reset(agd_ctx* c, int rows, int L, void* stream) {
   API_CK(c, need_final(c));
   if (c->rec_mode != 2) { agd_set_error("hook_reset: recorder is not in hook.py mode (agd_record_config(2, ..))"); return fail_ctx(c); }
   if (rows < 1 || L < 1) { agd_set_error("hook_reset: rows %d latent side %d", rows, L); return fail_ctx(c); }
+  if (c->ctx_T > 96) { agd_set_error("hook_reset: the hook.py recorder takes contexts of at most 96 tokens (this one has %d)", c->ctx_T); return fail_ctx(c); }
   API_CK(c, hook_reset_rows(c, rows, L, S(stream)));
   c->rec_B = c->rec_is_train ? (rows + 1) / 2 : rows; c->rec_L = c->rec_Lh = c->rec_Lw = L;
   return 0;
@@ -2887,6 +2917,9 @@ AGD_API int agd_record_reset_hw(agd_ctx* c, int batch, int Lh, int Lw, void* str
   if (batch < 1 || Lh < 1 || Lw < 1) { agd_set_error("record_reset: batch %d latent size %d x %d", batch, Lh, Lw); return fail_ctx(c); }
   if (c->rec_mode == 2 && Lh != Lw) { agd_set_error("record_reset: the hook.py recorder takes square latents only (got %d x %d)", Lh, Lw); return fail_ctx(c); }
   const int T = c->rec_T_cfg > 0 ? c->rec_T_cfg : c->cfg.max_tokens;
+  const bool long_ctx = c->ctx_T > 96;                 // attention_long.hip records per-head rows only: no head-group sums at any level
+  if (c->rec_mode == 2 && long_ctx) { agd_set_error("record_reset: the hook.py recorder takes contexts of at most 96 tokens (this one has %d)", c->ctx_T); return fail_ctx(c); }
+  if (c->rec_mode == 1 && long_ctx && T > c->ctx_T) { agd_set_error("record_reset: rec_tokens %d > the context's %d tokens", T, c->ctx_T); return fail_ctx(c); }
   c->rec_T = T;
   if (c->rec_mode == 1) {
     for (auto& xl : c->xl) {
@@ -2898,7 +2931,7 @@ AGD_API int agd_record_reset_hw(agd_ctx* c, int batch, int Lh, int Lw, void* str
       // daam averages clamp(bicubic(map), 0) over every (layer, head) map.  At latent resolution the resize is the identity and the
       // clamp cannot fire (sums of probabilities), so heads are summed in the recording kernel: down to 1/8 of the state and traffic
       xl.acc_heads = xl.heads;
-      if (xl.level == 0) {   // heads per workgroup: as many as still leave >= 256 workgroups (UNet batch x head groups x 128-query tiles)
+      if (xl.level == 0 && !long_ctx) {   // heads per workgroup: as many as still leave >= 256 workgroups (UNet batch x head groups x 128-query tiles)
         int hpb = xl.heads;
         while (hpb > 1 && hpb % 2 == 0 && (long long)2 * batch * (xl.heads / hpb) * ((h * w + 127) / 128) < 256) hpb /= 2;
         xl.acc_heads = xl.heads / hpb;
@@ -3006,6 +3039,7 @@ AGD_API int agd_attn_processor(agd_ctx* c, const char* layer, const float* hidde
     if (ctx_emb) API_CK(c, agd_set_context(c, ctx_emb, batch2, tokens, stream));
     else if (c->ctx_T <= 0) { agd_set_error("attn_processor: attn2 called without encoder_hidden_states and no context set"); return fail_ctx(c); }
     if (c->ctx_B2 != batch2) { agd_set_error("attn_processor: context batch %d != %d", c->ctx_B2, batch2); return fail_ctx(c); }
+    if (record && c->ctx_T > 96) { agd_set_error("attn_processor: recording takes contexts of at most 96 tokens (this one has %d)", c->ctx_T); return fail_ctx(c); }
   } else if (ctx_emb) {
     agd_set_error("attn_processor: attn1 is the self-attention module (encoder_hidden_states must be NULL)"); return fail_ctx(c);
   }
@@ -3091,6 +3125,7 @@ AGD_API int agd_attn_processor_backward(agd_ctx* c, const char* layer, const flo
   XLayer& xl = c->xl[it->second];
   if (ctx_emb) API_CK(c, agd_set_context(c, ctx_emb, batch2, tokens, stream));
   if (c->ctx_B2 != batch2 || c->ctx_T < 1) { agd_set_error("attn_processor_backward: context batch %d != %d", c->ctx_B2, batch2); return fail_ctx(c); }
+  if (c->ctx_T > 96) { agd_set_error("attn_processor_backward: takes contexts of at most 96 tokens (this one has %d)", c->ctx_T); return fail_ctx(c); }
   const int C = xl.C, H = xl.heads, D = C / H, T = c->ctx_T, M = batch2 * n_query, Dc = c->cfg.cross_attention_dim;
   const std::string t = xl.name.substr(0, xl.name.size() - 5);
   const WMat* wq = getW(c, t + "attn2.to_q.weight"); const WMat* wo = getW(c, t + "attn2.to_out.0.weight");
@@ -3555,6 +3590,47 @@ AGD_API int agd_op_attention_ex(const float* q, const float* k, const float* v, 
     a.rec = probs_out + (long long)rec_b0 * a.rec_img_stride;      // the kernel indexes the recording rows from rec_b0
   }
   CK(launch_attention(a, st));
+  CK(launch_bf16_to_f32(ob, o, nq, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
+// attention_long.hip alone (tests/test_attention_long_gpu.py): per-head recording at 97 .. AGD_MAX_CONTEXT_TOKENS keys.  Operands as
+// agd_op_attention_ex (packed fp32, rounded to bf16 here); layout 0 packed, 2 = k | v as the column blocks of one [B][Nk][2C] buffer, as the
+// engine's projected context lies.  probs_inout [B][H][Nk][Nq] is ADDED to (the caller zeroes it, or launches twice for 2 p): batch rows
+// >= rec_b0 and token rows < rec_T only.  Every refusal comes before any allocation or launch.  Syncs.
+AGD_API int agd_op_attention_long(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk, float scale,
+                                  int layout, float* probs_inout, int rec_b0, int rec_T, void* stream) {
+  if (D != 32 && D != 40 && D != 64 && D != 80 && D != 128 && D != 160) { agd_set_error("attention_long: unsupported head dim D=%d", D); return -1; }
+  if (Nk <= 96 || Nk > AGD_MAX_CONTEXT_TOKENS) { agd_set_error("attention_long: Nk=%d keys outside [97, %d]", Nk, AGD_MAX_CONTEXT_TOKENS); return -1; }
+  if (B < 1 || H < 1 || Nq < 1) { agd_set_error("attention_long: bad shape B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk); return -1; }
+  if (!q || !k || !v || !o || !probs_inout) { agd_set_error("attention_long: q, k, v, o and probs_inout are required"); return -1; }
+  if (layout != 0 && layout != 2) { agd_set_error("attention_long: layout=%d (0 packed, 2 fused k|v rows)", layout); return -1; }
+  if (rec_b0 < 0 || rec_b0 > B) { agd_set_error("attention_long: rec_b0=%d outside [0, %d]", rec_b0, B); return -1; }
+  if (rec_T < 1 || rec_T > Nk) { agd_set_error("attention_long: rec_T=%d outside [1, %d]", rec_T, Nk); return -1; }
+  hipStream_t st = S(stream); Tmp tmp;
+  const int C = H * D;
+  const long long nq = (long long)B * Nq * C, nk = (long long)B * Nk * C;
+  bf16_t* qb = tmp.get<bf16_t>((size_t)nq); bf16_t* kb = tmp.get<bf16_t>((size_t)nk); bf16_t* vb = tmp.get<bf16_t>((size_t)nk);
+  bf16_t* ob = tmp.get<bf16_t>((size_t)nq);
+  bf16_t* fused = layout ? tmp.get<bf16_t>((size_t)2 * nk) : nullptr;
+  if (!qb || !kb || !vb || !ob || (layout && !fused)) return -1;
+  CK(launch_f32_to_bf16(q, qb, nq, st));
+  CK(launch_f32_to_bf16(k, kb, nk, st));
+  CK(launch_f32_to_bf16(v, vb, nk, st));
+  AttnP a{}; a.q = qb; a.k = kb; a.v = vb; a.o = ob; a.ldq = a.ldk = a.ldv = a.ldo = C;
+  a.sq = (long long)Nq * C; a.so = a.sq; a.sk = (long long)Nk * C; a.sv = a.sk;
+  if (layout == 2) {
+    for (int col = 0; col < 2; ++col)
+      if (hipMemcpy2DAsync(fused + (size_t)col * C, (size_t)2 * C * 2, col ? vb : kb, (size_t)C * 2, (size_t)C * 2, (size_t)B * Nk, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        agd_set_error("attention_long: layout copy failed"); return -1; }
+    a.k = fused; a.v = fused + C; a.ldk = a.ldv = 2 * C; a.sk = a.sv = (long long)Nk * 2 * C;
+  }
+  a.B = B; a.H = H; a.D = D; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
+  a.record_mode = 1; a.rec_b0 = rec_b0; a.rec_T = rec_T;
+  a.rec_head_stride = (long long)Nk * Nq; a.rec_img_stride = a.rec_head_stride * H;
+  a.rec = probs_inout + (long long)rec_b0 * a.rec_img_stride;      // the kernel indexes the recording rows from rec_b0
+  CK(launch_attention_long(a, st));
   CK(launch_bf16_to_f32(ob, o, nq, st));
   hipStreamSynchronize(st);
   return 0;

@@ -329,6 +329,10 @@ def parse_args(argv=None):
                         "shallowest layers on the cached deep features (1: off; 2 - 3 suggested at 50 steps); plain txt2img only")
     p.add_argument("--deepcache-branch", type=int, default=None, metavar="B",
                    help="DeepCache: the layers 0 .. B of the first down block run on a shallow evaluation (default 0); needs --deepcache-interval")
+    p.add_argument("--max-embeddings-multiples", type=int, default=None, metavar="M", choices=[1, 2, 3, 4],
+                   help="weighted and long prompts (lpw_stable_diffusion's rules): in the prompt, after its placeholders are filled, (x) weighs "
+                        "x by 1.1, [x] by 1 / 1.1, (x:w) by w, and up to 75 M tokens are kept (contexts of 77, 152, 227, 302 rows); heat maps "
+                        "follow the weight-stripped tokens; plain txt2img only (default: off, parentheses are literal, 75 tokens)")
     p.add_argument("--timestep-spacing", type=str, default=None, choices=["leading", "trailing", "linspace"],
                    help="the scheduler's timestep grid (default: the checkpoint's; DDIM and img2img take all three, DPM-Solver++ its own "
                         "three, PNDM runs 'leading' only)")
@@ -348,6 +352,11 @@ def parse_args(argv=None):
                            or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama or args.guidance_rescale):
         p.error("--pag-scale with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
                 "--gligen-phrases / --gligen-layouts, --panorama or --guidance-rescale is not implemented")
+    if args.max_embeddings_multiples is not None and (
+            args.controlnet_model_path or args.adapter_model_path or args.ip_adapter_path or args.init_image or args.instruct_image
+            or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama):
+        p.error("--max-embeddings-multiples with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
+                "--gligen-phrases / --gligen-layouts or --panorama is not implemented")
     if args.deepcache_branch is not None and args.deepcache_interval is None:
         p.error("--deepcache-branch needs --deepcache-interval N")
     if args.deepcache_interval is not None and args.deepcache_interval < 1:
@@ -671,6 +680,8 @@ def main(argv=None):
                 control = dict(control or {}, guidance_rescale=args.guidance_rescale)
             if args.pag_scale:
                 control = dict(control or {}, pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale)
+            if args.max_embeddings_multiples is not None:
+                control = dict(control or {}, max_embeddings_multiples=args.max_embeddings_multiples)
             imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
                                        height=height, width=width)
         if not gather:

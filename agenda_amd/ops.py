@@ -217,6 +217,30 @@ def attention(q, k, v, heads, scale=None, return_probs=False, *, causal=False, m
     return (o, probs) if return_probs else o
 
 
+def attention_long(q, k, v, heads, scale=None, *, layout=0, rec_b0=0, rec_T=None, probs=None):
+    """The recording kernel for 97..320 keys alone (`agd_op_attention_long`, csrc/attention_long.hip): q [B,Nq,H*D], k/v [B,Nk,H*D] ->
+    (o [B,Nq,H*D], probs [B,H,Nk,Nq]).  layout 0 packed, 2 k|v as column blocks of one [B,Nk,2C] buffer.  Only batch rows >= rec_b0 and
+    token rows < rec_T (default Nk) are recorded.  The kernel ADDS, as it does into the DAAM accumulators: `probs` given = added to in
+    place, else a zeroed tensor."""
+    lib = _lib.load()
+    q, k, v = _f32c(q), _f32c(k), _f32c(v)
+    B, Nq, Cc = q.shape
+    Nk = k.shape[1]
+    if k.shape != (B, Nk, Cc) or v.shape != k.shape:
+        raise ValueError(f"attention_long: k {tuple(k.shape)} / v {tuple(v.shape)} must both be [B, Nk, H*D] = [{B}, Nk, {Cc}]")
+    D = Cc // heads
+    scale = D ** -0.5 if scale is None else scale
+    o = torch.empty_like(q)
+    if probs is None:
+        probs = torch.zeros(B, heads, max(Nk, 1), max(Nq, 1), device=q.device, dtype=torch.float32)
+    elif tuple(probs.shape) != (B, heads, Nk, Nq) or probs.dtype != torch.float32 or not probs.is_contiguous() or not probs.is_cuda:
+        raise ValueError(f"attention_long: probs must be a contiguous fp32 GPU tensor {(B, heads, Nk, Nq)}")
+    _lib.check(lib.agd_op_attention_long(_lib.ptr(_given(q)), _lib.ptr(_given(k)), _lib.ptr(_given(v)), _lib.ptr(_given(o)), B, heads, D, Nq, Nk,
+                                         float(scale), int(layout), _lib.ptr(probs), int(rec_b0), Nk if rec_T is None else int(rec_T),
+                                         _lib.current_stream_ptr()), None, "agd_op_attention_long")
+    return o, probs
+
+
 def attention_headsum(q, k, v, heads, scale=None):
     """As `attention(..., return_probs=True)` with the probabilities summed over the heads: probs [B,Nk,Nq] (Nk<=96) -- the form
     the daam recorder keeps for the layers at latent resolution."""

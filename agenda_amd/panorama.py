@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag
 from .scheduler import DDIMScheduler
 
 STRIDE = 8            # latent pixels between views (diffusers get_views default)
@@ -75,9 +75,11 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
                  circular_padding: bool = False, negative_prompt=None, num_images_per_prompt: int = 1,
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
-                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 max_embeddings_multiples: Optional[int] = None):
         refuse_pag("StableDiffusionPanoramaPipeline", pag_scale, pag_adaptive_scale)
         refuse_deepcache("StableDiffusionPanoramaPipeline", getattr(self, "_deepcache", None))
+        refuse_long_prompt("StableDiffusionPanoramaPipeline", max_embeddings_multiples, prompt_embeds)
         if guidance_rescale:
             raise ValueError(f"guidance_rescale={guidance_rescale!r}: guidance rescale is not implemented for the panorama pipeline "
                              "(its views are stepped one by one); leave it 0")

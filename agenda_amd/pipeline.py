@@ -109,6 +109,20 @@ def refuse_deepcache(pipeline: str, deepcache, what: str = "") -> None:
                          "call disable_deepcache() first")
 
 
+LONG_CONTEXT = 96      # tokens up to which every pipeline, recorder and adapter runs; beyond, StableDiffusionPipeline's txt2img / img2img only
+
+
+def refuse_long_prompt(pipeline: str, max_embeddings_multiples, prompt_embeds) -> None:
+    """The pipelines that run something beside the plain UNet refuse weighted / long prompts by name: the argument, and given
+    prompt_embeds of more than 96 tokens (the engine's fused attn2 forms and their recorders stop there)."""
+    if max_embeddings_multiples is not None:
+        raise ValueError(f"max_embeddings_multiples={max_embeddings_multiples!r}: weighted and long prompts are not implemented for {pipeline} "
+                         "(StableDiffusionPipeline's txt2img and img2img run them); leave it None")
+    if prompt_embeds is not None and prompt_embeds.shape[1] > LONG_CONTEXT:
+        raise ValueError(f"prompt_embeds of {prompt_embeds.shape[1]} tokens: a context over {LONG_CONTEXT} tokens is not implemented for {pipeline} "
+                         "(StableDiffusionPipeline's txt2img and img2img run it)")
+
+
 def refuse_deepcache_beside(deepcache, pag_scale: float, ip_adapter, ip_adapter_image, ip_adapter_image_embeds) -> None:
     """What a txt2img / img2img call can carry that the shallow walk does not, decided from the call's arguments alone, before any device
     work: a non-zero pag_scale, and an image prompt for a loaded IP-Adapter whose scale is not 0 (`ip_adapter`: the pipeline's adapter
@@ -1015,6 +1029,7 @@ class StableDiffusionPipeline:
         self._trace = None
         self._hooker = None
         self._last_prompt = None
+        self._last_tokens = None          # the weight-stripped token stream of the last weighted prompt (max_embeddings_multiples), else None
         self._progress = {}
         self._lora = None                 # load_lora_weights: {"targets": n, "fused": scale or None}
         self._ip_adapter = None           # load_ip_adapter: {"embed_dim": E, "n_tokens": n, "scale": s}
@@ -1415,20 +1430,47 @@ class StableDiffusionPipeline:
     def encode_prompt(self, prompts: List[str], negative: Optional[List[str]] = None) -> torch.Tensor:
         """[uncond x B, cond x B] context, the CFG batch order (hook.py:48-49)."""
         neg = negative if negative is not None else [""] * len(prompts)
-        self._last_prompt = prompts[0]
+        self._last_prompt, self._last_tokens = prompts[0], None
         return torch.cat([self.text_encoder(neg), self.text_encoder(prompts)], 0)
 
-    def _expand_prompts(self, prompt, negative_prompt, num_images_per_prompt: int, prompt_embeds: Optional[torch.Tensor]):
+    def encode_prompt_weighted(self, prompts: List[str], negative: Optional[List[str]], max_embeddings_multiples: int) -> torch.Tensor:
+        """`encode_prompt` through the weighted / long-prompt encoder (lpw.py): [uncond x B, cond x B] of T = 75 m_eff + 2 rows."""
+        from . import lpw
+        neg = negative if negative is not None else [""] * len(prompts)
+        emb, toks = lpw.encode_weighted(self.tokenizer, self.text_encoder, prompts, neg, max_embeddings_multiples)
+        self._last_prompt, self._last_tokens = prompts[0], toks
+        return emb
+
+    def _expand_prompts(self, prompt, negative_prompt, num_images_per_prompt: int, prompt_embeds: Optional[torch.Tensor],
+                        max_embeddings_multiples: Optional[int] = None):
         """The call's context and how it was batched: (prompt_embeds, prompt batch, images per prompt).  `prompt` is a string or a list,
         every entry repeated num_images_per_prompt times; `negative_prompt` a string (for every row) or one entry per row.  Given
-        `prompt_embeds` are taken as they are, one image per row."""
+        `prompt_embeds` are taken as they are, one image per row.  max_embeddings_multiples: None = the plain encoder (parentheses stay
+        literal, 75 tokens), 1 .. 4 = the weighted one for prompt and negative_prompt."""
         if prompt_embeds is not None:
             return prompt_embeds, prompt_embeds.shape[0] // 2, 1
         prompts = [prompt] if isinstance(prompt, str) else list(prompt)
         pb = len(prompts)
         prompts = [p for p in prompts for _ in range(num_images_per_prompt)]
         negs = None if negative_prompt is None else ([negative_prompt] * len(prompts) if isinstance(negative_prompt, str) else list(negative_prompt))
+        if max_embeddings_multiples is not None:
+            return self.encode_prompt_weighted(prompts, negs, max_embeddings_multiples), pb, num_images_per_prompt
         return self.encode_prompt(prompts, negs), pb, num_images_per_prompt
+
+    def _refuse_long_beside(self, prompt_embeds: torch.Tensor, max_embeddings_multiples, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        """Weighted / long prompts run the plain UNet recorded by trace() alone: an installed hooker and an active IP-Adapter refuse the
+        argument, and a context over 96 tokens."""
+        T = prompt_embeds.shape[1]
+        if T <= LONG_CONTEXT and max_embeddings_multiples is None:
+            return
+        what = f"max_embeddings_multiples={max_embeddings_multiples!r}" if max_embeddings_multiples is not None else f"a context of {T} tokens (over {LONG_CONTEXT})"
+        if self._hooker is not None:
+            raise ValueError(f"a UNetCrossAttentionHooker is installed: {what} is not implemented with it (weighted / long prompts record "
+                             "through trace()); remove it with unet.set_attn_processor('default')")
+        st = getattr(self, "_ip_adapter", None)
+        if (ip_adapter_image is not None or ip_adapter_image_embeds is not None) and st is not None and st["scale"] != 0.0:
+            raise ValueError(f"an active IP-Adapter (scale {st['scale']!r}): {what} is not implemented with it; "
+                             "leave the image prompt out or set_ip_adapter_scale(0)")
 
     def _draw_latents(self, B: int, Lh: int, Lw: int, generator, latents: Optional[torch.Tensor]) -> torch.Tensor:
         """The initial latents [B, C, Lh, Lw] on the device, scaled by the scheduler's init_noise_sigma: `latents` when given, else drawn."""
@@ -1454,10 +1496,13 @@ class StableDiffusionPipeline:
         """Sets the call's context and, with a tracer or a hooker installed, starts their recording of B images at latent size L."""
         self.engine.set_context(prompt_embeds)
         self._apply_record_mode()
+        T = prompt_embeds.shape[1]
+        if self._trace is not None and T > LONG_CONTEXT:       # a long context records its T rows, unless the tracer was given rec_tokens
+            self.engine.record_config(1, False, self._trace._rows_for(T))
         if self._trace is not None or self._hooker is not None:
             self.engine.record_reset(B, L)
             if self._trace is not None:
-                self._trace._on_generate(B, L, self._last_prompt)
+                self._trace._on_generate(B, L, self._last_prompt, tokens=self._last_tokens, context_tokens=T)
             if self._hooker is not None:
                 self._hooker._on_generate(B, L, prompt_embeds.shape[1])
 
@@ -1468,7 +1513,10 @@ class StableDiffusionPipeline:
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
                  cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 max_embeddings_multiples: Optional[int] = None):
+        from .lpw import check_multiples
+        check_multiples(max_embeddings_multiples)
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
         check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
@@ -1480,8 +1528,9 @@ class StableDiffusionPipeline:
         Lh, Lw = height // self.vae_scale_factor, width // self.vae_scale_factor
         self._refuse_rectangular_hook(Lh, Lw)
         L = Lh if Lh == Lw else (Lh, Lw)                       # the square path passes one side, exactly as before
-        prompt_embeds, pb, ipp = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds)
+        prompt_embeds, pb, ipp = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, max_embeddings_multiples)
         B = prompt_embeds.shape[0] // 2
+        self._refuse_long_beside(prompt_embeds, max_embeddings_multiples, ip_adapter_image, ip_adapter_image_embeds)
         self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
         self._begin_recording(prompt_embeds, B, L)
@@ -1590,9 +1639,12 @@ class StableDiffusionPipeline:
                 guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None, prompt_embeds: Optional[torch.Tensor] = None,
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+                guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                max_embeddings_multiples: Optional[int] = None):
         """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
+        from .lpw import check_multiples
+        check_multiples(max_embeddings_multiples)
         # img2img runs the strength-truncated DDIM schedule.  A checkpoint whose own scheduler is PNDM (SD-1.x) or DPM-Solver++ gets a
         # DDIM scheduler built from the same scheduler config for this call (the reference has no img2img call site; strength-truncated
         # PLMS and DPM-Solver++ img2img are not implemented)
@@ -1612,7 +1664,9 @@ class StableDiffusionPipeline:
         L = Lh if Lh == Lw else (Lh, Lw)
         if prompt_embeds is None:
             prompts = [prompt] * B if isinstance(prompt, str) else list(prompt)
-            prompt_embeds = self.encode_prompt(prompts)
+            prompt_embeds = self.encode_prompt(prompts) if max_embeddings_multiples is None else \
+                self.encode_prompt_weighted(prompts, None, max_embeddings_multiples)
+        self._refuse_long_beside(prompt_embeds, max_embeddings_multiples, ip_adapter_image, ip_adapter_image_embeds)
         self._apply_ip_adapter(B, B, 1, ip_adapter_image, ip_adapter_image_embeds)
         shape = (B, self.cfg.unet.out_channels, Lh, Lw)
         if generator is not None and generator.device.type != "cpu":

@@ -109,6 +109,12 @@ class SyntheticTextEncoder:
         x = torch.stack(rows)
         return x.to(torch.bfloat16).to(torch.float32)
 
+    def encode_ids(self, ids: torch.Tensor) -> torch.Tensor:
+        """ids [n, 77] -> [n, 77, D]: what `__call__` computes from the ids of its prompts (the chunks of a long prompt, lpw.py)"""
+        self.resize_token_embeddings(len(self.tokenizer))
+        x = self._table[ids.to(torch.int64)] + self._pos
+        return x.to(torch.bfloat16).to(torch.float32)
+
 
 class HipCLIPTextEncoder:
     """`pipeline.text_encoder` on the GPU (agd_text_encode: CLIP text transformer as HIP kernels).  Keeps the
@@ -151,3 +157,11 @@ class HipCLIPTextEncoder:
         for tid in range(self.base_vocab, self._emb.weight.shape[0]):        # learned / added tokens
             self.engine.text_set_embedding_row(tid, self._emb.weight[tid])
         return self.engine.text_encode(self._ids(prompts)).cpu()
+
+    def encode_ids(self, ids: torch.Tensor) -> torch.Tensor:
+        """ids [n, 77] -> [n, 77, D] in one agd_text_encode call (the chunks of a long prompt, lpw.py)"""
+        for tid in range(self.base_vocab, self._emb.weight.shape[0]):
+            self.engine.text_set_embedding_row(tid, self._emb.weight[tid])
+        if isinstance(self.tokenizer, SimpleTokenizer):                  # (the stand-in's ids grow with its vocabulary, as in _ids)
+            ids = ids.clamp(max=self._emb.weight.shape[0] - 1)
+        return self.engine.text_encode(ids.to(torch.int32).contiguous()).cpu()

@@ -61,7 +61,14 @@ int agd_load_tensor(agd_ctx* ctx, const char* name, const void* ptr, int dtype, 
 int agd_finalize(agd_ctx* ctx);                    /* after the last agd_load_tensor */
 
 /* ---- text context: `encoder_hidden_states` [2B, T, ctx_dim] fp32, rows [0,B) unconditional,
- * [B,2B) conditional (CFG order assumed by hook.py:48-49).  Projects K/V of every attn2 once. */
+ * [B,2B) conditional (CFG order assumed by hook.py:48-49).  Projects K/V of every attn2 once.
+ * T <= AGD_MAX_CONTEXT_TOKENS.  Up to 96 tokens everything runs as it always has.  Beyond (long and weighted prompts: 152 / 227 / 302 rows)
+ * attn2 runs to_q, attention, to_out as separate launches, DAAM records per-head rows at every level through csrc/attention_long.hip --
+ * call agd_record_reset AFTER agd_set_context, rec_tokens up to T -- and the fused loops (img2img, LoRA, FreeU, guidance_rescale, PAG,
+ * DeepCache, rectangular sizes included), agd_unet_forward_hw and agd_deepcache_forward_hw take it.  Refused by name with such a context: the
+ * hook.py recorder, recording through agd_attn_processor / agd_cross_attn, agd_attn_processor_backward, agd_unet_forward_ts*,
+ * agd_denoise_panorama, and a set ControlNet, GLIGEN, inpainting, InstructPix2Pix, T2I-Adapter or IP-Adapter state. */
+#define AGD_MAX_CONTEXT_TOKENS 320
 int agd_set_context(agd_ctx* ctx, const float* ctx_emb, int batch2, int tokens, void* stream);
 
 /* ---- `text_encoder(input_ids)[0]` (CLIPTextModel.last_hidden_state): ids int32 [B, T] (host or device) ->
@@ -363,7 +370,11 @@ int agd_set_option(agd_ctx* ctx, const char* name, int value);
  * mode 0 off; 1 DAAM (per-layer/head time sums, mid block excluded, conditional half);
  * 2 HOOK (hook.py: head-mean per call, every attn2 incl. mid; is_train=1 keeps all batch rows).
  * rec_tokens: token rows recorded (<= tokens; rows beyond len(prompt)+2 are never read by daam); takes effect at the
- * next agd_record_reset, which (re)sizes the accumulators for it. */
+ * next agd_record_reset, which (re)sizes the accumulators for it.
+ * A context beyond 96 tokens (agd_set_context): mode 1 only, rec_tokens up to the context's T (larger is refused by agd_record_reset), the
+ * accumulators hold per-head rows at every level (no head-group sums at latent resolution) and are written by csrc/attention_long.hip.
+ * Accumulators sized before the context was set, for head-group sums or for more rows than it has, make the next recording call fail
+ * by name ("reset after agd_set_context"); mode 2 is refused by agd_record_reset / agd_hook_reset and by the calls themselves. */
 int agd_record_config(agd_ctx* ctx, int mode, int is_train, int rec_tokens);
 int agd_record_reset(agd_ctx* ctx, int batch, int latent_side, void* stream);   /* hooker.clear() / new trace */
 /* DAAM: layer accumulators of (latent_h / f) x (latent_w / f), f = 2^level; agd_daam_global then writes [rows][latent_h][latent_w].
@@ -488,6 +499,13 @@ int agd_op_attention(const float* q, const float* k, const float* v, float* o, i
 int agd_op_attention_ex(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk, float scale,
                         int causal, const float* mask, const float* k2, const float* v2, int Nk2, int layout, float* probs_out,
                         int record, int rec_b0, int rec_T, void* stream);
+/* The recording kernel for contexts beyond 96 tokens alone (csrc/attention_long.hip: two passes over 64-key tiles, so that the recorded
+ * probabilities are divided by the row sum over ALL keys).  Operands as agd_op_attention_ex; 97 <= Nk <= AGD_MAX_CONTEXT_TOKENS; layout 0
+ * packed or 2 (k | v as the column blocks of one [B,Nk,2C] buffer).  probs_inout [B,H,Nk,Nq] is ADDED to, as the DAAM accumulators are (the
+ * caller zeroes it): batch rows >= rec_b0 (0 .. B) and token rows < rec_T (1 .. Nk) only; the rest is not touched.  Refusals come with a
+ * message, before anything is launched.  Syncs. */
+int agd_op_attention_long(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk, float scale,
+                          int layout, float* probs_inout, int rec_b0, int rec_T, void* stream);
 /* same, the probabilities summed over the heads (the recording form of the daam layers at latent resolution): probs_sum_out [B,Nk,Nq] */
 int agd_op_attention_headsum(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                              float scale, float* probs_sum_out, void* stream);
