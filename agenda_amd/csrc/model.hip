@@ -3408,9 +3408,21 @@ AGD_API int agd_op_layernorm(const float* x, const float* gamma, const float* be
 // b1 [8C], w2 [C][4C], b2 [C], x / y [M][C] fp32 (x is rounded to bf16 first, as the residual stream is stored)
 AGD_API int agd_op_ff_fused(const float* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2,
                             const float* b2, float* y, int M, int C, float eps, void* stream) {
+  return agd_op_ff_fused_ex(x, gamma, beta, w1, b1, w2, b2, y, M, C, eps, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, stream);
+}
+// agd_op_ff_fused reaching every form of launch_ff_fused.  wp != null: the proj_out stage -- pout [M][C] = (x + FF(x)) . wp^T + bp + xres, xres
+// [xres_rows > 0 ? xres_rows : M][C] (output row m adds row m % xres_rows), y is then not written (may be null); premul: w2 is the caller's
+// Wp W2 [C][4C] and bp the caller's Wp b2 + bp (b2 is not read).  colstat (optional, with wp): [ceil(M / 128)][C][2] device floats, left as the
+// kernel writes them.  inplace: the launch runs with out == h, as the transformer runs it.
+AGD_API int agd_op_ff_fused_ex(const float* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2,
+                               const float* b2, float* y, int M, int C, float eps, const float* wp, const float* bp, const float* xres,
+                               int xres_rows, float* pout, int premul, float* colstat, int inplace, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;
   if (C != 320) { agd_set_error("op_ff_fused: C = %d (320 only)", C); return -1; }
+  if (M < 1 || xres_rows < 0 || !x || !gamma || !beta || !w1 || !b1 || !w2 || !b2 || (!wp && !y)) { agd_set_error("op_ff_fused: bad arguments (M %d xres_rows %d)", M, xres_rows); return -1; }
+  if (colstat && !wp) { agd_set_error("op_ff_fused: colstat belongs to the proj_out stage"); return -1; }
   const int H8 = 8 * C, H4 = 4 * C;
+  const long long xr_rows = xres_rows > 0 ? xres_rows : M;
   bf16_t* xb = tmp.get<bf16_t>((size_t)M * C); bf16_t* yb = tmp.get<bf16_t>((size_t)M * C);
   bf16_t* w1b = tmp.get<bf16_t>((size_t)H8 * C); bf16_t* w1l = tmp.get<bf16_t>((size_t)H8 * C); bf16_t* w1f = tmp.get<bf16_t>((size_t)H8 * C);
   bf16_t* w2b = tmp.get<bf16_t>((size_t)C * H4); bf16_t* w2f = tmp.get<bf16_t>((size_t)C * H4);
@@ -3422,9 +3434,24 @@ AGD_API int agd_op_ff_fused(const float* x, const float* gamma, const float* bet
   CK(launch_frag_order_w1(w1l, w1f, C, H4, st));
   CK(launch_convert_weight(w2, w2b, C, H4, 1, H4, 0, st));
   CK(launch_frag_order_w(w2b, w2f, C, H4, C / 64, 128, st));
-  FFusedP fp{}; fp.h = xb; fp.out = yb; fp.w1f = w1f; fp.cs1 = cs; fp.b1 = bf; fp.w2f = w2f; fp.b2 = b2; fp.M = M; fp.ln_eps = eps;
+  FFusedP fp{}; fp.h = xb; fp.out = inplace ? xb : yb; fp.w1f = w1f; fp.cs1 = cs; fp.b1 = bf; fp.w2f = w2f; fp.b2 = b2; fp.M = M; fp.ln_eps = eps;
+  bf16_t* pb = nullptr;
+  fp.premul = premul ? 1 : 0; fp.xres_rows = xres_rows; fp.colstat = colstat; fp.bp = bp;
+  if (wp) {
+    bf16_t* wpb = tmp.get<bf16_t>((size_t)C * C); bf16_t* wpf = tmp.get<bf16_t>((size_t)C * C); pb = tmp.get<bf16_t>((size_t)M * C);
+    if (!wpb || !wpf || !pb) return -1;
+    CK(launch_convert_weight(wp, wpb, C, C, 1, C, 0, st));
+    CK(launch_frag_order_w(wpb, wpf, C, C, C / 64, C, st));
+    fp.wpf = wpf; fp.pout = pout ? pb : nullptr;
+    if (xres) {
+      bf16_t* xrb = tmp.get<bf16_t>((size_t)xr_rows * C); if (!xrb) return -1;
+      CK(launch_f32_to_bf16(xres, xrb, xr_rows * C, st));
+      fp.xres = xrb;
+    }
+  }
   CK(launch_ff_fused(fp, C, st));
-  CK(launch_bf16_to_f32(yb, y, (long long)M * C, st));
+  if (wp) CK(launch_bf16_to_f32(pb, pout, (long long)M * C, st));
+  else CK(launch_bf16_to_f32(fp.out, y, (long long)M * C, st));
   hipStreamSynchronize(st);
   return 0;
 }
@@ -3434,26 +3461,104 @@ AGD_API int agd_op_ff_fused(const float* x, const float* gamma, const float* bet
 // over the heads (the recorder's head-group form, all images recording)
 AGD_API int agd_op_attn_chain(const float* x, const float* gamma, const float* beta, const float* wq, const float* kv, const float* wo,
                               const float* bo, float* y, float* probs_sum, int B, int HW, int T, int C, int heads, float eps, void* stream) {
+  hipStream_t st = S(stream);
+  const int rows32 = (heads >> 8) & 1; heads &= 255;     // (bit 8 of `heads`: the 32-row panel form of the C = 640 kernel, tests)
+  if (probs_sum && B > 0 && T > 0 && HW > 0 && hipMemsetAsync(probs_sum, 0, (size_t)B * T * HW * 4, st) != hipSuccess) { agd_set_error("memset probs"); return -1; }
+  return agd_op_attn_chain_ex(x, gamma, beta, wq, kv, wo, bo, y, B, HW, T, C, heads, eps, nullptr, nullptr, nullptr, nullptr, 0, nullptr, probs_sum, 8, 0, T, T,
+                              rows32, 0, stream);
+}
+// agd_op_attn_chain reaching every form of launch_attn_chain.  o1 != null: the prologue h1 = o1 . wo1^T + bo1 + x runs first (o1 has x's rows);
+// h1 (optional) receives it -- the kernel overwrites its stored h1 with the final rows, so the entry takes it from a launch of its own with
+// to_out's matrix and bias zeroed, whose output is h1 bit for bit (0 + 0 + h1, rounded again to the bf16 value it already is).  src_rows > 0:
+// x / o1 hold src_rows rows and output row m reads input row m % src_rows.  rowstat (optional): [B * HW][2] device floats.  rec (optional): the
+// recorder rows [B - rec_b0][8 / rec_hpb][rec_rows][HW] device floats, ADDED to as the kernel does (never zeroed here); token rows >= rec_T are
+// left alone (rec_T <= rec_rows).  inplace: out == h.
+AGD_API int agd_op_attn_chain_ex(const float* x, const float* gamma, const float* beta, const float* wq, const float* kv, const float* wo,
+                                 const float* bo, float* y, int B, int HW, int T, int C, int heads, float eps, const float* o1, const float* wo1,
+                                 const float* bo1, float* h1, int src_rows, float* rowstat, float* rec, int rec_hpb, int rec_b0, int rec_T,
+                                 int rec_rows, int rows32, int inplace, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;
-  const long long M = (long long)B * HW;
-  bf16_t* xb = tmp.get<bf16_t>((size_t)M * C); bf16_t* yb = tmp.get<bf16_t>((size_t)M * C); bf16_t* kvb = tmp.get<bf16_t>((size_t)B * T * 2 * C);
+  if (C != 320 && C != 640) { agd_set_error("op_attn_chain: C %d", C); return -1; }
+  if (B < 1 || HW < 1 || (long long)B * HW >= (1LL << 31) || T < 0 || src_rows < 0 || !x || !gamma || !beta || !wq || !kv || !wo || !bo || !y) { agd_set_error("op_attn_chain: bad arguments (B %d HW %d T %d src_rows %d)", B, HW, T, src_rows); return -1; }
+  if (o1 && (!wo1 || !bo1)) { agd_set_error("op_attn_chain: the prologue needs wo1 and bo1"); return -1; }
+  if (h1 && !o1) { agd_set_error("op_attn_chain: h1 is the prologue's"); return -1; }
+  if (rec && (rec_b0 < 0 || rec_b0 > B || rec_T < 1 || rec_T > rec_rows)) { agd_set_error("op_attn_chain: recorder rows b0 %d T %d of %d", rec_b0, rec_T, rec_rows); return -1; }
+  const long long M = (long long)B * HW, Min = src_rows > 0 ? src_rows : M;
+  bf16_t* xb = tmp.get<bf16_t>((size_t)Min * C); bf16_t* yb = tmp.get<bf16_t>((size_t)M * C); bf16_t* kvb = tmp.get<bf16_t>((size_t)B * T * 2 * C);
   bf16_t* wqb = tmp.get<bf16_t>((size_t)C * C); bf16_t* wqf = tmp.get<bf16_t>((size_t)C * C);
   bf16_t* wob = tmp.get<bf16_t>((size_t)C * C); bf16_t* wof = tmp.get<bf16_t>((size_t)C * C);
   if (!xb || !yb || !kvb || !wqb || !wqf || !wob || !wof) return -1;
-  if (C != 320 && C != 640) { agd_set_error("op_attn_chain: C %d", C); return -1; }
-  CK(launch_f32_to_bf16(x, xb, M * C, st));
-  CK(launch_f32_to_bf16(kv, kvb, (long long)B * T * 2 * C, st));
+  CK(launch_f32_to_bf16(x, xb, Min * C, st));
+  if (T > 0) CK(launch_f32_to_bf16(kv, kvb, (long long)B * T * 2 * C, st));
   CK(launch_convert_weight(wq, wqb, C, C, 1, C, 0, st)); CK(launch_frag_order_w(wqb, wqf, C, C, 5, C, st));
   CK(launch_convert_weight(wo, wob, C, C, 1, C, 0, st)); CK(launch_frag_order_w(wob, wof, C, C, 5, C, st));
-  AttnChainP ap{}; ap.h = xb; ap.out = yb; ap.gamma = gamma; ap.beta = beta; ap.ln_eps = eps; ap.wqf = wqf; ap.wof = wof; ap.bo = bo;
-  ap.rows32 = (heads >> 8) & 1; heads &= 255;            // (bit 8 of `heads`: the 32-row panel form of the C = 640 kernel, tests)
-  ap.kv = kvb; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = (int)M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)(C / heads));
-  if (probs_sum) {
-    if (hipMemsetAsync(probs_sum, 0, (size_t)B * T * HW * 4, st) != hipSuccess) { agd_set_error("memset probs"); return -1; }
-    ap.record = 1; ap.rec = probs_sum; ap.rec_b0 = 0; ap.rec_T = T; ap.rec_hpb = heads; ap.rec_head_stride = (long long)T * HW; ap.rec_img_stride = (long long)T * HW;
+  AttnChainP ap{}; ap.h = xb; ap.out = inplace ? xb : yb; ap.gamma = gamma; ap.beta = beta; ap.ln_eps = eps; ap.wqf = wqf; ap.wof = wof; ap.bo = bo;
+  ap.rows32 = rows32; ap.src_rows = src_rows;
+  ap.kv = kvb; ap.ldkv = 2 * C; ap.skv = (long long)T * 2 * C; ap.M = (int)M; ap.HW = HW; ap.T = T; ap.scale = 1.0f / sqrtf((float)(heads > 0 ? C / heads : C));
+  if (o1) {
+    bf16_t* o1b = tmp.get<bf16_t>((size_t)Min * C); bf16_t* w1b = tmp.get<bf16_t>((size_t)C * C); bf16_t* w1f = tmp.get<bf16_t>((size_t)C * C);
+    if (!o1b || !w1b || !w1f) return -1;
+    CK(launch_f32_to_bf16(o1, o1b, Min * C, st));
+    CK(launch_convert_weight(wo1, w1b, C, C, 1, C, 0, st)); CK(launch_frag_order_w(w1b, w1f, C, C, 5, C, st));
+    ap.o1 = o1b; ap.wo1f = w1f; ap.bo1 = bo1;
+  }
+  if (h1) {                                              // (nothing recorded, no statistics: the launch below is the one under test)
+    bf16_t* zw = tmp.get<bf16_t>((size_t)C * C); float* zb = tmp.get<float>(C); bf16_t* hb = tmp.get<bf16_t>((size_t)M * C);
+    if (!zw || !zb || !hb) return -1;
+    if (hipMemsetAsync(zw, 0, (size_t)C * C * 2, st) != hipSuccess || hipMemsetAsync(zb, 0, (size_t)C * 4, st) != hipSuccess) { agd_set_error("op_attn_chain: memset"); return -1; }
+    AttnChainP a1 = ap; a1.wof = zw; a1.bo = zb; a1.out = inplace ? xb : hb;
+    CK(launch_attn_chain(a1, C, heads, st));
+    CK(launch_bf16_to_f32(a1.out, h1, M * C, st));
+  }
+  ap.rowstat_out = rowstat;
+  if (rec) {
+    const int slices = (rec_hpb >= 1 && rec_hpb <= 8 && 8 % rec_hpb == 0) ? 8 / rec_hpb : 1;       // (any other head group: the launcher refuses)
+    ap.record = 1; ap.rec = rec; ap.rec_b0 = rec_b0; ap.rec_T = rec_T; ap.rec_hpb = rec_hpb;
+    ap.rec_head_stride = (long long)rec_rows * HW; ap.rec_img_stride = ap.rec_head_stride * slices;
   }
   CK(launch_attn_chain(ap, C, heads, st));
-  CK(launch_bf16_to_f32(yb, y, M * C, st));
+  CK(launch_bf16_to_f32(ap.out, y, M * C, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
+// The block head as ONE launch (tblock.hip launch_qkv_chain): GroupNorm -> proj_in -> h -> norm1 -> q | k | v.  x [M][C] = the raw rows of M / HW images
+// (NHWC), part = the caller's partial-sum table of those rows (layout as agd_op_groupnorm_ex, bm pixels per tile), w_in [C][C] + b_in, wqkv [3C][C]
+// (q rows, k rows, v rows); h [M][C], qkv [M][3C].  flags bit 0: the GroupNorm is applied inside the kernel (the plain proj_in matrix in fragment
+// order); clear: it is folded into per-image matrices by launch_gn_fold_weight, written in the chain's fragment order (column ranges of 80: NI = 5
+// whatever C).  bit 1: rows64, bit 2: sched2.
+AGD_API int agd_op_qkv_chain(const float* x, const float* gn_gamma, const float* gn_beta, int groups, float gn_eps, const float* part, int bm,
+                             const float* w_in, const float* b_in, const float* gamma, const float* beta, float ln_eps, const float* wqkv, float* h,
+                             float* qkv, int M, int HW, int C, int flags, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (M < 1 || HW < 1 || groups < 1 || bm < 1 || C < 64 || C > 1280 || C % 64) { agd_set_error("op_qkv_chain: bad shape (M %d HW %d C %d groups %d bm %d)", M, HW, C, groups, bm); return -1; }
+  if (!x || !gn_gamma || !gn_beta || !part || !w_in || !b_in || !gamma || !beta || !wqkv || !h || !qkv) { agd_set_error("op_qkv_chain: bad arguments"); return -1; }
+  const int B = M / HW > 0 ? M / HW : 1;
+  const size_t MC = (size_t)M * C;
+  bf16_t* xb = tmp.get<bf16_t>(MC); bf16_t* hb = tmp.get<bf16_t>(MC); bf16_t* qb = tmp.get<bf16_t>(3 * MC);
+  bf16_t* wib = tmp.get<bf16_t>((size_t)C * C); bf16_t* wqb = tmp.get<bf16_t>((size_t)3 * C * C); bf16_t* wqf = tmp.get<bf16_t>((size_t)3 * C * C);
+  if (!xb || !hb || !qb || !wib || !wqb || !wqf) return -1;
+  CK(launch_f32_to_bf16(x, xb, (long long)MC, st));
+  CK(launch_convert_weight(w_in, wib, C, C, 1, C, 0, st));
+  CK(launch_convert_weight(wqkv, wqb, 3 * C, C, 1, C, 0, st));
+  QkvChainP qp{}; qp.x = xb; qp.h = hb; qp.qkv = qb; qp.gamma = gamma; qp.beta = beta; qp.ln_eps = ln_eps; qp.M = M; qp.HW = HW;
+  qp.rows64 = (flags >> 1) & 1; qp.sched2 = (flags >> 2) & 1;
+  if (C != 320 && C != 640) return launch_qkv_chain(qp, C, st);                          // (refused there, by name; the re-layouts below need C % 80 == 0)
+  CK(launch_frag_order_w(wqb, wqf, 3 * C, C, 5, C, st));
+  qp.wqkvf = wqf;
+  if (flags & 1) {
+    bf16_t* wif = tmp.get<bf16_t>((size_t)C * C); if (!wif) return -1;
+    CK(launch_frag_order_w(wib, wif, C, C, 5, C, st));
+    qp.wbf = wif; qp.wb_stride = 0; qp.rowadd = b_in; qp.rowadd_stride = 0;
+    qp.gn_part = part; qp.gn_bm = bm; qp.gn_groups = groups; qp.gn_eps = gn_eps; qp.gn_gamma = gn_gamma; qp.gn_beta = gn_beta;
+  } else {
+    bf16_t* wb = tmp.get<bf16_t>((size_t)B * C * C); float* radd = tmp.get<float>((size_t)B * C); if (!wb || !radd) return -1;
+    CK(launch_gn_fold_weight(part, bm, B, HW, C, groups, gn_eps, gn_gamma, gn_beta, wib, b_in, C, wb, radd, st, 5));
+    qp.wbf = wb; qp.wb_stride = (long long)C * C; qp.rowadd = radd; qp.rowadd_stride = C;
+  }
+  CK(launch_qkv_chain(qp, C, st));
+  CK(launch_bf16_to_f32(hb, h, (long long)MC, st));
+  CK(launch_bf16_to_f32(qb, qkv, (long long)(3 * MC), st));
   hipStreamSynchronize(st);
   return 0;
 }

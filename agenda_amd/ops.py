@@ -154,6 +154,104 @@ def attn_chain(x, gamma, beta, wq, kv, wo, bo, heads=8, eps=1e-5, return_probs=F
     return (y, pr) if return_probs else y
 
 
+def ff_premul_weights(w2, b2, wp, bp):
+    """The pre-multiplied form's operands as the loader builds them: Wp W2 through the library's own GEMM, rounded to bf16 once, and
+    Wp b2 + bp in fp64 from the bf16 Wp (rounded to fp32 once).  -> (w2p [C, 4C], bcp [C]), fp32 on the GPU"""
+    wpb = _f32c(wp).to(torch.bfloat16).float()
+    w2p = linear(wpb, _f32c(w2).t().contiguous()).to(torch.bfloat16).float()
+    bcp = (wpb.double() @ _f32c(b2).double() + _f32c(bp).double()).float()
+    return w2p, bcp
+
+
+def ff_fused_ex(x, gamma, beta, w1, b1, w2, b2, eps=1e-5, *, wp=None, bp=None, xres=None, xres_rows=0, premul=False, colstat=False, inplace=False):
+    """`ff_fused` reaching every form of the kernel (agd_op_ff_fused_ex); x [M, C].  wp / bp / xres: the proj_out stage behind it, -> pout
+    [M, C] = (x + FF(x)) wp^T + bp + xres, xres [xres_rows or M, C] (output row m adds row m % xres_rows).  premul: the launch gets
+    `ff_premul_weights(w2, b2, wp, bp)` in place of w2 and bp.  colstat: also the [ceil(M / 128), C, 2] channel sums of pout's tiles.
+    inplace: the launch writes over its own input."""
+    lib = _lib.load()
+    x2 = _f32c(x)
+    M, Cc = x2.shape
+    y = pout = cst = xr = None
+    w2_, bp_ = _f32c(w2), (None if bp is None else _f32c(bp))
+    if wp is not None:
+        pout = torch.empty_like(x2)
+        if xres is not None:
+            xr = _f32c(xres)
+            assert tuple(xr.shape) == ((xres_rows if xres_rows > 0 else M), Cc), "xres [xres_rows or M, C]"
+        if premul:
+            w2_, bp_ = ff_premul_weights(w2, b2, wp, bp)
+        if colstat:
+            cst = torch.full(((M + 127) // 128, Cc, 2), float("nan"), device=x2.device, dtype=torch.float32)
+    else:
+        y = torch.empty_like(x2)
+        if colstat:
+            cst = torch.zeros(1, device=x2.device)
+    _lib.check(lib.agd_op_ff_fused_ex(_lib.ptr(x2), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(_f32c(w1)), _lib.ptr(_f32c(b1)),
+                                      _lib.ptr(w2_), _lib.ptr(_f32c(b2)), _lib.ptr(y), M, Cc, float(eps), _lib.ptr(None if wp is None else _f32c(wp)),
+                                      _lib.ptr(bp_), _lib.ptr(xr), int(xres_rows), _lib.ptr(pout), int(bool(premul)), _lib.ptr(cst), int(bool(inplace)),
+                                      _lib.current_stream_ptr()), None, "agd_op_ff_fused_ex")
+    out = y if wp is None else pout
+    return (out, cst) if colstat else out
+
+
+def attn_chain_ex(x, gamma, beta, wq, kv, wo, bo, heads=8, eps=1e-5, *, hw=None, o1=None, wo1=None, bo1=None, src_rows=0, rowstat=False, rec=None,
+                  rec_hpb=8, rec_b0=0, rec_T=None, rows32=False, inplace=False):
+    """`attn_chain` reaching every form of the kernel (agd_op_attn_chain_ex); kv [B, T, 2C]; x [B, HW, C], or with src_rows > 0 x [src_rows, C]
+    and hw given: output row m reads input row m % src_rows.  o1 (x's shape) / wo1 / bo1: the attn1.to_out prologue, h1 = o1 wo1^T + bo1 + x is
+    the chain's input.  rec: the recorder rows [B - rec_b0, 8 / rec_hpb, rows, HW], fp32 on the GPU, ADDED to in place (token rows < rec_T,
+    default all the buffer's).  -> dict: y [B, HW, C]; h1 (with the prologue); rowstat [B, HW, 2] (if asked)."""
+    lib = _lib.load()
+    x, kv = _f32c(x), _f32c(kv)
+    Cc = x.shape[-1]
+    B, T = kv.shape[:2]
+    if src_rows > 0:
+        assert x.dim() == 2 and x.shape[0] == src_rows and hw, "src_rows: x [src_rows, C] and hw"
+        HW = int(hw)
+    else:
+        assert x.dim() == 3 and x.shape[0] == B, "x [B, HW, C]"
+        HW = x.shape[1]
+    dev = x.device
+    out = {"y": torch.empty(B, HW, Cc, device=dev, dtype=torch.float32)}
+    pre = o1 is not None
+    if pre:
+        o1 = _f32c(o1)
+        assert o1.shape == x.shape, "o1 has x's shape"
+        out["h1"] = torch.empty(B, HW, Cc, device=dev, dtype=torch.float32)
+    if rowstat:
+        out["rowstat"] = torch.full((B, HW, 2), float("nan"), device=dev, dtype=torch.float32)
+    rec_rows = 0
+    if rec is not None:
+        assert rec.is_cuda and rec.dtype == torch.float32 and rec.is_contiguous() and rec.dim() == 4 and rec.shape[3] == HW, "rec [B - rec_b0, groups, rows, HW]"
+        assert 0 <= rec_b0 <= B and rec.shape[0] == max(B - rec_b0, 0) and rec.shape[0] > 0, "one recorder image per recording batch row"
+        assert rec_hpb not in (1, 2, 4, 8) or rec.shape[1] == 8 // rec_hpb, "one slice per head group"
+        rec_rows = rec.shape[2]
+        rec_T = rec_rows if rec_T is None else int(rec_T)
+    _lib.check(lib.agd_op_attn_chain_ex(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(_f32c(wq)), _lib.ptr(_given(kv)), _lib.ptr(_f32c(wo)),
+                                        _lib.ptr(_f32c(bo)), _lib.ptr(out["y"]), B, HW, T, Cc, int(heads), float(eps), _lib.ptr(o1),
+                                        _lib.ptr(_f32c(wo1) if pre else None), _lib.ptr(_f32c(bo1) if pre else None), _lib.ptr(out.get("h1")), int(src_rows),
+                                        _lib.ptr(out.get("rowstat")), _lib.ptr(rec), int(rec_hpb), int(rec_b0), int(rec_T or 0), int(rec_rows), int(bool(rows32)),
+                                        int(bool(inplace)), _lib.current_stream_ptr()), None, "agd_op_attn_chain_ex")
+    return out
+
+
+def qkv_chain(x, hw, gn_gamma, gn_beta, groups, part, bm, w_in, b_in, gamma, beta, wqkv, *, gn_eps=1e-6, ln_eps=1e-5, inside=False, rows64=False, sched2=False):
+    """GroupNorm -> proj_in -> h -> norm1 -> q | k | v as ONE launch (agd_op_qkv_chain): x [M, C] = the raw rows of M / hw images, part
+    [M // hw, hw // bm, C, 2] fp32 = the partial sums of those rows per tile of bm pixels (the table the producing GEMM leaves).  inside: the
+    GroupNorm is applied by the kernel; else it is folded into per-image proj_in matrices first.  -> (h [M, C], qkv [M, 3C])"""
+    lib = _lib.load()
+    x, part = _f32c(x), _f32c(part)
+    M, Cc = x.shape
+    h = torch.empty(M, Cc, device=x.device, dtype=torch.float32)
+    qkv = torch.empty(M, 3 * Cc, device=x.device, dtype=torch.float32)
+    if hw > 0 and bm > 0:
+        assert part.numel() >= max(M // hw, 1) * (hw // bm) * Cc * 2, "partial-sum table [M // hw, hw // bm, C, 2] fp32"
+    _lib.check(lib.agd_op_qkv_chain(_lib.ptr(x), _lib.ptr(_f32c(gn_gamma)), _lib.ptr(_f32c(gn_beta)), int(groups), float(gn_eps), _lib.ptr(_given(part)), int(bm),
+                                    _lib.ptr(_f32c(w_in)), _lib.ptr(_f32c(b_in)), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), float(ln_eps),
+                                    _lib.ptr(_f32c(wqkv)), _lib.ptr(h), _lib.ptr(qkv), M, int(hw), Cc, (1 if inside else 0) | (2 if rows64 else 0) | (4 if sched2 else 0),
+                                    _lib.current_stream_ptr()), None, "agd_op_qkv_chain")
+    return h, qkv
+
+
 def xattn_premul(x, gamma, beta, wq, kv, wo, bo, heads=8, eps=1e-5, return_probs=False):
     """x + to_out(attention(to_q(LayerNorm(x)), k, v)) through the pre-multiplied context matrices of the C = 1280 blocks (xattn_pre.hip): x [B, HW, C],
     kv [B, T, 2C] (K columns then V columns).  With return_probs: also every head's probabilities, [B, heads, T, HW]."""

@@ -446,6 +446,35 @@ int agd_op_ff_fused(const float* x, const float* gamma, const float* beta, const
  * C = 320 (HW a multiple of 128) or C = 640 (HW a multiple of 64), 8 heads, T <= 96 */
 int agd_op_attn_chain(const float* x, const float* gamma, const float* beta, const float* wq, const float* kv, const float* wo,
                       const float* bo, float* y, float* probs_sum, int B, int HW, int T, int C, int heads, float eps, void* stream);
+/* The three row-panel chains of csrc/tblock.hip reaching EVERY form of their launchers, for per-kernel tests.  Context-free; inputs fp32,
+ * rounded to bf16 by the entry; outputs bf16 widened exactly; weights converted and put into fragment order by the library's own kernels, as
+ * the loader does; whatever a launcher refuses comes back as -1 with its message.
+ *
+ * agd_op_ff_fused_ex: agd_op_ff_fused plus the proj_out stage -- wp [C][C] != NULL: pout [M][C] = (x + FF(x)) wp^T + bp + xres, with xres
+ * [xres_rows > 0 ? xres_rows : M][C] (output row m adds row m % xres_rows) and y not written (may be NULL).  premul: w2 is the caller's product
+ * Wp W2 [C][4C] and bp the caller's Wp b2 + bp.  colstat (optional, with wp): [ceil(M / 128)][C][2] device floats = per-(128-row tile, channel)
+ * sum and sum of squares of the bf16 pout.  inplace: the launch writes over its own input rows (out == h).
+ *
+ * agd_op_attn_chain_ex: agd_op_attn_chain plus the attn1.to_out prologue (o1, wo1 [C][C], bo1: h1 = o1 wo1^T + bo1 + x is formed first and is
+ * the chain's input; h1 (optional) [B * HW][C] receives it), src_rows > 0 (x / o1 hold src_rows rows, output row m reads row m % src_rows),
+ * rowstat (optional) [B * HW][2] = (sum, sum of squares) of each bf16 output row, and the recorder as the kernel sees it: rec (optional)
+ * [B - rec_b0][8 / rec_hpb][rec_rows][HW] device floats that the launch ADDS to (never zeroed here): images >= rec_b0, head groups of rec_hpb
+ * in {1, 2, 4, 8}, token rows < rec_T <= rec_rows.  rows32: allow the 32-row panels of C = 640.  inplace: out == h.
+ *
+ * agd_op_qkv_chain: GroupNorm -> proj_in -> h -> norm1 -> q | k | v as one launch.  x [M][C] raw rows of M / HW images (NHWC), part = the
+ * caller's partial-sum table of those rows (layout of agd_op_groupnorm_ex, bm pixels per tile), w_in [C][C], b_in [C], wqkv [3C][C] (q, k, v
+ * rows); h [M][C], qkv [M][3C].  flags bit 0: the GroupNorm is applied inside the kernel, clear: folded into per-image matrices
+ * (launch_gn_fold_weight in the chain's fragment order); bit 1: 64-row panels (C = 320); bit 2: the second schedule.  C = 320 or 640. */
+int agd_op_ff_fused_ex(const float* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* y, int M, int C, float eps, const float* wp, const float* bp, const float* xres,
+                       int xres_rows, float* pout, int premul, float* colstat, int inplace, void* stream);
+int agd_op_attn_chain_ex(const float* x, const float* gamma, const float* beta, const float* wq, const float* kv, const float* wo,
+                         const float* bo, float* y, int B, int HW, int T, int C, int heads, float eps, const float* o1, const float* wo1,
+                         const float* bo1, float* h1, int src_rows, float* rowstat, float* rec, int rec_hpb, int rec_b0, int rec_T,
+                         int rec_rows, int rows32, int inplace, void* stream);
+int agd_op_qkv_chain(const float* x, const float* gn_gamma, const float* gn_beta, int groups, float gn_eps, const float* part, int bm,
+                     const float* w_in, const float* b_in, const float* gamma, const float* beta, float ln_eps, const float* wqkv, float* h,
+                     float* qkv, int M, int HW, int C, int flags, void* stream);
 /* the same function through the pre-multiplied form of the C = 1280 blocks (csrc/xattn_pre.hip; hook.py:91-120 behind norm2): the context products
  * K'' = gamma scale (k Wq), V'' = Wo v are built first, then S = LN-folded x K''^T -> softmax -> P V''^T + bo + x as two GEMMs.
  * probs (may be NULL): [B][heads][T][HW], every head's probabilities (the recorder's per-(image, head) rows).  Needs HW % 64 == 0, T <= 80,
