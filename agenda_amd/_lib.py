@@ -77,6 +77,20 @@ class AgdGligenConfig(C.Structure):
     ]
 
 
+class AgdIgemmDesc(C.Structure):
+    """`agd_igemm_desc`: one implicit-GEMM launch stated field by field (agd_op_igemm)."""
+    _fields_ = (
+        [(n, C.c_int) for n in (
+            "struct_size", "images", "H", "W", "C0", "C1", "ksize", "stride", "pad", "up", "hout", "wout", "sc_C0", "sc_C1", "N", "K", "w_per_image",
+            "bias_mode", "rowadd_ld", "ldr", "geglu", "act", "out_f32", "ldo", "batch", "rowstat_slots", "ln_slots", "colstat_rows", "gn_groups",
+            "gn_silu", "gn_keep_out", "halo", "p8", "smap", "pc", "kg2", "wreg", "xcd_block")]
+        + [(n, C.c_float) for n in ("alpha", "ln_invC", "ln_eps", "gn_eps")]
+        + [(n, C.c_longlong) for n in ("sA0", "sA1", "sW", "sO", "sR", "n_src0", "n_src1", "n_sc0", "n_sc1", "n_w", "n_res", "n_out")]
+        + [(n, C.c_void_p) for n in ("src0", "src1", "sc0", "sc1", "w", "bias", "rowadd", "residual", "ln_stats", "ln_cs", "gn_gamma", "gn_beta",
+                                     "out", "gn_y", "rowstat", "colstat")]
+        + [("cfg", C.c_int * 3), ("ran", C.c_int * 2), ("gn_fused", C.c_int), ("can_fuse_sc", C.c_int)])
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -183,6 +197,7 @@ _SIGS = {
     "agd_op_groupnorm_ex": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [C.c_float, C.c_int, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), _P]),
     "agd_op_gn_fold": (C.c_int, [_P, _P] + [C.c_int] * 5 + [C.c_float] + [_P] * 4 + [C.c_int, C.c_int] + [_P] * 5 + [_P]),
     "agd_op_conv_groupnorm": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, _P]),
+    "agd_op_igemm": (C.c_int, [C.POINTER(AgdIgemmDesc), _P]),
     "agd_op_layernorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "agd_op_layernorm_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), _P]),
     "agd_op_ff_fused": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_float, _P]),

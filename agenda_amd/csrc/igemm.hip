@@ -517,6 +517,13 @@ static bool reduce_gn_ok(const IgemmP& p) {
   if (!p.gn_y || !p.gn_gamma || !p.gn_beta || p.gn_groups < 1 || p.out_f32 || p.geglu || p.batch > 1) return false;
   const int HWo = p.Hout * p.Wout;
   if (p.N % p.gn_groups || (p.N / p.gn_groups) % 4 || p.M % HWo || p.ldo != p.N || (p.residual && p.ldr % 4)) return false;
+  // the pass reads bias / rowadd / gamma / beta as 16-byte quads and residual / out / gn_y as 8-byte ones: operands that are not aligned for
+  // that (or a bias announced and absent) take the plain slab pass, and the caller's own GroupNorm launches
+  auto al = [](const void* q, unsigned a) { return ((unsigned long long)q & (a - 1)) == 0; };
+  if (p.bias_mode && !p.bias) return false;
+  if (!al(p.gn_gamma, 16) || !al(p.gn_beta, 16) || !al(p.gn_y, 8) || !al(p.out, 8) || (p.residual && !al(p.residual, 8))) return false;
+  if (p.bias_mode == 1 && !al(p.bias, 16)) return false;
+  if (p.rowadd && (!al(p.rowadd, 16) || p.rowadd_ld % 4)) return false;
   return (long long)HWo * (p.N / p.gn_groups / 4) <= 1024 * 3 && p.act <= 1;
 }
 
@@ -525,6 +532,7 @@ static int launch_splitk_reduce(const IgemmP& p, int splits, hipStream_t st) {
   if (reduce_gn_ok(p)) {
     const long long quads = (long long)p.Hout * p.Wout * (p.N / p.gn_groups / 4);
     const dim3 g(p.gn_groups, p.M / (p.Hout * p.Wout));
+    if (p.ran) p.ran[1] = IGEMM_SLAB_GN;
     // slab loads per round: all of a 2-way split at once; the 8 x 8 maps' 8 - 10 slabs (one quad per thread) all at once
     if (quads <= 1024) hipLaunchKernelGGL((splitk_reduce_gn_kernel<1, 9>), g, dim3(1024), 0, st, p, splits);
     else if (quads <= 2048) hipLaunchKernelGGL((splitk_reduce_gn_kernel<2, 2>), g, dim3(1024), 0, st, p, splits);
@@ -533,6 +541,7 @@ static int launch_splitk_reduce(const IgemmP& p, int splits, hipStream_t st) {
     if (p.gn_fused) *p.gn_fused = 1;
     return 0;
   }
+  if (p.ran) p.ran[1] = IGEMM_SLAB_PLAIN;
   const long long total = (long long)p.M * (p.N >> 2);
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, st, p, splits);
@@ -583,6 +592,7 @@ static int launch_one(const IgemmP& p_in, int splits, hipStream_t st) {
   int dev = 0; HIP_CHECK_RET(hipGetDevice(&dev));
   if (dev < 0 || dev >= AGD_MAX_DEVICES) { agd_set_error("igemm: device ordinal %d out of range", dev); return -1; }
   if (!attr[dev]) { HIP_CHECK_RET(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); attr[dev] = true; }
+  if (p.ran) p.ran[0] = IGEMM_RAN_GENERAL;
   hipLaunchKernelGGL(kfn, grid, dim3(NT), lds, st, p);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
@@ -606,6 +616,7 @@ static int launch_halo(const IgemmP& p_in, int splits, hipStream_t st) {
   int dev = 0; HIP_CHECK_RET(hipGetDevice(&dev));
   if (dev < 0 || dev >= AGD_MAX_DEVICES) { agd_set_error("igemm: device ordinal %d out of range", dev); return -1; }
   if (!attr[dev]) { HIP_CHECK_RET(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 160 * 128 + BST * BN * 128 + 4096)); attr[dev] = true; }
+  if (p.ran) p.ran[0] = IGEMM_RAN_HALO;
   hipLaunchKernelGGL(kfn, dim3(tiles, 1, splits), dim3(256), lds, st, p, Wt, HRP);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
@@ -629,6 +640,7 @@ static int launch_pch(const IgemmP& p_in, int splits, hipStream_t st) {
   int dev = 0; HIP_CHECK_RET(hipGetDevice(&dev));
   if (dev < 0 || dev >= AGD_MAX_DEVICES) { agd_set_error("igemm_pch: device ordinal %d out of range", dev); return -1; }
   if (!attr[dev]) { HIP_CHECK_RET(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 144 * 128 + 5 * 160 * 128 + 4 * 1024)); attr[dev] = true; }
+  if (p.ran) p.ran[0] = IGEMM_RAN_PCH;
   hipLaunchKernelGGL(kfn, dim3(tiles, 1, splits), dim3(512), lds, st, p, Wt, HRP);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
@@ -728,6 +740,7 @@ static int launch_pc(const IgemmP& p, int splits, hipStream_t st) {
   if (!attr[dev][slot]) { HIP_CHECK_RET(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS)); attr[dev][slot] = true; }
   IgemmP pp = p; pick_xcd_block(pp, BM, BN);
   void* args[] = {&pp};
+  if (pp.ran) pp.ran[0] = IGEMM_RAN_PC;
   HIP_CHECK_RET(hipLaunchKernel(kfn, dim3((unsigned)tiles, 1, (unsigned)splits), dim3(G::THREADS), args, G::LDS, st));
   if (splits > 1) return launch_splitk_reduce(pp, splits, st);
   return 0;
@@ -758,6 +771,7 @@ static int launch_8p(const IgemmP& p, hipStream_t st) {
   if (!attr[dev][slot]) { HIP_CHECK_RET(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS)); attr[dev][slot] = true; }
   IgemmP pp = p; pick_xcd_block(pp, G::BM, G::BN);
   void* args[] = {&pp};
+  if (pp.ran) pp.ran[0] = IGEMM_RAN_8P;
   HIP_CHECK_RET(hipLaunchKernel(kfn, dim3(tiles), dim3(512), args, G::LDS, st));
   return 0;
 }
@@ -810,6 +824,8 @@ extern "C" __attribute__((visibility("default"))) int agd_smap_ts(int wg, unsign
 static bool nosplit_early(const IgemmP& p) { return p.rowstat_out || p.ln_stats || p.colstat_out; }
 int launch_igemm(const IgemmP& p_in, hipStream_t st) {
   IgemmP p = p_in;
+  if (p.cfg_out) p.ran = nullptr;      // a query launches nothing
+  if (p.ran) { p.ran[0] = IGEMM_RAN_NONE; p.ran[1] = IGEMM_SLAB_NONE; }
 #ifdef AGD_EXPERIMENTS
   static bool env_read = false;
   if (!env_read) { env_read = true; const char* e = getenv("AGD_IGEMM_CFG"); if (e) g_igemm_cfg = atoi(e); }
@@ -841,6 +857,12 @@ int launch_igemm(const IgemmP& p_in, hipStream_t st) {
   if (p.M < 1 || p.N < 1) { agd_set_error("igemm: empty problem M=%d N=%d", p.M, p.N); return -1; }
   if (p.rowadd && p.M >= (1 << 24)) { agd_set_error("igemm: rowadd needs M < 2^24"); return -1; }
   if (p.geglu && (p.N % 128)) { agd_set_error("igemm: geglu needs N %% 128 == 0"); return -1; }
+  // forms on which the epilogue's vector path, its element path and the slab passes do not state the same function (igemm_epilogue.h): no caller
+  // needs them, so they are refused here instead of computed three ways
+  if (p.geglu && (!p.bias || p.bias_mode != 1)) { agd_set_error("igemm: geglu needs a per-column bias [values | gates] (bias %s, bias_mode %d)", p.bias ? "given" : "null", p.bias_mode); return -1; }
+  if (p.geglu && p.rowadd) { agd_set_error("igemm: geglu takes no rowadd"); return -1; }
+  if (p.ln_stats && p.alpha != 1.f) { agd_set_error("igemm: LayerNorm fold needs alpha == 1 (alpha %g)", (double)p.alpha); return -1; }
+  if (p.ln_stats && p.bias_mode == 2) { agd_set_error("igemm: LayerNorm fold takes no per-row bias (bias_mode 2)"); return -1; }
   if ((p.rowstat_out || p.colstat_out) && (p.geglu || p.out_f32 || p.batch > 1)) { agd_set_error("igemm: row / column statistics only for plain bf16 launches"); return -1; }
   if (p.ln_stats && (!p.ln_cs || p.ln_slots < 1 || p.batch > 1)) { agd_set_error("igemm: LayerNorm fold needs colsum + slots"); return -1; }
   const int batch = p.batch > 0 ? p.batch : 1;
@@ -932,6 +954,7 @@ int launch_igemm(const IgemmP& p_in, hipStream_t st) {
     if (!attr[dev][S >= 2]) { HIP_CHECK_RET(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); attr[dev][S >= 2] = true; }
     IgemmP pp = p;
     void* args[] = {&pp};
+    if (pp.ran) pp.ran[0] = IGEMM_RAN_SMAP;
     HIP_CHECK_RET(hipLaunchKernel(kfn, dim3((unsigned)tiles, 1, (unsigned)S), dim3(512), args, lds, st));
     if (S >= 2) return launch_splitk_reduce(pp, S, st);
     return 0;
@@ -961,6 +984,7 @@ int launch_igemm(const IgemmP& p_in, hipStream_t st) {
       const int wn = w160 ? 5 : 4, kgn = kg2 ? 2 : 1;
       IgemmP pp = p; pick_xcd_block(pp, 64, bn);
       void* args[] = {&pp};
+      if (pp.ran) pp.ran[0] = IGEMM_RAN_WREG;
       HIP_CHECK_RET(hipLaunchKernel(kfn, dim3((unsigned)tiles), dim3(wn * 64 * kgn), args, kgn * (3 * 64 * 128 + wn * 1024) + 64 * 8, st));
       return 0;
     }

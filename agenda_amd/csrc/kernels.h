@@ -65,7 +65,11 @@ struct IgemmP {
   int pc;                           // caller: producer / consumer kernel (igemm_pc.h) -- bit 0 = the 1x1 launches on 64 x 160 tiles (16 x 16 / 8 x 8 maps), bit 1 = 3x3 convs of the 16 x 16 maps
   int stagger;                      // timing experiments only: start delay of the CU's second workgroup, x1024 cycles
   int dbg;                          // timing experiments only (builds with -DAGD_EXPERIMENTS)
+  int* ran;                         // tests (host pointer, may be null): written on the host before each launch -- ran[0] = the kernel family (IGEMM_RAN_*),
+                                    // ran[1] = the slab pass of a split-K launch (IGEMM_SLAB_*); both stay 0 when nothing is launched
 };
+enum { IGEMM_RAN_NONE = 0, IGEMM_RAN_GENERAL = 1, IGEMM_RAN_HALO = 2, IGEMM_RAN_PCH = 3, IGEMM_RAN_PC = 4, IGEMM_RAN_8P = 5, IGEMM_RAN_SMAP = 6, IGEMM_RAN_WREG = 7 };
+enum { IGEMM_SLAB_NONE = 0, IGEMM_SLAB_PLAIN = 1, IGEMM_SLAB_GN = 2 };
 int launch_igemm(const IgemmP& p, hipStream_t st);
 int igemm_query(const IgemmP& p, int* cfg3);       // {BM, BN, K splits} launch_igemm would use; launches nothing
 

@@ -3387,6 +3387,83 @@ AGD_API int agd_op_conv_groupnorm(const float* x, const float* w, const float* b
   return 0;
 }
 
+// One launch_igemm call stated field by field (include/agenda_hip.h agd_igemm_desc).  (Test entry point: every gather and epilogue form, every
+// kernel family, with the family and slab pass that ran reported back.)
+static_assert(AGD_IGEMM_GENERAL == IGEMM_RAN_GENERAL && AGD_IGEMM_HALO == IGEMM_RAN_HALO && AGD_IGEMM_PCH == IGEMM_RAN_PCH && AGD_IGEMM_PC == IGEMM_RAN_PC &&
+              AGD_IGEMM_8P == IGEMM_RAN_8P && AGD_IGEMM_SMAP == IGEMM_RAN_SMAP && AGD_IGEMM_WREG == IGEMM_RAN_WREG && AGD_IGEMM_SLAB_PLAIN == IGEMM_SLAB_PLAIN &&
+              AGD_IGEMM_SLAB_GN == IGEMM_SLAB_GN, "the public family codes restate the launcher's");
+AGD_API int agd_op_igemm(agd_igemm_desc* d, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!d || d->struct_size != (int)sizeof(agd_igemm_desc)) { agd_set_error("op_igemm: descriptor size mismatch"); return -1; }
+  d->cfg[0] = d->cfg[1] = d->cfg[2] = 0; d->ran[0] = d->ran[1] = 0; d->gn_fused = 0; d->can_fuse_sc = -1;
+  if (d->images < 1 || d->H < 1 || d->W < 1 || d->N < 1 || d->K < 1 || d->stride < 1 || d->up < 1 || d->ksize < 1 || !d->src0 || !d->w || !d->out ||
+      d->n_src0 < 1 || d->n_w < 1 || d->n_out < 1 || (d->src1 != nullptr) != (d->n_src1 > 0) || (d->sc0 != nullptr) != (d->n_sc0 > 0) ||
+      (d->sc1 != nullptr) != (d->n_sc1 > 0) || (d->residual != nullptr) != (d->n_res > 0)) { agd_set_error("op_igemm: bad descriptor (shape, or a pointer and its element count disagree)"); return -1; }
+  const int Hout = d->hout > 0 ? d->hout : (d->H * d->up + 2 * d->pad - d->ksize) / d->stride + 1;
+  const int Wout = d->wout > 0 ? d->wout : (d->W * d->up + 2 * d->pad - d->ksize) / d->stride + 1;
+  if (Hout < 1 || Wout < 1) { agd_set_error("op_igemm: empty output map"); return -1; }
+  {  // every buffer the launch walks must cover what the descriptor says of it
+    const long long nb = d->batch > 1 ? d->batch - 1 : 0, px = (long long)d->images * d->H * d->W, M_ = (long long)d->images * Hout * Wout;
+    const long long nout = d->geglu ? d->N / 2 : d->N, nkk = (long long)d->N * d->K;
+    const long long w_need = d->w_per_image ? (long long)(d->images - 1) * (d->sW ? d->sW : nkk) + nkk : nb * d->sW + nkk;
+    if (d->sA0 < 0 || d->sA1 < 0 || d->sW < 0 || d->sO < 0 || d->sR < 0 || d->C0 < 0 || d->C1 < 0 || d->sc_C0 < 0 || d->sc_C1 < 0 || d->ldo < nout || (d->residual && d->ldr < nout) ||
+        nb * d->sA0 + px * d->C0 > d->n_src0 || (d->src1 && nb * d->sA1 + px * d->C1 > d->n_src1) || (d->C1 > 0 && !d->src1) ||
+        (d->sc0 && M_ * d->sc_C0 > d->n_sc0) || (d->sc1 && M_ * d->sc_C1 > d->n_sc1) || (d->sc_C0 > 0 && !d->sc0) || (d->sc_C1 > 0 && !d->sc1) ||
+        w_need > d->n_w || nb * d->sO + (M_ - 1) * d->ldo + nout > d->n_out || (d->residual && nb * d->sR + (M_ - 1) * d->ldr + nout > d->n_res) ||
+        (d->gn_y && d->ldo != d->N)) { agd_set_error("op_igemm: a buffer is smaller than the descriptor's shape and strides need"); return -1; }
+  }
+  auto to_bf = [&](const float* x, long long n) -> bf16_t* {
+    if (!x) return nullptr;
+    bf16_t* b = tmp.get<bf16_t>((size_t)n);
+    if (b && launch_f32_to_bf16(x, b, n, st)) return nullptr;
+    return b;
+  };
+  bf16_t* s0 = to_bf(d->src0, d->n_src0); bf16_t* s1 = to_bf(d->src1, d->n_src1);
+  bf16_t* c0 = to_bf(d->sc0, d->n_sc0); bf16_t* c1 = to_bf(d->sc1, d->n_sc1); bf16_t* rb = to_bf(d->residual, d->n_res);
+  if (!s0 || (d->src1 && !s1) || (d->sc0 && !c0) || (d->sc1 && !c1) || (d->residual && !rb)) return -1;
+  // the matrices: rounded (and, GEGLU, interleaved as the loader interleaves them) one [N][K] matrix at a time
+  const long long nk = (long long)d->N * d->K;
+  if (d->n_w % nk) { agd_set_error("op_igemm: n_w is not a whole number of [N][K] matrices"); return -1; }
+  bf16_t* wb = tmp.get<bf16_t>((size_t)d->n_w); if (!wb) return -1;
+  for (long long i = 0; i < d->n_w / nk; ++i) CK(launch_convert_weight(d->w + i * nk, wb + i * nk, d->N, d->K, 1, d->K, d->geglu ? 16 : 0, st));
+  bf16_t* ob = nullptr; bf16_t* gb = nullptr;
+  if (!d->out_f32) { ob = to_bf(d->out, d->n_out); if (!ob) return -1; }
+  const long long n_gn = (long long)d->images * Hout * Wout * d->N;
+  if (d->gn_y) { gb = to_bf(d->gn_y, n_gn); if (!gb) return -1; }
+  IgemmP p{};
+  p.src0 = s0; p.src1 = s1; p.C0 = d->C0; p.C1 = d->C1; p.Hin = d->H; p.Win = d->W; p.Hout = Hout; p.Wout = Wout;
+  p.ksize = d->ksize; p.stride = d->stride; p.pad = d->pad; p.up = d->up;
+  p.sc0 = c0; p.sc1 = c1; p.sc_C0 = d->sc_C0; p.sc_C1 = d->sc_C1;
+  p.W = wb; p.bias = d->bias; p.bias_mode = d->bias_mode; p.rowadd = d->rowadd; p.rowadd_ld = d->rowadd_ld; p.residual = rb; p.ldr = d->ldr;
+  p.out = d->out_f32 ? (void*)d->out : (void*)ob; p.out_f32 = d->out_f32; p.ldo = d->ldo;
+  p.M = d->images * Hout * Wout; p.N = d->N; p.K = d->K; p.alpha = d->alpha; p.geglu = d->geglu; p.act = d->act;
+  p.batch = d->batch > 0 ? d->batch : 1; p.sA0 = d->sA0; p.sA1 = d->sA1; p.sW = d->sW; p.sO = d->sO; p.sR = d->sR;
+  p.zero_page = op_zero_page();
+  p.w_per_image = d->w_per_image; if (p.w_per_image && !p.sW) p.sW = nk;
+  p.rowstat_out = d->rowstat; p.rowstat_slots = d->rowstat_slots;
+  p.ln_stats = d->ln_stats; p.ln_slots = d->ln_slots; p.ln_cs = d->ln_cs; p.ln_invC = d->ln_invC; p.ln_eps = d->ln_eps;
+  p.colstat_out = d->colstat; p.colstat_rows = d->colstat_rows;
+  p.gn_gamma = d->gn_gamma; p.gn_beta = d->gn_beta; p.gn_y = gb; p.gn_groups = d->gn_groups; p.gn_eps = d->gn_eps; p.gn_silu = d->gn_silu;
+  p.gn_keep_out = d->gn_keep_out; p.gn_fused = &d->gn_fused;
+  p.halo = d->halo; p.p8 = d->p8; p.smap = d->smap; p.pc = d->pc; p.kg2 = d->kg2; p.xcd_block = d->xcd_block;
+  if (d->wreg) {      // the fragment-order copy the weight-streaming kernel reads, as agd_op_linear makes it
+    const int ni = d->geglu ? 4 : 2;
+    if (d->N % (ni * 64) || d->n_w != nk) { agd_set_error("op_igemm: the weight-streaming kernel needs one matrix with N %% %d == 0", ni * 64); return -1; }
+    bf16_t* wf = tmp.get<bf16_t>((size_t)nk); if (!wf) return -1;
+    CK(launch_frag_order_w(wb, wf, d->N, d->K, ni, d->K, st));
+    p.Wfrag = wf; p.wfrag_ni = ni; p.wreg = d->wreg; p.wreg_mmin = 1; p.wreg_mmax = 1 << 30;
+  }
+  (void)igemm_query(p, d->cfg);                              // (a refused query leaves zeros; the launch below states the reason)
+  if (p.sc0) d->can_fuse_sc = igemm_can_fuse_shortcut(p) ? 1 : 0;
+  p.ran = d->ran;
+  const int rc = launch_igemm(p, st);
+  if (rc) { hipStreamSynchronize(st); return rc; }
+  if (ob) CK(launch_bf16_to_f32(ob, d->out, d->n_out, st));
+  if (gb) CK(launch_bf16_to_f32(gb, d->gn_y, n_gn, st));
+  if (hipStreamSynchronize(st) != hipSuccess) { agd_set_error("op_igemm: the launch failed"); return -1; }
+  return 0;
+}
+
 // *inst (may be null): which layernorm_kernel<LPR, MAXV> ran, as 100 * LPR + MAXV (6404, 1605 or 1610)
 AGD_API int agd_op_layernorm_ex(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, int* inst, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;

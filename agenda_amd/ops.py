@@ -49,6 +49,103 @@ def linear(x, w, bias=None, residual=None, geglu=False, p8=0, wreg=False, kgroup
     return y.reshape(*x.shape[:-1], Nout)
 
 
+IGEMM_FAMILY = {0: "none", 1: "general", 2: "halo", 3: "pch", 4: "pc", 5: "8p", 6: "smap", 7: "wreg"}     # agd_igemm_desc.ran[0]
+IGEMM_SLAB = {0: "none", 1: "plain", 2: "gn"}                                                           # agd_igemm_desc.ran[1]
+IGEMM_SENTINEL = -24576.0        # exact in bf16: what `igemm` pre-fills every output buffer with
+IGEMM_GUARD_ROWS = 16            # rows allocated (and pre-filled) behind the M rows of every output
+
+
+def igemm(src0, w, *, src1=None, sc0=None, sc1=None, ksize=1, stride=1, pad=None, up=1, hout=0, wout=0, bias=None, bias_mode=None, rowadd=None,
+          rowadd_ld=None, residual=None, ldr=None, alpha=1.0, geglu=False, act=0, out_f32=True, ldo=None, batch=1, strides=None, w_per_image=False,
+          rowstat_slots=0, ln_stats=None, ln_cs=None, ln_invC=0.0, ln_eps=0.0, colstat_rows=0, gn=None, halo=0, p8=0, smap=0, pc=0, kg2=0, wreg=0,
+          xcd_block=0, check=True):
+    """One implicit-GEMM launch stated field by field (`agd_op_igemm`, the launcher's `IgemmP`).  src0 / src1 / sc0 / sc1: NHWC
+    [images, H, W, C] (batch > 1: [batch, 1, H, W, C] with `strides` = (sA0, sA1, sW, sO, sR) in elements); w [N, K] or [images or batch, N, K]
+    in the kernel's K order (tap-major, then the shortcut columns; geglu: value rows then gate rows); residual [M, ldr] (batch: [batch, M, ldr]).
+    bias / rowadd / ln_stats / ln_cs and gn["gamma"] / gn["beta"] reach the launch as the tensors they are (storage offset included).
+    gn: {"gamma", "beta", "groups", "eps", "silu", "keep_out"} -- the GroupNorm a split-K launch's slab pass may apply.
+    -> dict: out [M + IGEMM_GUARD_ROWS, ldo] (batch > 1: the flat buffer), pre-filled with IGEMM_SENTINEL; rc / err (check=False: a refusal is
+    returned, not raised); cfg (BM, BN, splits); family / slab (names of IGEMM_FAMILY / IGEMM_SLAB); gn_fused; can_fuse_sc; gn_y [M, N];
+    rowstat [M + guard, slots, 2]; colstat [ceil(M / 64), N, 2] (the launch fills M / BM tiles of it)."""
+    lib = _lib.load()
+    d = _lib.AgdIgemmDesc()
+    d.struct_size = ctypes.sizeof(d)
+    keep = []
+
+    def dev(t):
+        if t is None:
+            return None, 0
+        t = _f32c(t)
+        keep.append(t)
+        return t.data_ptr(), t.numel()
+
+    def given(t):
+        if t is None:
+            return None
+        assert t.is_cuda and t.dtype == torch.float32
+        keep.append(t)
+        return t.data_ptr()
+
+    images, H, W, C0 = src0.shape[-4:]
+    d.images, d.H, d.W, d.C0 = images, H, W, C0
+    d.C1 = 0 if src1 is None else src1.shape[-1]
+    d.ksize, d.stride, d.up, d.hout, d.wout = ksize, stride, up, hout, wout
+    d.pad = (1 if ksize == 3 else 0) if pad is None else pad
+    Ho = hout if hout > 0 else (H * up + 2 * d.pad - ksize) // stride + 1
+    Wo = wout if wout > 0 else (W * up + 2 * d.pad - ksize) // stride + 1
+    M = images * Ho * Wo
+    N, K = w.shape[-2:]
+    Nout = N // 2 if geglu else N
+    d.N, d.K, d.w_per_image = N, K, int(bool(w_per_image))
+    d.sc_C0 = 0 if sc0 is None else sc0.shape[-1]
+    d.sc_C1 = 0 if sc1 is None else sc1.shape[-1]
+    d.src0, d.n_src0 = dev(src0)
+    d.src1, d.n_src1 = dev(src1)
+    d.sc0, d.n_sc0 = dev(sc0)
+    d.sc1, d.n_sc1 = dev(sc1)
+    d.w, d.n_w = dev(w)
+    d.residual, d.n_res = dev(residual)
+    d.bias = given(bias)
+    d.bias_mode = (0 if bias is None else 1) if bias_mode is None else bias_mode
+    d.rowadd = given(rowadd)
+    d.rowadd_ld = (0 if rowadd is None else N) if rowadd_ld is None else rowadd_ld
+    d.ldr = (residual.shape[-1] if residual is not None else Nout) if ldr is None else ldr
+    d.ldo = Nout if ldo is None else ldo
+    d.alpha, d.geglu, d.act, d.out_f32, d.batch = float(alpha), int(bool(geglu)), int(act), int(bool(out_f32)), int(batch)
+    if strides is not None:
+        d.sA0, d.sA1, d.sW, d.sO, d.sR = (int(s) for s in strides)
+    d.ln_stats, d.ln_cs = given(ln_stats), given(ln_cs)
+    d.ln_slots = 0 if ln_stats is None else ln_stats.shape[-2]
+    d.ln_invC, d.ln_eps = float(ln_invC), float(ln_eps)
+    d.halo, d.p8, d.smap, d.pc, d.kg2, d.wreg, d.xcd_block = int(halo), int(p8), int(smap), int(pc), int(kg2), int(wreg), int(xcd_block)
+    device = src0.device
+    rows = M + IGEMM_GUARD_ROWS
+    n_out = (batch - 1) * d.sO + rows * d.ldo if batch > 1 else rows * d.ldo
+    out = torch.full((n_out,), IGEMM_SENTINEL, device=device, dtype=torch.float32)
+    d.out, d.n_out = out.data_ptr(), n_out
+    res = {}
+    if rowstat_slots > 0:
+        res["rowstat"] = torch.full((rows, rowstat_slots, 2), IGEMM_SENTINEL, device=device, dtype=torch.float32)
+        d.rowstat, d.rowstat_slots = res["rowstat"].data_ptr(), rowstat_slots
+    if colstat_rows > 0:
+        res["colstat"] = torch.full(((M + 63) // 64, N, 2), IGEMM_SENTINEL, device=device, dtype=torch.float32)
+        d.colstat, d.colstat_rows = res["colstat"].data_ptr(), colstat_rows
+    if gn is not None:
+        res["gn_y"] = torch.full((M, N), IGEMM_SENTINEL, device=device, dtype=torch.float32)
+        d.gn_y, d.gn_gamma, d.gn_beta = res["gn_y"].data_ptr(), given(gn["gamma"]), given(gn["beta"])
+        d.gn_groups, d.gn_eps, d.gn_silu, d.gn_keep_out = int(gn["groups"]), float(gn.get("eps", 1e-5)), int(gn.get("silu", 0)), int(gn.get("keep_out", 0))
+    rc = lib.agd_op_igemm(ctypes.byref(d), _lib.current_stream_ptr())
+    err = ""
+    if rc != 0:
+        msg = lib.agd_last_error(None)
+        err = msg.decode() if msg else "?"
+        if check:
+            raise _lib.AgendaHipError(f"agd_op_igemm failed (rc={rc}): {err}")
+    res.update(out=out if batch > 1 else out.view(rows, d.ldo), rc=rc, err=err, cfg=tuple(d.cfg), family=IGEMM_FAMILY.get(d.ran[0], d.ran[0]),
+               slab=IGEMM_SLAB.get(d.ran[1], d.ran[1]), gn_fused=d.gn_fused, can_fuse_sc=d.can_fuse_sc, M=M, Nout=Nout)
+    return res
+
+
 GN_PATH_PARTIAL, GN_PATH_TWO_KERNEL = 1, 2      # what return_path reports: the partial-sum kernel, or statistics kernel + apply kernel
 
 

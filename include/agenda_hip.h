@@ -506,6 +506,40 @@ int agd_op_gn_fold(const float* x_nchw, const float* part, int bm, int B, int C,
  * partial sums and the GroupNorm skips its statistics pass (the production path), fused == 0: the two-kernel GroupNorm. */
 int agd_op_conv_groupnorm(const float* x_nchw, const float* w, const float* bias, const float* gamma, const float* beta, float* y_nchw,
                           int B, int Cin, int H, int W, int Cout, int groups, float eps, int silu, int fused, void* stream);
+/* One implicit-GEMM launch stated field by field (igemm.hip launch_igemm): the entry fills the launcher's descriptor itself, so no ctx option
+ * stands between a test and the launcher.  Every pointer is a device pointer.  Activations, weights and the residual are fp32 and are rounded
+ * to bf16 by the entry (n_* = their element counts); bias / rowadd / ln_stats / ln_cs / gn_gamma / gn_beta are handed to the launch AS GIVEN
+ * (address and all).  Outputs go into caller-allocated, caller-pre-filled buffers of the full pitch: `out` fp32 [n_out] (a bf16 launch gets
+ * the buffer's values rounded to bf16 first and its result widened exactly afterwards, so a pre-filled bf16-exact sentinel survives where
+ * the launch stores nothing), `gn_y` alike, `rowstat` / `colstat` fp32 tables written in place.  M = images * Hout * Wout; a linear layer is
+ * images = 1, H = 1, W = rows.  w: [N][K] (w_per_image: [images][N][K]; batch > 1: as sW says), k = tap * (C0 + C1) + c, then the sc_C0 + sc_C1
+ * shortcut columns; geglu: rows [values ; gates], interleaved by the entry as the loader does.
+ * Returned in the struct: cfg = igemm_query's {BM, BN, K splits} (zeros where the query refuses), ran = {kernel family, slab pass} (AGD_IGEMM_*),
+ * gn_fused, can_fuse_sc = igemm_can_fuse_shortcut of this launch (-1 without shortcut sources).  0, or -1 with the error text set. */
+enum { AGD_IGEMM_NONE = 0, AGD_IGEMM_GENERAL = 1, AGD_IGEMM_HALO = 2, AGD_IGEMM_PCH = 3, AGD_IGEMM_PC = 4, AGD_IGEMM_8P = 5, AGD_IGEMM_SMAP = 6,
+       AGD_IGEMM_WREG = 7 };
+enum { AGD_IGEMM_SLAB_NONE = 0, AGD_IGEMM_SLAB_PLAIN = 1, AGD_IGEMM_SLAB_GN = 2 };
+typedef struct agd_igemm_desc {
+  int struct_size;                 /* sizeof(agd_igemm_desc), ABI guard */
+  int images, H, W, C0, C1;        /* two NHWC sources [images][H][W][C0 | C1] */
+  int ksize, stride, pad, up, hout, wout;   /* hout / wout > 0: override the output size (the asymmetric pad-0 stride-2 form) */
+  int sc_C0, sc_C1;                /* conv_shortcut sources' channels */
+  int N, K, w_per_image;
+  int bias_mode, rowadd_ld, ldr, geglu, act, out_f32, ldo;
+  int batch;
+  int rowstat_slots, ln_slots, colstat_rows;
+  int gn_groups, gn_silu, gn_keep_out;
+  int halo, p8, smap, pc, kg2, wreg, xcd_block;
+  float alpha, ln_invC, ln_eps, gn_eps;
+  long long sA0, sA1, sW, sO, sR;
+  long long n_src0, n_src1, n_sc0, n_sc1, n_w, n_res, n_out;
+  const float* src0; const float* src1; const float* sc0; const float* sc1; const float* w;
+  const float* bias; const float* rowadd; const float* residual;
+  const float* ln_stats; const float* ln_cs; const float* gn_gamma; const float* gn_beta;
+  float* out; float* gn_y; float* rowstat; float* colstat;
+  int cfg[3]; int ran[2]; int gn_fused; int can_fuse_sc;     /* out */
+} agd_igemm_desc;
+int agd_op_igemm(agd_igemm_desc* d, void* stream);
 int agd_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps,
                      void* stream);
 /* the same; *inst (may be NULL) = which instantiation of the LayerNorm kernel ran, as 100 * lanes per row + vectors per lane (6404, 1605, 1610).
