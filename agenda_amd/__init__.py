@@ -14,10 +14,11 @@ from .inpaint import StableDiffusionInpaintPipeline  # noqa: F401
 from .ip2p import StableDiffusionInstructPix2PixPipeline  # noqa: F401
 from .gligen import StableDiffusionGLIGENPipeline  # noqa: F401
 from .panorama import StableDiffusionPanoramaPipeline, get_views  # noqa: F401
+from .regions import StableDiffusionRegionPipeline  # noqa: F401
 
 __all__ = ["StableDiffusionPipeline", "StableDiffusionPAGPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
            "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic", "ip_adapter",
            "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
            "StableDiffusionInpaintPipeline",
            "StableDiffusionInstructPix2PixPipeline",
-           "StableDiffusionGLIGENPipeline", "StableDiffusionPanoramaPipeline", "get_views", "DeepCacheSDHelper"]
+           "StableDiffusionGLIGENPipeline", "StableDiffusionPanoramaPipeline", "get_views", "StableDiffusionRegionPipeline", "DeepCacheSDHelper"]

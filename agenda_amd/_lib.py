@@ -91,6 +91,15 @@ class AgdIgemmDesc(C.Structure):
         + [("cfg", C.c_int * 3), ("ran", C.c_int * 2), ("gn_fused", C.c_int), ("can_fuse_sc", C.c_int)])
 
 
+class AgdRegionsDesc(C.Structure):
+    """`agd_regions_desc`: what one agd_denoise_regions call reads (masks, noise, backgrounds on the device; idx, sqrt_ac on the host)."""
+    _fields_ = [
+        ("struct_size", C.c_int), ("regions", C.c_int), ("bootstrapping", C.c_int), ("n_backgrounds", C.c_int),
+        ("masks", C.c_void_p), ("noise", C.c_void_p), ("backgrounds", C.c_void_p),
+        ("idx", C.POINTER(C.c_int)), ("sqrt_ac", C.POINTER(C.c_float)),
+    ]
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -220,6 +229,10 @@ _SIGS = {
     "agd_op_window_mean": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
     "agd_denoise_panorama": (C.c_int, [_P, _P] + [C.c_int] * 7 + [C.POINTER(C.c_float)] * 3 + [C.c_float, _P]),
     "agd_daam_global_panorama": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "agd_op_region_masks": (C.c_int, [_P, C.c_int, C.c_int, _P] + [C.c_int] * 6 + [_P]),
+    "agd_op_region_spread": (C.c_int, [_P] * 5 + [C.c_int] * 6 + [C.POINTER(C.c_int), C.c_float, C.c_float, _P]),
+    "agd_op_region_mean": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
+    "agd_denoise_regions": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AgdRegionsDesc), C.c_int] + [C.POINTER(C.c_float)] * 3 + [C.c_float, _P]),
     "agd_freeu_set": (C.c_int, [_P] + [C.c_float] * 4),
     "agd_freeu_clear": (C.c_int, [_P]),
     "agd_freeu_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),

@@ -329,6 +329,17 @@ int launch_window_mean(const float* views, float* canvas, int B, int C, int Lh, 
 // dst [halves][B * reps][row_bytes] = src [halves][B][row_bytes], row r of a half reading row r % B
 int launch_tile_rows(const void* src, void* dst, int halves, int B, int reps, size_t row_bytes, hipStream_t st);
 
+// Region-based MultiDiffusion (regions.hip): row (region r, image p) = r * B + p of masks [R][B][HW] and of the region buffer x [R][B][C][HW], fp32.
+// masks: pixel masks uint8 (> 127) or fp32 (> 0.5) [per_image ? B : 1][R - 1][H][W] -> latent masks, nearest sample at the whole ratio H / Lh,
+// row 0 = max(0, 1 - sum of the others).  spread: x = canvas for region 0 and when !boot, else canvas m + (sa bgs[idx.v[r]] + sb noise) (1 - m).
+// mean: canvas = sum_r m_r x_r / sum_r m_r in ascending r (the sum itself where no mask covers the element).
+#define AGD_MAX_REGIONS 8
+struct RegionIdx { int v[AGD_MAX_REGIONS]; };            // v[r]: the background of region r at this step (v[0] unused)
+int launch_region_masks(const void* px, int px_f32, int per_image, float* masks, int R, int B, int H, int W, int Lh, int Lw, hipStream_t st);
+int launch_region_spread(const float* canvas, float* x, const float* masks, const float* noise, const float* bgs, int R, int B, int C,
+                         long long HW, int n_bg, int boot, RegionIdx idx, float sa, float sb, hipStream_t st);
+int launch_region_mean(const float* x, const float* masks, float* canvas, int R, int B, int C, long long HW, hipStream_t st);
+
 // export path (bit-exact with numpy min-max/astype and PIL Image.resize BICUBIC on uint8)
 int launch_heatmap_u8(const float* hm, int n, int npix, unsigned char* out, hipStream_t st);
 int launch_pil_resample(const unsigned char* in, unsigned char* out, const int* bounds, const int* kk, int ksize,

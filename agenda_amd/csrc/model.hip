@@ -163,6 +163,7 @@ struct agd_ctx {
   int rec_base = 0, rec_call = 0;
   int pano_B = 0, pano_Lh = 0, pano_Lw = 0, pano_stride = 0;        // the last agd_denoise_panorama that recorded (agd_daam_global_panorama reads its geometry)
   DBuf pano_ctxb;                                                // agd_denoise_panorama: the prompts' bf16 context [2 B][T][D], kept while the tiled one is in place
+  DBuf reg_xb;                                                   // agd_denoise_regions' region buffer [R][B][C][Lh][Lw] (scratch: no state)
   DBuf pano_viewb, pano_hmb;                                     // agd_denoise_panorama's views [V][B][C][win][win]; agd_daam_global_panorama's per-view maps
   // denoise scratch
   DBuf latb, epsb, vae_imgb, plmsb, dpmb;
@@ -1567,7 +1568,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   hipDeviceSynchronize();
   for (void* p : c->owned) hipFree(p);
   for (auto& xl : c->xl) { xl.kvb.release(); xl.accb.release(); }
-  c->pano_viewb.release(); c->pano_hmb.release(); c->pano_ctxb.release(); c->i2_latb.release();
+  c->pano_viewb.release(); c->pano_hmb.release(); c->reg_xb.release(); c->pano_ctxb.release(); c->i2_latb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
   c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->dc_buf.release(); c->cn_embb.release(); c->lora_descb.release();
@@ -2210,8 +2211,9 @@ struct CallCond {
     return e;
   }
 };
-// who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama, agd_deepcache_forward_hw
-enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA, CALL_DC_FORWARD };
+// who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama, agd_deepcache_forward_hw,
+// agd_denoise_regions
+enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA, CALL_DC_FORWARD, CALL_REGIONS };
 enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, ST_DC, N_COND_STATES };                       // the states a call can meet, in the order of a row's cells
 // One row per refusing party: a state (self) that, when set, refuses to run beside others in the callers that consult it, or an entry point
 // that runs the UNet alone (self < 0: it refuses whenever it is the caller).  with[s]: nullptr = allowed beside state s, else the refusal.
@@ -2297,6 +2299,19 @@ static const ConflictRow kDcConflicts[] = {
   { -1, 1u << CALL_PANORAMA, { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
     "denoise_panorama: a DeepCache schedule is set; DeepCache on a panorama is not implemented (agd_deepcache_clear first)" } },
 };
+// agd_denoise_regions' row, consulted after the three tables above, in a table of its own for the same reason: it runs the UNet alone on its
+// R x batch rows and reads none of these states.
+static const ConflictRow kRegionConflicts[] = {
+  { -1, 1u << CALL_REGIONS, {   // denoise_regions
+    "denoise_regions: a ControlNet schedule is set; ControlNet with region prompts is not implemented (clear it first)",
+    "denoise_regions: a GLIGEN schedule is set; GLIGEN with region prompts is not implemented (clear it first)",
+    "denoise_regions: an inpainting state is set; inpainting with region prompts is not implemented (agd_inpaint_clear first)",
+    "denoise_regions: an InstructPix2Pix state is set; InstructPix2Pix with region prompts is not implemented (agd_ip2p_clear first)",
+    "denoise_regions: a T2I-Adapter schedule is set; the T2I-Adapter with region prompts is not implemented (clear it first)",
+    "denoise_regions: an IP-Adapter image is set; denoise_regions runs without it (agd_ip_adapter_clear first)",
+    "denoise_regions: a Perturbed-Attention Guidance schedule is set; Perturbed-Attention Guidance with region prompts is not implemented (agd_pag_clear first)",
+    "denoise_regions: a DeepCache schedule is set; DeepCache with region prompts is not implemented (agd_deepcache_clear first)" } },
+};
 // an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
 static int ip2p_check_unet(agd_ctx* c, const char* what) {
   const agd_config& g = c->cfg;
@@ -2315,9 +2330,9 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   set[ST_CN] = !c->cn_sched.empty(); set[ST_GL] = !c->gl_sched.empty(); set[ST_INP] = c->ip_mode != 0; set[ST_I2P] = c->i2_on;
   set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f; set[ST_PAG] = !c->pag_sched.empty();
   set[ST_DC] = !c->dc_sched.empty();
-  for (const ConflictRow* t : {kConflicts, kPagConflicts, kDcConflicts}) {          // (b) rows top to bottom, the first set cell wins
+  for (const ConflictRow* t : {kConflicts, kPagConflicts, kDcConflicts, kRegionConflicts}) {   // (b) rows top to bottom, the first set cell wins
     const size_t rows = t == kConflicts ? sizeof(kConflicts) / sizeof(kConflicts[0]) : t == kPagConflicts ? sizeof(kPagConflicts) / sizeof(kPagConflicts[0])
-                                        : sizeof(kDcConflicts) / sizeof(kDcConflicts[0]);
+                                        : t == kDcConflicts ? sizeof(kDcConflicts) / sizeof(kDcConflicts[0]) : sizeof(kRegionConflicts) / sizeof(kRegionConflicts[0]);
     for (size_t k = 0; k < rows; ++k) {
       const ConflictRow& r = t[k];
       if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
@@ -2330,6 +2345,7 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
     if (c->rec_mode == 2) FAIL("long context: the hook.py recorder takes contexts of at most 96 tokens (this one has %d)", T);
     if (who == CALL_UNET_FORWARD_TS) FAIL("unet_forward_ts: a context of %d tokens is not supported (at most 96)", T);
     if (who == CALL_PANORAMA) FAIL("denoise_panorama: a context of %d tokens is not supported (at most 96)", T);
+    if (who == CALL_REGIONS) FAIL("denoise_regions: a context of %d tokens is not supported (at most 96)", T);
     static const struct { int st; const char* what; } kLong[] = {
       {ST_CN, "a ControlNet schedule"}, {ST_GL, "a GLIGEN schedule"}, {ST_INP, "an inpainting state"}, {ST_I2P, "an InstructPix2Pix state"},
       {ST_AD, "a T2I-Adapter schedule"}, {ST_IPA, "an IP-Adapter image"} };
@@ -2341,7 +2357,9 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   // the entry points that run the UNet alone have refused every state they read; the latents must be all the UNet takes
   if (who == CALL_PANORAMA && c->cfg.in_channels != c->cfg.out_channels)
     FAIL("denoise_panorama: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels);
-  if (who == CALL_UNET_FORWARD_TS || who == CALL_PANORAMA) return 0;
+  if (who == CALL_REGIONS && c->cfg.in_channels != c->cfg.out_channels)
+    FAIL("denoise_regions: the UNet takes %d input channels (an inpainting UNet), the latents have %d", c->cfg.in_channels, c->cfg.out_channels);
+  if (who == CALL_UNET_FORWARD_TS || who == CALL_PANORAMA || who == CALL_REGIONS) return 0;
   if (who == CALL_IP2P_LOOP) {
     CK(ip2p_check_unet(c, "ip2p"));
     if (c->i2_B != rows || c->i2_Lh != Lh || c->i2_Lw != Lw)
@@ -2745,6 +2763,71 @@ AGD_API int agd_denoise_panorama(agd_ctx* c, float* canvas, int batch, int Lh, i
     }
     ProfScope ps(c, st, PC_ELEM, 0, 4.0 * batch * (double)img * V + 4.0 * batch * (double)Cl * Lh * Lw);
     API_CK(c, launch_window_mean(views, canvas, batch, Cl, Lh, Lw, window, stride, 1, batch, st));
+  }
+  return 0;
+}
+
+// ---- Region-based MultiDiffusion (Bar-Tal et al. 2023, region_based.py of its repository [upstream-knowledge], parity-unpinned; regions.hip) ----
+// The DDIM loop of R regions on ONE canvas [batch][4][Lh][Lw] fp32, in place.  Per step: the spread hands the canvas to every region (for
+// the first d->bootstrapping steps a foreground region sees a noised constant-colour background outside its mask), the CFG UNet runs the
+// 2 R batch rows in one forward against the context [uncond x R batch | cond x R batch] set by agd_set_context, the DDIM step updates the
+// R batch rows, and the masked mean writes the canvas.  Row (region r, image p) = r * batch + p; with the DAAM recorder on that is also its
+// state of an agd_record_reset_hw(ctx, R * batch, Lh, Lw).  Nothing of the call is kept in the context.
+static int check_regions_desc(const agd_regions_desc* d, int n_steps) {
+  if (!d) FAIL("denoise_regions: null descriptor");
+  if (d->struct_size != (int)sizeof(agd_regions_desc)) FAIL("denoise_regions: descriptor struct_size %d, this library has %zu", d->struct_size, sizeof(agd_regions_desc));
+  const int R = d->regions;
+  if (R < 1 || R > AGD_MAX_REGIONS) FAIL("denoise_regions: %d regions (1 .. %d)", R, AGD_MAX_REGIONS);
+  if (d->bootstrapping < 0 || d->bootstrapping > n_steps) FAIL("denoise_regions: bootstrapping %d outside 0 .. %d (the call's steps)", d->bootstrapping, n_steps);
+  if (!d->masks) FAIL("denoise_regions: null masks");
+  if (d->bootstrapping > 0 && R > 1) {
+    if (d->n_backgrounds < 1) FAIL("denoise_regions: %d backgrounds for %d bootstrapped steps (at least 1)", d->n_backgrounds, d->bootstrapping);
+    if (!d->noise || !d->backgrounds || !d->idx || !d->sqrt_ac) FAIL("denoise_regions: null noise, backgrounds, idx or sqrt_ac with %d bootstrapped steps", d->bootstrapping);
+    for (int s = 0; s < d->bootstrapping; ++s)
+      for (int r = 1; r < R; ++r) {
+        const int k = d->idx[s * (R - 1) + (r - 1)];
+        if (k < 0 || k >= d->n_backgrounds) FAIL("denoise_regions: background index %d (step %d, region %d) outside 0 .. %d", k, s, r, d->n_backgrounds - 1);
+      }
+  }
+  return 0;
+}
+AGD_API int agd_denoise_regions(agd_ctx* c, float* canvas, int batch, int Lh, int Lw, const agd_regions_desc* d, int n_steps,
+                                const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream) {
+  API_CK(c, need_final(c));
+  hipStream_t st = S(stream);
+  API_CK(c, check_latent_hw(c, "denoise_regions", Lh, Lw));
+  if (batch < 1 || n_steps < 1 || !canvas || !timesteps || !alpha_t || !alpha_prev) { agd_set_error("denoise_regions: batch %d, steps %d or a null argument", batch, n_steps); return fail_ctx(c); }
+  API_CK(c, check_regions_desc(d, n_steps));
+  const int R = d->regions, rows = R * batch;
+  API_CK(c, refuse_guidance_rescale(c, "denoise_regions"));
+  CallCond cc; API_CK(c, resolve_cond(c, CALL_REGIONS, n_steps, rows, Lh, Lw, &cc));
+  if (c->rec_mode == 2) { agd_set_error("denoise_regions: the hook.py recorder is installed; region prompts record through the DAAM recorder only"); return fail_ctx(c); }
+  if (c->ctx_B2 != 2 * rows) { agd_set_error("denoise_regions: context batch %d != 2 * regions * batch = 2 * %d * %d", c->ctx_B2, R, batch); return fail_ctx(c); }
+  if (c->rec_mode == 1 && (c->rec_B != rows || c->rec_Lh != Lh || c->rec_Lw != Lw)) {
+    agd_set_error("denoise_regions: the recorder holds %d images at %d x %d, this call records %d regions x %d images at %d x %d (agd_record_reset_hw(ctx, regions * batch, Lh, Lw))",
+                  c->rec_B, c->rec_Lh, c->rec_Lw, R, batch, Lh, Lw);
+    return fail_ctx(c);
+  }
+  const int Cl = c->cfg.out_channels; const long long HW = (long long)Lh * Lw;
+  API_CK(c, ensure_lat(c, 2 * rows, Lh, Lw));
+  const size_t img = (size_t)Cl * HW;
+  API_CK(c, c->reg_xb.ensure((size_t)rows * img * sizeof(float)));
+  float* x = c->reg_xb.as<float>();                                 // [R][batch][Cl][Lh][Lw]
+  const float* tp_all = nullptr;
+  API_CK(c, embed_all_timesteps(c, st, timesteps, n_steps, &tp_all));
+  for (int s = 0; s < n_steps; ++s) {
+    const bool boot = s < d->bootstrapping && R > 1;
+    RegionIdx ri = {};
+    if (boot) for (int r = 1; r < R; ++r) ri.v[r] = d->idx[s * (R - 1) + (r - 1)];
+    { ProfScope ps(c, st, PC_ELEM, 0, (boot ? 16.0 : 8.0) * rows * (double)img);
+      API_CK(c, launch_region_spread(canvas, x, d->masks, d->noise, d->backgrounds, R, batch, Cl, HW, d->n_backgrounds, boot, ri,
+                                     boot ? d->sqrt_ac[2 * s] : 0.f, boot ? d->sqrt_ac[2 * s + 1] : 0.f, st)); }
+    API_CK(c, prep_unet_input(c, st, x, rows, (int)HW));
+    API_CK(c, unet_walk(c, st, c->lat_bf16, 2 * rows, Lh, Lw, timesteps[s], c->eps_nhwc, tp_all + (size_t)s * c->tproj_total, true));
+    { ProfScope ps(c, st, PC_ELEM, 0);
+      API_CK(c, launch_cfg_ddim(c->eps_nhwc, c->cfg.out_channels, x, rows, Cl, (int)HW, guidance, alpha_t[s], alpha_prev[s], c->cfg.prediction_type, nullptr, st)); }
+    ProfScope ps(c, st, PC_ELEM, 0, 4.0 * rows * (double)img + 4.0 * rows * (double)HW + 4.0 * batch * (double)img);
+    API_CK(c, launch_region_mean(x, d->masks, canvas, R, batch, Cl, HW, st));
   }
   return 0;
 }
@@ -3902,6 +3985,21 @@ AGD_API int agd_op_window_mean(const float* views, float* canvas, int B, int C, 
   if (pano_view_grid(Lh, Lw, window, stride, &nbh, &nbw)) return -1;
   if (!canvas || !views) { agd_set_error("op_window_mean: null argument"); return -1; }
   return launch_window_mean(views, canvas, B, C, Lh, Lw, window, stride, (long long)nbh * nbw, 1, S(stream));
+}
+// regions.hip in isolation (include/agenda_hip.h states the layouts); idx is a host array of R - 1 indices, NULL = a step that is not bootstrapped
+AGD_API int agd_op_region_masks(const void* px, int px_f32, int per_image, float* masks, int R, int B, int H, int W, int Lh, int Lw, void* stream) {
+  return launch_region_masks(px, px_f32, per_image, masks, R, B, H, W, Lh, Lw, S(stream));
+}
+AGD_API int agd_op_region_spread(const float* canvas, float* x, const float* masks, const float* noise, const float* bgs, int R, int B, int C, int Lh,
+                                 int Lw, int n_bg, const int* idx, float sa, float sb, void* stream) {
+  if (Lh < 1 || Lw < 1 || R < 1 || R > AGD_MAX_REGIONS) { agd_set_error("op_region_spread: %d regions (1 .. %d) at latent size %d x %d", R, AGD_MAX_REGIONS, Lh, Lw); return -1; }
+  RegionIdx ri = {};
+  if (idx) for (int r = 1; r < R; ++r) ri.v[r] = idx[r - 1];
+  return launch_region_spread(canvas, x, masks, noise, bgs, R, B, C, (long long)Lh * Lw, n_bg, idx != nullptr, ri, sa, sb, S(stream));
+}
+AGD_API int agd_op_region_mean(const float* x, const float* masks, float* canvas, int R, int B, int C, int Lh, int Lw, void* stream) {
+  if (Lh < 1 || Lw < 1) { agd_set_error("op_region_mean: latent size %d x %d", Lh, Lw); return -1; }
+  return launch_region_mean(x, masks, canvas, R, B, C, (long long)Lh * Lw, S(stream));
 }
 
 #ifdef AGD_EXPERIMENTS   // the micro-benchmark entry points exist only in the experiments library (make exp): tools/kb*.py

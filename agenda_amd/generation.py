@@ -94,6 +94,8 @@ def generate_batch(pipe, seeds: Sequence[int], words: Sequence[str], prompt: Opt
                 # integer (view) indexing: a python list index makes torch upload an index tensor with a BLOCKING pageable copy, i.e. a host
                 # sync at the end of every batch
                 hms.append(torch.stack([torch.stack([g.heat_maps[int(i)] for i in r]).mean(0) for r in word_rows]))
+            elif words and getattr(trc, "regions", None) is not None:      # a region call: the canvas map composed from the regions' states
+                hms.append(torch.stack([trc.compute_region_word_heat_map(w, image_index=i).heatmap for w in words]))
             elif words:
                 hms.append(torch.stack([g.compute_word_heat_map(w).heatmap for w in words]))
             else:
@@ -310,6 +312,18 @@ def parse_args(argv=None):
                    help="MultiDiffusion panorama txt2img (StableDiffusionPanoramaPipeline): --height / --width give the canvas, each a multiple of 64 "
                         "and at least the checkpoint's size (default: that size x 4 times it); DDIM only")
     p.add_argument("--view-batch-size", type=int, default=None, help="panorama: views per UNet call (default: all views of a step at once)")
+    p.add_argument("--region-prompts", type=str, default=None, nargs="+", metavar="P",
+                   help="region-based MultiDiffusion (StableDiffusionRegionPipeline): one prompt per foreground region, the same layout for "
+                        "every seed; --prompt is the background's; DDIM only, any checkpoint")
+    p.add_argument("--region-boxes", type=float, default=None, nargs="+", metavar="V",
+                   help="regions: x0 y0 x1 y1 per region prompt, normalised to [0, 1]")
+    p.add_argument("--region-masks", type=str, default=None, nargs="+", metavar="FILE",
+                   help="regions: one mask image per region prompt (white = the region), of the generated size")
+    p.add_argument("--region-layouts", type=str, default=None,
+                   help="regions: a JSON file holding a list of {\"prompts\": [...], \"boxes\": [[x0, y0, x1, y1], ...]}; seed s uses layout s mod n")
+    p.add_argument("--bootstrapping", type=int, default=None, metavar="N",
+                   help="regions: the first N steps show every foreground region a random constant-colour background outside its mask "
+                        "(default 20, clipped to the steps)")
     p.add_argument("--gligen-beta", type=float, default=0.3, help="GLIGEN: gligen_scheduled_sampling_beta (the grounded share of the evaluations)")
     p.add_argument("--freeu", type=float, default=None, nargs=4, metavar=("S1", "S2", "B1", "B2"),
                    help="FreeU (enable_freeu) on every UNet evaluation, with any pipeline: the skip filters' scales and the backbone scales of "
@@ -433,6 +447,37 @@ def parse_args(argv=None):
             p.error(f"--{name} {v}: a positive multiple of 64")
     if args.view_batch_size is not None and not args.panorama:
         p.error("--view-batch-size needs --panorama")
+    region = args.region_prompts is not None or args.region_layouts is not None
+    if not region and (args.region_boxes is not None or args.region_masks is not None or args.bootstrapping is not None):
+        p.error("--region-boxes / --region-masks / --bootstrapping need --region-prompts or --region-layouts")
+    if region:
+        # everything StableDiffusionRegionPipeline refuses is refused here, before a device is touched
+        if (args.panorama or args.gligen_phrases is not None or args.gligen_layouts is not None or args.controlnet_model_path or args.control_image
+                or args.adapter_model_path or args.ip_adapter_path or args.init_image or args.instruct_image):
+            p.error("region prompts with --panorama, GLIGEN, ControlNet, a T2I-Adapter, an IP-Adapter, inpainting or InstructPix2Pix are not implemented")
+        if args.guidance_rescale or args.pag_scale or (args.deepcache_interval or 1) > 1 or args.max_embeddings_multiples is not None:
+            p.error("region prompts with --guidance-rescale, --pag-scale, --deepcache-interval or --max-embeddings-multiples are not implemented")
+        if args.region_layouts is not None and (args.region_prompts is not None or args.region_boxes is not None or args.region_masks is not None):
+            p.error("--region-layouts replaces --region-prompts / --region-boxes / --region-masks")
+        if args.region_prompts is not None and (args.region_boxes is None) == (args.region_masks is None):
+            p.error("--region-prompts takes exactly one of --region-boxes and --region-masks")
+        if args.region_boxes is not None and len(args.region_boxes) != 4 * len(args.region_prompts):
+            p.error(f"--region-boxes takes four values per region prompt ({len(args.region_prompts)} prompts, {len(args.region_boxes)} values)")
+        if args.region_masks is not None and len(args.region_masks) != len(args.region_prompts):
+            p.error(f"--region-masks takes one file per region prompt ({len(args.region_prompts)} prompts, {len(args.region_masks)} files)")
+        if args.bootstrapping is not None and args.bootstrapping < 0:
+            p.error(f"--bootstrapping {args.bootstrapping}: a number of steps >= 0")
+        if args.scheduler is None:
+            args.scheduler = "DDIMScheduler"
+        from .regions import check_region_args, check_region_count
+        try:
+            for lay in region_layouts_from_args(args):                        # (mask files are opened, and their size checked, per batch)
+                if lay["boxes"] is not None:
+                    check_region_args(args.scheduler, len(lay["prompts"]), None, lay["boxes"], 64, 64)
+                else:
+                    check_region_count(args.scheduler, len(lay["prompts"]))
+        except (ValueError, OSError) as e:
+            p.error(f"region prompts: {e}")
     if args.panorama:
         # everything StableDiffusionPanoramaPipeline refuses is refused here, before a device is touched
         if args.controlnet_model_path or args.init_image or args.gligen_phrases is not None or args.gligen_layouts is not None:
@@ -487,6 +532,76 @@ def gligen_layouts_from_args(args) -> Optional[List[dict]]:
         return None
     v = args.gligen_boxes
     return [{"phrases": list(args.gligen_phrases), "boxes": [v[4 * i: 4 * i + 4] for i in range(len(args.gligen_phrases))]}]
+
+
+def region_layouts_from_args(args) -> Optional[List[dict]]:
+    """The region layouts of the run: one from --region-prompts with --region-boxes or --region-masks, or the list of --region-layouts;
+    None without either.  A layout is {"prompts": [...], "boxes": [[x0, y0, x1, y1], ...] or None, "masks": [files] or None}."""
+    if args.region_layouts is not None:
+        with open(args.region_layouts) as f:
+            lays = json.load(f)
+        if not isinstance(lays, list) or not lays or not all(isinstance(x, dict) and {"prompts", "boxes"} <= set(x) for x in lays):
+            raise ValueError(f"{args.region_layouts}: a non-empty list of {{'prompts': [...], 'boxes': [...]}} objects")
+        return [{"prompts": list(x["prompts"]), "boxes": [list(map(float, b)) for b in x["boxes"]], "masks": None} for x in lays]
+    if args.region_prompts is None:
+        return None
+    v = args.region_boxes
+    return [{"prompts": list(args.region_prompts), "masks": list(args.region_masks) if args.region_masks is not None else None,
+             "boxes": None if v is None else [v[4 * i: 4 * i + 4] for i in range(len(args.region_prompts))]}]
+
+
+def region_inputs_for(layout: dict, bootstrapping: Optional[int]) -> dict:
+    """The region pipeline's keyword arguments for a batch whose images share `layout`."""
+    from PIL import Image
+    kw = {"region_prompts": layout["prompts"]}
+    if layout["boxes"] is not None:
+        kw["region_boxes"] = layout["boxes"]
+    else:
+        kw["region_masks"] = [Image.open(f).convert("L") for f in layout["masks"]]
+    if bootstrapping is not None:
+        kw["bootstrapping"] = bootstrapping
+    return kw
+
+
+def generate_region_batch(pipe, layouts: Sequence[dict], bootstrapping: Optional[int], seeds: Sequence[int], words, **kw):
+    """`generate_batch` for region prompts: seed s takes layout s mod n; the seeds of one layout run as one call (a call's images share its
+    region prompts), and the results come back in the order of `seeds`.  The bootstrap draws come from a CPU generator seeded with the
+    first seed of each call, so a batch paints the same images in every run."""
+    groups = {}
+    for k, s_ in enumerate(seeds):
+        groups.setdefault(int(s_) % len(layouts), []).append(k)
+    imgs, hms = [None] * len(seeds), [None] * len(seeds)
+    for li, ks in groups.items():
+        sub = [seeds[k] for k in ks]
+        control = dict(region_inputs_for(layouts[li], bootstrapping), generator=torch.Generator().manual_seed(int(sub[0])))
+        im, hm = generate_batch(pipe, sub, words, control=control, **kw)
+        for j, k in enumerate(ks):
+            imgs[k], hms[k] = im[j], hm[j]
+    return torch.stack(imgs), torch.stack(hms)
+
+
+def write_region_layouts(save_dir: str, records: dict):
+    """region_layouts.json: each saved image's file name -> its region prompts and boxes (normalised and in saved-image pixels) or mask files."""
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "region_layouts.json"), "w") as f:
+        json.dump(records, f, indent=2, sort_keys=True)
+
+
+def region_records(seeds, layouts, image_size, images_dir: Optional[str] = None) -> dict:
+    """The region_layouts.json entries of the seeds whose image was written (`images_dir` given: skipped black images have no file)."""
+    sh, sw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
+    out = {}
+    for s in seeds:
+        name = f"{s}.png"
+        if images_dir is not None and not os.path.exists(os.path.join(images_dir, name)):
+            continue
+        lay = layouts[int(s) % len(layouts)]
+        out[name] = {"prompts": lay["prompts"]}
+        if lay["boxes"] is not None:
+            out[name].update(boxes=lay["boxes"], boxes_px=[[b[0] * sw, b[1] * sh, b[2] * sw, b[3] * sh] for b in lay["boxes"]])
+        else:
+            out[name].update(masks=lay["masks"])
+    return out
 
 
 def gligen_inputs_for(layouts: Sequence[dict], seeds: Sequence[int], beta: float) -> dict:
@@ -610,6 +725,10 @@ def main(argv=None):
     if args.panorama:
         from .panorama import StableDiffusionPanoramaPipeline
         cls = StableDiffusionPanoramaPipeline
+    rg_layouts = region_layouts_from_args(args)
+    if rg_layouts is not None:
+        from .regions import StableDiffusionRegionPipeline
+        cls = StableDiffusionRegionPipeline
     i2_files = None
     if args.instruct_image:
         from .ip2p import StableDiffusionInstructPix2PixPipeline
@@ -653,7 +772,7 @@ def main(argv=None):
     per_rank = (args.num_images + world - 1) // world
     rounds = (per_rank + args.batch_size - 1) // args.batch_size if gather else (len(seeds) + args.batch_size - 1) // args.batch_size
     S = args.image_size
-    gl_done = {}
+    gl_done, rg_done = {}, {}
     for r in range(rounds):
         chunk = seeds[r * args.batch_size:(r + 1) * args.batch_size]
         if chunk:
@@ -682,13 +801,20 @@ def main(argv=None):
                 control = dict(control or {}, pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale)
             if args.max_embeddings_multiples is not None:
                 control = dict(control or {}, max_embeddings_multiples=args.max_embeddings_multiples)
-            imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
-                                       height=height, width=width)
+            if rg_layouts is not None:                                               # (parse_args refused every other control)
+                imgs, hms = generate_region_batch(pipe, rg_layouts, args.bootstrapping, chunk, words, prompt=prompt,
+                                                  num_inference_steps=args.num_inference_steps, height=height, width=width)
+            else:
+                imgs, hms = generate_batch(pipe, chunk, words, prompt=prompt, num_inference_steps=args.num_inference_steps, control=control,
+                                           height=height, width=width)
         if not gather:
             save_outputs(args.save_dir, chunk, imgs, hms, words, S, stack_words=args.stack)
             if gl_layouts is not None:
                 gl_done.update(gligen_records(chunk, gl_layouts, S, os.path.join(args.save_dir, "images")))
                 write_gligen_layouts(args.save_dir, gl_done)
+            if rg_layouts is not None:
+                rg_done.update(region_records(chunk, rg_layouts, S, os.path.join(args.save_dir, "images")))
+                write_region_layouts(args.save_dir, rg_done)
             continue
         # export on the producing GPU (resize 512 -> S, min-max -> uint8 -> resize), then ONE gather of the finished
         # payloads (S*S*3 + S*S per word bytes per image instead of the full-size tensors); rank 0 writes the files
@@ -709,6 +835,9 @@ def main(argv=None):
             if gl_layouts is not None:
                 gl_done.update(gligen_records(all_seeds, gl_layouts, S, os.path.join(args.save_dir, "images")))
                 write_gligen_layouts(args.save_dir, gl_done)
+            if rg_layouts is not None:
+                rg_done.update(region_records(all_seeds, rg_layouts, S, os.path.join(args.save_dir, "images")))
+                write_region_layouts(args.save_dir, rg_done)
     if world > 1:
         dist.barrier()
         if own_group:

@@ -23,7 +23,8 @@ from .config import SDConfig, UNetConfig
 WEIGHT_NAMES = ("ip-adapter_sd15.safetensors", "ip-adapter_sd15.bin", "ip_adapter.safetensors", "ip_adapter.bin")
 PROJ_KEYS = ("image_proj.proj.weight", "image_proj.proj.bias", "image_proj.norm.weight", "image_proj.norm.bias")
 REFUSED_PIPELINES = ("StableDiffusionControlNetPipeline", "StableDiffusionAdapterPipeline", "StableDiffusionGLIGENPipeline",
-                     "StableDiffusionInpaintPipeline", "StableDiffusionInstructPix2PixPipeline", "StableDiffusionPanoramaPipeline")
+                     "StableDiffusionInpaintPipeline", "StableDiffusionInstructPix2PixPipeline", "StableDiffusionPanoramaPipeline",
+                     "StableDiffusionRegionPipeline")
 
 
 def attn2_blocks(ucfg: UNetConfig) -> List[str]:

@@ -570,6 +570,74 @@ def window_mean(views, batch, Lh, Lw, stride=8):
     return out
 
 
+def region_masks(pixel_masks, batch, Lh, Lw, regions=None):
+    """Region-based MultiDiffusion's mask front end: pixel masks [R - 1, H, W] (shared by the images) or [B, R - 1, H, W], uint8 (set: > 127)
+    or float (set: > 0.5; bool counts as uint8 0 / 255) -> latent masks fp32 [R, B, Lh, Lw], nearest-sampled, row 0 the background
+    max(0, 1 - sum of the others).  `pixel_masks` None (with regions=1): the background alone."""
+    lib = _lib.load()
+    if pixel_masks is None:
+        R, H, W, px, f32, per = int(regions or 1), 0, 0, None, 0, 0
+        dev = torch.device("cuda", torch.cuda.current_device())
+    else:
+        px = pixel_masks.detach()
+        assert px.is_cuda, "ops run on the GPU only (no CPU fallback)"
+        if px.dtype == torch.bool:
+            px = px.to(torch.uint8) * 255
+        elif px.dtype != torch.uint8:
+            px = px.to(torch.float32)
+        px = px.contiguous()
+        if px.ndim not in (3, 4) or (px.ndim == 4 and px.shape[0] != batch):
+            raise ValueError(f"region_masks: masks {tuple(px.shape)} must be [R - 1, H, W] or [{batch}, R - 1, H, W]")
+        per, (n, H, W) = int(px.ndim == 4), px.shape[-3:]
+        R, f32, dev = n + 1, int(px.dtype == torch.float32), px.device
+        if regions is not None and regions != R:
+            raise ValueError(f"region_masks: {n} masks for {regions} regions")
+    out = torch.empty(R, batch, Lh, Lw, device=dev, dtype=torch.float32)
+    _lib.check(lib.agd_op_region_masks(_lib.ptr(px), f32, per, _lib.ptr(out), R, batch, H, W, Lh, Lw, _lib.current_stream_ptr()), None,
+               "agd_op_region_masks")
+    return out
+
+
+def region_spread(canvas, masks, noise=None, backgrounds=None, idx=None, sa=0.0, sb=0.0):
+    """Region-based MultiDiffusion's spread: canvas [B, C, Lh, Lw], masks [R, B, Lh, Lw] -> x [R * B, C, Lh, Lw] (row r * B + p).  idx None: a
+    step past the bootstrapping phase, every region is the canvas.  Else idx holds R - 1 indices into backgrounds [N, C, Lh, Lw] and
+    x[r] = canvas m + (sa backgrounds[idx[r - 1]] + sb noise) (1 - m) for r >= 1; region 0 is the canvas."""
+    lib = _lib.load()
+    canvas, masks = _f32c(canvas), _f32c(masks)
+    B, Cc, Lh, Lw = canvas.shape
+    R = masks.shape[0]
+    if tuple(masks.shape) != (R, B, Lh, Lw):
+        raise ValueError(f"region_spread: masks {tuple(masks.shape)} for a canvas {tuple(canvas.shape)}")
+    ci, nbg = None, 0
+    if idx is not None:
+        noise, backgrounds = _f32c(noise), _f32c(backgrounds)
+        idx = [int(i) for i in idx]
+        if len(idx) != R - 1 or tuple(noise.shape) != tuple(canvas.shape) or tuple(backgrounds.shape[1:]) != (Cc, Lh, Lw):
+            raise ValueError(f"region_spread: {len(idx)} indices, noise {tuple(noise.shape)}, backgrounds {tuple(backgrounds.shape)} for {R} regions "
+                             f"of a canvas {tuple(canvas.shape)}")
+        import ctypes
+        ci, nbg = (ctypes.c_int * max(len(idx), 1))(*idx), backgrounds.shape[0]
+    out = torch.empty(R * B, Cc, Lh, Lw, device=canvas.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_region_spread(_lib.ptr(canvas), _lib.ptr(out), _lib.ptr(masks), _lib.ptr(noise) if idx is not None else None,
+                                        _lib.ptr(backgrounds) if idx is not None else None, R, B, Cc, Lh, Lw, nbg, ci, float(sa), float(sb),
+                                        _lib.current_stream_ptr()), None, "agd_op_region_spread")
+    return out
+
+
+def region_mean(x, masks):
+    """Region-based MultiDiffusion's masked mean: x [R * B, C, Lh, Lw] (row r * B + p), masks [R, B, Lh, Lw] -> canvas [B, C, Lh, Lw],
+    sum_r m_r x_r / sum_r m_r in ascending r (0 where no mask covers the element)."""
+    lib = _lib.load()
+    x, masks = _f32c(x), _f32c(masks)
+    R, B, Lh, Lw = masks.shape
+    if x.ndim != 4 or x.shape[0] != R * B or tuple(x.shape[2:]) != (Lh, Lw):
+        raise ValueError(f"region_mean: x {tuple(x.shape)} for masks {tuple(masks.shape)}")
+    out = torch.empty(B, x.shape[1], Lh, Lw, device=x.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_region_mean(_lib.ptr(x), _lib.ptr(masks), _lib.ptr(out), R, B, x.shape[1], Lh, Lw, _lib.current_stream_ptr()), None,
+               "agd_op_region_mean")
+    return out
+
+
 def freeu(hidden, skip, b, s):
     """FreeU on one resnet's inputs, the production kernel: hidden [B, Ch, H, W] with its first Ch // 2 channels times b, skip [B, Cs, H, W]
     with the four lowest frequencies of every map times s (diffusers fourier_filter, threshold 1).  Inputs are rounded to bf16; the outputs

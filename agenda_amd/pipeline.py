@@ -717,6 +717,37 @@ class Engine:
         self._ck(rc, "agd_daam_global_panorama")
         return out
 
+    def denoise_regions(self, canvas: torch.Tensor, masks: torch.Tensor, noise: Optional[torch.Tensor], backgrounds: Optional[torch.Tensor],
+                        idx, sqrt_ac, bootstrapping: int, timesteps, a_t, a_p, guidance: float):
+        """The fused region-based MultiDiffusion DDIM loop (`agd_denoise_regions`) on a canvas [B,4,Lh,Lw] in place.  masks [R,B,Lh,Lw] on
+        the device; for the first `bootstrapping` steps: noise [B,4,Lh,Lw], backgrounds [N,4,Lh,Lw], idx[bootstrapping][R-1] (host
+        integers) and sqrt_ac[bootstrapping] = (sqrt(ac_t), sqrt(1 - ac_t)) pairs.  The context must hold 2 R B rows."""
+        for t in (canvas, masks, noise, backgrounds):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+        b, _, Lh, Lw = canvas.shape
+        R = masks.shape[0]
+        if tuple(masks.shape) != (R, b, Lh, Lw):
+            raise ValueError(f"denoise_regions: masks {tuple(masks.shape)} for a canvas {tuple(canvas.shape)}")
+        if noise is not None and tuple(noise.shape) != tuple(canvas.shape):
+            raise ValueError(f"denoise_regions: noise {tuple(noise.shape)} for a canvas {tuple(canvas.shape)}")
+        if backgrounds is not None and (backgrounds.ndim != 4 or tuple(backgrounds.shape[1:]) != tuple(canvas.shape[1:])):
+            raise ValueError(f"denoise_regions: backgrounds {tuple(backgrounds.shape)} for a canvas {tuple(canvas.shape)}")
+        flat_idx = [int(v) for row in (idx if idx is not None else []) for v in row]
+        flat_ac = [float(v) for pair in (sqrt_ac if sqrt_ac is not None else []) for v in pair]
+        if len(flat_idx) != max(int(bootstrapping), 0) * (R - 1) or len(flat_ac) != 2 * max(int(bootstrapping), 0):
+            raise ValueError(f"denoise_regions: {len(flat_idx)} indices and {len(flat_ac) // 2} sqrt_ac pairs for {bootstrapping} bootstrapped "
+                             f"steps of {R - 1} foreground regions")
+        ci = (C.c_int * max(len(flat_idx), 1))(*flat_idx)
+        cf = (C.c_float * max(len(flat_ac), 1))(*flat_ac)
+        d = _lib.AgdRegionsDesc(struct_size=C.sizeof(_lib.AgdRegionsDesc), regions=R, bootstrapping=int(bootstrapping),
+                                n_backgrounds=0 if backgrounds is None else int(backgrounds.shape[0]),
+                                masks=masks.data_ptr(), noise=None if noise is None else noise.data_ptr(),
+                                backgrounds=None if backgrounds is None else backgrounds.data_ptr(),
+                                idx=C.cast(ci, C.POINTER(C.c_int)), sqrt_ac=C.cast(cf, C.POINTER(C.c_float)))
+        self._ck(self.lib.agd_denoise_regions(self.ctx, _lib.ptr(canvas), b, Lh, Lw, C.byref(d), len(timesteps), _floats(timesteps), _floats(a_t),
+                                              _floats(a_p), float(guidance), self._stream()), "agd_denoise_regions")
+        return canvas
+
     def cfg_ddim_step(self, eps: torch.Tensor, latents: torch.Tensor, guidance: float, alpha_t: float, alpha_prev: float):
         """`scheduler.step` of the call-by-call loop: CFG combine of eps [2B,4,L,L] (rows [0,B) unconditional) + one DDIM
         (eta 0) update of `latents` [B,4,L,L] in place (`agd_cfg_ddim_step`; the fused loop is `denoise`)."""

@@ -12,6 +12,13 @@ A panorama (StableDiffusionPanoramaPipeline) gives maps [rows, Lh, Lw] over the 
 for a square generate of the window size, then the mean over the views that cover each latent pixel (the rule that fuses the latents).
 daam has no panorama support; this definition is this project's (parity-unpinned).
 
+A region call (StableDiffusionRegionPipeline) keeps one DAAM state per (region r, image p), image r * B + p of the recorder:
+`compute_global_heat_map(image_index=p, region=r)` gives region r's maps, rows and word lookup following region r's prompt (region None =
+region 0, the background).  `compute_region_word_heat_map(word, image_index=p)` is the canvas map [Lh, Lw] = sum_r m_r w_r / sum_r m_r with
+m_r the region's latent mask and w_r its word heat map of `word`; a region whose prompt does not contain the word contributes zeros.  The map
+of "car" over the canvas is thus composed from the regions that generated each pixel.  daam has no such notion; this definition is this
+project's (parity-unpinned).
+
 A context of more than 77 rows (`max_embeddings_multiples`, or long `prompt_embeds`): daam records 77-wide maps only, so this too is the
 project's definition (parity-unpinned).  The recorder keeps all T context rows (unless the tracer was given `rec_tokens`); the global map
 is truncated to tokens + 2 rows, counted on the weight-stripped token stream of the prompt (every weighted piece tokenised on its own, cut
@@ -113,15 +120,30 @@ class trace:
         return self.rec_tokens
 
     def _on_generate(self, batch: int, latent_side, prompt: Optional[str], panorama: bool = False, tokens: Optional[List[str]] = None,
-                     context_tokens: Optional[int] = None):
+                     context_tokens: Optional[int] = None, regions: Optional[dict] = None):
         self.batch, self.latent_side, self.last_prompt, self._ran = batch, latent_side, prompt, True
         self.last_tokens, self._rows = tokens, self._rows_for(context_tokens)
         self.panorama = panorama             # a StableDiffusionPanoramaPipeline call: latent_side is the canvas (Lh, Lw)
+        # a StableDiffusionRegionPipeline call: {"prompts": [background, region 1, ...] or None, "masks": [R, B, Lh, Lw], "count": R}
+        self.regions = regions
 
-    def compute_global_heat_map(self, prompt: Optional[str] = None, image_index: int = 0, normalize: bool = False) -> GlobalHeatMap:
-        """Heat maps [rows, Lh, Lw] of image `image_index` (word maps from it are [Lh, Lw])."""
+    def compute_global_heat_map(self, prompt: Optional[str] = None, image_index: int = 0, normalize: bool = False,
+                                region: Optional[int] = None) -> GlobalHeatMap:
+        """Heat maps [rows, Lh, Lw] of image `image_index` (word maps from it are [Lh, Lw]).  `region`: after a region call, the region
+        whose DAAM state and prompt are read (None: region 0, the background)."""
         if not self._ran:
             raise RuntimeError("No heat maps found. Did you forget to call `with trace(...)`?")
+        regions = getattr(self, "regions", None)
+        if regions is None:
+            if region is not None:
+                raise ValueError(f"region={region!r}: the last generate was not a StableDiffusionRegionPipeline call")
+        else:
+            r = 0 if region is None else int(region)
+            if not 0 <= r < regions["count"] or not 0 <= image_index < self.batch:
+                raise ValueError(f"region {r} of {regions['count']}, image {image_index} of {self.batch}")
+            if prompt is None and regions["prompts"] is not None:
+                prompt = regions["prompts"][r]
+            image_index = r * self.batch + image_index
         # the weighted prompt of the last generate is counted on its own token stream; any other prompt given here as daam counts it
         tokens = self.last_tokens if prompt is None or prompt == self.last_prompt else None
         prompt = prompt if prompt is not None else self.last_prompt
@@ -137,3 +159,30 @@ class trace:
         if normalize:
             maps = maps / (maps[1:-1].sum(0, keepdim=True) + 1e-6)
         return GlobalHeatMap(self.pipe.tokenizer, prompt or "", maps, tokens)
+
+    def compute_region_word_heat_map(self, word: str, image_index: int = 0, word_idx: Optional[int] = None) -> WordHeatMap:
+        """The canvas map [Lh, Lw] of `word` after a region call: sum_r m_r w_r / sum_r m_r, with w_r region r's word heat map and m_r its
+        latent mask; a region whose prompt does not contain the word contributes zeros (a word no region contains raises).  `word_idx`:
+        the token position instead of the word, read in every region.  Plain torch on the device tensors."""
+        regions = getattr(self, "regions", None)
+        if not self._ran or regions is None:
+            raise RuntimeError("compute_region_word_heat_map needs a StableDiffusionRegionPipeline call under this trace")
+        masks = regions["masks"][:, image_index]                 # [R, Lh, Lw]
+        num, found = torch.zeros_like(masks[0]), False
+        for r in range(regions["count"]):
+            g = self.compute_global_heat_map(image_index=image_index, region=r)
+            if word_idx is not None:
+                if word_idx + 1 >= g.heat_maps.shape[0]:
+                    raise ValueError(f"token index {word_idx + 1} beyond the {g.heat_maps.shape[0]} recorded rows")
+                w = g.heat_maps[int(word_idx) + 1]
+            else:
+                try:
+                    w = g.compute_word_heat_map(word).heatmap
+                except ValueError:
+                    continue                                     # not in this region's prompt: zeros
+            found = True
+            num = num + masks[r] * w
+        if not found:
+            raise ValueError(f"Search word {word} not found in any region's prompt!")
+        den = masks.sum(0)
+        return WordHeatMap(torch.where(den > 0, num / den, num), word)

@@ -67,7 +67,7 @@ int agd_finalize(agd_ctx* ctx);                    /* after the last agd_load_te
  * call agd_record_reset AFTER agd_set_context, rec_tokens up to T -- and the fused loops (img2img, LoRA, FreeU, guidance_rescale, PAG,
  * DeepCache, rectangular sizes included), agd_unet_forward_hw and agd_deepcache_forward_hw take it.  Refused by name with such a context: the
  * hook.py recorder, recording through agd_attn_processor / agd_cross_attn, agd_attn_processor_backward, agd_unet_forward_ts*,
- * agd_denoise_panorama, and a set ControlNet, GLIGEN, inpainting, InstructPix2Pix, T2I-Adapter or IP-Adapter state. */
+ * agd_denoise_panorama, agd_denoise_regions, and a set ControlNet, GLIGEN, inpainting, InstructPix2Pix, T2I-Adapter or IP-Adapter state. */
 #define AGD_MAX_CONTEXT_TOKENS 320
 int agd_set_context(agd_ctx* ctx, const float* ctx_emb, int batch2, int tokens, void* stream);
 
@@ -630,6 +630,45 @@ int agd_op_window_mean(const float* views, float* canvas, int B, int C, int Lh, 
 int agd_denoise_panorama(agd_ctx* ctx, float* canvas, int batch, int Lh, int Lw, int window, int stride, int view_batch, int n_steps,
                          const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
 int agd_daam_global_panorama(agd_ctx* ctx, int img, int rows, float* out, void* stream);
+
+/* ---- Region-based MultiDiffusion (Bar-Tal et al. 2023; the MultiDiffusion repository's region_based.py [upstream-knowledge], parity-unpinned:
+ * diffusers 0.21.2 has no such pipeline; csrc/regions.hip).  R regions share ONE latent canvas [batch][4][Lh][Lw]; region 0 is the background.
+ * Row (region r, image p) is r * batch + p everywhere: the latent masks [R][batch][Lh * Lw] fp32 (one value per latent pixel), the UNet batch
+ * within a CFG half, the context rows and the DAAM states.  At most AGD_MAX_REGIONS regions.
+ * agd_op_region_masks (seam for tests, and the pipeline's mask front end): pixel masks on the device, uint8 (set: > 127; px_f32 = 0) or fp32
+ *   (set: > 0.5; px_f32 = 1), [per_image ? B : 1][R - 1][H][W] -> masks.  H / Lh and W / Lw must be whole; latent (y, x) reads pixel
+ *   (y H / Lh, x W / Lw) (torch's nearest sample); row 0 is max(0, 1 - the sum of the foreground rows).  R = 1 reads no pixels.
+ * agd_op_region_spread (seam for tests): x [R][B][C][Lh * Lw] from canvas [B][C][Lh * Lw].  idx == NULL (a step past the bootstrapping
+ *   phase): every region is the canvas.  Else idx is a HOST array of R - 1 background indices in 0 .. n_bg - 1 and, for r >= 1,
+ *   x = canvas m + (sa bgs[idx[r - 1]] + sb noise) (1 - m) with bgs [n_bg][C][Lh * Lw] and noise [B][C][Lh * Lw]; region 0 is the canvas.
+ * agd_op_region_mean (seam for tests): canvas = sum_r m_r x_r / sum_r m_r, both sums in ascending r in fp32, one division per element; the
+ *   sum itself (0) where no mask covers the element.  Deterministic, no atomics; any channel count.
+ * agd_denoise_regions: the DDIM loop on the canvas in place.  Per step s: spread (bootstrapped while s < bootstrapping, with the step's
+ *   sqrt_ac pair and idx row), the CFG UNet on the 2 R batch rows in ONE forward -- the context set by agd_set_context must hold
+ *   [uncond x R batch | cond x R batch] -- the DDIM step on the R batch rows, then the masked mean.  Stateless: everything the call reads
+ *   comes in the descriptor and nothing is kept.  With the DAAM recorder on it must hold R batch images at Lh x Lw
+ *   (agd_record_reset_hw(ctx, R * batch, Lh, Lw)); agd_daam_global(ctx, r * batch + p, ...) is region r's map of image p.
+ *   Refused by name before the first launch: a ControlNet, GLIGEN or T2I-Adapter schedule, an IP-Adapter image, either inpainting state, an
+ *   InstructPix2Pix state, a Perturbed-Attention Guidance or DeepCache schedule, a guidance rescale, the hook.py recorder, a context over 96
+ *   tokens, an inpainting UNet, and a bad descriptor.  FreeU and LoRA belong to the UNet and apply unchanged. */
+#define AGD_MAX_REGIONS 8
+typedef struct agd_regions_desc {
+  int struct_size;                 /* sizeof(agd_regions_desc), ABI guard */
+  int regions;                     /* R >= 1 */
+  int bootstrapping;               /* 0 .. n_steps: the first steps whose foreground regions see a background outside their mask */
+  int n_backgrounds;               /* N >= 1 when bootstrapping > 0 and R > 1 */
+  const float* masks;              /* device [R][batch][Lh * Lw] */
+  const float* noise;              /* device [batch][4][Lh][Lw]: the call's initial latents */
+  const float* backgrounds;        /* device [N][4][Lh][Lw]: encoded constant-colour images, times the scaling factor */
+  const int* idx;                  /* host [bootstrapping][R - 1], each in 0 .. N - 1 */
+  const float* sqrt_ac;            /* host [bootstrapping][2]: (sqrt(ac_t), sqrt(1 - ac_t)) of the step */
+} agd_regions_desc;
+int agd_op_region_masks(const void* px, int px_f32, int per_image, float* masks, int R, int B, int H, int W, int Lh, int Lw, void* stream);
+int agd_op_region_spread(const float* canvas, float* x, const float* masks, const float* noise, const float* bgs, int R, int B, int C, int Lh,
+                         int Lw, int n_bg, const int* idx, float sa, float sb, void* stream);
+int agd_op_region_mean(const float* x, const float* masks, float* canvas, int R, int B, int C, int Lh, int Lw, void* stream);
+int agd_denoise_regions(agd_ctx* ctx, float* canvas, int batch, int Lh, int Lw, const agd_regions_desc* desc, int n_steps,
+                        const float* timesteps, const float* alpha_t, const float* alpha_prev, float guidance, void* stream);
 
 /* ---- FreeU (Si et al. 2023; diffusers >= 0.22 enable_freeu(s1, s2, b1, b2) / disable_freeu [upstream-knowledge]; csrc/freeu.hip): a
  * training-free re-weighting of the UNet decoder.  In up block i in {0, 1}, for every resnet of the block and immediately before its concat,
