@@ -5,6 +5,7 @@ scripts use (StableDiffusionPipeline, daam.trace, the attention-processor hooker
 from . import config, synthetic, ip_adapter  # noqa: F401
 from .pipeline import StableDiffusionPipeline, PipelineOutput, Engine, DeepCacheSDHelper  # noqa: F401
 from .pipeline import StableDiffusionPipeline as StableDiffusionPAGPipeline  # noqa: F401  (diffusers' name: the same class, pag_applied_layers=)
+from .pipeline import StableDiffusionPipeline as SemanticStableDiffusionPipeline  # noqa: F401  (diffusers' name: the same class, editing_prompt=)
 from .trace import trace, GlobalHeatMap, WordHeatMap, compute_token_merge_indices  # noqa: F401
 from .hook import UNetCrossAttentionHooker  # noqa: F401
 from .scheduler import DDIMScheduler  # noqa: F401
@@ -16,7 +17,7 @@ from .gligen import StableDiffusionGLIGENPipeline  # noqa: F401
 from .panorama import StableDiffusionPanoramaPipeline, get_views  # noqa: F401
 from .regions import StableDiffusionRegionPipeline  # noqa: F401
 
-__all__ = ["StableDiffusionPipeline", "StableDiffusionPAGPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
+__all__ = ["StableDiffusionPipeline", "StableDiffusionPAGPipeline", "SemanticStableDiffusionPipeline", "PipelineOutput", "Engine", "trace", "GlobalHeatMap", "WordHeatMap",
            "compute_token_merge_indices", "UNetCrossAttentionHooker", "DDIMScheduler", "config", "synthetic", "ip_adapter",
            "ControlNetModel", "StableDiffusionControlNetPipeline", "T2IAdapter", "StableDiffusionAdapterPipeline",
            "StableDiffusionInpaintPipeline",

@@ -100,6 +100,18 @@ class AgdRegionsDesc(C.Structure):
     ]
 
 
+AGD_MAX_EDIT_CONCEPTS = 8
+
+
+class AgdSegaDesc(C.Structure):
+    """`agd_sega_desc`: the Semantic Guidance schedule of the calls to come (agd_sega_set copies the host arrays)."""
+    _fields_ = [
+        ("struct_size", C.c_int), ("concepts", C.c_int), ("n_evals", C.c_int), ("mom_scale", C.c_float), ("mom_beta", C.c_float),
+        ("coef", C.POINTER(C.c_float)), ("q", C.POINTER(C.c_double)), ("w_mom", C.POINTER(C.c_float)), ("w_add", C.POINTER(C.c_float)),
+        ("add_mom", C.POINTER(C.c_float)),
+    ]
+
+
 class AgendaHipError(RuntimeError):
     pass
 
@@ -246,6 +258,12 @@ _SIGS = {
     "agd_pag_counts": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "agd_op_pag_v_rows": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "agd_op_pag_fold": (C.c_int, [_P, _P, C.c_longlong, C.c_float, _P]),
+    "agd_sega_set": (C.c_int, [_P, C.POINTER(AgdSegaDesc)]),
+    "agd_sega_clear": (C.c_int, [_P]),
+    "agd_sega_counts": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "agd_op_sega_threshold": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double), _P, _P]),
+    "agd_op_sega_fold": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.c_float, C.c_float, C.c_float, _P]),
     "agd_deepcache_set": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.c_int]),
     "agd_deepcache_clear": (C.c_int, [_P]),
     "agd_deepcache_counts": (C.c_int, [_P, C.POINTER(C.c_longlong)]),

@@ -20,7 +20,7 @@ import torch
 
 from .config import AdapterConfig, SDConfig, adapter_config_for, adapter_config_from_json, adapter_schedule
 from .controlnet import evaluation_count
-from .pipeline import StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 
 _WEIGHTS = "diffusion_pytorch_model.safetensors"
 _IMAGE_HELP = "image: a PIL image, a list of PIL images, a uint8 [B,H,W,C] or a float [B,C,H,W] tensor in [0,1]"
@@ -177,8 +177,9 @@ class StableDiffusionAdapterPipeline(StableDiffusionPipeline):
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  num_images_per_prompt: int = 1, adapter_conditioning_scale: float = 1.0, adapter_conditioning_factor: float = 1.0,
                  cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         refuse_pag("StableDiffusionAdapterPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionAdapterPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionAdapterPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionAdapterPipeline", max_embeddings_multiples, prompt_embeds)
         if isinstance(adapter_conditioning_scale, (list, tuple)):

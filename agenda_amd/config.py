@@ -515,6 +515,84 @@ def pag_schedule(timesteps, pag_scale: float, pag_adaptive_scale: float = 0.0) -
     return [max(0.0, p - a * (1000.0 - float(t))) for t in timesteps]
 
 
+MAX_EDIT_CONCEPTS = 8          # AGD_MAX_EDIT_CONCEPTS
+
+
+def sega_per_concept(name: str, value, K: int, default=None) -> list:
+    """A per-concept argument of Semantic Guidance: a scalar (for every concept) or a list of K, as upstream; None is `default`."""
+    if value is None:
+        value = default
+    if isinstance(value, (list, tuple)):
+        if len(value) != K:
+            raise ValueError(f"{name} has {len(value)} entries for {K} editing concepts (a scalar, or one entry per concept)")
+        return list(value)
+    return [value] * K
+
+
+def sega_schedule(n_evaluations: int, concepts: int, reverse_editing_direction=False, edit_guidance_scale=5, edit_threshold=0.9,
+                  edit_warmup_steps=10, edit_cooldown_steps=None, edit_weights=None) -> dict:
+    """The host scalars of a Semantic Guidance call [upstream-knowledge: diffusers 0.21.2 SemanticStableDiffusionPipeline; parity-unpinned], one
+    row per model evaluation i counted from 0 (PNDM's extra evaluation and img2img's shortened grid count as they run).  Concept k is active at
+    i iff i < cooldown_k (None: always); coef[i][k] = sign_k scale_k if active else 0; w_mom[i] = softmax_k(weight_k if active else 0) over all
+    K; with W = {k : i >= warmup_k}: w_add = w_mom and add_mom = 1 if W is everything, both 0 if W is empty, else w_add = the softmax of the
+    same values over W alone (0 elsewhere) and add_mom = 0.  Computed in float64, rounded to fp32.  Returns {"concepts", "n_evals", "coef",
+    "w_mom", "w_add" ([n][K] lists), "add_mom" ([n]), "q" ([K], float64), "walks", "folds"} -- walks: the evaluations with a non-zero coef."""
+    import math
+    import struct
+    K, n = concepts, n_evaluations
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"n_evaluations={n!r}: a call runs at least one model evaluation")
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1 or K > MAX_EDIT_CONCEPTS:
+        raise ValueError(f"editing_prompt: {K!r} editing concepts (1 .. {MAX_EDIT_CONCEPTS})")
+    rev = sega_per_concept("reverse_editing_direction", reverse_editing_direction, K, False)
+    scale = [float(x) for x in sega_per_concept("edit_guidance_scale", edit_guidance_scale, K, 5)]
+    q = [float(x) for x in sega_per_concept("edit_threshold", edit_threshold, K, 0.9)]
+    warm = sega_per_concept("edit_warmup_steps", edit_warmup_steps, K, 10)
+    cool = sega_per_concept("edit_cooldown_steps", edit_cooldown_steps, K, None)
+    wts = [float(x) for x in sega_per_concept("edit_weights", edit_weights, K, 1.0)]
+    for k in range(K):
+        if not math.isfinite(scale[k]):
+            raise ValueError(f"edit_guidance_scale={scale[k]!r} for concept {k}: a finite number")
+        if not (0.0 <= q[k] <= 1.0):
+            raise ValueError(f"edit_threshold={q[k]!r} for concept {k}: a quantile in [0, 1]")
+        if not math.isfinite(wts[k]):
+            raise ValueError(f"edit_weights={wts[k]!r} for concept {k}: a finite number")
+        if isinstance(warm[k], bool) or not isinstance(warm[k], int) or warm[k] < 0:
+            raise ValueError(f"edit_warmup_steps={warm[k]!r} for concept {k}: an integer >= 0")
+        if cool[k] is not None and (isinstance(cool[k], bool) or not isinstance(cool[k], int) or cool[k] < 0):
+            raise ValueError(f"edit_cooldown_steps={cool[k]!r} for concept {k}: None or an integer >= 0")
+
+    def f32(x: float) -> float:
+        return struct.unpack("f", struct.pack("f", x))[0]
+
+    def softmax(vals):
+        mx = max(vals)
+        e = [math.exp(v - mx) for v in vals]
+        s = sum(e)
+        return [x / s for x in e]
+
+    coef, w_mom, w_add, add_mom = [], [], [], []
+    for i in range(n):
+        active = [cool[k] is None or i < cool[k] for k in range(K)]
+        coef.append([f32((-1.0 if rev[k] else 1.0) * scale[k]) if active[k] else 0.0 for k in range(K)])
+        vals = [wts[k] if active[k] else 0.0 for k in range(K)]
+        wm = softmax(vals)
+        W = [k for k in range(K) if i >= warm[k]]
+        if len(W) == K:
+            wa, am = wm, 1.0
+        elif not W:
+            wa, am = [0.0] * K, 0.0
+        else:
+            sub = softmax([vals[k] for k in W])
+            wa = [0.0] * K
+            for j, k in enumerate(W):
+                wa[k] = sub[j]
+            am = 0.0
+        w_mom.append([f32(x) for x in wm]); w_add.append([f32(x) for x in wa]); add_mom.append(am)
+    return {"concepts": K, "n_evals": n, "coef": coef, "w_mom": w_mom, "w_add": w_add, "add_mom": add_mom, "q": q,
+            "walks": sum(1 for row in coef if any(c != 0.0 for c in row)), "folds": n}
+
+
 def deepcache_schedule(n_evaluations: int, cache_interval: int) -> List[int]:
     """DeepCache's uniform schedule [upstream-knowledge: DeepCacheSDHelper, skip_mode "uniform"; parity-unpinned]: one flag per model
     evaluation of a call, counted from 0 whatever the scheduler (PNDM's extra evaluation and img2img's tail of the grid included) --

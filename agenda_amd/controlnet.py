@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .config import ControlNetConfig, SDConfig, controlnet_config_from_json, controlnet_keep_schedule
-from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 from .scheduler import DPMSolverMultistepScheduler, PNDMScheduler
 
 _WEIGHTS = "diffusion_pytorch_model.safetensors"
@@ -174,8 +174,9 @@ class StableDiffusionControlNetPipeline(StableDiffusionPipeline):
                  num_images_per_prompt: int = 1, controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
                  control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, cross_attention_kwargs: Optional[dict] = None,
                  guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         refuse_pag("StableDiffusionControlNetPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionControlNetPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionControlNetPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionControlNetPipeline", max_embeddings_multiples, prompt_embeds)
         if guess_mode:

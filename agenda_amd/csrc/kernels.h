@@ -1,6 +1,7 @@
 // Internal launcher interface between the C-ABI/runtime (model.hip) and the HIP kernels.
 #pragma once
 #include "common.h"
+#include "../../include/agenda_hip.h"   // the C ABI's limits that size kernel arguments (AGD_MAX_EDIT_CONCEPTS)
 
 // ---------------------------------------------------------------------------------------
 // Implicit GEMM:  out[M][N] = epilogue( alpha * sum_k A[m][k] * W[n][k] )
@@ -284,6 +285,20 @@ int launch_adapter_add(const bf16_t* h, const float* f, bf16_t* y, float* part, 
 // two-way step kernels; e_p == e_c leaves both rows untouched
 int launch_pag_v_rows(const bf16_t* qkv, bf16_t* att, int M, int C, hipStream_t st);
 int launch_pag_fold(float* eps, long long n, float p, hipStream_t st);
+
+// Semantic Guidance (sega.hip): one evaluation's scalars per concept -- coef, the rank lo and fraction f of the quantile (sega_rank: p = q (HW - 1)
+// in double, lo = floor(p), f = float(p - lo)) and the two weights -- passed by value.  threshold: eps fp32 [(2 + K) B][HW][4] -> thr [B][K][4],
+// one workgroup per (image, concept), exact order statistics of |(e_k - e_u) coef_k| by radix select (integer LDS atomics only), staged in LDS
+// up to SEGA_STAGE_MAX_HW pixels; a concept with coef == 0 gives thr = 0 without reading its rows.  fold: G_k = v_k where |v_k| >= thr else 0,
+// g = sum w_mom G + mu m, added = sum w_add G + add_mom mu m, m <- beta m + (1 - beta) g, rows [0, 2 B) += added; C != 4 is refused by name.
+#define SEGA_STAGE_MAX_HW 9216
+struct SegaEvalP { float coef[AGD_MAX_EDIT_CONCEPTS]; int lo[AGD_MAX_EDIT_CONCEPTS]; float f[AGD_MAX_EDIT_CONCEPTS];
+                   float w_mom[AGD_MAX_EDIT_CONCEPTS]; float w_add[AGD_MAX_EDIT_CONCEPTS]; };
+void sega_rank(double q, int HW, int* lo, float* f);
+int sega_staged(int HW);
+int launch_sega_threshold(const float* eps, int B, int K, int C, int HW, const SegaEvalP& p, float* thr, hipStream_t st);
+int launch_sega_fold(float* eps, float* mom, const float* thr, int B, int K, int C, int HW, const SegaEvalP& p, float mu, float beta, float add_mom,
+                     hipStream_t st);
 
 // DeepCache (deepcache.hip): the capture of a full evaluation -- two byte regions (the cached activation, its GroupNorm partial sums) copied
 // bit for bit in one launch, 16-byte loads and stores with the tail bytes handled (every region 16-byte aligned, else refused; a region of 0

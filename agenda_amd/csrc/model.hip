@@ -256,6 +256,11 @@ struct agd_ctx {
   // sums were left, the consumer runs its own statistics pass).  dc_valid: the slot holds a capture of (dc_rows, dc_Lh, dc_Lw, dc_b).
   // dc_counts: full evaluations that captured / shallow evaluations
   std::vector<int> dc_sched; int dc_branch = 0; long long dc_counts[2] = {0, 0};
+  // Semantic Guidance (agd_sega_set / agd_sega_clear): sega_K > 0 = set; the descriptor's arrays, copied -- coef, w_mom, w_add [n][K], add_mom [n],
+  // q [K].  sega_momb: the momentum fp32 [B][HW][4], zeroed at the start of every call; sega_thrb: the thresholds [B][K][4] of the evaluation
+  // in flight.  sega_counts: concept walks / folds
+  int sega_K = 0, sega_n = 0; float sega_mu = 0.f, sega_beta = 0.f; std::vector<float> sega_coef, sega_wmom, sega_wadd, sega_addmom; std::vector<double> sega_q;
+  DBuf sega_momb, sega_thrb; long long sega_counts[2] = {0, 0};
   DBuf dc_buf; Act dc_act; bool dc_valid = false; int dc_rows = 0, dc_Lh = 0, dc_Lw = 0, dc_b = 0;
   // profiling
   EvalCond cur;                                       // the forward being walked (unet_walk sets it; tblock_plan, down_mid_walk and adapter_add read it)
@@ -1571,7 +1576,7 @@ AGD_API void agd_destroy(agd_ctx* c) {
   c->pano_viewb.release(); c->pano_hmb.release(); c->reg_xb.release(); c->pano_ctxb.release(); c->i2_latb.release();
   c->ctxb.release(); c->hook_sumb.release(); c->hook_scratchb.release(); c->hook_headsb.release(); c->hook_storeb.release(); c->bwd_wsb.release();
   for (auto& xl : c->xl) { xl.wqTb.release(); xl.wkvTb.release(); xl.woTb.release(); xl.pm_kppb.release(); xl.pm_vppb.release(); xl.pm_csb.release(); }
-  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->dc_buf.release(); c->cn_embb.release(); c->lora_descb.release();
+  c->latb.release(); c->epsb.release(); c->vae_imgb.release(); c->plmsb.release(); c->dpmb.release(); c->gr_factb.release(); c->sega_momb.release(); c->sega_thrb.release(); c->dc_buf.release(); c->cn_embb.release(); c->lora_descb.release();
   for (auto& f : c->gl_f) f.gkvb.release();
   c->gl_objb.release();
   for (auto& b : c->ad_featb) b.release();
@@ -2205,6 +2210,7 @@ struct CallCond {
   const float* pag = nullptr;                                      // the PAG scales: the loop runs a third walk where pag[i] > 0 (at(i) stays the main walk's)
   // DeepCache's flags (1 = full, 0 = shallow) of the call's dc_n evaluations at branch dc_b: a full evaluation captures iff the next one is shallow
   const int* dc = nullptr; int dc_n = 0, dc_b = 0;
+  bool sega = false;                                               // a Semantic Guidance state: the loop runs the concept walk, the threshold and the fold
   EvalCond at(int i) const {
     EvalCond e; e.cn_scale = cn ? cn[i] : 0.f; e.grounded = gl && gl[i]; e.ad_scale = ad ? ad[i] : 0.f; e.ipa = ipa;
     if (dc) { e.dc = !dc[i] ? DC_SHALLOW : (i + 1 < dc_n && !dc[i + 1]) ? DC_CAPTURE : 0; e.dc_branch = dc_b; }
@@ -2214,7 +2220,7 @@ struct CallCond {
 // who resolves: agd_unet_forward_hw, agd_unet_forward_ts_hw, run_eval_loop, run_ip2p_loop, agd_denoise_panorama, agd_deepcache_forward_hw,
 // agd_denoise_regions
 enum Caller { CALL_UNET_FORWARD, CALL_UNET_FORWARD_TS, CALL_EVAL_LOOP, CALL_IP2P_LOOP, CALL_PANORAMA, CALL_DC_FORWARD, CALL_REGIONS };
-enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, ST_DC, N_COND_STATES };                       // the states a call can meet, in the order of a row's cells
+enum CondState { ST_CN, ST_GL, ST_INP, ST_I2P, ST_AD, ST_IPA, ST_PAG, ST_DC, ST_SEGA, N_COND_STATES };                       // the states a call can meet, in the order of a row's cells
 // One row per refusing party: a state (self) that, when set, refuses to run beside others in the callers that consult it, or an entry point
 // that runs the UNet alone (self < 0: it refuses whenever it is the caller).  with[s]: nullptr = allowed beside state s, else the refusal.
 // Rows are looked at top to bottom, the first set cell wins.  Whatever is not here is allowed: ControlNet + GLIGEN, GLIGEN + either
@@ -2312,6 +2318,29 @@ static const ConflictRow kRegionConflicts[] = {
     "denoise_regions: a Perturbed-Attention Guidance schedule is set; Perturbed-Attention Guidance with region prompts is not implemented (agd_pag_clear first)",
     "denoise_regions: a DeepCache schedule is set; DeepCache with region prompts is not implemented (agd_deepcache_clear first)" } },
 };
+// Semantic Guidance's rows, consulted last, in a table of their own for the same reason (the tables above leave their ST_SEGA cell empty).  The
+// concept walk runs the plain UNet on K B rows of its own context: nothing that is set for 2 B rows, or that runs a walk of its own, beside it.
+#define SEGA_NULL8 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr
+static const ConflictRow kSegaConflicts[] = {
+  { ST_SEGA, 1u << CALL_UNET_FORWARD | 1u << CALL_EVAL_LOOP | 1u << CALL_IP2P_LOOP, {   // sega
+    "sega: a ControlNet schedule is set; Semantic Guidance with a ControlNet is not implemented (clear one of them)",
+    "sega: a GLIGEN schedule is set; Semantic Guidance with GLIGEN is not implemented (clear one of them)",
+    "sega: an inpainting state is set; Semantic Guidance with inpainting is not implemented (agd_inpaint_clear or agd_sega_clear first)",
+    "sega: an InstructPix2Pix state is set; Semantic Guidance with InstructPix2Pix is not implemented (agd_ip2p_clear or agd_sega_clear first)",
+    "sega: a T2I-Adapter schedule is set; Semantic Guidance with a T2I-Adapter is not implemented (clear one of them)",
+    "sega: an IP-Adapter image is set; Semantic Guidance with an IP-Adapter is not implemented (agd_ip_adapter_clear or agd_sega_clear first)",
+    "sega: a Perturbed-Attention Guidance schedule is set; Semantic Guidance with Perturbed-Attention Guidance is not implemented (agd_pag_clear or agd_sega_clear first)",
+    "sega: a DeepCache schedule is set; Semantic Guidance with DeepCache is not implemented (agd_deepcache_clear or agd_sega_clear first)",
+    nullptr } },
+  { -1, 1u << CALL_UNET_FORWARD_TS, { SEGA_NULL8,
+    "unet_forward_ts: a Semantic Guidance state is set; per-image timesteps run the UNet alone (agd_sega_clear first)" } },
+  { -1, 1u << CALL_PANORAMA, { SEGA_NULL8,
+    "denoise_panorama: a Semantic Guidance state is set; Semantic Guidance on a panorama is not implemented (agd_sega_clear first)" } },
+  { -1, 1u << CALL_DC_FORWARD, { SEGA_NULL8,
+    "deepcache_forward: a Semantic Guidance state is set; DeepCache with Semantic Guidance is not implemented (agd_sega_clear first)" } },
+  { -1, 1u << CALL_REGIONS, { SEGA_NULL8,
+    "denoise_regions: a Semantic Guidance state is set; Semantic Guidance with region prompts is not implemented (agd_sega_clear first)" } },
+};
 // an InstructPix2Pix UNet reads the latent channels and the VAE's latent channels
 static int ip2p_check_unet(agd_ctx* c, const char* what) {
   const agd_config& g = c->cfg;
@@ -2329,10 +2358,11 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   bool set[N_COND_STATES];
   set[ST_CN] = !c->cn_sched.empty(); set[ST_GL] = !c->gl_sched.empty(); set[ST_INP] = c->ip_mode != 0; set[ST_I2P] = c->i2_on;
   set[ST_AD] = !c->ad_sched.empty(); set[ST_IPA] = c->ipa_B2 > 0 && c->ipa_scale != 0.f; set[ST_PAG] = !c->pag_sched.empty();
-  set[ST_DC] = !c->dc_sched.empty();
-  for (const ConflictRow* t : {kConflicts, kPagConflicts, kDcConflicts, kRegionConflicts}) {   // (b) rows top to bottom, the first set cell wins
+  set[ST_DC] = !c->dc_sched.empty(); set[ST_SEGA] = c->sega_K > 0;
+  for (const ConflictRow* t : {kConflicts, kPagConflicts, kDcConflicts, kRegionConflicts, kSegaConflicts}) {   // (b) rows top to bottom, the first set cell wins
     const size_t rows = t == kConflicts ? sizeof(kConflicts) / sizeof(kConflicts[0]) : t == kPagConflicts ? sizeof(kPagConflicts) / sizeof(kPagConflicts[0])
-                                        : t == kDcConflicts ? sizeof(kDcConflicts) / sizeof(kDcConflicts[0]) : sizeof(kRegionConflicts) / sizeof(kRegionConflicts[0]);
+                                        : t == kDcConflicts ? sizeof(kDcConflicts) / sizeof(kDcConflicts[0])
+                                        : t == kRegionConflicts ? sizeof(kRegionConflicts) / sizeof(kRegionConflicts[0]) : sizeof(kSegaConflicts) / sizeof(kSegaConflicts[0]);
     for (size_t k = 0; k < rows; ++k) {
       const ConflictRow& r = t[k];
       if (!((r.callers >> who) & 1) || (r.self >= 0 && !set[r.self])) continue;
@@ -2348,7 +2378,7 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
     if (who == CALL_REGIONS) FAIL("denoise_regions: a context of %d tokens is not supported (at most 96)", T);
     static const struct { int st; const char* what; } kLong[] = {
       {ST_CN, "a ControlNet schedule"}, {ST_GL, "a GLIGEN schedule"}, {ST_INP, "an inpainting state"}, {ST_I2P, "an InstructPix2Pix state"},
-      {ST_AD, "a T2I-Adapter schedule"}, {ST_IPA, "an IP-Adapter image"} };
+      {ST_AD, "a T2I-Adapter schedule"}, {ST_IPA, "an IP-Adapter image"}, {ST_SEGA, "a Semantic Guidance state"} };
     for (const auto& k : kLong) {
       if (!set[k.st] || (k.st == ST_INP && who != CALL_EVAL_LOOP) || (k.st == ST_I2P && who != CALL_IP2P_LOOP)) continue;   // (only where the caller reads the state)
       FAIL("long context: %s is set; a context of %d tokens (over 96) runs the plain UNet only (clear it first)", k.what, T);
@@ -2405,6 +2435,13 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
     if ((int)c->pag_sched.size() != n) FAIL("pag: the schedule has %zu scales, this call runs %d model evaluations (agd_pag_set)", c->pag_sched.size(), n);
     out->pag = c->pag_sched.data();
   }
+  if (set[ST_SEGA]) {
+    if (c->sega_n != n) FAIL("sega: the schedule covers %d model evaluations, this call runs %d (agd_sega_set)", c->sega_n, n);
+    if (c->cfg.out_channels != 4) FAIL("sega: the UNet has %d output channels; the Semantic Guidance kernels read rows of 4 (out_channels = 4)", c->cfg.out_channels);
+    if (who == CALL_UNET_FORWARD && (rows % (2 + c->sega_K) || rows < 2 + c->sega_K))
+      FAIL("sega: unet_forward on %d rows; %d concepts take (2 + K) B = a multiple of %d rows", rows, c->sega_K, 2 + c->sega_K);
+    out->sega = true;
+  }
   if (set[ST_DC] && who == CALL_EVAL_LOOP) {
     if ((int)c->dc_sched.size() != n) FAIL("deepcache: the schedule has %zu flags, this call runs %d model evaluations (agd_deepcache_set)", c->dc_sched.size(), n);
     if (c->dc_branch > c->cfg.layers_per_block - 1) FAIL("deepcache: branch %d (this UNet has branches 0 .. %d)", c->dc_branch, c->cfg.layers_per_block - 1);
@@ -2415,13 +2452,14 @@ static int resolve_cond(agd_ctx* c, Caller who, int n, int rows, int Lh, int Lw,
   }
   return 0;
 }
-// The perturbed walk of a Perturbed-Attention Guidance evaluation runs `rows` images against context rows [row0, row0 + rows) of what
-// agd_set_context projected -- in a loop the [cond x B] half of [uncond x B | cond x B] (PanoCtx::point's arithmetic), in agd_unet_forward_hw
-// all of it -- and records nothing.  The engine is put back as it was when the walk ends, on an error too.
-struct PagWalk {
+// A non-recording side walk of `rows` images against context rows [row0, row0 + rows) of what agd_set_context projected (PanoCtx::point's
+// arithmetic).  Perturbed-Attention Guidance's perturbed walk: in a loop the [cond x B] half of [uncond x B | cond x B], in
+// agd_unet_forward_hw all of it.  Semantic Guidance's concept walk: the K B rows from row 2 B on.  Nothing is recorded, and the engine is put
+// back as it was when the walk ends, on an error too.  count: the feature's walk counter, advanced once.
+struct SideWalk {
   struct Saved { bf16_t* kv; bf16_t* kpp; bf16_t* vpp; float* kcs; float* kbs; };
   agd_ctx* c; int B2, mode; std::vector<Saved> saved;
-  PagWalk(agd_ctx* c_, int row0, int rows) : c(c_), B2(c_->ctx_B2), mode(c_->rec_mode) {
+  SideWalk(agd_ctx* c_, int row0, int rows, long long* count) : c(c_), B2(c_->ctx_B2), mode(c_->rec_mode) {
     const size_t off = (size_t)row0;
     if (off) {
       saved.reserve(c->xl.size());
@@ -2433,9 +2471,9 @@ struct PagWalk {
         xl.pm_kpp += off * HT * xl.C; xl.pm_vpp += off * HT * xl.C; xl.pm_kcs += off * HT; xl.pm_kbs += off * HT;
       }
     }
-    c->ctx_B2 = rows; c->rec_mode = 0; c->pag_counts[0]++;
+    c->ctx_B2 = rows; c->rec_mode = 0; ++*count;
   }
-  ~PagWalk() {
+  ~SideWalk() {
     for (size_t k = 0; k < saved.size(); ++k) {
       XLayer& xl = c->xl[k]; const Saved& v = saved[k];
       xl.kv = v.kv; xl.pm_kpp = v.kpp; xl.pm_vpp = v.vpp; xl.pm_kcs = v.kcs; xl.pm_kbs = v.kbs;
@@ -2443,6 +2481,57 @@ struct PagWalk {
     c->ctx_B2 = B2; c->rec_mode = mode; c->cur.pag = false;
   }
 };
+// Semantic Guidance (sega.hip).  SegaMain: the main walk of an evaluation sees the first `rows` = 2 B rows of the (2 + K) B-row context (they
+// are its head: no pointer moves), so the shared prefix and the recorders' conditional half are what they are without the state; rows == 0:
+// nothing changes.  The engine is put back when the walk ends, on an error too.
+struct SegaMain {
+  agd_ctx* c; int B2;
+  SegaMain(agd_ctx* c_, int rows) : c(c_), B2(c_->ctx_B2) { if (rows) c->ctx_B2 = rows; }
+  ~SegaMain() { c->ctx_B2 = B2; }
+};
+// evaluation i's scalars for the kernels
+static SegaEvalP sega_eval(const agd_ctx* c, int i, int HW) {
+  SegaEvalP p{};
+  for (int k = 0; k < c->sega_K; ++k) {
+    p.coef[k] = c->sega_coef[(size_t)i * c->sega_K + k]; p.w_mom[k] = c->sega_wmom[(size_t)i * c->sega_K + k]; p.w_add[k] = c->sega_wadd[(size_t)i * c->sega_K + k];
+    sega_rank(c->sega_q[k], HW, &p.lo[k], &p.f[k]);
+  }
+  return p;
+}
+// What follows the main walk of evaluation i of a Semantic Guidance call on `batch` images: lat_bf16 rows [0, 2 B) hold the main walk's input,
+// eps rows [0, 2 B) its output.  walk_always: agd_unet_forward_hw returns the concept rows, so it walks them whatever the coefficients.
+static int sega_after_main(agd_ctx* c, hipStream_t st, int i, int batch, int Lh, int Lw, float t, const float* tproj_row, const EvalCond& ec, bool walk_always) {
+  const int K = c->sega_K, HW = Lh * Lw, B2 = 2 * batch;
+  const long long ne = (long long)batch * HW * 4;
+  const SegaEvalP p = sega_eval(c, i, HW);
+  bool any = false;
+  for (int k = 0; k < K; ++k) any = any || p.coef[k] != 0.f;
+  float* thr = c->sega_thrb.as<float>();
+  if (any || walk_always) {
+    // e_k: the conditional rows again (K copies of their input), concept k's B rows against context rows [(2 + k) B, (3 + k) B), into eps
+    // rows [2 B, (2 + K) B); nothing is recorded
+    bf16_t* xin_k = c->lat_bf16 + (size_t)B2 * HW * 64;
+    { ProfScope ps(c, st, PC_ELEM, 0); CK(launch_tile_rows(c->lat_bf16 + (size_t)batch * HW * 64, xin_k, 1, batch, K, (size_t)HW * 64 * 2, st)); }
+    { SideWalk sw(c, B2, K * batch, &c->sega_counts[0]);
+      CK(unet_walk(c, st, xin_k, K * batch, Lh, Lw, t, c->eps_nhwc + 2 * ne, tproj_row, false, 0, ec)); }
+  }
+  ProfScope ps(c, st, PC_ELEM, 0);
+  if (any) CK(launch_sega_threshold(c->eps_nhwc, batch, K, c->cfg.out_channels, HW, p, thr, st));
+  CK(launch_sega_fold(c->eps_nhwc, c->sega_momb.as<float>(), thr, batch, K, c->cfg.out_channels, HW, p, c->sega_mu, c->sega_beta, c->sega_addmom[i], st));
+  c->sega_counts[1]++;
+  return 0;
+}
+// a Semantic Guidance call's buffers for `batch` images, the momentum zeroed
+static int sega_begin(agd_ctx* c, hipStream_t st, int batch, int Lh, int Lw) {
+  const size_t ne = (size_t)batch * Lh * Lw * 4;
+  if (c->ctx_B2 != (2 + c->sega_K) * batch)
+    FAIL("sega: the context holds %d rows; %d concepts on %d images take (2 + K) B = %d: [uncond x B | cond x B | concept_0 x B | ...] (agd_set_context)",
+         c->ctx_B2, c->sega_K, batch, (2 + c->sega_K) * batch);
+  CK(ensure_lat(c, (2 + c->sega_K) * batch, Lh, Lw));
+  CK(c->sega_momb.ensure(ne * sizeof(float))); CK(c->sega_thrb.ensure((size_t)batch * c->sega_K * 4 * sizeof(float)));
+  if (hipMemsetAsync(c->sega_momb.p, 0, ne * sizeof(float), st) != hipSuccess) FAIL("sega: momentum clear failed");
+  return 0;
+}
 // the UNet input of one CFG evaluation: the latents (txt2img) or latents | mask | masked-image latents (9-channel inpainting), both CFG halves
 static int prep_unet_input(agd_ctx* c, hipStream_t st, const float* latents, int batch, int HW) {
   ProfScope ps(c, st, PC_ELEM, 0);
@@ -2473,9 +2562,15 @@ AGD_API int agd_unet_forward_hw(agd_ctx* c, const float* sample, int batch2, int
   CallCond cc; API_CK(c, resolve_cond(c, CALL_UNET_FORWARD, 1, batch2, Lh, Lw, &cc));
   { ProfScope ps(c, st, PC_ELEM, 0); API_CK(c, launch_prep_latents(sample, c->lat_bf16, batch2, Cl, Lh * Lw, 64, 1, 1.0f, st)); }
   EvalCond ec = cc.at(0);
-  if (cc.pag && cc.pag[0] > 0.f) {                                  // every row is the perturbed branch, against the caller's context as it is; nothing is recorded
+  if (cc.sega) {                                                   // one Semantic Guidance evaluation on (2 + K) B rows: the folded pair, then the concept rows
+    const int batch = batch2 / (2 + c->sega_K);
+    API_CK(c, sega_begin(c, st, batch, Lh, Lw));
+    { SegaMain sm(c, 2 * batch);
+      API_CK(c, unet_walk(c, st, c->lat_bf16, 2 * batch, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec)); }
+    API_CK(c, sega_after_main(c, st, 0, batch, Lh, Lw, timestep, nullptr, ec, true));
+  } else if (cc.pag && cc.pag[0] > 0.f) {                                  // every row is the perturbed branch, against the caller's context as it is; nothing is recorded
     ec.pag = true;
-    PagWalk pw(c, 0, c->ctx_B2);
+    SideWalk pw(c, 0, c->ctx_B2, &c->pag_counts[0]);
     API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec));
   } else {
     API_CK(c, unet_walk(c, st, c->lat_bf16, batch2, Lh, Lw, timestep, c->eps_nhwc, nullptr, false, 0, ec));
@@ -2618,8 +2713,12 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   if (c->i2_on) return run_ip2p_loop(c, st, latents, batch, Lh, Lw, n, timesteps, step);
   const int B2 = 2 * batch, HW = Lh * Lw;
   CK(ensure_lat(c, B2, Lh, Lw));
-  if (c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
+  if (c->sega_K == 0 && c->ctx_B2 != B2) FAIL("denoise: context batch %d != 2*batch %d", c->ctx_B2, B2);
   CallCond cc; CK(resolve_cond(c, CALL_EVAL_LOOP, n, batch, Lh, Lw, &cc));
+  if (cc.sega) {                                                   // Semantic Guidance: a K B-row concept walk where a concept is active, the fold at every evaluation
+    CK(refuse_guidance_rescale(c, "the Semantic Guidance denoise loop"));
+    CK(sega_begin(c, st, batch, Lh, Lw));
+  }
   struct DcLoop { agd_ctx* c; DcLoop(agd_ctx* c_) : c(c_) { deepcache_invalidate(c); } ~DcLoop() { deepcache_invalidate(c); } } dc_loop(c);   // a cache never outlives, or enters, a loop
   if (cc.pag) {                                                    // Perturbed-Attention Guidance: a third, B-row walk where its scale is > 0
     CK(refuse_guidance_rescale(c, "the Perturbed-Attention Guidance denoise loop"));
@@ -2630,7 +2729,9 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
   const long long ne = (long long)batch * HW * c->cfg.out_channels;   // one branch of eps
   for (int i = 0; i < n; ++i) {
     CK(prep_unet_input(c, st, latents, batch, HW));
-    CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cc.at(i)));
+    { SegaMain sm(c, cc.sega ? B2 : 0);
+      CK(unet_walk(c, st, c->lat_bf16, B2, Lh, Lw, timesteps[i], c->eps_nhwc, tp_all + (size_t)i * c->tproj_total, true, 0, cc.at(i))); }
+    if (cc.sega) CK(sega_after_main(c, st, i, batch, Lh, Lw, timesteps[i], tp_all + (size_t)i * c->tproj_total, cc.at(i), false));
     if (cc.pag && cc.pag[i] > 0.f) {
       // e_p: the conditional rows again (a copy of their input, the conditional half of the context) with the applied layers perturbed,
       // into eps rows [2 B, 3 B); then d = p (e_c - e_p) lands on both rows the step kernel reads
@@ -2638,7 +2739,7 @@ static int run_eval_loop(agd_ctx* c, hipStream_t st, float* latents, int batch, 
       { ProfScope ps(c, st, PC_ELEM, 0);
         if (hipMemcpyAsync(xin_p, c->lat_bf16 + (size_t)batch * HW * 64, (size_t)batch * HW * 64 * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) FAIL("pag: input copy failed"); }
       { EvalCond ep = cc.at(i); ep.pag = true;
-        PagWalk pw(c, batch, batch);
+        SideWalk pw(c, batch, batch, &c->pag_counts[0]);
         CK(unet_walk(c, st, xin_p, batch, Lh, Lw, timesteps[i], c->eps_nhwc + 2 * ne, tp_all + (size_t)i * c->tproj_total, false, 0, ep)); }
       { ProfScope ps(c, st, PC_ELEM, 0); CK(launch_pag_fold(c->eps_nhwc, ne, cc.pag[i], st)); }
     }
@@ -4886,6 +4987,63 @@ AGD_API int agd_op_pag_v_rows(agd_ctx* c, const void* qkv, void* att, int M, int
   hipStream_t st = S(stream);                                       // (c may be null: it only keeps the error text)
   API_CK(c, launch_pag_v_rows((const bf16_t*)qkv, (bf16_t*)att, M, C, st));
   hipStreamSynchronize(st);
+  return 0;
+}
+// ---- Semantic Guidance (sega.hip) -------------------------------------------------------------------------------------------------------
+AGD_API int agd_sega_set(agd_ctx* c, const agd_sega_desc* d) {
+  API_CK(c, need_final(c));
+  if (!d || d->struct_size != (int)sizeof(agd_sega_desc)) { agd_set_error("sega_set: descriptor struct_size %d, this library has %zu", d ? d->struct_size : -1, sizeof(agd_sega_desc)); return fail_ctx(c); }
+  const int K = d->concepts, n = d->n_evals;
+  if (K < 1 || K > AGD_MAX_EDIT_CONCEPTS) { agd_set_error("sega_set: %d concepts (1 .. %d)", K, AGD_MAX_EDIT_CONCEPTS); return fail_ctx(c); }
+  if (n < 1 || !d->coef || !d->q || !d->w_mom || !d->w_add || !d->add_mom) { agd_set_error("sega_set: %d evaluations or a null array", n); return fail_ctx(c); }
+  if (!std::isfinite(d->mom_scale) || !std::isfinite(d->mom_beta)) { agd_set_error("sega_set: momentum scale %g, beta %g (finite numbers)", (double)d->mom_scale, (double)d->mom_beta); return fail_ctx(c); }
+  for (int k = 0; k < K; ++k)
+    if (!(d->q[k] >= 0.0 && d->q[k] <= 1.0)) { agd_set_error("sega_set: q[%d] is %g (a quantile in [0, 1])", k, d->q[k]); return fail_ctx(c); }
+  for (long long j = 0; j < (long long)n * K; ++j)
+    if (!std::isfinite(d->coef[j]) || !std::isfinite(d->w_mom[j]) || !std::isfinite(d->w_add[j])) {
+      agd_set_error("sega_set: evaluation %lld, concept %lld: coef %g, w_mom %g, w_add %g (finite numbers)", j / K, j % K, (double)d->coef[j], (double)d->w_mom[j], (double)d->w_add[j]); return fail_ctx(c); }
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(d->add_mom[i])) { agd_set_error("sega_set: add_mom[%d] is %g (a finite number)", i, (double)d->add_mom[i]); return fail_ctx(c); }
+  c->sega_coef.assign(d->coef, d->coef + (size_t)n * K); c->sega_wmom.assign(d->w_mom, d->w_mom + (size_t)n * K);
+  c->sega_wadd.assign(d->w_add, d->w_add + (size_t)n * K); c->sega_addmom.assign(d->add_mom, d->add_mom + n); c->sega_q.assign(d->q, d->q + K);
+  c->sega_K = K; c->sega_n = n; c->sega_mu = d->mom_scale; c->sega_beta = d->mom_beta;
+  return 0;
+}
+AGD_API int agd_sega_clear(agd_ctx* c) {
+  if (!c) { agd_set_error("sega_clear: null context"); return -1; }
+  c->sega_K = 0; c->sega_n = 0; c->sega_coef.clear(); c->sega_wmom.clear(); c->sega_wadd.clear(); c->sega_addmom.clear(); c->sega_q.clear();
+  return 0;
+}
+AGD_API int agd_sega_counts(agd_ctx* c, long long* walks, long long* folds) {
+  if (!c || !walks || !folds) { agd_set_error("sega_counts: null argument"); return fail_ctx(c); }
+  *walks = c->sega_counts[0]; *folds = c->sega_counts[1];
+  return 0;
+}
+static int sega_op_scalars(const char* what, int K, int HW, const float* coef, const double* q, const float* w_mom, const float* w_add, SegaEvalP* p) {
+  if (K < 1 || K > AGD_MAX_EDIT_CONCEPTS || HW < 1 || !coef) { agd_set_error("%s: %d concepts (1 .. %d), %d pixels or a null array", what, K, AGD_MAX_EDIT_CONCEPTS, HW); return -1; }
+  *p = SegaEvalP{};
+  for (int k = 0; k < K; ++k) {
+    p->coef[k] = coef[k]; p->w_mom[k] = w_mom ? w_mom[k] : 0.f; p->w_add[k] = w_add ? w_add[k] : 0.f;
+    if (q) {
+      if (!(q[k] >= 0.0 && q[k] <= 1.0)) { agd_set_error("%s: q[%d] is %g (a quantile in [0, 1])", what, k, q[k]); return -1; }
+      sega_rank(q[k], HW, &p->lo[k], &p->f[k]);
+    }
+  }
+  return 0;
+}
+AGD_API int agd_op_sega_threshold(agd_ctx* c, const float* eps, int B, int K, int HW, const float* coef, const double* q, float* thr, void* stream) {
+  hipStream_t st = S(stream);
+  if (!q) { agd_set_error("op_sega_threshold: null q"); return fail_ctx(c); }
+  SegaEvalP p; API_CK(c, sega_op_scalars("op_sega_threshold", K, HW, coef, q, nullptr, nullptr, &p));
+  API_CK(c, launch_sega_threshold(eps, B, K, 4, HW, p, thr, st));
+  return 0;
+}
+AGD_API int agd_op_sega_fold(agd_ctx* c, float* eps, float* m, const float* thr, int B, int K, int HW, const float* coef, const float* w_mom,
+                             const float* w_add, float add_mom, float mom_scale, float mom_beta, void* stream) {
+  hipStream_t st = S(stream);
+  if (!w_mom || !w_add) { agd_set_error("op_sega_fold: null weights"); return fail_ctx(c); }
+  SegaEvalP p; API_CK(c, sega_op_scalars("op_sega_fold", K, HW, coef, nullptr, w_mom, w_add, &p));
+  API_CK(c, launch_sega_fold(eps, m, thr, B, K, 4, HW, p, mom_scale, mom_beta, add_mom, st));
   return 0;
 }
 AGD_API int agd_op_pag_fold(agd_ctx* c, float* eps, long long n, float p, void* stream) {

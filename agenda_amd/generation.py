@@ -242,6 +242,45 @@ def save_outputs(save_dir: str, seeds, images_u8, heatmaps, words, image_size, s
                 Image.fromarray(arr).save(os.path.join(save_dir, sub, f"{seed}.png"))
 
 
+def sega_arguments(p, args) -> Optional[dict]:
+    """The Semantic Guidance flags as the pipeline's keywords (None without --editing-prompt), refused where they cannot run."""
+    flags = {"reverse_editing_direction": args.reverse_editing_direction, "edit_guidance_scale": args.edit_guidance_scale,
+             "edit_warmup_steps": args.edit_warmup_steps, "edit_cooldown_steps": args.edit_cooldown_steps,
+             "edit_threshold": args.edit_threshold, "edit_weights": args.edit_weights}
+    scalars = {"edit_momentum_scale": args.edit_momentum_scale, "edit_mom_beta": args.edit_mom_beta}
+    if args.editing_prompt is None:
+        given = [k for k, v in {**flags, **scalars}.items() if v is not None]
+        if given:
+            p.error(f"--{given[0].replace('_', '-')} needs --editing-prompt")
+        return None
+    K = len(args.editing_prompt)
+    if K > 8:
+        p.error(f"--editing-prompt: {K} concepts (at most 8)")
+    if (args.controlnet_model_path or args.adapter_model_path or args.ip_adapter_path or args.init_image or args.instruct_image
+            or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama or args.guidance_rescale or args.pag_scale
+            or args.region_prompts is not None or args.region_layouts is not None or (args.deepcache_interval or 1) > 1
+            or args.max_embeddings_multiples is not None):
+        p.error("--editing-prompt with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
+                "--gligen-phrases / --gligen-layouts, --panorama, --region-prompts / --region-layouts, --guidance-rescale, --pag-scale, "
+                "--deepcache-interval or --max-embeddings-multiples is not implemented")
+    out = {"editing_prompt": list(args.editing_prompt)}
+    for name, v in flags.items():
+        if v is None:
+            continue
+        if len(v) not in (1, K):
+            p.error(f"--{name.replace('_', '-')}: {len(v)} values for {K} concepts (one, or one per concept)")
+        v = [bool(x) for x in v] if name == "reverse_editing_direction" else list(v)
+        out[name] = v[0] if len(v) == 1 else v
+    if args.edit_threshold is not None and not all(0.0 <= q <= 1.0 for q in args.edit_threshold):
+        p.error(f"--edit-threshold {' '.join(str(q) for q in args.edit_threshold)}: quantiles in [0, 1]")
+    for name, v in scalars.items():
+        if v is not None:
+            if not math.isfinite(v):
+                p.error(f"--{name.replace('_', '-')} {v}: a finite number")
+            out[name] = v
+    return out
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Image and attention map generation (MI355X).")
     p.add_argument("--save-dir", type=str, default="Data/Synthetic")
@@ -347,6 +386,22 @@ def parse_args(argv=None):
                    help="weighted and long prompts (lpw_stable_diffusion's rules): in the prompt, after its placeholders are filled, (x) weighs "
                         "x by 1.1, [x] by 1 / 1.1, (x:w) by w, and up to 75 M tokens are kept (contexts of 77, 152, 227, 302 rows); heat maps "
                         "follow the weight-stripped tokens; plain txt2img only (default: off, parentheses are literal, 75 tokens)")
+    p.add_argument("--editing-prompt", type=str, default=None, nargs="+", metavar="P",
+                   help="Semantic Guidance (Brack et al. 2023; SemanticStableDiffusionPipeline): up to 8 edit concepts, each steering only "
+                        "the image regions where its direction is strongest; the prompt, the seed and the heat maps stay as they are; plain "
+                        "txt2img only.  The --edit-* / --reverse-editing-direction flags take one value for all concepts or one per concept")
+    p.add_argument("--reverse-editing-direction", type=int, default=None, nargs="+", metavar="R", choices=[0, 1],
+                   help="SEGA: 1 steers away from the concept, 0 towards it (default 0)")
+    p.add_argument("--edit-guidance-scale", type=float, default=None, nargs="+", metavar="S", help="SEGA: the concept's guidance scale (default 5)")
+    p.add_argument("--edit-warmup-steps", type=int, default=None, nargs="+", metavar="N",
+                   help="SEGA: model evaluations before the concept is applied (default 10)")
+    p.add_argument("--edit-cooldown-steps", type=int, default=None, nargs="+", metavar="N",
+                   help="SEGA: the evaluation from which the concept is no longer applied (default: never)")
+    p.add_argument("--edit-threshold", type=float, default=None, nargs="+", metavar="Q",
+                   help="SEGA: the quantile in [0, 1] of the direction's magnitude below which the image is left untouched (default 0.9)")
+    p.add_argument("--edit-weights", type=float, default=None, nargs="+", metavar="W", help="SEGA: the concepts' relative weights (default 1)")
+    p.add_argument("--edit-momentum-scale", type=float, default=None, metavar="MU", help="SEGA: the momentum added to the guidance (default 0.1)")
+    p.add_argument("--edit-mom-beta", type=float, default=None, metavar="BETA", help="SEGA: how much of the momentum is kept per evaluation (default 0.4)")
     p.add_argument("--timestep-spacing", type=str, default=None, choices=["leading", "trailing", "linspace"],
                    help="the scheduler's timestep grid (default: the checkpoint's; DDIM and img2img take all three, DPM-Solver++ its own "
                         "three, PNDM runs 'leading' only)")
@@ -371,6 +426,7 @@ def parse_args(argv=None):
             or args.gligen_phrases is not None or args.gligen_layouts is not None or args.panorama):
         p.error("--max-embeddings-multiples with --controlnet-model-path, --adapter-model-path, --ip-adapter-path, --init-image, --instruct-image, "
                 "--gligen-phrases / --gligen-layouts or --panorama is not implemented")
+    args.sega = sega_arguments(p, args)
     if args.deepcache_branch is not None and args.deepcache_interval is None:
         p.error("--deepcache-branch needs --deepcache-interval N")
     if args.deepcache_interval is not None and args.deepcache_interval < 1:
@@ -801,6 +857,8 @@ def main(argv=None):
                 control = dict(control or {}, pag_scale=args.pag_scale, pag_adaptive_scale=args.pag_adaptive_scale)
             if args.max_embeddings_multiples is not None:
                 control = dict(control or {}, max_embeddings_multiples=args.max_embeddings_multiples)
+            if args.sega is not None:
+                control = dict(control or {}, **args.sega)
             if rg_layouts is not None:                                               # (parse_args refused every other control)
                 imgs, hms = generate_region_batch(pipe, rg_layouts, args.bootstrapping, chunk, words, prompt=prompt,
                                                   num_inference_steps=args.num_inference_steps, height=height, width=width)

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .config import SDConfig, cross_attn_layer_names
-from .pipeline import StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 
 MAX_OBJS = 30                 # [upstream-knowledge] StableDiffusionGLIGENPipeline.__call__: max_objs = 30
 FOURIER_FREQS = 8             # [upstream-knowledge] PositionNet(fourier_freqs=8)
@@ -276,8 +276,9 @@ class StableDiffusionGLIGENPipeline(StableDiffusionPipeline):
                  gligen_phrases=None, gligen_boxes=None, gligen_inpaint_image=None, negative_prompt=None, num_images_per_prompt: int = 1,
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                  output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         refuse_pag("StableDiffusionGLIGENPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionGLIGENPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionGLIGENPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionGLIGENPipeline", max_embeddings_multiples, prompt_embeds)
         if gligen_inpaint_image is not None:

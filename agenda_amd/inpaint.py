@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .config import SDConfig, inpaint_flavour, inpaint_variant
-from .pipeline import PipelineOutput, StableDiffusionPipeline, check_guidance_rescale, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, check_guidance_rescale, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 
 
@@ -194,10 +194,11 @@ class StableDiffusionInpaintPipeline(StableDiffusionPipeline):
                  noise_enc_image: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  noise_enc_masked: Optional[torch.Tensor] = None, cross_attention_kwargs: Optional[dict] = None,
                  guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         """image / mask_image as `prepare_mask_and_image` takes them.  Noise draws come from a CPU generator in diffusers' order, or are
         passed explicitly (noise_enc_image [N,4,L,L], noise (or latents) [B,4,L,L], noise_enc_masked [N,4,L,L]; N distinct images)."""
         refuse_pag("StableDiffusionInpaintPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionInpaintPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionInpaintPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionInpaintPipeline", max_embeddings_multiples, prompt_embeds)
         if image is None or mask_image is None:

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .config import SDConfig, ip2p_variant
-from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 
 
 def check_unet(cfg: SDConfig) -> None:
@@ -114,10 +114,11 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionPipeline):
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
                  height: Optional[int] = None, width: Optional[int] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         """image as `prepare_image` takes it; height and width are the image's (given ones must equal them: nothing is resized).
         prompt_embeds is [2B,T,D] = [uncond | cond]."""
         refuse_pag("StableDiffusionInstructPix2PixPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionInstructPix2PixPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionInstructPix2PixPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionInstructPix2PixPipeline", max_embeddings_multiples, prompt_embeds)
         if image is None:

@@ -693,6 +693,44 @@ def pag_fold(eps, p):
     return eps
 
 
+def _sega_rows(eps, B, K):
+    eps = _f32c(eps)
+    if eps.ndim != 3 or eps.shape[0] != (2 + K) * B or eps.shape[2] != 4:
+        raise ValueError(f"sega: eps {tuple(eps.shape)} must be [(2 + K) B, HW, 4] = [{(2 + K) * B}, HW, 4] (NHWC rows: uncond | cond | concepts)")
+    return eps
+
+
+def sega_threshold(eps, B, coef, q):
+    """The Semantic Guidance threshold, the production kernel: eps fp32 [(2 + K) B, HW, 4] (uncond x B | cond x B | concept_k x B), coef [K]
+    (this evaluation's sign * scale, 0 = inactive: the concept's rows are not read, thr = 0) and q [K] in [0, 1] -> thr fp32 [B, K, 4], the
+    exact q-quantile of |(e_k - e_u) coef_k| over the HW pixels per image, concept and channel."""
+    import ctypes as C
+    lib = _lib.load()
+    K = len(coef)
+    eps = _sega_rows(eps, B, K)
+    thr = torch.empty(B, K, 4, dtype=torch.float32, device=eps.device)
+    _lib.check(lib.agd_op_sega_threshold(None, _lib.ptr(eps), B, K, eps.shape[1], (C.c_float * K)(*[float(c) for c in coef]),
+                                         (C.c_double * K)(*[float(x) for x in q]), _lib.ptr(thr), _lib.current_stream_ptr()),
+               None, "agd_op_sega_threshold")
+    return thr
+
+
+def sega_fold(eps, m, thr, B, coef, w_mom, w_add, add_mom, mom_scale, mom_beta):
+    """The Semantic Guidance fold, the production kernel: eps fp32 [(2 + K) B, HW, 4], momentum m fp32 [B, HW, 4], thr [B, K, 4] and this
+    evaluation's scalars -> (a folded copy of eps -- rows [0, 2 B) plus `added`, the concept rows as they were -- and the updated momentum)."""
+    import ctypes as C
+    lib = _lib.load()
+    K = len(coef)
+    eps = _sega_rows(eps, B, K).clone()
+    m, thr = _f32c(m).clone(), _f32c(thr)
+    if tuple(m.shape) != (B, eps.shape[1], 4) or tuple(thr.shape) != (B, K, 4) or len(w_mom) != K or len(w_add) != K:
+        raise ValueError(f"sega_fold: m {tuple(m.shape)} must be [{B}, {eps.shape[1]}, 4], thr {tuple(thr.shape)} [{B}, {K}, 4], the weights lists of {K}")
+    fl = lambda v: (C.c_float * K)(*[float(x) for x in v])  # noqa: E731
+    _lib.check(lib.agd_op_sega_fold(None, _lib.ptr(eps), _lib.ptr(m), _lib.ptr(thr), B, K, eps.shape[1], fl(coef), fl(w_mom), fl(w_add),
+                                    float(add_mom), float(mom_scale), float(mom_beta), _lib.current_stream_ptr()), None, "agd_op_sega_fold")
+    return eps, m
+
+
 def deepcache_capture(act, part=None):
     """DeepCache's capture launch, the production kernel: two device byte regions (the cached activation and its GroupNorm partial sums, any
     dtype, any byte count; `part` None or empty = the cpart_bm == 0 case, one region) -> bit-for-bit copies (act_copy, part_copy) made by ONE

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag
+from .pipeline import PipelineOutput, StableDiffusionPipeline, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega
 from .scheduler import DDIMScheduler
 
 STRIDE = 8            # latent pixels between views (diffusers get_views default)
@@ -76,8 +76,9 @@ class StableDiffusionPanoramaPipeline(StableDiffusionPipeline):
                  generator: Union[torch.Generator, Sequence[torch.Generator], None] = None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", cross_attention_kwargs: Optional[dict] = None,
                  guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         refuse_pag("StableDiffusionPanoramaPipeline", pag_scale, pag_adaptive_scale)
+        refuse_sega("StableDiffusionPanoramaPipeline", editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache("StableDiffusionPanoramaPipeline", getattr(self, "_deepcache", None))
         refuse_long_prompt("StableDiffusionPanoramaPipeline", max_embeddings_multiples, prompt_embeds)
         if guidance_rescale:

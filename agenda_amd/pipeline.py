@@ -86,6 +86,65 @@ def refuse_pag(pipeline: str, pag_scale: float, pag_adaptive_scale: float = 0.0)
                          f"for {pipeline} (StableDiffusionPipeline's txt2img and img2img run it); leave both 0")
 
 
+def check_sega(editing_prompt=None, editing_prompt_embeddings=None, reverse_editing_direction=False, edit_guidance_scale=5,
+               edit_warmup_steps=10, edit_cooldown_steps=None, edit_threshold=0.9, edit_momentum_scale=0.1, edit_mom_beta=0.4,
+               edit_weights=None, sem_guidance=None, pag_scale: float = 0.0, guidance_rescale: float = 0.0, deepcache=None, ip_adapter=None,
+               ip_adapter_image=None, ip_adapter_image_embeds=None, max_embeddings_multiples=None) -> Optional[dict]:
+    """Semantic Guidance's arguments (diffusers 0.21.2 SemanticStableDiffusionPipeline [upstream-knowledge]), decided from the call's
+    arguments alone, before any device work.  No editing prompt: None (the plain call).  Else the concepts -- {"K", "prompts" (a list, or
+    None), "embeds" ([K, T, D], or None), "args" (`config.sega_schedule`'s keywords), "mu", "beta"} -- after every refusal: both forms of the
+    concepts, more than 8 of them, a per-concept list whose length is not K, a threshold outside [0, 1], upstream's `sem_guidance`, and what
+    the concept walk does not run beside (pag_scale, guidance_rescale, an enabled DeepCache, an active IP-Adapter, weighted prompts)."""
+    from .config import MAX_EDIT_CONCEPTS, sega_schedule
+    if sem_guidance is not None:
+        raise ValueError("sem_guidance: precomputed guidance vectors are not implemented (the engine computes the guidance of every "
+                         "evaluation on the device); leave it None")
+    if editing_prompt is not None and editing_prompt_embeddings is not None:
+        raise ValueError("editing_prompt and editing_prompt_embeddings are both given; pass the concepts in one form")
+    if editing_prompt is None and editing_prompt_embeddings is None:
+        return None
+    if editing_prompt is not None:
+        prompts = [editing_prompt] if isinstance(editing_prompt, str) else list(editing_prompt)
+        if not all(isinstance(p, str) for p in prompts):
+            raise ValueError(f"editing_prompt={editing_prompt!r}: a string or a list of strings")
+        K, embeds, name = len(prompts), None, "editing_prompt"
+    else:
+        embeds, prompts, name = editing_prompt_embeddings, None, "editing_prompt_embeddings"
+        if not torch.is_tensor(embeds) or embeds.ndim != 3:
+            raise ValueError("editing_prompt_embeddings: a tensor [K, T, D], one row of tokens per concept")
+        K = embeds.shape[0]
+    if K < 1 or K > MAX_EDIT_CONCEPTS:
+        raise ValueError(f"{name}: {K} editing concepts (1 .. {MAX_EDIT_CONCEPTS})")
+    args = dict(reverse_editing_direction=reverse_editing_direction, edit_guidance_scale=edit_guidance_scale, edit_threshold=edit_threshold,
+                edit_warmup_steps=edit_warmup_steps, edit_cooldown_steps=edit_cooldown_steps, edit_weights=edit_weights)
+    sega_schedule(1, K, **args)                                # (every per-concept refusal, by the argument's name)
+    mu, beta = float(edit_momentum_scale), float(edit_mom_beta)
+    if not math.isfinite(mu):
+        raise ValueError(f"edit_momentum_scale={edit_momentum_scale!r}: a finite number")
+    if not math.isfinite(beta):
+        raise ValueError(f"edit_mom_beta={edit_mom_beta!r}: a finite number")
+    if pag_scale:
+        raise ValueError(f"pag_scale={pag_scale!r} with {name}: Semantic Guidance beside Perturbed-Attention Guidance is not implemented; leave one out")
+    if guidance_rescale:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} with {name}: guidance rescale beside Semantic Guidance is not implemented; leave one out")
+    refuse_deepcache("StableDiffusionPipeline", deepcache, f"{name} (Semantic Guidance)")
+    if (ip_adapter_image is not None or ip_adapter_image_embeds is not None) and ip_adapter is not None and ip_adapter["scale"] != 0.0:
+        raise ValueError(f"an active IP-Adapter (scale {ip_adapter['scale']!r}) with {name}: Semantic Guidance beside an image prompt is not "
+                         "implemented; leave the image prompt out or set_ip_adapter_scale(0)")
+    if max_embeddings_multiples is not None:
+        raise ValueError(f"max_embeddings_multiples={max_embeddings_multiples!r} with {name}: Semantic Guidance with weighted / long prompts "
+                         "is not implemented; leave it None")
+    return {"K": K, "prompts": prompts, "embeds": embeds, "args": args, "mu": mu, "beta": beta}
+
+
+def refuse_sega(pipeline: str, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None) -> None:
+    """The pipelines that run beside something the concept walk does not carry refuse Semantic Guidance's arguments by name."""
+    for name, v in (("editing_prompt", editing_prompt), ("editing_prompt_embeddings", editing_prompt_embeddings), ("sem_guidance", sem_guidance)):
+        if v is not None:
+            raise ValueError(f"{name}: Semantic Guidance is not implemented for {pipeline} (StableDiffusionPipeline's txt2img and img2img "
+                             "run it); leave it None")
+
+
 def check_deepcache(cache_interval, cache_branch_id, layers_per_block: int, skip_mode: str = "uniform") -> None:
     """`enable_deepcache`'s arguments: an integer interval >= 1, a branch among the layers of the first down block, the uniform schedule."""
     for name, v in (("cache_interval", cache_interval), ("cache_branch_id", cache_branch_id)):
@@ -526,6 +585,25 @@ class Engine:
         w, l = C.c_longlong(0), C.c_longlong(0)
         self._ck(self.lib.agd_pag_counts(self.ctx, C.byref(w), C.byref(l)), "agd_pag_counts")
         return int(w.value), int(l.value)
+
+    def sega_set(self, sched: dict, mom_scale: float, mom_beta: float):
+        """`agd_sega_set`: Semantic Guidance for the calls to come, until sega_clear -- `sched` is `config.sega_schedule`'s result (the
+        per-evaluation coef / w_mom / w_add / add_mom and the concepts' quantiles); the context must then hold (2 + K) B rows."""
+        K, n = int(sched["concepts"]), int(sched["n_evals"])
+        flat = lambda rows: (C.c_float * (n * K))(*[float(x) for r in rows for x in r])  # noqa: E731
+        d = _lib.AgdSegaDesc(struct_size=C.sizeof(_lib.AgdSegaDesc), concepts=K, n_evals=n, mom_scale=float(mom_scale), mom_beta=float(mom_beta),
+                             coef=flat(sched["coef"]), q=(C.c_double * K)(*[float(x) for x in sched["q"]]), w_mom=flat(sched["w_mom"]),
+                             w_add=flat(sched["w_add"]), add_mom=(C.c_float * n)(*[float(x) for x in sched["add_mom"]]))
+        self._ck(self.lib.agd_sega_set(self.ctx, C.byref(d)), "agd_sega_set")
+
+    def sega_clear(self):
+        self._ck(self.lib.agd_sega_clear(self.ctx), "agd_sega_clear")
+
+    def sega_counts(self) -> Tuple[int, int]:
+        """`agd_sega_counts`: (concept walks run, folds run) since the engine was created."""
+        w, f = C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.lib.agd_sega_counts(self.ctx, C.byref(w), C.byref(f)), "agd_sega_counts")
+        return int(w.value), int(f.value)
 
     def deepcache_set(self, full_flags, branch: int = 0):
         """`agd_deepcache_set`: DeepCache for the calls to come, until deepcache_clear -- one flag per model evaluation (1 = the full walk,
@@ -1523,9 +1601,10 @@ class StableDiffusionPipeline:
             raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {expect}")
         return self.engine._h2d(latents.to(torch.float32) * self.scheduler.init_noise_sigma).clone()
 
-    def _begin_recording(self, prompt_embeds: torch.Tensor, B: int, L):
-        """Sets the call's context and, with a tracer or a hooker installed, starts their recording of B images at latent size L."""
-        self.engine.set_context(prompt_embeds)
+    def _begin_recording(self, prompt_embeds: torch.Tensor, B: int, L, context: Optional[torch.Tensor] = None):
+        """Sets the call's context and, with a tracer or a hooker installed, starts their recording of B images at latent size L.
+        `context`: what the engine gets when it is more than the prompts' rows (Semantic Guidance's concept rows behind them)."""
+        self.engine.set_context(prompt_embeds if context is None else context)
         self._apply_record_mode()
         T = prompt_embeds.shape[1]
         if self._trace is not None and T > LONG_CONTEXT:       # a long context records its T rows, unless the tracer was given rec_tokens
@@ -1545,12 +1624,19 @@ class StableDiffusionPipeline:
                  prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil", num_images_per_prompt: int = 1,
                  cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
                  guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 max_embeddings_multiples: Optional[int] = None):
+                 max_embeddings_multiples: Optional[int] = None,
+                 editing_prompt: Union[str, List[str], None] = None, editing_prompt_embeddings: Optional[torch.Tensor] = None,
+                 reverse_editing_direction=False, edit_guidance_scale=5, edit_warmup_steps=10, edit_cooldown_steps=None, edit_threshold=0.9,
+                 edit_momentum_scale: float = 0.1, edit_mom_beta: float = 0.4, edit_weights=None, sem_guidance=None):
         from .lpw import check_multiples
         check_multiples(max_embeddings_multiples)
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
         check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        sega = check_sega(editing_prompt, editing_prompt_embeddings, reverse_editing_direction, edit_guidance_scale, edit_warmup_steps,
+                          edit_cooldown_steps, edit_threshold, edit_momentum_scale, edit_mom_beta, edit_weights, sem_guidance, pag_scale,
+                          guidance_rescale, getattr(self, "_deepcache", None), getattr(self, "_ip_adapter", None), ip_adapter_image,
+                          ip_adapter_image_embeds, max_embeddings_multiples)
         refuse_deepcache_beside(getattr(self, "_deepcache", None), pag_scale, getattr(self, "_ip_adapter", None), ip_adapter_image, ip_adapter_image_embeds)
         self._apply_lora_scale(cross_attention_kwargs)
         side = self.cfg.default_sample_size * self.vae_scale_factor
@@ -1562,11 +1648,12 @@ class StableDiffusionPipeline:
         prompt_embeds, pb, ipp = self._expand_prompts(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, max_embeddings_multiples)
         B = prompt_embeds.shape[0] // 2
         self._refuse_long_beside(prompt_embeds, max_embeddings_multiples, ip_adapter_image, ip_adapter_image_embeds)
+        context = self._sega_context(sega, prompt_embeds, B)   # (its refusals come as soon as the prompts' context is known: nothing is on the device yet)
         self._apply_ip_adapter(B, pb, ipp, ip_adapter_image, ip_adapter_image_embeds)
         lat = self._draw_latents(B, Lh, Lw, generator, latents)
-        self._begin_recording(prompt_embeds, B, L)
+        self._begin_recording(prompt_embeds, B, L, context)
         with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, self.scheduler, num_inference_steps), \
-                self._deepcached(self.scheduler, num_inference_steps):
+                self._deepcached(self.scheduler, num_inference_steps), self._sega(sega, self.scheduler, num_inference_steps):
             self._denoise(lat, num_inference_steps, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)
@@ -1616,6 +1703,40 @@ class StableDiffusionPipeline:
             yield
         finally:
             self.engine.pag_clear()
+
+    def _sega_context(self, sega: Optional[dict], prompt_embeds: torch.Tensor, B: int) -> Optional[torch.Tensor]:
+        """The context of a Semantic Guidance call: [uncond x B | cond x B | concept_0 x B | ... | concept_{K-1} x B], the concepts shared by
+        the call's images (an editing prompt is encoded as a prompt is).  None without concepts.  A context over 96 tokens and given
+        embeddings of another shape are refused before anything is encoded."""
+        if sega is None:
+            return None
+        T, D = prompt_embeds.shape[1], prompt_embeds.shape[2]
+        if T > LONG_CONTEXT:
+            raise ValueError(f"a context of {T} tokens (over {LONG_CONTEXT}) with an editing prompt: Semantic Guidance with long prompts is not implemented")
+        if sega["embeds"] is not None and tuple(sega["embeds"].shape[1:]) != (T, D):
+            raise ValueError(f"editing_prompt_embeddings of shape {tuple(sega['embeds'].shape)}: the prompts' context has {T} tokens of {D} (expected [K, {T}, {D}])")
+        emb = sega["embeds"] if sega["embeds"] is not None else self.text_encoder(sega["prompts"])
+        if tuple(emb.shape[1:]) != (T, D):
+            raise ValueError(f"editing_prompt encodes to {tuple(emb.shape)}: the prompts' context has {T} tokens of {D} (expected [K, {T}, {D}])")
+        emb = emb.to(device=prompt_embeds.device, dtype=prompt_embeds.dtype)
+        return torch.cat([prompt_embeds, emb.repeat_interleave(B, dim=0)], 0)
+
+    @contextlib.contextmanager
+    def _sega(self, sega: Optional[dict], scheduler, num_inference_steps: int, strength: float = 1.0):
+        """Semantic Guidance (Brack et al. 2023; diffusers 0.21.2 SemanticStableDiffusionPipeline) around one call's denoise loop: the
+        schedule of every model evaluation (`config.sega_schedule` over the length of `inpaint.evaluation_timesteps`) is set for the loop and
+        cleared when it ends, on an error too, so the next call without an editing prompt is the plain one.  None sets nothing."""
+        if sega is None:
+            yield
+            return
+        from .config import sega_schedule
+        from .inpaint import evaluation_timesteps
+        sched = sega_schedule(len(evaluation_timesteps(scheduler, num_inference_steps, strength)), sega["K"], **sega["args"])
+        self.engine.sega_set(sched, sega["mu"], sega["beta"])
+        try:
+            yield
+        finally:
+            self.engine.sega_clear()
 
     @contextlib.contextmanager
     def _deepcached(self, scheduler, num_inference_steps: int, strength: float = 1.0):
@@ -1671,7 +1792,10 @@ class StableDiffusionPipeline:
                 noise_enc: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, output_type: str = "pil",
                 cross_attention_kwargs: Optional[dict] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                max_embeddings_multiples: Optional[int] = None):
+                max_embeddings_multiples: Optional[int] = None,
+                editing_prompt: Union[str, List[str], None] = None, editing_prompt_embeddings: Optional[torch.Tensor] = None,
+                reverse_editing_direction=False, edit_guidance_scale=5, edit_warmup_steps=10, edit_cooldown_steps=None, edit_threshold=0.9,
+                edit_momentum_scale: float = 0.1, edit_mom_beta: float = 0.4, edit_weights=None, sem_guidance=None):
         """image: float [B,3,H,W] in [-1,1] (or uint8 [B,H,W,3]).  Noise draws come from a CPU generator (or are passed
         explicitly) for the same host-reproducibility reason as the txt2img latents."""
         from .lpw import check_multiples
@@ -1682,6 +1806,10 @@ class StableDiffusionPipeline:
         self._refuse_inpainting_unet()
         check_guidance_rescale(guidance_rescale)
         check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        sega = check_sega(editing_prompt, editing_prompt_embeddings, reverse_editing_direction, edit_guidance_scale, edit_warmup_steps,
+                          edit_cooldown_steps, edit_threshold, edit_momentum_scale, edit_mom_beta, edit_weights, sem_guidance, pag_scale,
+                          guidance_rescale, getattr(self, "_deepcache", None), getattr(self, "_ip_adapter", None), ip_adapter_image,
+                          ip_adapter_image_embeds, max_embeddings_multiples)
         refuse_deepcache_beside(getattr(self, "_deepcache", None), pag_scale, getattr(self, "_ip_adapter", None), ip_adapter_image, ip_adapter_image_embeds)
         self._apply_lora_scale(cross_attention_kwargs)
         sched = self.scheduler if isinstance(self.scheduler, DDIMScheduler) else DDIMScheduler.from_config(self.cfg.sched)
@@ -1698,6 +1826,7 @@ class StableDiffusionPipeline:
             prompt_embeds = self.encode_prompt(prompts) if max_embeddings_multiples is None else \
                 self.encode_prompt_weighted(prompts, None, max_embeddings_multiples)
         self._refuse_long_beside(prompt_embeds, max_embeddings_multiples, ip_adapter_image, ip_adapter_image_embeds)
+        context = self._sega_context(sega, prompt_embeds, B)   # (refused here, before the image prompt, the noise draws and the VAE encode)
         self._apply_ip_adapter(B, B, 1, ip_adapter_image, ip_adapter_image_embeds)
         shape = (B, self.cfg.unet.out_channels, Lh, Lw)
         if generator is not None and generator.device.type != "cpu":
@@ -1713,9 +1842,9 @@ class StableDiffusionPipeline:
         x0 = (mean + torch.exp(0.5 * logvar) * noise_enc.to(mean.device)) * self.cfg.vae.scaling_factor
         a = float(sched.alphas_cumprod[int(ts[0])])
         lat = (a ** 0.5 * x0 + (1 - a) ** 0.5 * noise.to(mean.device)).contiguous()
-        self._begin_recording(prompt_embeds, B, L)
+        self._begin_recording(prompt_embeds, B, L, context)
         with self._guidance_rescaled(guidance_rescale), self._pag(pag_scale, pag_adaptive_scale, sched, num_inference_steps, strength), \
-                self._deepcached(sched, num_inference_steps, strength):
+                self._deepcached(sched, num_inference_steps, strength), self._sega(sega, sched, num_inference_steps, strength):
             self.engine.denoise(lat, ts, a_t, a_p, guidance_scale)
         if output_type == "latent":
             return PipelineOutput(images=[], latents=lat)

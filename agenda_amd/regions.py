@@ -24,7 +24,7 @@ from typing import List, Optional, Sequence, Union
 
 import torch
 
-from .pipeline import (LONG_CONTEXT, PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag)
+from .pipeline import (LONG_CONTEXT, PipelineOutput, StableDiffusionPipeline, check_image_size, refuse_deepcache, refuse_long_prompt, refuse_pag, refuse_sega)
 from .scheduler import DDIMScheduler
 
 MAX_REGIONS = 8        # R, the background included (AGD_MAX_REGIONS)
@@ -125,9 +125,10 @@ class StableDiffusionRegionPipeline(StableDiffusionPipeline):
                  prompt_embeds: Optional[torch.Tensor] = None, region_prompt_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
                  cross_attention_kwargs: Optional[dict] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0,
                  pag_adaptive_scale: float = 0.0, max_embeddings_multiples: Optional[int] = None, ip_adapter_image=None,
-                 ip_adapter_image_embeds=None):
+                 ip_adapter_image_embeds=None, editing_prompt=None, editing_prompt_embeddings=None, sem_guidance=None):
         # ---- refusals: all by name, before any device work ------------------------------------------------------------------------
         refuse_pag(NAME, pag_scale, pag_adaptive_scale)
+        refuse_sega(NAME, editing_prompt, editing_prompt_embeddings, sem_guidance)
         refuse_deepcache(NAME, getattr(self, "_deepcache", None))
         refuse_long_prompt(NAME, max_embeddings_multiples, prompt_embeds)
         if region_prompt_embeds is not None and region_prompt_embeds.shape[-2] > LONG_CONTEXT:

@@ -766,6 +766,55 @@ int agd_deepcache_counts(agd_ctx* ctx, long long* out);
 int agd_deepcache_forward_hw(agd_ctx* ctx, const float* sample, int rows, int Lh, int Lw, float timestep, int branch, int shallow, float* out, void* stream);
 int agd_op_deepcache_capture(agd_ctx* ctx, const void* src0, void* dst0, long long bytes0, const void* src1, void* dst1, long long bytes1, void* stream);
 
+/* ---- Semantic Guidance (Brack et al. 2023, "SEGA: Instructing Text-to-Image Models using Semantic Guidance"; diffusers 0.21.2
+ * SemanticStableDiffusionPipeline [upstream-knowledge]; csrc/sega.hip).  Up to AGD_MAX_EDIT_CONCEPTS edit concepts, shared by the images of a
+ * call, each with a UNet branch of its own.  Evaluation i counts the model evaluations of a call from 0 (PLMS's extra evaluation has its own
+ * index).  For concept k, in fp32 and in this operation order:
+ *   v_k = (e_k - e_u) * coef[i][k]
+ *   thr = quantile(|v_k| over the HW latent pixels, q[k]) per image and channel: p = q (HW - 1) in double, lo = floor(p), f = float(p - lo),
+ *         a, b the lo-th and min(lo + 1, HW - 1)-th smallest values, thr = min(b, a + f (b - a))
+ *   G_k = v_k where |v_k| >= thr, else 0;  a concept with coef[i][k] == 0 contributes exactly 0 and its eps rows are not read
+ *   g = sum_k w_mom[i][k] G_k + mom_scale m;   added = sum_k w_add[i][k] G_k + add_mom[i] mom_scale m;   m <- mom_beta m + (1 - mom_beta) g
+ * with the momentum m fp32, one value per image and latent element, zero at the start of every fused loop (and of every agd_unet_forward_hw).
+ * `added` lands on both e_u and e_c, so the schedulers' two-way step kernels compute e_u + s (e_c - e_u) + added unchanged.
+ * agd_sega_set: context state after agd_finalize, until cleared; the descriptor's host arrays are copied.  coef, w_mom, w_add: [n_evals][concepts],
+ *   add_mom: [n_evals], q: [concepts] in [0, 1]; every number finite.  With the state set, agd_set_context must hold (2 + K) B rows:
+ *   [uncond x B | cond x B | concept_0 x B | ... | concept_{K-1} x B]; the loops refuse any other row count by name.  Per evaluation of
+ *   agd_denoise*, agd_denoise_plms*, agd_denoise_dpm* (n_evals is checked against theirs): the main 2 B-row walk exactly as without the state
+ *   (it sees a context of 2 B rows: shared prefix and recorders unchanged); where any coef[i][k] != 0 one non-recording walk of K B rows
+ *   against context rows [2 B, (2 + K) B) on K copies of the conditional rows' input, into eps rows [2 B, (2 + K) B); the threshold launch
+ *   (skipped with the walk) and the fold launch (every evaluation: momentum outlives cool-down); then the step.
+ *   agd_unet_forward_hw with the state set and n_evals == 1 runs one such evaluation on its (2 + K) B sample rows -- the concept walk always
+ *   runs there, on copies of the conditional rows -- and returns all rows: the folded pair, then the concept rows as the walk left them.
+ *   Refused by name before the first launch: a ControlNet, GLIGEN or T2I-Adapter schedule, either inpainting state, an InstructPix2Pix state,
+ *   a Perturbed-Attention Guidance or DeepCache schedule, an active IP-Adapter, a set guidance rescale, agd_denoise_panorama,
+ *   agd_denoise_regions, agd_deepcache_forward_hw, agd_unet_forward_ts*, a context over 96 tokens, and out_channels != 4.
+ * agd_sega_clear: the plain loops again, launch for launch (bit-identical results).
+ * agd_sega_counts (seam for tests): concept walks and folds run since agd_create.
+ * agd_op_sega_threshold (seam for tests): eps fp32 [(2 + K) B][HW][4] on the device, coef / q host arrays of K -> thr fp32 [B][K][4] on the
+ *   device.  One workgroup per (image, concept): radix select on the bit patterns of |v| with integer LDS atomics (two runs give equal bits);
+ *   the patterns are staged in LDS up to 9216 pixels and re-read through L2 beyond.  Any HW >= 1.
+ * agd_op_sega_fold (seam for tests): the fold alone, eps rows [0, 2 B) and m [B][HW][4] updated in place, the concept rows left as they are.
+ *   For both seams ctx may be NULL (it only keeps the error text). */
+#define AGD_MAX_EDIT_CONCEPTS 8
+typedef struct agd_sega_desc {
+  int struct_size;                 /* sizeof(agd_sega_desc), ABI guard */
+  int concepts;                    /* K: 1 .. AGD_MAX_EDIT_CONCEPTS */
+  int n_evals;                     /* model evaluations of the calls to come */
+  float mom_scale, mom_beta;       /* edit_momentum_scale, edit_mom_beta */
+  const float* coef;               /* [n_evals][concepts] */
+  const double* q;                 /* [concepts] */
+  const float* w_mom;              /* [n_evals][concepts] */
+  const float* w_add;              /* [n_evals][concepts] */
+  const float* add_mom;            /* [n_evals] */
+} agd_sega_desc;
+int agd_sega_set(agd_ctx* ctx, const agd_sega_desc* desc);
+int agd_sega_clear(agd_ctx* ctx);
+int agd_sega_counts(agd_ctx* ctx, long long* walks, long long* folds);
+int agd_op_sega_threshold(agd_ctx* ctx, const float* eps, int B, int K, int HW, const float* coef, const double* q, float* thr, void* stream);
+int agd_op_sega_fold(agd_ctx* ctx, float* eps, float* m, const float* thr, int B, int K, int HW, const float* coef, const float* w_mom,
+                     const float* w_add, float add_mom, float mom_scale, float mom_beta, void* stream);
+
 /* ---- per-kernel-class timing (HIP events on the launch stream) */
 #define AGD_N_CLASSES 11
 int agd_profile_begin(agd_ctx* ctx);
