@@ -227,6 +227,13 @@ _SIGS = {
     "agd_op_attn_chain_ex": (C.c_int, [_P] * 8 + [C.c_int] * 5 + [C.c_float] + [_P] * 4 + [C.c_int, _P, _P] + [C.c_int] * 6 + [_P]),
     "agd_op_qkv_chain": (C.c_int, [_P] * 3 + [C.c_int, C.c_float, _P, C.c_int] + [_P] * 4 + [C.c_float] + [_P] * 3 + [C.c_int] * 4 + [_P]),
     "agd_op_xattn_premul": (C.c_int, [_P] * 9 + [C.c_int] * 5 + [C.c_float, _P]),
+    "agd_op_xattn_context": (C.c_int, [_P] * 9 + [C.c_int] * 4 + [_P]),
+    "agd_op_xattn_scores": (C.c_int, [_P, _P, C.c_int] + [_P] * 5 + [C.c_int] * 8 + [C.c_float, _P]),
+    "agd_op_ipa_linear": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [_P]),
+    "agd_op_ipa_layernorm": (C.c_int, [_P] * 4 + [C.c_int, C.c_int, C.c_float, _P]),
+    "agd_op_ipa_context": (C.c_int, [_P] * 10 + [C.c_int] * 5 + [_P]),
+    "agd_op_ipa_scores": (C.c_int, [_P] * 5 + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
+    "agd_op_ipa_add": (C.c_int, [_P] * 3 + [C.c_int] * 4 + [C.c_float, C.c_int, _P]),
     "agd_op_attention": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "agd_op_attention_ex": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "agd_op_attention_long": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float, C.c_int, _P, C.c_int, C.c_int, _P]),

@@ -3862,6 +3862,137 @@ AGD_API int agd_op_xattn_premul(const float* x, const float* gamma, const float*
   return 0;
 }
 
+// The stages of agd_op_xattn_premul and of the IP-Adapter branch (ipadapter.hip) one at a time (tests/test_premul_ops_gpu.py).  Context-free; fp32 in
+// and out, bf16 quantities rounded / widened by launch_f32_to_bf16 / launch_bf16_to_f32; every output buffer the kernels write into is first filled
+// with the byte 0x7F (bf16 0x7F7F, fp32 0x7F7F7F7F: huge finite values), so an element a kernel leaves out shows.  What a launcher refuses
+// comes back as -1 with its message.
+static size_t opn(long long n) { return n > 0 ? (size_t)n : 0; }
+static int op_fill(void* p, size_t bytes, hipStream_t st) {
+  if (bytes && hipMemsetAsync(p, 0x7F, bytes, st) != hipSuccess) { agd_set_error("op: memset failed"); return -1; }
+  return 0;
+}
+// the context products exactly as agd_op_xattn_premul builds them: kv [B][T][2C], wq / wo [C][C] -> kpp [B][heads][80][C], cs / bs [B][heads][80],
+// vpp [B][C][heads][80], the padding included
+AGD_API int agd_op_xattn_context(const float* kv, const float* wq, const float* wo, const float* gamma, const float* beta, float* kpp, float* cs,
+                                 float* bs, float* vpp, int B, int T, int C, int heads, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!kv || !wq || !wo || !gamma || !beta || !kpp || !cs || !bs || !vpp || B < 1 || T < 1 || C < 1 || heads < 1) { agd_set_error("op_xattn_context: bad arguments (B %d T %d C %d heads %d)", B, T, C, heads); return -1; }
+  const size_t HT = (size_t)heads * XATTN_TP, CC = (size_t)C * C;
+  bf16_t* kvb = tmp.get<bf16_t>((size_t)B * T * 2 * C); bf16_t* wqb = tmp.get<bf16_t>(CC); bf16_t* wqT = tmp.get<bf16_t>(CC); bf16_t* wob = tmp.get<bf16_t>(CC);
+  float* wqbeta = tmp.get<float>(C); bf16_t* kb = tmp.get<bf16_t>((size_t)B * HT * C); bf16_t* vb = tmp.get<bf16_t>((size_t)B * HT * C);
+  if (!kvb || !wqb || !wqT || !wob || !wqbeta || !kb || !vb) return -1;
+  CK(launch_f32_to_bf16(kv, kvb, (long long)B * T * 2 * C, st));
+  CK(launch_convert_weight(wq, wqb, C, C, 1, C, 0, st)); CK(launch_transpose_bf16(wqb, C, C, wqT, st));
+  CK(launch_convert_weight(wo, wob, C, C, 1, C, 0, st));
+  CK(launch_matvec_bf16(wqb, beta, wqbeta, C, C, st));
+  CK(op_fill(kb, (size_t)B * HT * C * 2, st)); CK(op_fill(vb, (size_t)B * HT * C * 2, st)); CK(op_fill(cs, (size_t)B * HT * 4, st)); CK(op_fill(bs, (size_t)B * HT * 4, st));
+  XattnPremulP pm{}; pm.kv = kvb; pm.ldkv = 2 * C; pm.skv = (long long)T * 2 * C; pm.wqT = wqT; pm.wo = wob; pm.gamma = gamma; pm.wqb = wqbeta;
+  pm.B = B; pm.T = T; pm.C = C; pm.H = heads; pm.scale = 1.0f / sqrtf((float)(C / heads > 0 ? C / heads : 1)); pm.kpp = kb; pm.kcs = cs; pm.kbs = bs; pm.vpp = vb;
+  CK(launch_xattn_premul(pm, st));
+  CK(launch_bf16_to_f32(kb, kpp, (long long)B * HT * C, st));
+  CK(launch_bf16_to_f32(vb, vpp, (long long)B * HT * C, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// launch_xattn_s alone on the caller's K'' / cs / bs: x [B * HW][C], stats (optional) [B * HW][slots][2] = the row's (sum, sum of squares) in slots
+// partial sums (NULL: one slot from launch_rowstat_bf16), kpp [B][heads][80][C], cs / bs [B][heads][80] -> P [B * HW][heads * 80].  rec (optional):
+// [B - rec_b0][heads][rec_rows][HW] device floats the launch ADDS to (never zeroed here): images >= rec_b0, token rows < rec_T <= rec_rows.
+AGD_API int agd_op_xattn_scores(const float* x, const float* stats, int slots, const float* kpp, const float* cs, const float* bs, float* P, float* rec,
+                                int rec_b0, int rec_T, int rec_rows, int B, int HW, int T, int C, int heads, float eps, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!x || !kpp || !cs || !bs || !P || B < 1 || HW < 1 || C < 1 || heads < 1 || (stats && slots < 1)) { agd_set_error("op_xattn_scores: bad arguments (B %d HW %d C %d heads %d slots %d)", B, HW, C, heads, slots); return -1; }
+  if (rec && (rec_b0 < 0 || rec_b0 >= B || rec_T < 1 || rec_T > rec_rows || rec_T > XATTN_TP)) { agd_set_error("op_xattn_scores: recorder rows b0 %d T %d of %d", rec_b0, rec_T, rec_rows); return -1; }
+  const long long M = (long long)B * HW; const size_t HT = (size_t)heads * XATTN_TP;
+  if (M >= (1LL << 31)) { agd_set_error("op_xattn_scores: %lld rows", M); return -1; }
+  bf16_t* xb = tmp.get<bf16_t>((size_t)M * C); bf16_t* kb = tmp.get<bf16_t>((size_t)B * HT * C); bf16_t* Pb = tmp.get<bf16_t>((size_t)M * HT);
+  float* rst = stats ? nullptr : tmp.get<float>((size_t)M * 2);
+  if (!xb || !kb || !Pb || (!stats && !rst)) return -1;
+  CK(launch_f32_to_bf16(x, xb, M * C, st));
+  CK(launch_f32_to_bf16(kpp, kb, (long long)B * HT * C, st));
+  if (!stats) CK(launch_rowstat_bf16(xb, rst, (int)M, C, st));
+  CK(op_fill(Pb, (size_t)M * HT * 2, st));
+  XattnSP sp{}; sp.x = xb; sp.ln_stats = stats ? stats : rst; sp.ln_slots = stats ? slots : 1; sp.ln_invC = 1.0f / (float)C; sp.ln_eps = eps;
+  sp.kpp = kb; sp.kcs = cs; sp.kbs = bs; sp.P = Pb; sp.M = (int)M; sp.HW = HW; sp.C = C; sp.H = heads; sp.T = T;
+  if (rec) { sp.rec = rec; sp.rec_b0 = rec_b0; sp.rec_T = rec_T; sp.rec_head_stride = (long long)rec_rows * HW; sp.rec_img_stride = sp.rec_head_stride * heads; }
+  CK(launch_xattn_s(sp, st));
+  CK(launch_bf16_to_f32(Pb, P, M * (long long)HT, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// launch_ipa_linear: y [R][N] = x [R][K] . bf16(w [N][K])^T (+ bias [N], optional)
+AGD_API int agd_op_ipa_linear(const float* x, const float* w, const float* bias, float* y, int R, int N, int K, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!x || !w || !y) { agd_set_error("op_ipa_linear: bad arguments"); return -1; }
+  bf16_t* wb = tmp.get<bf16_t>(opn((long long)N * K)); if (!wb) return -1;
+  CK(launch_f32_to_bf16(w, wb, (long long)opn((long long)N * K), st));
+  CK(op_fill(y, opn((long long)R * N) * 4, st));
+  CK(launch_ipa_linear(x, wb, bias, y, R, N, K, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// launch_ipa_layernorm on a copy of x [rows][C] -> y
+AGD_API int agd_op_ipa_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, void* stream) {
+  hipStream_t st = S(stream);
+  if (!x || !gamma || !beta || !y) { agd_set_error("op_ipa_layernorm: bad arguments"); return -1; }
+  const size_t bytes = opn((long long)rows * C) * 4;
+  if (bytes && hipMemcpyAsync(y, x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) { agd_set_error("op_ipa_layernorm: copy failed"); return -1; }
+  CK(launch_ipa_layernorm(y, gamma, beta, rows, C, eps, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// the Wq . beta mat-vec and launch_ipa_premul as agd_ip_adapter_set runs them: kip / vip [B][nt][C] fp32, wq / wo [C][C] -> kpp [B][colsP][C],
+// cs / bs [B][colsP], vpp [B][C][colsP]
+AGD_API int agd_op_ipa_context(const float* kip, const float* vip, const float* wq, const float* wo, const float* gamma, const float* beta, float* kpp,
+                               float* cs, float* bs, float* vpp, int B, int C, int heads, int nt, int colsP, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!kip || !vip || !wq || !wo || !gamma || !beta || !kpp || !cs || !bs || !vpp || B < 1 || C < 1 || heads < 1 || nt < 1 || colsP < 1) { agd_set_error("op_ipa_context: bad arguments (B %d C %d heads %d tokens %d cols %d)", B, C, heads, nt, colsP); return -1; }
+  const size_t CC = (size_t)C * C, n = (size_t)B * colsP * C;
+  bf16_t* wqb = tmp.get<bf16_t>(CC); bf16_t* wob = tmp.get<bf16_t>(CC); float* wqbeta = tmp.get<float>(C); bf16_t* kb = tmp.get<bf16_t>(n); bf16_t* vb = tmp.get<bf16_t>(n);
+  if (!wqb || !wob || !wqbeta || !kb || !vb) return -1;
+  CK(launch_convert_weight(wq, wqb, C, C, 1, C, 0, st)); CK(launch_convert_weight(wo, wob, C, C, 1, C, 0, st));
+  CK(launch_matvec_bf16(wqb, beta, wqbeta, C, C, st));
+  CK(op_fill(kb, n * 2, st)); CK(op_fill(vb, n * 2, st)); CK(op_fill(cs, (size_t)B * colsP * 4, st)); CK(op_fill(bs, (size_t)B * colsP * 4, st));
+  IpaPremulP pm{}; pm.kip = kip; pm.vip = vip; pm.wq = wqb; pm.wo = wob; pm.gamma = gamma; pm.wqb = wqbeta;
+  pm.B = B; pm.C = C; pm.H = heads; pm.nt = nt; pm.colsP = colsP; pm.scale = 1.0f / sqrtf((float)(C / heads > 0 ? C / heads : 1));
+  pm.kpp = kb; pm.cs = cs; pm.bs = bs; pm.vpp = vb;
+  CK(launch_ipa_premul(pm, st));
+  CK(launch_bf16_to_f32(kb, kpp, (long long)n, st));
+  CK(launch_bf16_to_f32(vb, vpp, (long long)n, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// launch_ipa_scores: h [B * HW][C], kpp [B][colsP][C], cs / bs [B][colsP] -> P.  P is the CALLER's [B * HW + guard_rows][colsP] floats (bf16 values):
+// rounded to bf16, handed to the kernel and widened back whole, so rows the kernel must not touch come back as they went in
+AGD_API int agd_op_ipa_scores(const float* h, const float* kpp, const float* cs, const float* bs, float* P, int B, int HW, int C, int heads, int nt,
+                              int colsP, float eps, int guard_rows, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!h || !kpp || !cs || !bs || !P || B < 1 || HW < 1 || C < 1 || colsP < 1 || guard_rows < 0) { agd_set_error("op_ipa_scores: bad arguments (B %d HW %d C %d cols %d)", B, HW, C, colsP); return -1; }
+  const long long M = (long long)B * HW, np = (M + guard_rows) * colsP;
+  bf16_t* hb = tmp.get<bf16_t>((size_t)M * C); bf16_t* kb = tmp.get<bf16_t>((size_t)B * colsP * C); bf16_t* Pb = tmp.get<bf16_t>((size_t)np);
+  if (!hb || !kb || !Pb) return -1;
+  CK(launch_f32_to_bf16(h, hb, M * C, st)); CK(launch_f32_to_bf16(kpp, kb, (long long)B * colsP * C, st)); CK(launch_f32_to_bf16(P, Pb, np, st));
+  IpaScoreP sp{}; sp.h = hb; sp.kpp = kb; sp.cs = cs; sp.bs = bs; sp.P = Pb; sp.B = B; sp.HW = HW; sp.C = C; sp.H = heads; sp.nt = nt; sp.colsP = colsP; sp.eps = eps;
+  CK(launch_ipa_scores(sp, st));
+  CK(launch_bf16_to_f32(Pb, P, np, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+// launch_ipa_add: h += s P V''^T.  h is the CALLER's [B * HW + guard_rows][C] floats, updated in place through bf16 as above; P [B * HW][colsP],
+// vpp [B][C][colsP]
+AGD_API int agd_op_ipa_add(float* h, const float* P, const float* vpp, int B, int HW, int C, int colsP, float s, int guard_rows, void* stream) {
+  hipStream_t st = S(stream); Tmp tmp;
+  if (!h || !P || !vpp || B < 1 || HW < 1 || C < 1 || colsP < 1 || guard_rows < 0) { agd_set_error("op_ipa_add: bad arguments (B %d HW %d C %d cols %d)", B, HW, C, colsP); return -1; }
+  const long long M = (long long)B * HW, nh = (M + guard_rows) * C;
+  bf16_t* hb = tmp.get<bf16_t>((size_t)nh); bf16_t* Pb = tmp.get<bf16_t>((size_t)M * colsP); bf16_t* vb = tmp.get<bf16_t>((size_t)B * C * colsP);
+  if (!hb || !Pb || !vb) return -1;
+  CK(launch_f32_to_bf16(h, hb, nh, st)); CK(launch_f32_to_bf16(P, Pb, M * colsP, st)); CK(launch_f32_to_bf16(vpp, vb, (long long)B * C * colsP, st));
+  IpaAddP ap{}; ap.h = hb; ap.P = Pb; ap.vpp = vb; ap.B = B; ap.HW = HW; ap.C = C; ap.colsP = colsP; ap.s = s;
+  CK(launch_ipa_add(ap, st));
+  CK(launch_bf16_to_f32(hb, h, nh, st));
+  hipStreamSynchronize(st);
+  return 0;
+}
+
 AGD_API int agd_op_attention(const float* q, const float* k, const float* v, float* o, int B, int H, int D, int Nq, int Nk,
                                 float scale, float* probs_out, void* stream) {
   hipStream_t st = S(stream); Tmp tmp;

@@ -364,6 +364,133 @@ def xattn_premul(x, gamma, beta, wq, kv, wo, bo, heads=8, eps=1e-5, return_probs
     return (y, pr) if return_probs else y
 
 
+XATTN_TP = 80                    # token rows per head of the pre-multiplied matrices (kernels.h)
+
+
+def xattn_context(kv, wq, wo, gamma, beta, heads=8):
+    """The context products of `xattn_premul` as its launches write them (agd_op_xattn_context): kv [B, T, 2C] ->
+    (kpp [B, H, 80, C], cs [B, H, 80], bs [B, H, 80], vpp [B, C, H, 80]), the bf16 ones widened, the padding included."""
+    lib = _lib.load()
+    kv = _f32c(kv)
+    B, T, C2 = kv.shape
+    Cc, H = C2 // 2, int(heads)
+    dev = kv.device
+    kpp = torch.empty(B, H, XATTN_TP, Cc, device=dev, dtype=torch.float32)
+    cs = torch.empty(B, H, XATTN_TP, device=dev, dtype=torch.float32)
+    bs = torch.empty_like(cs)
+    vpp = torch.empty(B, Cc, H, XATTN_TP, device=dev, dtype=torch.float32)
+    _lib.check(lib.agd_op_xattn_context(_lib.ptr(_given(kv)), _lib.ptr(_f32c(wq)), _lib.ptr(_f32c(wo)), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(kpp),
+                                        _lib.ptr(cs), _lib.ptr(bs), _lib.ptr(vpp), B, T, Cc, H, _lib.current_stream_ptr()), None, "agd_op_xattn_context")
+    return kpp, cs, bs, vpp
+
+
+def xattn_scores(x, kpp, cs, bs, T, heads=8, eps=1e-5, *, stats=None, rec=None, rec_b0=0, rec_T=None):
+    """`xattn_s_kernel` alone (agd_op_xattn_scores): x [B, HW, C], kpp [B, H, 80, C], cs / bs [B, H, 80] (the caller's, hand-made ones included)
+    -> P [B, HW, H, 80].  stats [B * HW, slots, 2]: the rows' (sum, sum of squares) as slots partial sums (None: one slot, computed by the
+    library).  rec: [B - rec_b0, H, rows, HW] fp32 on the GPU, ADDED to in place and never zeroed (token rows < rec_T, default all rows)."""
+    lib = _lib.load()
+    x, kpp, cs, bs = _f32c(x), _f32c(kpp), _f32c(cs), _f32c(bs)
+    B, HW, Cc = x.shape
+    H = int(heads)
+    assert kpp.shape == (B, H, XATTN_TP, Cc) and cs.shape == (B, H, XATTN_TP) and bs.shape == cs.shape, "kpp [B, H, 80, C], cs / bs [B, H, 80]"
+    slots = 0
+    if stats is not None:
+        stats = _f32c(stats)
+        assert stats.dim() == 3 and stats.shape[0] == B * HW and stats.shape[2] == 2, "stats [B * HW, slots, 2]"
+        slots = stats.shape[1]
+    rec_rows = 0
+    if rec is not None:
+        assert rec.is_cuda and rec.dtype == torch.float32 and rec.is_contiguous() and rec.dim() == 4, "rec: contiguous fp32 on the GPU"
+        assert 0 <= rec_b0 < B and rec.shape[0] == B - rec_b0 and rec.shape[1] == H and rec.shape[3] == HW, "rec [B - rec_b0, H, rows, HW]"
+        rec_rows = rec.shape[2]
+        rec_T = rec_rows if rec_T is None else int(rec_T)
+    P = torch.empty(B, HW, H, XATTN_TP, device=x.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_xattn_scores(_lib.ptr(x), _lib.ptr(stats), slots, _lib.ptr(kpp), _lib.ptr(cs), _lib.ptr(bs), _lib.ptr(P), _lib.ptr(rec), int(rec_b0),
+                                       int(rec_T or 0), int(rec_rows), B, HW, int(T), Cc, H, float(eps), _lib.current_stream_ptr()), None, "agd_op_xattn_scores")
+    return P
+
+
+def ipa_cols(heads, nt):
+    """heads * nt padded to a multiple of 16: the column count of the IP-Adapter's pre-multiplied matrices"""
+    return (int(heads) * int(nt) + 15) // 16 * 16
+
+
+def ipa_linear(x, w, bias=None):
+    """`ipa_linear_kernel` (agd_op_ipa_linear): fp32 rows x [R, K] against bf16(w [N, K]) (+ bias) -> [R, N] fp32"""
+    lib = _lib.load()
+    x, w = _f32c(x), _f32c(w)
+    R, K = x.shape
+    N = w.shape[0]
+    y = torch.empty(R, N, device=x.device, dtype=torch.float32)
+    _lib.check(lib.agd_op_ipa_linear(_lib.ptr(x), _lib.ptr(w), _lib.ptr(None if bias is None else _f32c(bias)), _lib.ptr(y), R, N, K, _lib.current_stream_ptr()),
+               None, "agd_op_ipa_linear")
+    return y
+
+
+def ipa_layernorm(x, gamma, beta, eps=1e-5):
+    """`ipa_layernorm_kernel` (agd_op_ipa_layernorm): fp32 LayerNorm of the rows of x [rows, C]"""
+    lib = _lib.load()
+    x = _f32c(x)
+    rows, Cc = x.shape
+    y = torch.empty_like(x)
+    _lib.check(lib.agd_op_ipa_layernorm(_lib.ptr(x), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)), _lib.ptr(y), rows, Cc, float(eps), _lib.current_stream_ptr()),
+               None, "agd_op_ipa_layernorm")
+    return y
+
+
+def ipa_context(kip, vip, wq, wo, gamma, beta, heads, *, cols=None):
+    """The IP-Adapter's context products (agd_op_ipa_context: the Wq . beta mat-vec and launch_ipa_premul): kip / vip [B, nt, C] fp32 ->
+    (kpp [B, colsP, C], cs [B, colsP], bs [B, colsP], vpp [B, C, colsP]) with colsP = heads * nt padded to 16 (cols: another count, to be refused)."""
+    lib = _lib.load()
+    kip, vip = _f32c(kip), _f32c(vip)
+    B, nt, Cc = kip.shape
+    colsP = ipa_cols(heads, nt) if cols is None else int(cols)
+    dev = kip.device
+    kpp = torch.empty(B, colsP, Cc, device=dev, dtype=torch.float32)
+    cs = torch.empty(B, colsP, device=dev, dtype=torch.float32)
+    bs = torch.empty_like(cs)
+    vpp = torch.empty(B, Cc, colsP, device=dev, dtype=torch.float32)
+    _lib.check(lib.agd_op_ipa_context(_lib.ptr(kip), _lib.ptr(vip), _lib.ptr(_f32c(wq)), _lib.ptr(_f32c(wo)), _lib.ptr(_f32c(gamma)), _lib.ptr(_f32c(beta)),
+                                      _lib.ptr(kpp), _lib.ptr(cs), _lib.ptr(bs), _lib.ptr(vpp), B, Cc, int(heads), nt, colsP, _lib.current_stream_ptr()),
+               None, "agd_op_ipa_context")
+    return kpp, cs, bs, vpp
+
+
+IPA_SENTINEL = -24576.0          # exact in bf16: what `ipa_scores` / `ipa_add` fill the guard rows with
+
+
+def ipa_scores(h, kpp, cs, bs, heads, nt, eps=1e-5, *, out=None, guard_rows=0):
+    """`ipa_scores_kernel` (agd_op_ipa_scores): h [B, HW, C], kpp [B, colsP, C], cs / bs [B, colsP] -> P [B, HW, colsP].  out: the caller's
+    [B * HW + guard_rows, colsP] fp32 buffer (bf16 values) the kernel writes into; without it one is made, filled with IPA_SENTINEL, and returned
+    whole when guard_rows > 0."""
+    lib = _lib.load()
+    h, kpp, cs, bs = _f32c(h), _f32c(kpp), _f32c(cs), _f32c(bs)
+    B, HW, Cc = h.shape
+    colsP = kpp.shape[1]
+    assert kpp.shape == (B, colsP, Cc) and cs.shape == (B, colsP) and bs.shape == cs.shape, "kpp [B, colsP, C], cs / bs [B, colsP]"
+    if out is None:
+        out = torch.full((B * HW + guard_rows, colsP), IPA_SENTINEL, device=h.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B * HW + guard_rows, colsP), "out [B * HW + guard_rows, colsP]"
+    _lib.check(lib.agd_op_ipa_scores(_lib.ptr(h), _lib.ptr(kpp), _lib.ptr(cs), _lib.ptr(bs), _lib.ptr(out), B, HW, Cc, int(heads), int(nt), colsP, float(eps),
+                                     int(guard_rows), _lib.current_stream_ptr()), None, "agd_op_ipa_scores")
+    return out if guard_rows else out.reshape(B, HW, colsP)
+
+
+def ipa_add(h, P, vpp, s, *, guard_rows=0):
+    """`ipa_add_kernel` (agd_op_ipa_add): h' = bf16(h + s P V''^T) on a copy of h [B, HW, C]; P [B, HW, colsP], vpp [B, C, colsP].  With guard_rows
+    the copy has that many rows of IPA_SENTINEL behind it and comes back whole, [B * HW + guard_rows, C]."""
+    lib = _lib.load()
+    h, P, vpp = _f32c(h), _f32c(P), _f32c(vpp)
+    B, HW, Cc = h.shape
+    colsP = P.shape[-1]
+    assert P.shape == (B, HW, colsP) and vpp.shape == (B, Cc, colsP), "P [B, HW, colsP], vpp [B, C, colsP]"
+    buf = torch.full((B * HW + guard_rows, Cc), IPA_SENTINEL, device=h.device, dtype=torch.float32)
+    buf[:B * HW] = h.reshape(B * HW, Cc)
+    _lib.check(lib.agd_op_ipa_add(_lib.ptr(buf), _lib.ptr(P), _lib.ptr(vpp), B, HW, Cc, colsP, float(s), int(guard_rows), _lib.current_stream_ptr()),
+               None, "agd_op_ipa_add")
+    return buf if guard_rows else buf.reshape(B, HW, Cc)
+
+
 def _given(t):
     """a tensor to hand over even when it is empty (an empty tensor has a null data pointer): the library refuses the shape, by name"""
     t = _f32c(t)

@@ -481,6 +481,30 @@ int agd_op_qkv_chain(const float* x, const float* gn_gamma, const float* gn_beta
  * head dim % 8 == 0, C % 160 == 0 and C % 64 == 0 (i.e. C a multiple of 320), heads x 80 a multiple of 64. */
 int agd_op_xattn_premul(const float* x, const float* gamma, const float* beta, const float* wq, const float* kv, const float* wo,
                         const float* bo, float* y, float* probs, int B, int HW, int T, int C, int heads, float eps, void* stream);
+/* The stages of agd_op_xattn_premul (csrc/xattn_pre.hip) and of the IP-Adapter branch (csrc/ipadapter.hip) one launcher at a time, for per-kernel
+ * tests.  Context-free, device pointers, fp32 in and out; bf16 quantities are rounded / widened on the device; every output the kernels write
+ * is pre-filled with the byte 0x7F so an element a kernel leaves out shows; a launcher's refusal comes back as -1 with its message.
+ *
+ * agd_op_xattn_context: kv [B][T][2C], wq / wo [C][C], gamma / beta [C] -> kpp [B][heads][80][C] (K''), cs / bs [B][heads][80], vpp [B][C][heads][80]
+ * (V''), built by the launches agd_op_xattn_premul makes, the zero padding of token rows >= T included.
+ * agd_op_xattn_scores: launch_xattn_s alone on the caller's K'' / cs / bs -> P [B * HW][heads * 80].  stats (may be NULL: one slot, computed here)
+ * [B * HW][slots][2] = partial (sum, sum of squares) of each row of x.  rec (may be NULL) [B - rec_b0][heads][rec_rows][HW] is ADDED to (never zeroed
+ * here): images >= rec_b0, token rows < rec_T <= rec_rows.
+ * agd_op_ipa_linear / agd_op_ipa_layernorm / agd_op_ipa_scores / agd_op_ipa_add: one launcher each.  agd_op_ipa_context: the Wq . beta mat-vec and
+ * launch_ipa_premul -> kpp [B][colsP][C], cs / bs [B][colsP], vpp [B][C][colsP].  agd_op_ipa_scores writes into the CALLER's P
+ * [B * HW + guard_rows][colsP] and agd_op_ipa_add updates the CALLER's h [B * HW + guard_rows][C] in place (both through bf16), so rows the kernel
+ * must not touch come back as they went in. */
+int agd_op_xattn_context(const float* kv, const float* wq, const float* wo, const float* gamma, const float* beta, float* kpp, float* cs,
+                         float* bs, float* vpp, int B, int T, int C, int heads, void* stream);
+int agd_op_xattn_scores(const float* x, const float* stats, int slots, const float* kpp, const float* cs, const float* bs, float* P, float* rec,
+                        int rec_b0, int rec_T, int rec_rows, int B, int HW, int T, int C, int heads, float eps, void* stream);
+int agd_op_ipa_linear(const float* x, const float* w, const float* bias, float* y, int R, int N, int K, void* stream);
+int agd_op_ipa_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps, void* stream);
+int agd_op_ipa_context(const float* kip, const float* vip, const float* wq, const float* wo, const float* gamma, const float* beta, float* kpp,
+                       float* cs, float* bs, float* vpp, int B, int C, int heads, int nt, int colsP, void* stream);
+int agd_op_ipa_scores(const float* h, const float* kpp, const float* cs, const float* bs, float* P, int B, int HW, int C, int heads, int nt,
+                      int colsP, float eps, int guard_rows, void* stream);
+int agd_op_ipa_add(float* h, const float* P, const float* vpp, int B, int HW, int C, int colsP, float s, int guard_rows, void* stream);
 int agd_op_groupnorm(const float* x_nchw, const float* gamma, const float* beta, float* y_nchw, int B, int C, int HW,
                      int groups, float eps, int silu, void* stream);
 /* agd_op_groupnorm reaching EVERY form of the GroupNorm launcher, for per-kernel tests: one source, or the channel concat x0 | x1 (both NCHW
